@@ -5,9 +5,10 @@ A "pass" is one trip of a wavefront of shading queries through the hot path: ``M
 warp + T Euler steps + Jacobian + guards, in-kernel RNG) followed by ``MyBSDF.pdf`` on the produced directions.
 The default workload is BASELINE.json configs[1]: single measured BSDF (aniso_miro_7_rgb), disk-domain net,
 1 Mi queries per wavefront, 8 denoise steps, per GPU (weak scaling: every rank owns its own wavefronts).  A "step"
-is ``passes_per_step`` consecutive wavefronts (chosen once, at setup, so that the K timed steps last >= 0.5 s
-whatever K is — a 20 ms timed region moves by percents with one clock hiccup); value = queries through
-sample()+pdf() per second, whole job.  Inputs are resident in HBM before the timed region.  There is no data-path
+is ``passes_per_step`` consecutive wavefronts: QUERIES_PER_STEP queries per GPU (32 wavefronts of the default workload),
+fixed by the workload alone, so that a step is the same work whatever --steps is and --steps K times exactly K of them;
+value = queries through sample()+pdf() per second, whole job.  Inputs are resident in HBM before the timed region,
+seeded, and the same from run to run.  There is no data-path
 collective; with N > 1 ranks the final (wo, pdf) shards are concatenated on rank 0 with one RCCL gather inside the
 timed region, and the line also carries the rate with no gather and with a gather every step.
 
@@ -16,11 +17,16 @@ timed region, and the line also carries the rate with no gather and with a gathe
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 50 --warmup 5     # or under an external launcher
     python bench.py --workload mixed_16Mi                               # configs[3] per-GPU share
+    python bench.py --full                                              # + every side figure below
+    python bench.py --dump-outputs bench_outputs                        # + the last step's results as .npy
 
 Prints ONE JSON line on rank 0: the contract's fields plus ``roofline`` (fused flow kernel vs the dense fp16-MFMA
-peak, HIP events on the launch stream; ``issue_bound``: shader cycles per tile-step vs the instruction-issue model
-of the loop), ``secondary`` (the other configs, timed in the same run), ``encoding_pass`` (HBM-bound),
-``cpu_baseline`` (the torch-eager port of the reference's CPU path on this box's host cores, bounded sample).
+peak, HIP events on the launch stream of the timed region).  A plain run does nothing else: set-up, warm-up, the
+timed steps, the outputs (--dump-outputs) and the line.  With --full it also measures, behind the timed region:
+``roofline.issue_bound`` (shader cycles per tile-step vs the instruction-issue model of the loop),
+``roofline.context_pair_ms``, ``roofline.board`` (energy), ``secondary`` (the other configs), ``encoding_pass``
+(HBM-bound), ``cpu_baseline`` (the torch-eager port of the reference's CPU path on the host cores, bounded sample)
+and, with N > 1 ranks, the two gather modes that are not judged.
 """
 import argparse
 import json
@@ -35,7 +41,10 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 PEAK_FP16_MFMA_TFLOPS = 2500.0  # dense, /opt/skills/guides/MI355X_MICROARCH.md "Peak BF16/FP16 MFMA"
-MIN_TIMED_S = 0.5
+# a step: this many queries per GPU, whole wavefronts (at least one).  Fixed, not timed at set-up: the pass seeds, and so the
+# outputs of the last step, depend on the step size, and two builds must compute the same outputs from the same arguments
+QUERIES_PER_STEP = 1 << 25
+DUMP_MAX_BYTES = 64 << 20
 
 WORKLOADS = {
     # name: (kind, material, domain, per-GPU queries per wavefront, T)
@@ -311,6 +320,10 @@ class SingleMaterial:
         from bsdf_diffusion_sampling_amd.sharding import pack_result
         return pack_result(self.wo[self.last], self.pdf_s[self.last])
 
+    def outputs(self):
+        """What a caller of the last pass receives: sample() -> (wo, its pdf), pdf() at wo."""
+        return {"wo": self.wo[self.last], "sample_pdf": self.pdf_s[self.last], "pdf": self.pdf_p[self.last]}
+
     def check(self):
         import torch
         w, p = self.wo[self.last], self.pdf_p[self.last]
@@ -393,6 +406,10 @@ class MixedMaterials:
         from bsdf_diffusion_sampling_amd.sharding import pack_result
         return pack_result(self.out[0], self.out[1])
 
+    def outputs(self):
+        wo, pdf, p = self.out
+        return {"wo": wo, "sample_pdf": pdf, "pdf": p}
+
     def check(self):
         import torch
         wo, pdf, p = self.out
@@ -447,6 +464,9 @@ class Teacher:
 
     def result(self):
         return self.x
+
+    def outputs(self):
+        return {"x": self.x}
 
     def check(self):
         import torch
@@ -526,6 +546,30 @@ def pass_seconds(wl, reps=3):
         wl.run_pass(k)
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / reps
+
+
+def dump_outputs(wl, out_dir):
+    """--dump-outputs: the arrays a caller of the timed path received in its last pass (``wl.outputs()``) as
+    <out_dir>/<name>.npy, float32, at most DUMP_MAX_BYTES in all.  A larger set is cut to one seeded sample of rows, the
+    same in every array and every run (their indices in rows.npy, float64), so that two builds compare row for row."""
+    import numpy as np
+    import torch
+    outs = wl.outputs()
+    n = next(iter(outs.values())).shape[0]
+    assert all(t.shape[0] == n for t in outs.values()), {k: tuple(t.shape) for k, t in outs.items()}
+    row_bytes = sum(4 * (t.numel() // max(n, 1)) for t in outs.values())
+    os.makedirs(out_dir, exist_ok=True)
+    rows = None
+    if n * row_bytes > DUMP_MAX_BYTES:
+        m = DUMP_MAX_BYTES // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(20240611).choice(n, m, replace=False))
+        idx = torch.from_numpy(rows).to(next(iter(outs.values())).device)
+        outs = {k: t.index_select(0, idx) for k, t in outs.items()}
+        np.save(os.path.join(out_dir, "rows.npy"), rows.astype(np.float64))
+    for k, t in outs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), t.detach().float().cpu().numpy())
+    return {"dir": out_dir, "arrays": {k: list(t.shape) for k, t in outs.items()}, "rows_of": n,
+            "rows": "all" if rows is None else f"{len(rows)} sampled (rows.npy)"}
 
 
 def kernel_source_sha256():
@@ -745,10 +789,9 @@ def worker(a):
             dist.barrier()
         torch.cuda.synchronize()
 
-    # ---- setup: clock settle, then size a step so that the timed region lasts >= MIN_TIMED_S ----
+    # ---- setup: clock settle; a step is R wavefronts, R fixed by the workload (QUERIES_PER_STEP) ----
     settle(wl, a.settle_ms)
-    t_pass = pass_seconds(wl)
-    R = a.passes_per_step or max(1, int(math.ceil(MIN_TIMED_S / (max(a.steps, 1) * max(t_pass, 1e-6)))))
+    R = a.passes_per_step or max(1, QUERIES_PER_STEP // n_local)
     if multi:
         t = torch.tensor([R], dtype=torch.int64, device=stage)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -811,8 +854,10 @@ def worker(a):
     by_op = profile_read_by_op(wl)     # the same launches by kind (sample / pdf / ...)
     profiling(wl, False)
     wl.check()
+    # the results of the last pass of the last step, before anything behind the timed region reuses the workload's buffers
+    dumped = dump_outputs(wl, a.dump_outputs) if a.dump_outputs and rank == 0 else None
     extra_regions = {}
-    if multi:
+    if multi and a.full:
         for mode in ("none", "final", "every"):
             if mode != judged_mode:
                 extra_regions[mode] = region(mode, (a.warmup + a.steps) * R)
@@ -841,8 +886,8 @@ def worker(a):
             "dtype": "fp16-MFMA split3 (hi+lo operands, fp32 accumulate) + fp32 VALU" if wl.precision == "split3" else wl.precision,
             "data": "synthetic",
             "config": dict(wl.config(), workload=a.workload, queries_per_wavefront_per_gpu=n_local, passes_per_step=R,
-                           queries_per_step=n_total * R, timed_region_s=dt, min_timed_region_s=MIN_TIMED_S,
-                           precision=wl.precision, settle_ms=a.settle_ms,
+                           queries_per_step=n_total * R, timed_region_s=dt,
+                           precision=wl.precision, settle_ms=a.settle_ms, full=a.full,
                            parallelism=f"query-sharded x{world}, no data-path collective" +
                                        ("" if world == 1 else {"final": "; one RCCL gather-to-root of the final (wo,pdf) shards inside the timed region",
                                                                "every": "; RCCL gather-to-root every step, overlapped on a side stream",
@@ -854,9 +899,11 @@ def worker(a):
         if multi:
             rates = {judged_mode: queries_timed / dt / 1e6}
             rates.update({m: queries_timed / t / 1e6 for m, t in extra_regions.items()})
-            out["multi_gpu"] = {"Msamples_per_s_no_gather": rates["none"], "Msamples_per_s_final_gather": rates["final"],
-                                "Msamples_per_s_gather_every_step_overlapped": rates["every"], "judged": judged_mode,
-                                "gather_bytes_per_rank": n_local * 16, "note": "each figure is its own timed region of the same K steps"}
+            out["multi_gpu"] = {"Msamples_per_s_no_gather": rates.get("none"), "Msamples_per_s_final_gather": rates.get("final"),
+                                "Msamples_per_s_gather_every_step_overlapped": rates.get("every"), "judged": judged_mode,
+                                "gather_bytes_per_rank": n_local * 16,
+                                "note": "each figure is its own timed region of the same K steps; the modes not judged are "
+                                        "timed under --full only (None otherwise)"}
         # ---- roofline of the dominant kernel: HIP events on the launch stream over the judged region ----
         avg_ms = kern_ms / max(n_launch, 1)
         flops_launch = wl.flops_per_pass / wl.launches_per_pass
@@ -897,8 +944,10 @@ def worker(a):
                          "pdf_Msamples_per_s": n_local / (split["pdf"] * 1e-3) / 1e6 if split.get("pdf") else None})
             # the per-query context in both call orders (outside the timed region): sample() fills / pdf() reads — the bench's
             # pass — and pdf() fills / sample() reads — the order of Mitsuba's path integrator (eval_pdf for the emitter
-            # sample first, rendering/brdf_measured_disk.py:126, then sample, :59) — next to the pair without a context
-            pair_ctx = wl.ctx if wl.ctx is not None else (wl.smp.new_context(n_local) if wl.smp.context_floats(n_local) * 4 <= CONTEXT_MAX_BYTES else None)
+            # sample first, rendering/brdf_measured_disk.py:126, then sample, :59) — next to the pair without a context (--full)
+            pair_ctx = None
+            if a.full:
+                pair_ctx = wl.ctx if wl.ctx is not None else (wl.smp.new_context(n_local) if wl.smp.context_floats(n_local) * 4 <= CONTEXT_MAX_BYTES else None)
             if pair_ctx is not None:
                 def pair(order, k):
                     kw_s = dict(T=wl.T, variant=wl.variant, seed=300 + k, out=(wl.wo[1], wl.pdf_s[1]))
@@ -934,62 +983,63 @@ def worker(a):
                                                      f"interleaved, {ROUNDS} rounds x {PAIRS} pairs each, outside the timed region")
                 pair_ctx = None   # (frees the 144 MiB record before the secondary workloads allocate)
             # issue-bound view: measured SIMD cycles per (16-query tile x Euler step) vs the instruction-issue model
-            try:
-                probe_mhz = _lib.shader_clock_mhz()
-                mhz = kern_mhz or probe_mhz
-                n_simd = torch.cuda.get_device_properties(dev_index).multi_processor_count * 4
-                tile_q = wl.smp.tile
-                tiles = n_local / tile_q
-                meas = avg_ms * 1e-3 * mhz * 1e6 * n_simd / (tiles * wl.T)
-                # loop-only: the same sample launch at T and 2T (outside the timed region) — the per-query prologue cancels
-                loop = {}
-                for TT in (wl.T, 2 * wl.T):
-                    for k in range(6):
-                        wl.smp.plugin_sample(wl.wi, None, T=TT, variant=wl.variant, seed=5 + k, out=(wl.wo[0], wl.pdf_s[0]))
-                    torch.cuda.synchronize()
-                    profiling(wl, True)
-                    for k in range(12):
-                        wl.smp.plugin_sample(wl.wi, None, T=TT, variant=wl.variant, seed=50 + k, out=(wl.wo[0], wl.pdf_s[0]))
-                    _, ms_tt = profile_read(wl)
-                    loop[TT] = (ms_tt / 12, profile_clock_mhz(wl))
-                    profiling(wl, False)
-                roof["flow_launches_after_timed_region"] += 36
-                # (each launch length is converted at the clock ITS launches ran at: the two may differ by a few per cent)
-                c_long = loop[2 * wl.T][0] * (loop[2 * wl.T][1] or mhz)
-                c_short = loop[wl.T][0] * (loop[wl.T][1] or mhz)
-                loop_mhz = loop[2 * wl.T][1] or mhz
-                meas_loop = (c_long - c_short) / wl.T * 1e-3 * 1e6 * n_simd / tiles
-                ib = {"shader_clock_mhz": mhz, "simds": n_simd, "tile_queries": tile_q,
-                      "shader_clock_basis": "the judged launches' own shader-cycle / wall-clock counters, every wave "
-                                            "(bsdfd_profile_clock_mhz); `probe_clock_mhz` is the stand-alone probe kernel (csrc/clock.hip), "
-                                            "a similar instruction mix but not the kernel itself",
-                      "probe_clock_mhz": probe_mhz,
-                      "measured_simd_cycles_per_tile_step": meas,
-                      "measured_loop_cycles_per_tile_step": meas_loop,
-                      "loop_basis": f"(sample launch at T={2 * wl.T} minus at T={wl.T}) / {wl.T}: {loop[2 * wl.T][0]:.4f} ms, {loop[wl.T][0]:.4f} ms "
-                                    f"at {loop_mhz:.0f} and {(loop[wl.T][1] or mhz):.0f} MHz — the per-query prologue and epilogue cancel",
-                      "note": "measured_simd_cycles = avg launch time x clock x SIMDs / (tiles x T) carries the per-query prologue's "
-                              "share; measured_loop_cycles is the Euler step alone and is what the model describes.  Model = sum over "
-                              "the loop's instructions of what each costs the SIMD (tools/isa_mix.py on the shipped build): in this "
-                              "VALU-heavy mix MFMA time and VALU time add — a 16x16x32 MFMA 16.4 cycles, a 32x32x16 32.1, a transcendental "
-                              "8.1 (tools/ubench/RESULTS.md; rounds 2-4 priced it at 11, round 5 measured ~7.5-8 in the kernels) — model/measured_loop ~ 1 means the step runs "
-                              "at the hardware's issue rate for this instruction mix.  A tile is `tile_queries` queries (one wave64)."}
-                mdl, mdl_prov = isa_model(tile_key(a.workload, tile_q))
-                ib["model_source"] = mdl_prov
-                if mdl and mdl.get("tile_queries", 16) != tile_q:
-                    ib["model_source"] = dict(mdl_prov, status=f"model is of the {mdl.get('tile_queries', 16)}-query-tile kernel, the run used {tile_q}")
-                    mdl = None
-                if mdl:
-                    ib.update({"model_issue_cycles_per_tile_step": mdl["issue_cycles_total"], "model_mfma_cycles": mdl["issue_cycles_mfma"],
-                               "model_valu_cycles": mdl["issue_cycles_valu"], "n_mfma": mdl["n_mfma"], "n_valu": mdl["n_valu"],
-                               "frac_of_issue_bound": mdl["issue_cycles_total"] / meas_loop,
-                               "frac_of_issue_bound_basis": "model / measured_loop_cycles_per_tile_step"})
-                roof["issue_bound"] = ib
-            except Exception as exc:
-                roof["issue_bound"] = {"error": repr(exc)}
+            if a.full:
+                try:
+                    probe_mhz = _lib.shader_clock_mhz()
+                    mhz = kern_mhz or probe_mhz
+                    n_simd = torch.cuda.get_device_properties(dev_index).multi_processor_count * 4
+                    tile_q = wl.smp.tile
+                    tiles = n_local / tile_q
+                    meas = avg_ms * 1e-3 * mhz * 1e6 * n_simd / (tiles * wl.T)
+                    # loop-only: the same sample launch at T and 2T (outside the timed region) — the per-query prologue cancels
+                    loop = {}
+                    for TT in (wl.T, 2 * wl.T):
+                        for k in range(6):
+                            wl.smp.plugin_sample(wl.wi, None, T=TT, variant=wl.variant, seed=5 + k, out=(wl.wo[0], wl.pdf_s[0]))
+                        torch.cuda.synchronize()
+                        profiling(wl, True)
+                        for k in range(12):
+                            wl.smp.plugin_sample(wl.wi, None, T=TT, variant=wl.variant, seed=50 + k, out=(wl.wo[0], wl.pdf_s[0]))
+                        _, ms_tt = profile_read(wl)
+                        loop[TT] = (ms_tt / 12, profile_clock_mhz(wl))
+                        profiling(wl, False)
+                    roof["flow_launches_after_timed_region"] += 36
+                    # (each launch length is converted at the clock ITS launches ran at: the two may differ by a few per cent)
+                    c_long = loop[2 * wl.T][0] * (loop[2 * wl.T][1] or mhz)
+                    c_short = loop[wl.T][0] * (loop[wl.T][1] or mhz)
+                    loop_mhz = loop[2 * wl.T][1] or mhz
+                    meas_loop = (c_long - c_short) / wl.T * 1e-3 * 1e6 * n_simd / tiles
+                    ib = {"shader_clock_mhz": mhz, "simds": n_simd, "tile_queries": tile_q,
+                          "shader_clock_basis": "the judged launches' own shader-cycle / wall-clock counters, every wave "
+                                                "(bsdfd_profile_clock_mhz); `probe_clock_mhz` is the stand-alone probe kernel (csrc/clock.hip), "
+                                                "a similar instruction mix but not the kernel itself",
+                          "probe_clock_mhz": probe_mhz,
+                          "measured_simd_cycles_per_tile_step": meas,
+                          "measured_loop_cycles_per_tile_step": meas_loop,
+                          "loop_basis": f"(sample launch at T={2 * wl.T} minus at T={wl.T}) / {wl.T}: {loop[2 * wl.T][0]:.4f} ms, {loop[wl.T][0]:.4f} ms "
+                                        f"at {loop_mhz:.0f} and {(loop[wl.T][1] or mhz):.0f} MHz — the per-query prologue and epilogue cancel",
+                          "note": "measured_simd_cycles = avg launch time x clock x SIMDs / (tiles x T) carries the per-query prologue's "
+                                  "share; measured_loop_cycles is the Euler step alone and is what the model describes.  Model = sum over "
+                                  "the loop's instructions of what each costs the SIMD (tools/isa_mix.py on the shipped build): in this "
+                                  "VALU-heavy mix MFMA time and VALU time add — a 16x16x32 MFMA 16.4 cycles, a 32x32x16 32.1, a transcendental "
+                                  "8.1 (tools/ubench/RESULTS.md; rounds 2-4 priced it at 11, round 5 measured ~7.5-8 in the kernels) — model/measured_loop ~ 1 means the step runs "
+                                  "at the hardware's issue rate for this instruction mix.  A tile is `tile_queries` queries (one wave64)."}
+                    mdl, mdl_prov = isa_model(tile_key(a.workload, tile_q))
+                    ib["model_source"] = mdl_prov
+                    if mdl and mdl.get("tile_queries", 16) != tile_q:
+                        ib["model_source"] = dict(mdl_prov, status=f"model is of the {mdl.get('tile_queries', 16)}-query-tile kernel, the run used {tile_q}")
+                        mdl = None
+                    if mdl:
+                        ib.update({"model_issue_cycles_per_tile_step": mdl["issue_cycles_total"], "model_mfma_cycles": mdl["issue_cycles_mfma"],
+                                   "model_valu_cycles": mdl["issue_cycles_valu"], "n_mfma": mdl["n_mfma"], "n_valu": mdl["n_valu"],
+                                   "frac_of_issue_bound": mdl["issue_cycles_total"] / meas_loop,
+                                   "frac_of_issue_bound_basis": "model / measured_loop_cycles_per_tile_step"})
+                    roof["issue_bound"] = ib
+                except Exception as exc:
+                    roof["issue_bound"] = {"error": repr(exc)}
         # the board's own view while the judged workload's passes run back to back (outside the timed region, whatever the
-        # workload): the flow kernels are power-limited — socket power at the limit, shader clock below boost
-        if rank == 0 and world == 1:
+        # workload, --full): the flow kernels are power-limited — socket power at the limit, shader clock below boost
+        if a.full and world == 1:
             try:
                 roof["board"] = board_energy(wl)
                 roof["flow_launches_after_timed_region"] = roof.get("flow_launches_after_timed_region", 0) + roof["board"].pop("launches", 0)
@@ -998,7 +1048,9 @@ def worker(a):
             roof["joule_per_Mquery"] = roof["board"].get("joule_per_Mquery")
             roof["socket_power_w"] = roof["board"].get("socket_power_w")
         out["roofline"] = roof
-        if world == 1 and not a.no_secondary:
+        if dumped is not None:
+            out["outputs"] = dumped
+        if a.full and world == 1 and not a.no_secondary:
             sec = {}
             for name in SECONDARY:
                 if name == a.workload:
@@ -1032,9 +1084,9 @@ def worker(a):
                 del xe, oe
             except Exception as exc:
                 out["encoding_pass"] = {"error": repr(exc)}
-        if world == 1 and not a.no_cpu_baseline and isinstance(wl, SingleMaterial):
+        if a.full and world == 1 and not a.no_cpu_baseline and isinstance(wl, SingleMaterial):
             out["cpu_baseline"] = cpu_baseline(wl.material, wl.domain, wl.T)
-        elif world == 1 and not a.no_cpu_baseline:
+        elif a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline("aniso_miro_7_rgb", "disk", 4)
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if multi:
@@ -1053,15 +1105,21 @@ def main():
     ap.add_argument("--gather", default="final", choices=["final", "every", "none"],
                     help="N>1: which timed region is the judged `value` — 'final': one RCCL gather of the last wavefront's "
                          "(wo,pdf) shards to rank 0 inside the region (the path has no data-path collective; the final "
-                         "concatenation is the only exchange); 'every': every step, overlapped on a side stream; the other "
-                         "modes are timed too and reported under `multi_gpu`")
+                         "concatenation is the only exchange); 'every': every step, overlapped on a side stream; with --full "
+                         "the other modes are timed too and reported under `multi_gpu`")
     ap.add_argument("--passes-per-step", type=int, default=0,
-                    help="wavefronts per step (0 = sized at setup so that the timed region lasts >= 0.5 s)")
+                    help="wavefronts per step (0 = QUERIES_PER_STEP queries per GPU: 32 wavefronts of the default workload)")
     ap.add_argument("--context", default=None, choices=["on", "off"],
                     help="per-query context hand-over from sample() to pdf() of the same wavefront (default off: it buys 1-2 %% of a pair "
-                         "for 5x the HBM traffic; roofline.context_pair_ms reports both forms either way)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+                         "for 5x the HBM traffic; with --full, roofline.context_pair_ms reports both forms either way)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure every side figure: issue bound, context pair, energy, the "
+                         "secondary workloads, the encoding pass, the CPU baseline, the gather modes not judged (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last pass as DIR/<name>.npy (float32, <= 64 MiB in all: a "
+                         "fixed seeded sample of rows beyond that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the secondary workloads and the encoding pass")
     ap.add_argument("--settle-ms", type=float, default=150.0,
                     help="setup: keep the GPU busy with the hot path for this long before the W warm-up steps, so "
                          "that the timed region does not start on an idle-clocked chip")

@@ -41,10 +41,17 @@ def _check_contract(d, n_gpus, workload):
     assert c["queries_per_step"] == c["queries_per_wavefront_per_gpu"] * c["passes_per_step"] * n_gpus
 
 
+def _check_step_size(d):
+    """A step is QUERIES_PER_STEP queries per GPU, whatever --steps is, and the timed region is exactly --steps of them."""
+    c = d["config"]
+    assert c["passes_per_step"] == max(1, (1 << 25) // c["queries_per_wavefront_per_gpu"]), c
+    assert abs(c["timed_region_s"] - d["steps"] * d["ms_per_step"] * 1e-3) < 1e-9 * c["timed_region_s"] + 1e-12
+
+
 def test_bench_line_single_gpu_with_secondary_and_cpu_baseline():
-    d = _run(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    d = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"])
     _check_contract(d, 1, "disk_1Mi_T8")
-    assert d["config"]["timed_region_s"] >= 0.45                     # sized at setup, whatever --steps is
+    _check_step_size(d)
     ib = d["roofline"]["issue_bound"]
     assert 1000 < ib["shader_clock_mhz"] < 2500, ib
     # in-kernel counters (within 1-3 % of GRBM_GUI_ACTIVE in every profiled run, profiles/r0N_*_pmc.json) vs the stand-alone probe
@@ -108,7 +115,7 @@ def test_bench_with_the_per_query_context_opted_in():
 def test_bench_self_launches_two_ranks(workload):
     one = _run(["--gpus", "1", "--workload", workload] + FAST)
     _check_contract(one, 1, workload)
-    two = _run(["--gpus", "2", "--workload", workload] + FAST, {"BSDFD_BENCH_BACKEND": "gloo"})
+    two = _run(["--gpus", "2", "--workload", workload, "--full"] + FAST, {"BSDFD_BENCH_BACKEND": "gloo"})
     _check_contract(two, 2, workload)
     ranks = two["config"]["ranks"]
     assert [r["rank"] for r in ranks] == [0, 1] and all(r["device"] == 0 for r in ranks)  # both on the one GPU here
@@ -130,7 +137,7 @@ def test_bench_self_launches_eight_ranks_gloo(workload):
     hook: rendezvous of 8 ranks, the all-reduce of the step size R, barrier + max-over-ranks timing, the three gather
     modes, an 8-entry rank report — everything of the N = 8 control flow except the RCCL transport itself."""
     args = ["--gpus", "8", "--workload", workload, "--steps", "2", "--warmup", "1", "--passes-per-step", "1", "--settle-ms", "20",
-            "--no-cpu-baseline", "--no-secondary"]
+            "--no-cpu-baseline", "--no-secondary", "--full"]
     d = _run(args, {"BSDFD_BENCH_BACKEND": "gloo"}, timeout=1500)
     _check_contract(d, 8, workload)
     ranks = d["config"]["ranks"]
@@ -162,10 +169,56 @@ def test_bench_rccl_branch_with_one_rank():
     communicator set-up on the device, device-side `dist.gather` of the (wo, pdf) shards in the three gather modes, the
     all-reduces of the step size and of the max-over-ranks time.  What stays unexercised on a 1-GPU box is only the transport
     between GPUs."""
-    d = _run(["--gpus", "1"] + FAST, {"BSDFD_BENCH_FORCE_PG": "1"})
+    d = _run(["--gpus", "1", "--full"] + FAST, {"BSDFD_BENCH_FORCE_PG": "1"})
     _check_contract(d, 1, "disk_1Mi_T8")
     assert d["config"]["backend"] == "nccl" and d["config"]["rccl_ranks"] == 1 and d["config"]["distinct_devices"] == 1
     mg = d["multi_gpu"]
     assert mg["judged"] == "final" and mg["Msamples_per_s_no_gather"] > 0 and mg["Msamples_per_s_gather_every_step_overlapped"] > 0
     plain = _run(["--gpus", "1"] + FAST)
     assert 0.5 * plain["value"] < mg["Msamples_per_s_no_gather"] < 1.5 * plain["value"]
+
+
+def test_bench_plain_run_is_lean_and_steps_set_the_timed_work(tmp_path):
+    """A plain run (no --full) prints the headline line and none of the side figures; --steps K times K steps of the same
+    size; --dump-outputs writes the last pass's results, the same bits from run to run with the same arguments."""
+    import numpy as np
+    base = ["--gpus", "1", "--warmup", "1", "--settle-ms", "20"]
+    a = _run(base + ["--steps", "2", "--dump-outputs", str(tmp_path / "a")])
+    b = _run(base + ["--steps", "2", "--dump-outputs", str(tmp_path / "b")])
+    c = _run(base + ["--steps", "5"])
+    for d in (a, b, c):
+        _check_contract(d, 1, "disk_1Mi_T8")
+        _check_step_size(d)
+        assert not {"secondary", "encoding_pass", "cpu_baseline", "multi_gpu"} & set(d), sorted(d)
+        assert not {"issue_bound", "context_pair_ms", "board"} & set(d["roofline"]), sorted(d["roofline"])
+        assert d["roofline"].get("flow_launches_after_timed_region") == 0
+    assert c["steps"] == 5 and c["config"]["queries_per_step"] == a["config"]["queries_per_step"]
+    n = a["config"]["queries_per_wavefront_per_gpu"]
+    assert a["outputs"]["rows"] == "all" and a["outputs"]["arrays"] == {"wo": [n, 3], "sample_pdf": [n], "pdf": [n]}
+    total = 0
+    for name in ("wo", "sample_pdf", "pdf"):
+        x, y = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert x.dtype == np.float32 and x.shape == tuple(a["outputs"]["arrays"][name])
+        assert np.array_equal(x, y, equal_nan=True), name
+        total += x.nbytes
+    assert total <= 64 << 20
+    wo = np.load(tmp_path / "a" / "wo.npy")
+    assert np.all(np.abs((wo.astype(np.float64) ** 2).sum(1) - 1) < 1e-4)
+
+
+def test_bench_dump_outputs_samples_a_large_output(tmp_path):
+    """mixed_16Mi's last pass (16 Mi rows x 5 floats) is over the 64 MiB cap: the same seeded rows of every array are written."""
+    import numpy as np
+    args = ["--gpus", "1", "--workload", "mixed_16Mi", "--steps", "1", "--warmup", "0", "--passes-per-step", "1", "--settle-ms", "20"]
+    a = _run(args + ["--dump-outputs", str(tmp_path / "a")])
+    b = _run(args + ["--dump-outputs", str(tmp_path / "b")])
+    rows = np.load(tmp_path / "a" / "rows.npy")
+    assert rows.dtype == np.float64 and np.array_equal(rows, np.load(tmp_path / "b" / "rows.npy"))
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < a["config"]["queries_per_wavefront_per_gpu"]
+    total = rows.nbytes
+    for name in ("wo", "sample_pdf", "pdf"):
+        x = np.load(tmp_path / "a" / (name + ".npy"))
+        assert x.dtype == np.float32 and x.shape[0] == rows.shape[0]
+        assert np.array_equal(x, np.load(tmp_path / "b" / (name + ".npy")), equal_nan=True), name
+        total += x.nbytes
+    assert total <= 64 << 20

@@ -254,34 +254,31 @@ def test_cpu_timing_record_present():
         assert 0.6 < c["port_sample_s"] / c["ref_sample_s"] < 1.4
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/rendering"), reason="reference tree only exists in the build container")
 def test_reference_modules_pack_to_the_shipped_weights():
-    """INTEGRATION.md level 1: the reference's OWN nn.Modules (imported in place, unmodified) can be
-    handed to our operators — packing them yields exactly the shipped .bsdfw weights."""
-    import importlib.util
-    import sys
-    sys.dont_write_bytecode = True
-    spec = importlib.util.spec_from_file_location("ref_model_for_test", "/root/reference/rendering/utils/model.py")
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
+    """INTEGRATION.md level 1: the reference's checkpoints (tests/golden/reference_checkpoints.npz: their state_dicts,
+    unchanged, tests/golden/make_checkpoint_golden.py) load strictly into the containers that carry the reference's class
+    names and state_dict keys, and packing them yields exactly the shipped .bsdfw weights."""
     from bsdf_diffusion_sampling_amd import model as M
-    ck = "/root/reference/rendering/checkpoints_new"
-    ds = ref.NN_cond_pos_simpler(input_dim=5, output_dim=2, N_NEURONS=32, POSITIONAL_ENCODING_BASIS_NUM=5)
-    ds.load_state_dict(torch.load(f"{ck}/chm_orange_rgb_disk/brdf_rectify_networkchm_orange_rgb.pth", map_location="cpu"))
-    db = ref.NN_cond_pretrain_disk_one(input_dim=2, N_NEURONS=16, POSITIONAL_ENCODING_BASIS_NUM=3)
-    db.load_state_dict(torch.load(f"{ck}/chm_orange_rgb_disk/brdf_pretrain_networkchm_orange_rgb.pth", map_location="cpu"))
+    ck = np.load(os.path.join(ROOT, "tests", "golden", "reference_checkpoints.npz"))
+
+    def sd(stem):
+        return {k[len(stem) + 1:]: torch.from_numpy(ck[k]) for k in ck.files if k.startswith(stem + "/")}
+
+    ds = M.NN_cond_pos_simpler(input_dim=5, output_dim=2, N_NEURONS=32, POSITIONAL_ENCODING_BASIS_NUM=5)
+    ds.load_state_dict(sd("chm_orange_rgb_disk/brdf_rectify_networkchm_orange_rgb"))
+    db = M.NN_cond_pretrain_disk_one(input_dim=2, N_NEURONS=16, POSITIONAL_ENCODING_BASIS_NUM=3)
+    db.load_state_dict(sd("chm_orange_rgb_disk/brdf_pretrain_networkchm_orange_rgb"))
     fw = M.to_flow_weights(db, ds, W.DOMAIN_DISK)
     ship = W.load(W.shipped_path("chm_orange_rgb", "disk"))
     for k in ("w_in", "w_hidden", "w_out", "base_w1", "base_b1", "base_w2", "base_b2"):
         assert np.array_equal(getattr(fw, k), getattr(ship, k)), k
-    dsp = ref.NN_cond_pos(input_dim=6, output_dim=2, N_NEURONS=32, POSITIONAL_ENCODING_BASIS_NUM=5)
-    dsp.load_state_dict(torch.load(f"{ck}/bsdf_3_spherical/brdf_rectify_network3.pth", map_location="cpu"))
-    dbp = ref.NN_cond_pretrain_spherical_one(input_dim=2, N_NEURONS=16)
-    dbp.load_state_dict(torch.load(f"{ck}/bsdf_3_spherical/brdf_pretrain_network3.pth", map_location="cpu"))
+    dsp = M.NN_cond_pos(input_dim=6, output_dim=2, N_NEURONS=32, POSITIONAL_ENCODING_BASIS_NUM=5)
+    dsp.load_state_dict(sd("bsdf_3_spherical/brdf_rectify_network3"))
+    dbp = M.NN_cond_pretrain_spherical_one(input_dim=2, N_NEURONS=16)
+    dbp.load_state_dict(sd("bsdf_3_spherical/brdf_pretrain_network3"))
     fws = M.to_flow_weights(dbp, dsp, W.DOMAIN_SPHERICAL)
     ships = W.load(W.shipped_path("bsdf_3", "spherical"))
     assert np.array_equal(fws.w_hidden, ships.w_hidden) and np.array_equal(fws.base_w1, ships.base_w1)
-    assert not os.path.exists("/root/reference/rendering/utils/__pycache__")
 
 
 def test_mitsuba_adapter_fails_loudly_without_mitsuba():
@@ -365,6 +362,39 @@ def test_bench_self_launch_fails_loudly_without_gpus():
                         "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode != 0
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_bench_dump_outputs_caps_the_bytes_with_one_seeded_row_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 .npy files of the last pass's arrays; over the cap, the same seeded rows of every array
+    (indices in rows.npy) and never more than the cap in all."""
+    import bench
+
+    class Wl:
+        def __init__(self, n):
+            g = torch.Generator().manual_seed(3)
+            self.out = {"wo": torch.randn(n, 3, generator=g), "sample_pdf": torch.rand(n, generator=g), "pdf": torch.rand(n, generator=g)}
+
+        def outputs(self):
+            return self.out
+
+    wl = Wl(1000)
+    d = bench.dump_outputs(wl, str(tmp_path / "all"))
+    assert d["rows"] == "all" and not (tmp_path / "all" / "rows.npy").exists()
+    for k, t in wl.out.items():
+        x = np.load(tmp_path / "all" / (k + ".npy"))
+        assert x.dtype == np.float32 and np.array_equal(x, t.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 10000)
+    for sub in ("s1", "s2"):
+        bench.dump_outputs(wl, str(tmp_path / sub))
+    rows = np.load(tmp_path / "s1" / "rows.npy")
+    assert rows.dtype == np.float64 and np.array_equal(rows, np.load(tmp_path / "s2" / "rows.npy"))
+    assert len(rows) == 10000 // (4 * 5 + 8) and np.all(np.diff(rows) > 0)
+    total = rows.nbytes
+    for k, t in wl.out.items():
+        x = np.load(tmp_path / "s1" / (k + ".npy"))
+        assert np.array_equal(x, t.numpy()[rows.astype(np.int64)])
+        total += x.nbytes
+    assert total <= 10000
 
 
 def test_torch_operator_library_registers_every_operator():

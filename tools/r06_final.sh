@@ -5,7 +5,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 cd $REPO
 O=gpurun_out/r06; mkdir -p $O
 bash tools/r06_tests.sh
-timeout 900 python3 bench.py > $O/bench_line.json 2> $O/bench_line.err
+timeout 900 python3 bench.py --full > $O/bench_line.json 2> $O/bench_line.err
 echo "bench rc=$?"; cut -c1-300 $O/bench_line.json
 timeout 900 python3 tools/plugin_parity_sweep.py --out $O/plugin_parity_77sets_final.json > $O/parity_final.log 2>&1
 echo "sweep rc=$?"
