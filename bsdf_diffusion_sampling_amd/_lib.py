@@ -17,9 +17,9 @@ SRC_PATH = os.path.join(_HERE, "csrc", "bsdfd.hip")
 SRC32_PATH = os.path.join(_HERE, "csrc", "flow32.hip")   # the 32-query-tile flow kernels
 SRC_PATHS = [SRC_PATH, SRC32_PATH, os.path.join(_HERE, "csrc", "wavefront.hip"), os.path.join(_HERE, "csrc", "encoding.hip"),
              os.path.join(_HERE, "csrc", "measured.hip"), os.path.join(_HERE, "csrc", "bucket.hip"),
-             os.path.join(_HERE, "csrc", "clock.hip")]  # translation units of libbsdfd.so
+             os.path.join(_HERE, "csrc", "bucket_wide.hip"), os.path.join(_HERE, "csrc", "clock.hip")]  # translation units of libbsdfd.so
 FLOW_TUS = (SRC_PATH, SRC32_PATH)   # ... whose device assembly the build verifies (_asmcheck)
-DEP_PATHS = SRC_PATHS + [os.path.join(_HERE, "csrc", f) for f in ("common.h", "flow_dev.h", "flow32.h")]
+DEP_PATHS = SRC_PATHS + [os.path.join(_HERE, "csrc", f) for f in ("common.h", "flow_dev.h", "flow32.h", "bucket_scan.h")]
 INCLUDE_DIR = os.path.join(ROOT, "include")
 ASM_CACHE_DIR = os.path.join(ROOT, "build", "asm")   # device assembly of the last product build (bsdfd.s, flow32.s)
 
@@ -37,13 +37,14 @@ EXPORTS = (
     "bsdfd_plugin_pdf_multi_ex", "bsdfd_plugin_sample_pdf_multi_ex",
     "bsdfd_flow_samples_only", "bsdfd_wf_primary", "bsdfd_wf_shade",
     "bsdfd_positional_encoding", "bsdfd_bucket_workspace_bytes", "bsdfd_bucket_by_material",
+    "bsdfd_bucket_wide_workspace_bytes", "bsdfd_bucket_by_material_wide",
     "bsdfd_gather_lanes", "bsdfd_scatter_lanes",
     "bsdfd_measured_create_from_file", "bsdfd_measured_destroy", "bsdfd_measured_get_info", "bsdfd_measured_eval",
     "bsdfd_measured_sample_weight",
     "bsdfd_set_profiling", "bsdfd_profile_read", "bsdfd_profile_read_op", "bsdfd_profile_clock_mhz", "bsdfd_last_kernel_ms", "bsdfd_shader_clock_mhz",
     "bsdfd_last_error", "bsdfd_version", "bsdfd_abi_version",
 )
-ABI_VERSION = 6   # BSDFD_ABI_VERSION of include/bsdfd.h these ctypes structs mirror (checked against the library in lib())
+ABI_VERSION = 7   # BSDFD_ABI_VERSION of include/bsdfd.h these ctypes structs mirror (checked against the library in lib())
 
 
 class WfScene(C.Structure):
@@ -398,6 +399,9 @@ def lib():
     L.bsdfd_bucket_workspace_bytes.argtypes = [i64, i32]
     L.bsdfd_bucket_workspace_bytes.restype = i64
     L.bsdfd_bucket_by_material.argtypes = [fp, i64, i32, fp, fp, fp, i64, vp]
+    L.bsdfd_bucket_wide_workspace_bytes.argtypes = [i64, i32]
+    L.bsdfd_bucket_wide_workspace_bytes.restype = i64
+    L.bsdfd_bucket_by_material_wide.argtypes = [fp, i64, i32, fp, fp, fp, i64, vp]
     L.bsdfd_gather_lanes.argtypes = [fp, i64, fp, fp, vp]
     L.bsdfd_scatter_lanes.argtypes = [fp, i64, fp, fp, fp, fp, fp, fp, vp]
     L.bsdfd_set_profiling.argtypes = [vp, i32]

@@ -35,27 +35,49 @@ def shard_sizes(n: int, world: int) -> List[int]:
     return [shard_range(n, r, world)[1] - shard_range(n, r, world)[0] for r in range(world)]
 
 
+# Widest table the dispatcher below sends to the native sort: the largest width at which it was measured faster than
+# torch.argsort + torch.bincount at both 1 Mi and 16 Mi ids (profiles/bucket_wide.json, tools/bucket_bench.py).
+NATIVE_MAX_MATERIALS = 65536
+_NARROW_MAX_MATERIALS = 64     # bsdfd_bucket_by_material (one counting pass); wider tables take the radix passes
+_WIDE_MAX_MATERIALS = 65536    # bsdfd_bucket_by_material_wide
+
+
+def bucket_by_material_native(material_id: torch.Tensor, n_materials: int):
+    """The native stable sort by material id, never the torch one: ``bsdfd_bucket_by_material`` (csrc/bucket.hip) up to 64
+    materials, ``bsdfd_bucket_by_material_wide`` (csrc/bucket_wide.hip, one counting pass per 6-bit digit) up to 65536.
+    Returns (perm, counts) on the ids' device; rows whose id is outside [0, n_materials) are left out of ``perm``
+    (``counts`` then sum to less than N and the tail of ``perm`` is unspecified).  Enqueued on the current stream."""
+    if not material_id.is_cuda:
+        raise ValueError("bucket_by_material_native needs a CUDA tensor (bucket_by_material serves CPU tensors with torch)")
+    if material_id.dim() != 1:
+        raise ValueError("material ids must be a 1-D tensor")
+    if not 1 <= n_materials <= _WIDE_MAX_MATERIALS:
+        raise ValueError(f"n_materials must be in [1, {_WIDE_MAX_MATERIALS}], got {n_materials}")
+    import ctypes as C
+    from . import _lib
+    ids = material_id.to(torch.int64).contiguous()
+    n = ids.shape[0]
+    L = _lib.lib()
+    size, sort = ((L.bsdfd_bucket_workspace_bytes, L.bsdfd_bucket_by_material) if n_materials <= _NARROW_MAX_MATERIALS
+                  else (L.bsdfd_bucket_wide_workspace_bytes, L.bsdfd_bucket_by_material_wide))
+    perm = torch.empty(n, dtype=torch.int64, device=ids.device)
+    counts = torch.empty(n_materials, dtype=torch.int64, device=ids.device)
+    ws = torch.empty(max(int(size(n, n_materials)), 1), dtype=torch.uint8, device=ids.device)
+    with torch.cuda.device(ids.device):
+        _lib.check(sort(C.c_void_p(ids.data_ptr()), n, n_materials, C.c_void_p(perm.data_ptr()), C.c_void_p(counts.data_ptr()),
+                        C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(torch.cuda.current_stream(ids.device).cuda_stream)))
+    return perm, counts
+
+
 def bucket_by_material(material_id: torch.Tensor, n_materials: int):
     """Config 4 (mixed-material batches): stable sort of queries by material id.
     Returns (perm, counts): ``perm`` gathers queries into contiguous per-material runs,
     ``counts[m]`` is the run length — one kernel launch per non-empty run.
-    CUDA tensors with <= 64 materials go through the native stable counting sort
-    (``bsdfd_bucket_by_material``, csrc/bucket.hip: 0.3 ms for 16 Mi ids vs 1.7 ms for torch.argsort);
-    CPU tensors (the gloo tests) use torch."""
-    if material_id.is_cuda and n_materials <= 64:
-        import ctypes as C
-        from . import _lib
-        ids = material_id.contiguous()
-        n = ids.shape[0]
-        L = _lib.lib()
-        perm = torch.empty(n, dtype=torch.int64, device=ids.device)
-        counts = torch.empty(n_materials, dtype=torch.int64, device=ids.device)
-        ws = torch.empty(max(int(L.bsdfd_bucket_workspace_bytes(n, n_materials)), 1), dtype=torch.uint8, device=ids.device)
-        with torch.cuda.device(ids.device):
-            _lib.check(L.bsdfd_bucket_by_material(C.c_void_p(ids.data_ptr()), n, n_materials, C.c_void_p(perm.data_ptr()),
-                                                  C.c_void_p(counts.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
-                                                  C.c_void_p(torch.cuda.current_stream(ids.device).cuda_stream)))
-        return perm, counts
+    CUDA tensors with up to ``NATIVE_MAX_MATERIALS`` materials go through the native sort
+    (``bucket_by_material_native``; 16 Mi ids: 0.2 ms over <= 64 materials, 0.6 ms over 79, 0.9 ms over 65536, against
+    1.7 - 2.3 ms for torch.argsort — profiles/bucket_wide.json); CPU tensors (the gloo tests) and wider tables use torch."""
+    if material_id.is_cuda and n_materials <= NATIVE_MAX_MATERIALS:
+        return bucket_by_material_native(material_id, n_materials)
     perm = torch.argsort(material_id, stable=True)
     counts = torch.bincount(material_id, minlength=n_materials)
     return perm, counts

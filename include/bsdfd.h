@@ -33,8 +33,9 @@ extern "C" {
  * field always selects the behaviour of the version that did not have it.  A host checks bsdfd_abi_version() ==
  * BSDFD_ABI_VERSION once after loading the library (the Python hosts do: _lib.lib()).
  *   5: bsdfd_desc.reserved became bsdfd_desc.tile (values other than 0 / 16 / 32 are rejected, 0 = library default).
- *   6: bsdfd_opts.row_index appended; bsdfd_abi_version() added. */
-#define BSDFD_ABI_VERSION 6
+ *   6: bsdfd_opts.row_index appended; bsdfd_abi_version() added.
+ *   7: bsdfd_bucket_wide_workspace_bytes() and bsdfd_bucket_by_material_wide() added. */
+#define BSDFD_ABI_VERSION 7
 
 #define BSDFD_OK 0
 #define BSDFD_EINVAL 1   /* bad argument / unsupported architecture */
@@ -294,6 +295,18 @@ int bsdfd_positional_encoding(const float* x, int64_t N, int32_t dim, int32_t ba
 int64_t bsdfd_bucket_workspace_bytes(int64_t N, int32_t n_materials);
 int bsdfd_bucket_by_material(const int64_t* material_id, int64_t N, int32_t n_materials, int64_t* perm,
                              int64_t* counts, void* workspace, int64_t workspace_bytes, void* hip_stream);
+
+/* The same sort for 1 <= n_materials <= 65536 (ABI 7): what the reference scene spells as one `mybsdf` instance per
+ * material, each lane dispatched to its instance by Mitsuba, for scenes with more than 64 of them.  Same contract as
+ * bsdfd_bucket_by_material: perm [N] in torch.argsort(stable=True) order, counts [n_materials] on the device; a lane whose
+ * id — the full 64-bit value — is outside [0, n_materials) is left out, the kept lanes fill perm[0 .. sum(counts)) and the
+ * rest of perm is unspecified.  One stable counting pass per 6-bit digit of the id (two passes up to 4096 materials, three
+ * above).  Deterministic, independent of what `workspace` (device scratch of bsdfd_bucket_wide_workspace_bytes(), 8-byte
+ * aligned) held before; allocates nothing and does not synchronise: everything is enqueued on hip_stream.  N == 0 only
+ * zeroes counts.  bsdfd_bucket_wide_workspace_bytes() returns 0 for N < 0 or n_materials outside [1, 65536]. */
+int64_t bsdfd_bucket_wide_workspace_bytes(int64_t N, int32_t n_materials);
+int bsdfd_bucket_by_material_wide(const int64_t* material_id, int64_t N, int32_t n_materials, int64_t* perm,
+                                  int64_t* counts, void* workspace, int64_t workspace_bytes, void* hip_stream);
 
 /* Bucket order <-> lane order around a run of bucketed calls (a renderer keeps a wavefront in bucket order across its
  * sample() and pdf() calls): wi_b[i] = wi[perm[i]] for the first n entries of perm (the lanes that carry a material), and
