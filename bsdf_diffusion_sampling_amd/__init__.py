@@ -8,6 +8,7 @@ Modules (everything below the tensors runs in libbsdfd.so, include/bsdfd.h; no C
   sampler             FlowSampler: the ctypes host of the fused flow kernels
   model, weights      reference-named weight containers, the neutral .bsdfw weight format
   materials           MaterialTable: material-tagged wavefronts (bucketing + segmented launches)
+  live                live_rows: an ``active`` mask -> the row list the flow kernels run on (csrc/live.hip)
   measured            MeasuredBSDF: the ground-truth evaluator behind eval() (RGL tensor files)
   encoding            positional_encoding_1 as a stand-alone pass
   wavefront           WavefrontRenderer / ArrayRenderer: the render loop around the plugin calls

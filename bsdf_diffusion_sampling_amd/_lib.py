@@ -17,7 +17,8 @@ SRC_PATH = os.path.join(_HERE, "csrc", "bsdfd.hip")
 SRC32_PATH = os.path.join(_HERE, "csrc", "flow32.hip")   # the 32-query-tile flow kernels
 SRC_PATHS = [SRC_PATH, SRC32_PATH, os.path.join(_HERE, "csrc", "wavefront.hip"), os.path.join(_HERE, "csrc", "encoding.hip"),
              os.path.join(_HERE, "csrc", "measured.hip"), os.path.join(_HERE, "csrc", "bucket.hip"),
-             os.path.join(_HERE, "csrc", "bucket_wide.hip"), os.path.join(_HERE, "csrc", "clock.hip")]  # translation units of libbsdfd.so
+             os.path.join(_HERE, "csrc", "bucket_wide.hip"), os.path.join(_HERE, "csrc", "live.hip"),
+             os.path.join(_HERE, "csrc", "clock.hip")]  # translation units of libbsdfd.so
 FLOW_TUS = (SRC_PATH, SRC32_PATH)   # ... whose device assembly the build verifies (_asmcheck)
 DEP_PATHS = SRC_PATHS + [os.path.join(_HERE, "csrc", f) for f in ("common.h", "flow_dev.h", "flow32.h", "bucket_scan.h")]
 INCLUDE_DIR = os.path.join(ROOT, "include")
@@ -26,6 +27,7 @@ ASM_CACHE_DIR = os.path.join(ROOT, "build", "asm")   # device assembly of the la
 PREC_DEFAULT, PREC_F32, PREC_SPLIT3, PREC_F16 = 0, 1, 2, 3
 PRECISIONS = {"default": PREC_DEFAULT, "f32": PREC_F32, "split3": PREC_SPLIT3, "f16": PREC_F16}
 PLUGIN_MEASURED, PLUGIN_FULLSPHERE = 0, 1
+LIVE_WI_UPPER, LIVE_DIR_UPPER = 1, 2   # BSDFD_LIVE_*: hemisphere tests of bsdfd_compact_live
 
 # every symbol include/bsdfd.h declares
 EXPORTS = (
@@ -34,17 +36,17 @@ EXPORTS = (
     "bsdfd_plugin_sample", "bsdfd_plugin_pdf", "bsdfd_plugin_sample_pdf", "bsdfd_plugin_sample_multi", "bsdfd_plugin_pdf_multi",
     "bsdfd_plugin_sample_pdf_multi",
     "bsdfd_context_bytes", "bsdfd_plugin_sample_ex", "bsdfd_plugin_pdf_ex", "bsdfd_plugin_sample_multi_ex",
-    "bsdfd_plugin_pdf_multi_ex", "bsdfd_plugin_sample_pdf_multi_ex",
+    "bsdfd_plugin_pdf_multi_ex", "bsdfd_plugin_sample_pdf_multi_ex", "bsdfd_plugin_sample_pdf_ex",
     "bsdfd_flow_samples_only", "bsdfd_wf_primary", "bsdfd_wf_shade",
     "bsdfd_positional_encoding", "bsdfd_bucket_workspace_bytes", "bsdfd_bucket_by_material",
     "bsdfd_bucket_wide_workspace_bytes", "bsdfd_bucket_by_material_wide",
-    "bsdfd_gather_lanes", "bsdfd_scatter_lanes",
+    "bsdfd_gather_lanes", "bsdfd_scatter_lanes", "bsdfd_live_workspace_bytes", "bsdfd_compact_live",
     "bsdfd_measured_create_from_file", "bsdfd_measured_destroy", "bsdfd_measured_get_info", "bsdfd_measured_eval",
     "bsdfd_measured_sample_weight",
     "bsdfd_set_profiling", "bsdfd_profile_read", "bsdfd_profile_read_op", "bsdfd_profile_clock_mhz", "bsdfd_last_kernel_ms", "bsdfd_shader_clock_mhz",
     "bsdfd_last_error", "bsdfd_version", "bsdfd_abi_version",
 )
-ABI_VERSION = 7   # BSDFD_ABI_VERSION of include/bsdfd.h these ctypes structs mirror (checked against the library in lib())
+ABI_VERSION = 8   # BSDFD_ABI_VERSION of include/bsdfd.h these ctypes structs mirror (checked against the library in lib())
 
 
 class WfScene(C.Structure):
@@ -386,6 +388,7 @@ def lib():
     L.bsdfd_plugin_sample_multi_ex.argtypes = [C.POINTER(vp), i32, C.POINTER(i64), i32, fp, fp, u64, u64, i32, fp, fp, op, vp]
     L.bsdfd_plugin_pdf_multi_ex.argtypes = [C.POINTER(vp), i32, C.POINTER(i64), i32, fp, fp, i32, fp, op, vp]
     L.bsdfd_plugin_sample_pdf_multi_ex.argtypes = [C.POINTER(vp), i32, C.POINTER(i64), i32, fp, fp, fp, u64, u64, i32, fp, fp, fp, op, vp]
+    L.bsdfd_plugin_sample_pdf_ex.argtypes = [vp, i32, fp, fp, fp, u64, u64, i64, i32, fp, fp, fp, op, vp]
     L.bsdfd_flow_samples_only.argtypes = [vp, fp, fp, i64, i32, fp, vp]
     L.bsdfd_wf_primary.argtypes = [C.POINTER(WfScene), i32, i32, i32, u64, u64, fp, fp, fp, fp, fp, vp]
     L.bsdfd_wf_shade.argtypes = [C.POINTER(WfScene), fp, i32, i32, i32, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp]
@@ -402,6 +405,9 @@ def lib():
     L.bsdfd_bucket_wide_workspace_bytes.argtypes = [i64, i32]
     L.bsdfd_bucket_wide_workspace_bytes.restype = i64
     L.bsdfd_bucket_by_material_wide.argtypes = [fp, i64, i32, fp, fp, fp, i64, vp]
+    L.bsdfd_live_workspace_bytes.argtypes = [i64]
+    L.bsdfd_live_workspace_bytes.restype = i64
+    L.bsdfd_compact_live.argtypes = [fp, fp, fp, i32, i64, fp, fp, fp, fp, fp, vp, i64, vp]
     L.bsdfd_gather_lanes.argtypes = [fp, i64, fp, fp, vp]
     L.bsdfd_scatter_lanes.argtypes = [fp, i64, fp, fp, fp, fp, fp, fp, vp]
     L.bsdfd_set_profiling.argtypes = [vp, i32]

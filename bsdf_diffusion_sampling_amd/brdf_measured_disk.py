@@ -38,7 +38,7 @@ class MyBSDF(NeuralBSDFCore):
 
     def sample(self, ctx, si, sample1=None, sample2=None, active=True, *, x0=None, seed=None):
         wi = _wi_of(si)
-        wo, pdf_sa = self.sample_t(wi, x0=x0, seed=seed)
+        wo, pdf_sa = self.sample_t(wi, x0=x0, seed=seed, active=self._mask(active, wi))
         bs = BSDFSample3f(wo=wo, pdf=pdf_sa, eta=1.0, sampled_type=self.m_flags, sampled_component=0)
         if self.bsdf is None:  # no ground-truth evaluator: the sampler-only use (bench / harness)
             return bs, None

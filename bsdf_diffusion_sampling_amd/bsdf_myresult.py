@@ -41,7 +41,7 @@ class MyBSDF(NeuralBSDFCore):
 
     def sample(self, ctx, si, sample1=None, sample2=None, active=True, *, x0=None, seed=None):
         wi = _wi_of(si)
-        wo, pdf_sa = self.sample_t(wi, x0=x0, seed=seed)
+        wo, pdf_sa = self.sample_t(wi, x0=x0, seed=seed, active=self._mask(active, wi))
         up = wo[:, 2] > 0
         bs = BSDFSample3f(wo=wo, pdf=pdf_sa, eta=torch.where(up, 1.0, 1.788),
                           sampled_type=torch.where(up, FLAG_DIFFUSE_REFLECTION, FLAG_DIFFUSE_TRANSMISSION),

@@ -286,6 +286,30 @@ void plugin_pdf_ex_out(int64_t h, int64_t variant, const Tensor& wi, const Tenso
                            pdf.data_ptr<float>(), &o, L.stream));
 }
 
+// the fused sample+pdf call with optional arguments (bsdfd_plugin_sample_pdf_ex, ABI 8: rng_index / row_index, no context)
+void plugin_sample_pdf_ex_out(int64_t h, int64_t variant, const Tensor& wi, const Tensor& wl, const std::optional<Tensor>& x0,
+                              int64_t seed, int64_t offset, int64_t T, Tensor wo, Tensor pdf_o, Tensor pdf_l,
+                              const std::optional<Tensor>& rng_index, const std::optional<Tensor>& row_index) {
+    const at::Device dev = wi.device();
+    const float* wip = in2d(wi, 3, "wi", dev);
+    const int64_t m = wi.size(0);
+    bsdfd_opts o{};
+    o.row_index = index_ptr(row_index, "row_index", dev);
+    const int64_t n = row_index.has_value() ? row_index->size(0) : m;
+    TORCH_CHECK(n <= m, "row_index names ", n, " rows, wi has ", m);
+    const float* wlp = in2d(wl, 3, "wl", dev, m);
+    const float* x0p = opt2d(x0, 2, "x0", dev, m);
+    in2d(wo, 3, "wo (out)", dev, m);
+    for (const Tensor* p : {&pdf_o, &pdf_l})
+        TORCH_CHECK(p->device() == dev && p->scalar_type() == at::kFloat && p->dim() == 1 && p->size(0) == m && p->is_contiguous(),
+                    "pdf (out) must be a contiguous float32 tensor of shape [", m, "] on ", dev);
+    o.rng_index = index_ptr(rng_index, "rng_index", dev, n);
+    Launch L(dev);
+    ok(bsdfd_plugin_sample_pdf_ex(as_handle(h), static_cast<int32_t>(variant), wip, x0p, wlp, static_cast<uint64_t>(seed),
+                                  static_cast<uint64_t>(offset), n, static_cast<int32_t>(T), wo.data_ptr<float>(),
+                                  pdf_o.data_ptr<float>(), pdf_l.data_ptr<float>(), &o, L.stream));
+}
+
 }  // namespace
 
 TORCH_LIBRARY(bsdfd, m) {
@@ -309,4 +333,7 @@ TORCH_LIBRARY(bsdfd, m) {
           "Tensor(b!) pdf, Tensor(c!)? ctx, Tensor? rng_index, bool ctx_read=False, Tensor? row_index=None) -> ()", &plugin_sample_ex_out);
     m.def("plugin_pdf_ex_out(int handle, int variant, Tensor wi, Tensor wo, int T, Tensor(a!) pdf, Tensor(b!)? ctx, bool ctx_write=False, "
           "Tensor? row_index=None) -> ()", &plugin_pdf_ex_out);
+    m.def("plugin_sample_pdf_ex_out(int handle, int variant, Tensor wi, Tensor wl, Tensor? x0, int seed, int offset, int T, "
+          "Tensor(a!) wo, Tensor(b!) pdf_o, Tensor(c!) pdf_l, Tensor? rng_index=None, Tensor? row_index=None) -> ()",
+          &plugin_sample_pdf_ex_out);
 }

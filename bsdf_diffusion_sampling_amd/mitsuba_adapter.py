@@ -76,6 +76,10 @@ def make_bsdf_class(domain: str = "disk", variant: str = "llvm_ad_rgb"):
         c = t.detach().to("cpu", torch.float32)
         return mi.Vector3f(c[:, 0], c[:, 1], c[:, 2])
 
+    def to_mask(active):
+        """Mitsuba's `active` (True or a DrJit mask) for the cores: they run the flow on the live lanes only."""
+        return True if active is True else active.torch().to(dev) if hasattr(active, "torch") else torch.as_tensor(active, device=dev)
+
     def to_mi_scalar(v, ctor):
         return ctor(v.detach().cpu()) if isinstance(v, torch.Tensor) else v
 
@@ -98,7 +102,7 @@ def make_bsdf_class(domain: str = "disk", variant: str = "llvm_ad_rgb"):
 
         def sample(self, ctx, si, sample1, sample2, active=True):
             self.gt.bind(ctx, si)
-            bs_t, weight = self.core.sample(ctx, SurfaceInteraction(to_dev(si.wi)))
+            bs_t, weight = self.core.sample(ctx, SurfaceInteraction(to_dev(si.wi)), active=to_mask(active))
             bs = mi.BSDFSample3f()
             bs.wo = to_vec3(bs_t.wo)
             bs.pdf = mi.Float(bs_t.pdf.detach().cpu())
@@ -113,7 +117,7 @@ def make_bsdf_class(domain: str = "disk", variant: str = "llvm_ad_rgb"):
             return to_vec3(self.core.eval(ctx, SurfaceInteraction(to_dev(si.wi)), to_dev(wo)))
 
         def pdf(self, ctx, si, wo, active=True):
-            return mi.Float(self.core.pdf_t(to_dev(si.wi), to_dev(wo)).cpu())
+            return mi.Float(self.core.pdf(ctx, SurfaceInteraction(to_dev(si.wi)), to_dev(wo), active=to_mask(active)).cpu())
 
         def eval_pdf(self, ctx, si, wo, active=True):
             return self.eval(ctx, si, wo, active), self.pdf(ctx, si, wo, active)

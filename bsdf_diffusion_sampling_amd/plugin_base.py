@@ -112,6 +112,11 @@ class NeuralBSDFCore:
         # `context_cache_patience` fills in a row that nobody read, filling stops (it costs ~1 % of a launch) and is retried
         # once every 64 calls
         self.context_cache_patience = int(get("context_cache_patience", 4))
+        # props["compact_active"] (default True): an `active` mask handed to sample() / pdf() / eval_pdf() reaches the flow
+        # kernels, which then run on the live lanes only (FlowSampler.plugin_*(active=): one compaction pass + one read-back of
+        # the live count per call; live lanes get the bits of the unmasked call, dead lanes 0).  False: the flow runs on every
+        # lane and the mask reaches only the weight pass of sample(), as before the option existed.
+        self.compact_active = bool(get("compact_active", True))
         self._ctx_unread_fills = 0
         self._ctx_skipped = 0
 
@@ -142,17 +147,23 @@ class NeuralBSDFCore:
 
     # -- tensor core -------------------------------------------------------
     def sample_t(self, wi: torch.Tensor, x0: Optional[torch.Tensor] = None, seed: Optional[int] = None,
-                 offset: int = 0):
+                 offset: int = 0, active: Optional[torch.Tensor] = None):
         """wi [N,3] -> (wo [N,3], pdf_sa [N]) with the warp and guards of sample() fused;
-        the firefly rule is separate (``apply_firefly_clamp``) because it needs eval()."""
+        the firefly rule is separate (``apply_firefly_clamp``) because it needs eval().
+        ``active`` (bool / uint8 [N]): evaluate the lanes it selects only, 0 elsewhere (bypasses the per-query context cache:
+        a context is indexed by the rows of the call that wrote it)."""
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
+        if active is not None:
+            return self.sampler.plugin_sample(wi, x0, T=self.T, variant=self.VARIANT, seed=seed, offset=offset, active=active)
         cin, cout, key = self._ctx_lookup(wi)
         res = self.sampler.plugin_sample(wi, x0, T=self.T, variant=self.VARIANT, seed=seed, offset=offset, ctx_out=cout, ctx_in=cin)
         self._ctx_done(wi, key, cin, cout)
         return res
 
-    def pdf_t(self, wi: torch.Tensor, wo: torch.Tensor) -> torch.Tensor:
+    def pdf_t(self, wi: torch.Tensor, wo: torch.Tensor, active: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if active is not None:
+            return self.sampler.plugin_pdf(wi, wo, T=self.T, variant=self.VARIANT, active=active)
         cin, cout, key = self._ctx_lookup(wi)
         res = self.sampler.plugin_pdf(wi, wo, T=self.T, variant=self.VARIANT, ctx_in=cin, ctx_out=cout)
         self._ctx_done(wi, key, cin, cout)
@@ -221,12 +232,24 @@ class NeuralBSDFCore:
         self._ctx = None
 
     def sample_pdf_t(self, wi: torch.Tensor, wl: torch.Tensor, x0: Optional[torch.Tensor] = None,
-                     seed: Optional[int] = None, offset: int = 0):
+                     seed: Optional[int] = None, offset: int = 0, active: Optional[torch.Tensor] = None):
         """``sample_t(wi)`` and ``pdf_t(wi, wl)`` of the same intersections in one launch (a renderer with
-        next-event estimation asks both per path): -> (wo [N,3], pdf(wo) [N], pdf(wl) [N])."""
+        next-event estimation asks both per path): -> (wo [N,3], pdf(wo) [N], pdf(wl) [N]).  ``active``: as in ``sample_t``."""
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
-        return self.sampler.plugin_sample_pdf(wi, wl, x0, T=self.T, variant=self.VARIANT, seed=seed, offset=offset)
+        return self.sampler.plugin_sample_pdf(wi, wl, x0, T=self.T, variant=self.VARIANT, seed=seed, offset=offset, active=active)
+
+    def _mask(self, active, wi: torch.Tensor) -> Optional[torch.Tensor]:
+        """The ``active`` argument of a protocol method as the [N] device mask the tensor core takes, or None: ``active is
+        True`` (Mitsuba's default) or ``props["compact_active"] = False``."""
+        if active is True or active is None or not self.compact_active:
+            return None
+        if not isinstance(active, torch.Tensor):
+            active = active.torch() if hasattr(active, "torch") else torch.as_tensor(active)
+        active = active.to(wi.device)
+        if active.dtype not in (torch.bool, torch.uint8):
+            active = active != 0
+        return active.expand(wi.shape[0]).contiguous() if active.dim() == 0 else active.contiguous()
 
     @staticmethod
     def apply_firefly_clamp(pdf: torch.Tensor, weight_lum: torch.Tensor, thr: float) -> torch.Tensor:
@@ -254,7 +277,8 @@ class NeuralBSDFCore:
         return torch.where(ok[:, None], value, torch.zeros_like(value))
 
     def pdf(self, ctx, si, wo, active=True):
-        return self.pdf_t(_wi_of(si), _vec(wo))
+        wi = _wi_of(si)
+        return self.pdf_t(wi, _vec(wo), active=self._mask(active, wi))
 
     def eval_pdf(self, ctx, si, wo, active=True):
         return self.eval(ctx, si, wo, active), self.pdf(ctx, si, wo, active)

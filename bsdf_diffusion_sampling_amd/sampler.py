@@ -242,7 +242,8 @@ class FlowSampler:
     def plugin_sample(self, wi, x0=None, T: int = 4, variant: int = _lib.PLUGIN_MEASURED, seed: int = 0,
                       offset: int = 0, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                       ctx_out: Optional[torch.Tensor] = None, rng_index: Optional[torch.Tensor] = None,
-                      ctx_in: Optional[torch.Tensor] = None, row_index: Optional[torch.Tensor] = None):
+                      ctx_in: Optional[torch.Tensor] = None, row_index: Optional[torch.Tensor] = None,
+                      active: Optional[torch.Tensor] = None):
         """``ctx_out`` (``new_context(N)``): also write the per-query context a later ``plugin_pdf(wi, ., ctx_in=)`` /
         ``plugin_sample(wi, ctx_in=)`` for the SAME ``wi`` reads instead of recomputing the prologue (identical results);
         ``ctx_in``: read the context an earlier call (``plugin_pdf(..., ctx_out=)`` or ``plugin_sample(..., ctx_out=)``) wrote
@@ -252,7 +253,25 @@ class FlowSampler:
         ``row_index`` (int64 [n], n <= N, distinct entries < N): the call processes n rows; row i reads ``wi`` / ``x0`` at row
         ``row_index[i]`` and writes ``wo`` / ``pdf`` there (bsdfd_opts.row_index: the gather / scatter of a bucketed wavefront
         inside the kernel's own loads and stores); rows it does not name are left as they are (zeros when ``out`` is None).
-        Its Philox counter is ``offset + row_index[i]`` unless ``rng_index`` is given."""
+        Its Philox counter is ``offset + row_index[i]`` unless ``rng_index`` is given.
+        ``active`` (bool / uint8 [N]): the ``active`` mask of the plugin protocol (rendering/brdf_measured_disk.py:59) — the flow
+        runs on the lanes it selects only (``live.live_rows``, then the ``row_index`` path: the live rows get exactly the bits
+        of the unmasked call), the dead rows of ``wo`` / ``pdf`` are 0, also in ``out=`` buffers.  One read-back of the live
+        count per call.  Not together with ``row_index``, ``rng_index`` or a context (those are indexed by the call's own rows:
+        whoever wants both passes ``row_index`` themselves)."""
+        if active is not None:
+            self._no_index_with_active(row_index, rng_index, ctx_in, ctx_out)
+            wi, m = self._chk_wi(wi)
+            if out is None:
+                out = (torch.empty((m, 3), dtype=torch.float32, device=self.device),
+                       torch.empty((m,), dtype=torch.float32, device=self.device))
+            else:
+                out = (self._chk(out[0], 3, "out wo", m), self._chk1(out[1], m, "out pdf"))
+            rows = self._live_rows(active, m, zero=(out[0], out[1], None))
+            if rows.shape[0] == 0:
+                return out
+            if rows.shape[0] < m:
+                return self._plugin_sample_ex(wi, x0, T, variant, seed, offset, out, None, None, row_index=rows)
         if ctx_out is not None and ctx_in is not None:
             raise RuntimeError("a call either writes a per-query context (ctx_out) or reads one (ctx_in), not both")
         if ctx_out is not None or ctx_in is not None or rng_index is not None or row_index is not None:
@@ -300,6 +319,30 @@ class FlowSampler:
                 raise RuntimeError("row_index names a row more than once")
         return m if row_index is None else row_index.shape[0]
 
+    # ---- `active` masks (live.py, csrc/live.hip) ----
+    @staticmethod
+    def _no_index_with_active(row_index, rng_index, ctx_in, ctx_out):
+        if row_index is not None or rng_index is not None or ctx_in is not None or ctx_out is not None:
+            raise ValueError("active= cannot be combined with row_index, rng_index or a per-query context: those are indexed by "
+                             "the call's own rows (compact the mask with live.live_rows and pass row_index instead)")
+
+    def _chk_wi(self, wi):
+        """(wi, rows) of a masked call: the mask is compacted before the launch that would check wi."""
+        if self._ops is not None:
+            self._dev_chk(wi, "wi")
+            if wi.dim() != 2:
+                raise RuntimeError(f"wi must have shape [N, 3], got {tuple(wi.shape)}")
+            return wi, wi.shape[0]
+        wi = self._chk(wi, 3, "wi")
+        return wi, wi.shape[0]
+
+    def _live_rows(self, active, m, wi=None, dir=None, flags=0, zero=(None, None, None)):
+        from .live import live_rows
+        if (not isinstance(active, torch.Tensor) or active.device != self.device or active.dtype not in (torch.bool, torch.uint8)
+                or active.dim() != 1 or active.shape[0] != m):
+            raise RuntimeError(f"active must be a bool / uint8 tensor of shape [{m}] on {self.device}")
+        return live_rows(active, wi, dir, flags, zero)
+
     def _plugin_sample_ex(self, wi, x0, T, variant, seed, offset, out, ctx, rng_index, ctx_read=False, row_index=None):
         mk = torch.empty if row_index is None else torch.zeros   # (rows a row_index does not name stay untouched)
         if self._ops is not None:
@@ -334,9 +377,58 @@ class FlowSampler:
         return wo, pdf
 
     def plugin_sample_pdf(self, wi, wl, x0=None, T: int = 4, variant: int = _lib.PLUGIN_MEASURED, seed: int = 0,
-                          offset: int = 0, out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None):
+                          offset: int = 0, out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None,
+                          rng_index: Optional[torch.Tensor] = None, row_index: Optional[torch.Tensor] = None,
+                          active: Optional[torch.Tensor] = None):
         """sample(wi) and pdf(wi, wl) of the same intersections in ONE launch (the per-query prologue is
-        shared): -> (wo [N,3], pdf(wo) [N], pdf(wl) [N]), identical to plugin_sample + plugin_pdf(wi, wl)."""
+        shared): -> (wo [N,3], pdf(wo) [N], pdf(wl) [N]), identical to plugin_sample + plugin_pdf(wi, wl).
+        ``rng_index`` / ``row_index`` / ``active``: as in ``plugin_sample`` (bsdfd_plugin_sample_pdf_ex; the fused call takes no
+        per-query context).  A masked call culls by the mask alone: ``wo`` / ``pdf(wo)`` are defined below the horizon too."""
+        if active is not None:
+            self._no_index_with_active(row_index, rng_index, None, None)
+            wi, m = self._chk_wi(wi)
+            if out is None:
+                out = (torch.empty((m, 3), dtype=torch.float32, device=self.device),
+                       torch.empty((m,), dtype=torch.float32, device=self.device),
+                       torch.empty((m,), dtype=torch.float32, device=self.device))
+            else:
+                out = (self._chk(out[0], 3, "out wo", m), self._chk1(out[1], m, "out pdf(wo)"), self._chk1(out[2], m, "out pdf(wl)"))
+            rows = self._live_rows(active, m, zero=out)
+            if rows.shape[0] == 0:
+                return out
+            if rows.shape[0] < m:
+                row_index = rows
+        if rng_index is not None or row_index is not None:
+            mk = torch.empty if row_index is None else torch.zeros   # (rows a row_index does not name stay untouched)
+            if self._ops is not None:
+                self._dev_chk(wi, "wi")
+                n = self._rows(row_index, wi.shape[0])
+                self._chk_index(rng_index, n)
+                if out is None:
+                    out = (mk((wi.shape[0], 3), dtype=torch.float32, device=self.device),
+                           mk((wi.shape[0],), dtype=torch.float32, device=self.device),
+                           mk((wi.shape[0],), dtype=torch.float32, device=self.device))
+                self._ops.plugin_sample_pdf_ex_out(self._hi, variant, wi, wl, x0, _i64(seed), _i64(offset), T, out[0], out[1], out[2],
+                                                   rng_index, row_index)
+                return out[0], out[1], out[2]
+            wi = self._chk(wi, 3, "wi")
+            m = wi.shape[0]
+            n = self._rows(row_index, m)
+            wl = self._chk(wl, 3, "wl", m)
+            x0 = self._chk(x0, 2, "x0", m)
+            self._chk_index(rng_index, n)
+            if out is None:
+                wo = mk((m, 3), dtype=torch.float32, device=self.device)
+                pdf_o = mk((m,), dtype=torch.float32, device=self.device)
+                pdf_l = mk((m,), dtype=torch.float32, device=self.device)
+            else:
+                wo, pdf_o, pdf_l = (self._chk(out[0], 3, "out wo", m), self._chk1(out[1], m, "out pdf(wo)"),
+                                    self._chk1(out[2], m, "out pdf(wl)"))
+            o = _lib.opts(rng_index=rng_index, row_index=row_index)
+            with torch.cuda.device(self.device):
+                _lib.check(self._L.bsdfd_plugin_sample_pdf_ex(self._h, variant, _ptr(wi), _ptr(x0), _ptr(wl), seed, offset, n, T,
+                                                              _ptr(wo), _ptr(pdf_o), _ptr(pdf_l), C.byref(o), self._stream()))
+            return wo, pdf_o, pdf_l
         if self._ops is not None and out is None:
             self._dev_chk(wi, "wi")
             return self._ops.plugin_sample_pdf(self._hi, variant, wi, wl, x0, _i64(seed), _i64(offset), T)
@@ -358,11 +450,27 @@ class FlowSampler:
 
     def plugin_pdf(self, wi, wo, T: int = 4, variant: int = _lib.PLUGIN_MEASURED,
                    out: Optional[torch.Tensor] = None, ctx_in: Optional[torch.Tensor] = None,
-                   ctx_out: Optional[torch.Tensor] = None, row_index: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   ctx_out: Optional[torch.Tensor] = None, row_index: Optional[torch.Tensor] = None,
+                   active: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``ctx_in``: the context an earlier ``plugin_sample`` / ``plugin_pdf`` call wrote (``ctx_out=``) for this very ``wi``
         array; ``ctx_out`` (``new_context(N)``): write it here (the call order of Mitsuba's path integrator: eval_pdf() for the
         emitter sample first, sample() second — rendering/brdf_measured_disk.py:126,59).  At most one of the two.
-        ``row_index``: as in ``plugin_sample`` (row i reads wi / wo at row ``row_index[i]`` and writes pdf there)."""
+        ``row_index``: as in ``plugin_sample`` (row i reads wi / wo at row ``row_index[i]`` and writes pdf there).
+        ``active``: as in ``plugin_sample`` (rendering/brdf_measured_disk.py:112).  For ``PLUGIN_MEASURED`` the lanes with
+        ``wi.z <= 0`` or ``wo.z <= 0`` are culled as well: their pdf is exactly 0 in the unmasked call too."""
+        if active is not None:
+            self._no_index_with_active(row_index, None, ctx_in, ctx_out)
+            wi, m = self._chk_wi(wi)
+            out = torch.empty((m,), dtype=torch.float32, device=self.device) if out is None else self._chk1(out, m, "out pdf")
+            if variant == _lib.PLUGIN_MEASURED:
+                rows = self._live_rows(active, m, wi=self._chk(wi, 3, "wi"), dir=self._chk(wo, 3, "wo", m),
+                                       flags=_lib.LIVE_WI_UPPER | _lib.LIVE_DIR_UPPER, zero=(None, out, None))
+            else:
+                rows = self._live_rows(active, m, zero=(None, out, None))
+            if rows.shape[0] == 0:
+                return out
+            if rows.shape[0] < m:
+                row_index = rows
         if ctx_out is not None and ctx_in is not None:
             raise RuntimeError("a call either writes a per-query context (ctx_out) or reads one (ctx_in), not both")
         if ctx_in is not None or ctx_out is not None or row_index is not None:

@@ -84,12 +84,16 @@ class WavefrontRenderer:
     """One material ball under an environment map, rendered in passes of ``spp`` samples per pixel.
 
     ``plugin`` is any of the ``MyBSDF`` mirrors (``sample_t`` / ``pdf_t``; its ``albedo`` tints the result).
+    ``skip_misses``: hand the sampler the mask "this path hit the ball" (``active=``; the primary kernel then also writes the
+    material ids it is built from), so that the flow runs on the hits only — a miss's sample / pdf is never read by the shade
+    kernel.  Same film bit for bit; one compaction pass and one read-back of the hit count per pass.  Off by default.
     """
 
     def __init__(self, plugin, camera: Optional[Camera] = None, env: Optional[torch.Tensor] = None,
                  sphere_center: Sequence[float] = (0.0, 0.0, 0.0), sphere_radius: float = 1.0,
-                 device: Optional[torch.device] = None, use_ground_truth: Optional[bool] = None):
+                 device: Optional[torch.device] = None, use_ground_truth: Optional[bool] = None, skip_misses: bool = False):
         self.plugin = plugin
+        self.skip_misses = bool(skip_misses)
         # shade with the ground-truth f (the plugin's native `measured` evaluator) when it is available,
         # else with the proxy f cos = albedo * pdf_net
         has_gt = hasattr(getattr(plugin, "bsdf", None), "eval_t")
@@ -124,7 +128,7 @@ class WavefrontRenderer:
             b = dict(wi=mk(n, 3), wl=mk(n, 3), nrm=mk(n, 3), dir=mk(n, 3), wo=mk(n, 3), pdf_o=mk(n), pdf_l=mk(n))
             if self.use_ground_truth:
                 b.update(f_o=mk(n, 3), f_l=mk(n, 3))
-            if self.needs_material_ids:
+            if self.needs_material_ids or self.skip_misses:
                 b["mat"] = torch.empty((n,), dtype=torch.int64, device=self.device)
             self._buf = {n: b}  # one tile shape at a time
         return b
@@ -171,10 +175,23 @@ class WavefrontRenderer:
         # sample(): Philox counter = global path index, key = (seed, pass) -> independent of the row split
         offset = row_begin * self.camera.width * spp
         skey = (seed * 0x9E3779B97F4A7C15 + pass_idx + 1) & 0xFFFFFFFFFFFFFFFF
+        hit = (b["mat"] == 0) if self.skip_misses else None       # ball 0 carries the material; 1 = floor (none here), 2 = miss
         if core.DOMAIN == W.DOMAIN_DISK:
             # one launch for sample(wi) and pdf(wi, wl): the per-intersection prologue is shared in registers
             core.sampler.plugin_sample_pdf(b["wi"], b["wl"], x0, T=core.T, variant=core.VARIANT, seed=skey, offset=offset,
-                                           out=(b["wo"], b["pdf_o"], b["pdf_l"]))
+                                           out=(b["wo"], b["pdf_o"], b["pdf_l"]), active=hit)
+        elif hit is not None:
+            # the spherical pair below on the hits only: ONE compaction serves both launches (a context is indexed by the call's
+            # own rows, so the row list is passed as such rather than the mask twice); the misses' results are zeroed in that pass
+            from .live import live_rows
+            rows = live_rows(hit, zero=(b["wo"], b["pdf_o"], b["pdf_l"]))
+            if rows.shape[0]:
+                if "ctx" not in b:
+                    b["ctx"] = core.sampler.new_context(n)
+                core.sampler.plugin_sample(b["wi"], x0, T=core.T, variant=core.VARIANT, seed=skey, offset=offset,
+                                           out=(b["wo"], b["pdf_o"]), ctx_out=b["ctx"], row_index=rows)
+                core.sampler.plugin_pdf(b["wi"], b["wl"], T=core.T, variant=core.VARIANT, out=b["pdf_l"], ctx_in=b["ctx"],
+                                        row_index=rows)
         else:
             # spherical nets: the single-op kernels form the Jacobian by meeting in the middle, the fused instantiation could not
             # (register budget) — two launches that share the prologue through the per-query context are the faster pair

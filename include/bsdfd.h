@@ -34,8 +34,9 @@ extern "C" {
  * BSDFD_ABI_VERSION once after loading the library (the Python hosts do: _lib.lib()).
  *   5: bsdfd_desc.reserved became bsdfd_desc.tile (values other than 0 / 16 / 32 are rejected, 0 = library default).
  *   6: bsdfd_opts.row_index appended; bsdfd_abi_version() added.
- *   7: bsdfd_bucket_wide_workspace_bytes() and bsdfd_bucket_by_material_wide() added. */
-#define BSDFD_ABI_VERSION 7
+ *   7: bsdfd_bucket_wide_workspace_bytes() and bsdfd_bucket_by_material_wide() added.
+ *   8: bsdfd_live_workspace_bytes(), bsdfd_compact_live() and bsdfd_plugin_sample_pdf_ex() added (`active` masks). */
+#define BSDFD_ABI_VERSION 8
 
 #define BSDFD_OK 0
 #define BSDFD_EINVAL 1   /* bad argument / unsupported architecture */
@@ -240,6 +241,13 @@ int bsdfd_plugin_sample_pdf_multi_ex(const bsdfd_handle* handles, int32_t n_hand
                                      int32_t variant, const float* wi, const float* x0, const float* wl, uint64_t seed,
                                      uint64_t offset, int32_t T, float* wo, float* pdf_wo, float* pdf_wl,
                                      const bsdfd_opts* opts, void* hip_stream);
+/* bsdfd_plugin_sample_pdf with optional arguments (ABI 8): the single-handle form of the call above, with its rules (rng_index
+ * and row_index; no per-query context).  With the row list of bsdfd_compact_live() as opts->row_index it is the fused
+ * sample() + pdf() of the lanes an `active` mask selects — the `active` argument of the reference's plugin methods
+ * (rendering/brdf_measured_disk.py:59,112), i.e. Mitsuba calling an instance on its lanes only.  NULL opts = the plain call. */
+int bsdfd_plugin_sample_pdf_ex(bsdfd_handle h, int32_t variant, const float* wi, const float* x0, const float* wl,
+                               uint64_t seed, uint64_t offset, int64_t N, int32_t T, float* wo, float* pdf_wo,
+                               float* pdf_wl, const bsdfd_opts* opts, void* hip_stream);
 
 /* Reflow teacher sampling without the Jacobian: x <- x + v(x, t/T | omega_i)/T for T steps
  * (learning_repo_cleanup/spherical_domain_sampling.py:147-166, disk_domain_sampling.py:93-110 —
@@ -315,6 +323,26 @@ int bsdfd_bucket_by_material_wide(const int64_t* material_id, int64_t N, int32_t
 int bsdfd_gather_lanes(const int64_t* perm, int64_t n, const float* wi, float* wi_b, void* hip_stream);
 int bsdfd_scatter_lanes(const int64_t* perm, int64_t n, const float* wo_b, const float* pdf_b, const float* pdf2_b,
                         float* wo, float* pdf, float* pdf2, void* hip_stream);
+
+/* ---- live lanes of a wavefront (ABI 8) -------------------------------------------------------------------
+ * Replaces the `active` argument of the reference's plugin methods (rendering/brdf_measured_disk.py:59,64,101,112: sample,
+ * the DrJit select on its weight, eval, pdf), which Mitsuba uses to call an instance on its lanes only: an order-preserving
+ * compaction of the N lanes of a wavefront into the row list the plugin-level calls take as bsdfd_opts.row_index.  Lane i is
+ * live when `active` is NULL or active[i] != 0, and (BSDFD_LIVE_WI_UPPER unset or wi[3i+2] > 0), and (BSDFD_LIVE_DIR_UPPER
+ * unset or dir[3i+2] > 0) — the comparisons of the kernels' own hemisphere guards, so NaN and +-0 are dead; the two flags
+ * cull the lanes for which the pdf of the `measured` plugins is 0 anyway (:112-124).  rows[0 .. count) receives the live row
+ * numbers in ascending order (rows holds up to N entries; the rest is unspecified), count is a DEVICE int64[1].  In the same
+ * pass the DEAD rows of up to three result arrays are set to 0 — zero_wo [N,3], zero_pdf [N], zero_pdf2 [N], each may be
+ * NULL; their live rows are not touched (the masked call writes them).  `workspace`: device scratch of
+ * bsdfd_live_workspace_bytes() (0 for N < 0), 8-byte aligned; the result does not depend on what it held before.  Allocates
+ * nothing and does not synchronise: everything is enqueued on hip_stream (no workgroup waits on another one).  N == 0 only
+ * writes count = 0. */
+#define BSDFD_LIVE_WI_UPPER 1
+#define BSDFD_LIVE_DIR_UPPER 2
+int64_t bsdfd_live_workspace_bytes(int64_t N);
+int bsdfd_compact_live(const unsigned char* active, const float* wi, const float* dir, int32_t flags, int64_t N,
+                       int64_t* rows, int64_t* count, float* zero_wo, float* zero_pdf, float* zero_pdf2,
+                       void* workspace, int64_t workspace_bytes, void* hip_stream);
 
 /* ---- ground-truth evaluator for eval(): RGL measured BSDF (rgb tensor files) -----------------------
  * Replaces, for the plugins' eval() / sample-weight / firefly rule, the Mitsuba `measured` BSDF the
