@@ -9,7 +9,9 @@ Modules (everything below the tensors runs in libbsdfd.so, include/bsdfd.h; no C
   model, weights      reference-named weight containers, the neutral .bsdfw weight format
   materials           MaterialTable: material-tagged wavefronts (bucketing + segmented launches)
   live                live_rows: an ``active`` mask -> the row list the flow kernels run on (csrc/live.hip)
-  measured            MeasuredBSDF: the ground-truth evaluator behind eval() (RGL tensor files)
+  measured            MeasuredBSDF: the ground-truth evaluator behind eval() (RGL tensor files);
+                      MeasuredTable: eval() of a mixed-material wavefront in one launch
+  measured_synth      synthetic RGL tensor files for tests and tools (numpy only)
   encoding            positional_encoding_1 as a stand-alone pass
   wavefront           WavefrontRenderer / ArrayRenderer: the render loop around the plugin calls
   sharding            query / image-row sharding over one process per GPU
@@ -18,5 +20,12 @@ Modules (everything below the tensors runs in libbsdfd.so, include/bsdfd.h; no C
 """
 from . import weights  # noqa: F401
 
-__all__ = ["weights"]
+__all__ = ["weights", "MeasuredTable"]
 __version__ = "0.1.0"
+
+
+def __getattr__(name):   # MeasuredTable on first use: importing the package stays free of torch
+    if name == "MeasuredTable":
+        from .measured import MeasuredTable
+        return MeasuredTable
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -16,11 +16,13 @@ LIB_PATH = os.environ.get("BSDFD_LIB_PATH") or DEFAULT_LIB_PATH  # override: A/B
 SRC_PATH = os.path.join(_HERE, "csrc", "bsdfd.hip")
 SRC32_PATH = os.path.join(_HERE, "csrc", "flow32.hip")   # the 32-query-tile flow kernels
 SRC_PATHS = [SRC_PATH, SRC32_PATH, os.path.join(_HERE, "csrc", "wavefront.hip"), os.path.join(_HERE, "csrc", "encoding.hip"),
-             os.path.join(_HERE, "csrc", "measured.hip"), os.path.join(_HERE, "csrc", "bucket.hip"),
+             os.path.join(_HERE, "csrc", "measured.hip"), os.path.join(_HERE, "csrc", "measured_table.hip"),
+             os.path.join(_HERE, "csrc", "bucket.hip"),
              os.path.join(_HERE, "csrc", "bucket_wide.hip"), os.path.join(_HERE, "csrc", "live.hip"),
              os.path.join(_HERE, "csrc", "clock.hip")]  # translation units of libbsdfd.so
 FLOW_TUS = (SRC_PATH, SRC32_PATH)   # ... whose device assembly the build verifies (_asmcheck)
-DEP_PATHS = SRC_PATHS + [os.path.join(_HERE, "csrc", f) for f in ("common.h", "flow_dev.h", "flow32.h", "bucket_scan.h")]
+DEP_PATHS = SRC_PATHS + [os.path.join(_HERE, "csrc", f) for f in ("common.h", "flow_dev.h", "flow32.h", "bucket_scan.h",
+                                                                     "measured_dev.h")]
 INCLUDE_DIR = os.path.join(ROOT, "include")
 ASM_CACHE_DIR = os.path.join(ROOT, "build", "asm")   # device assembly of the last product build (bsdfd.s, flow32.s)
 
@@ -43,6 +45,8 @@ EXPORTS = (
     "bsdfd_gather_lanes", "bsdfd_scatter_lanes", "bsdfd_live_workspace_bytes", "bsdfd_compact_live",
     "bsdfd_measured_create_from_file", "bsdfd_measured_destroy", "bsdfd_measured_get_info", "bsdfd_measured_eval",
     "bsdfd_measured_sample_weight",
+    "bsdfd_measured_table_create", "bsdfd_measured_table_destroy", "bsdfd_measured_eval_table",
+    "bsdfd_measured_sample_weight_table",
     "bsdfd_set_profiling", "bsdfd_profile_read", "bsdfd_profile_read_op", "bsdfd_profile_clock_mhz", "bsdfd_last_kernel_ms", "bsdfd_shader_clock_mhz",
     "bsdfd_last_error", "bsdfd_version", "bsdfd_abi_version",
 )
@@ -399,6 +403,11 @@ def lib():
     L.bsdfd_measured_get_info.argtypes = [vp] + [C.POINTER(i32)] * 5
     L.bsdfd_measured_eval.argtypes = [vp, fp, fp, i64, C.POINTER(C.c_float), fp, vp]
     L.bsdfd_measured_sample_weight.argtypes = [vp, fp, fp, fp, fp, i64, C.POINTER(C.c_float), C.c_float, fp, fp, vp]
+    L.bsdfd_measured_table_create.argtypes = [C.POINTER(vp), i32, C.POINTER(vp)]
+    L.bsdfd_measured_table_destroy.argtypes = [vp]
+    L.bsdfd_measured_table_destroy.restype = None
+    L.bsdfd_measured_eval_table.argtypes = [vp, fp, fp, fp, fp, i64, C.POINTER(C.c_float), fp, fp, vp]
+    L.bsdfd_measured_sample_weight_table.argtypes = [vp, fp, fp, fp, fp, fp, i64, C.POINTER(C.c_float), C.c_float, fp, fp, vp]
     L.bsdfd_bucket_workspace_bytes.argtypes = [i64, i32]
     L.bsdfd_bucket_workspace_bytes.restype = i64
     L.bsdfd_bucket_by_material.argtypes = [fp, i64, i32, fp, fp, fp, i64, vp]

@@ -1,0 +1,259 @@
+// measured_table.hip — eval() of a mixed-material wavefront in one launch: the RGL evaluator of measured.hip behind a
+// table of materials.
+//
+// A renderer's wavefront carries one material id per lane (bsdfd_wf_primary writes them).  Serving eval() through
+// bsdfd_measured_eval takes one launch per material on gathered slices; the evaluator is latency-bound (~60 dependent
+// gathers per pair from L2-resident tables), so many small launches are its worst case.  Here the lanes stay in LANE order:
+// one thread per row loads its id and evaluates the material the id names, through the same measured_f (measured_dev.h)
+// the single-material kernels inline — bit for bit what they return (measured_dev.h fixes where multiply-adds are fused).
+// Rows without ground truth get a quiet NaN, the "use the proxy" value bsdfd_wf_shade reads.
+//
+// Image-coherent lanes hit the same ball, so most waves carry ONE id: those take a wave-uniform path on which the descriptor
+// is addressed by a scalar and travels through uniform loads, as the kernel argument of the single-material kernel does;
+// waves with mixed ids load the descriptor's fields per lane.
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "bsdfd.h"
+#include "common.h"
+#include "measured_dev.h"
+
+using namespace measured_dev;
+
+namespace {
+
+// The device array holds MeasuredDev records, read here through a mirror type whose pointers are typed as GLOBAL pointers: a
+// pointer loaded from memory could point anywhere as far as the compiler knows, and the tables would be read with flat loads;
+// the single-material kernels get the descriptor as a kernel argument, whose pointers are known to be global.
+typedef const __attribute__((address_space(1))) float* gptr;
+struct TableG {
+    gptr data;
+    int w, h;
+};
+struct MeasuredDevG {
+    gptr phi_i, theta_i;
+    int n_phi, n_theta;
+    int isotropic, jacobian, reduction;
+    float fold_x, fold_y;
+    TableG ndf, sigma, vndf, rgb;
+    gptr vndf_cond, vndf_marg;
+};
+static_assert(sizeof(MeasuredDevG) == sizeof(MeasuredDev) && alignof(MeasuredDevG) == alignof(MeasuredDev) &&
+              offsetof(MeasuredDevG, fold_y) == offsetof(MeasuredDev, fold_y) && offsetof(MeasuredDevG, rgb) == offsetof(MeasuredDev, rgb) &&
+              offsetof(MeasuredDevG, vndf_marg) == offsetof(MeasuredDev, vndf_marg), "MeasuredDevG mirrors MeasuredDev");
+
+__device__ __forceinline__ Table generic(const TableG& t) { return Table{(const float*)t.data, t.w, t.h}; }
+__device__ __forceinline__ MeasuredDev generic(const MeasuredDevG& s) {
+    MeasuredDev m;
+    m.phi_i = (const float*)s.phi_i; m.theta_i = (const float*)s.theta_i;
+    m.n_phi = s.n_phi; m.n_theta = s.n_theta;
+    m.isotropic = s.isotropic; m.jacobian = s.jacobian; m.reduction = s.reduction;
+    m.fold_x = s.fold_x; m.fold_y = s.fold_y;
+    m.ndf = generic(s.ndf); m.sigma = generic(s.sigma); m.vndf = generic(s.vndf); m.rgb = generic(s.rgb);
+    m.vndf_cond = (const float*)s.vndf_cond; m.vndf_marg = (const float*)s.vndf_marg;
+    return m;
+}
+
+// slot of a material without ground truth: all zero (no tables)
+__device__ __forceinline__ bool has_ground_truth(const MeasuredDevG& m) { return m.rgb.data != nullptr; }
+
+__device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7fc00000); }
+
+// true when every live lane of the wave carries the id of its first live lane, which `first` then holds as a scalar.
+// Call with the dead lanes (rows past N) already retired.
+__device__ __forceinline__ bool wave_uniform_id(long long id, long long& first) {
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)id & 0xffffffffull));
+    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)id >> 32));
+    first = (long long)(((unsigned long long)hi << 32) | lo);
+    return __ballot(id != first) == 0ull;
+}
+
+__device__ __forceinline__ void store3(float* __restrict__ out, long long q, float a, float b, float c) {
+    out[3 * q] = a; out[3 * q + 1] = b; out[3 * q + 2] = c;
+}
+
+// one row of eval(): f_o = f(wi, wo) cos * tint and, with a light direction, f_l = f(wi, wl) cos * tint — what
+// measured_eval_kernel (measured.hip) computes for each pair
+__device__ __forceinline__ void eval_row(const MeasuredDev& m, const float* __restrict__ wi, const float* __restrict__ wo,
+                                         const float* __restrict__ wl, long long q, Tint tint, float* __restrict__ f_o,
+                                         float* __restrict__ f_l) {
+    float f[3];
+    measured_f(m, wi[3 * q], wi[3 * q + 1], wi[3 * q + 2], wo[3 * q], wo[3 * q + 1], wo[3 * q + 2], f);
+    store3(f_o, q, f[0] * tint.r, f[1] * tint.g, f[2] * tint.b);
+    if (wl) {
+        measured_f(m, wi[3 * q], wi[3 * q + 1], wi[3 * q + 2], wl[3 * q], wl[3 * q + 1], wl[3 * q + 2], f);
+        store3(f_l, q, f[0] * tint.r, f[1] * tint.g, f[2] * tint.b);
+    }
+}
+
+__device__ __forceinline__ void eval_row_nan(long long q, float* __restrict__ f_o, float* __restrict__ f_l) {
+    const float nan = quiet_nan();
+    store3(f_o, q, nan, nan, nan);
+    if (f_l) store3(f_l, q, nan, nan, nan);
+}
+
+__global__ __launch_bounds__(256) void measured_eval_table_kernel(const MeasuredDevG* __restrict__ table, int n_materials,
+                                                                  const long long* __restrict__ material_id,
+                                                                  const float* __restrict__ wi,
+                                                                  const float* __restrict__ wo,
+                                                                  const float* __restrict__ wl, long long n, Tint tint,
+                                                                  float* __restrict__ f_o, float* __restrict__ f_l) {
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    const long long id = material_id[q];
+    long long first;
+    if (wave_uniform_id(id, first)) {
+        if (first >= 0 && first < n_materials && has_ground_truth(table[first]))
+            eval_row(generic(table[first]), wi, wo, wl, q, tint, f_o, f_l);
+        else eval_row_nan(q, f_o, f_l);
+    } else {
+        if (id >= 0 && id < n_materials && has_ground_truth(table[id])) eval_row(generic(table[id]), wi, wo, wl, q, tint, f_o, f_l);
+        else eval_row_nan(q, f_o, f_l);
+    }
+}
+
+// one row of the plugins' sample() tail — measured_weight_kernel (measured.hip) for the row's material
+__device__ __forceinline__ void weight_row(const MeasuredDev& m, const float* __restrict__ wi, const float* __restrict__ wo,
+                                           const float* __restrict__ pdf_in, const unsigned char* __restrict__ active,
+                                           long long q, Tint tint, float thr, float* __restrict__ weight,
+                                           float* __restrict__ pdf_out) {
+    const float wiz = wi[3 * q + 2], woz = wo[3 * q + 2];
+    float f[3];
+    measured_f(m, wi[3 * q], wi[3 * q + 1], wiz, wo[3 * q], wo[3 * q + 1], woz, f);
+    const float pdf = pdf_in[q];
+    const bool act = wiz > 0.0f && (!active || active[q] != 0);
+    float v[3] = {0.f, 0.f, 0.f};
+    if (act && pdf > 0.0f) {
+        const float inv = 1.0f / pdf;
+        v[0] = f[0] * tint.r * inv; v[1] = f[1] * tint.g * inv; v[2] = f[2] * tint.b * inv;
+    }
+    const float lum = 0.2126f * v[0] + 0.7152f * v[1] + 0.0722f * v[2];
+    const float p = lum < thr ? pdf : 0.0f;
+    const bool keep = act && p > 0.0f && woz > 0.0f;
+    pdf_out[q] = p;
+    store3(weight, q, keep ? v[0] : 0.0f, keep ? v[1] : 0.0f, keep ? v[2] : 0.0f);
+}
+
+__device__ __forceinline__ void weight_row_nan(const float* __restrict__ pdf_in, long long q, float* __restrict__ weight,
+                                               float* __restrict__ pdf_out) {
+    const float nan = quiet_nan();
+    pdf_out[q] = pdf_in[q];
+    store3(weight, q, nan, nan, nan);
+}
+
+__global__ __launch_bounds__(256) void measured_weight_table_kernel(const MeasuredDevG* __restrict__ table, int n_materials,
+                                                                    const long long* __restrict__ material_id,
+                                                                    const float* __restrict__ wi,
+                                                                    const float* __restrict__ wo,
+                                                                    const float* __restrict__ pdf_in,
+                                                                    const unsigned char* __restrict__ active, long long n,
+                                                                    Tint tint, float thr, float* __restrict__ weight,
+                                                                    float* __restrict__ pdf_out) {
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    const long long id = material_id[q];
+    long long first;
+    if (wave_uniform_id(id, first)) {
+        if (first >= 0 && first < n_materials && has_ground_truth(table[first]))
+            weight_row(generic(table[first]), wi, wo, pdf_in, active, q, tint, thr, weight, pdf_out);
+        else weight_row_nan(pdf_in, q, weight, pdf_out);
+    } else {
+        if (id >= 0 && id < n_materials && has_ground_truth(table[id]))
+            weight_row(generic(table[id]), wi, wo, pdf_in, active, q, tint, thr, weight, pdf_out);
+        else weight_row_nan(pdf_in, q, weight, pdf_out);
+    }
+}
+
+}  // namespace
+
+struct bsdfd_measured_table_ctx {
+    MeasuredDev* dev;  // [n_materials] on the device; a slot without ground truth is all zero
+    int32_t n_materials;
+    int device;
+};
+
+namespace {
+
+int table_launch_checks(bsdfd_measured_table t, int64_t n) {
+    if (!t) return bsdfd_fail_(BSDFD_EINVAL, "null measured table");
+    if (n < 0) return bsdfd_fail_(BSDFD_EINVAL, "N must be >= 0");
+    int dev = -1;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev != t->device) return bsdfd_fail_(BSDFD_EINVAL, "measured table belongs to another device");
+    if ((long long)n > 0xffffffffLL - 255) return bsdfd_fail_(BSDFD_EINVAL, "N too large for one launch");   // grid * block < 2^32
+    return BSDFD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bsdfd_measured_table_create(const bsdfd_measured_handle* handles, int32_t n_materials, bsdfd_measured_table* out) {
+    if (!out) return bsdfd_fail_(BSDFD_EINVAL, "null argument");
+    *out = nullptr;
+    if (!handles) return bsdfd_fail_(BSDFD_EINVAL, "null handle array");
+    if (n_materials < 1 || n_materials > 65536) return bsdfd_fail_(BSDFD_EINVAL, "n_materials must be in [1, 65536]");
+    bool any = false;
+    for (int32_t m = 0; m < n_materials; ++m) any = any || handles[m] != nullptr;
+    if (!any) return bsdfd_fail_(BSDFD_EINVAL, "a measured table needs at least one material with ground truth");
+    int devid = -1;
+    HIP_TRY(hipGetDevice(&devid));
+    std::vector<MeasuredDev> host((size_t)n_materials, MeasuredDev{});
+    for (int32_t m = 0; m < n_materials; ++m) {
+        if (!handles[m]) continue;
+        if (handles[m]->device != devid)
+            return bsdfd_fail_(BSDFD_EINVAL, "measured handle " + std::to_string(m) + " belongs to another device");
+        host[(size_t)m] = handles[m]->dev;
+    }
+    void* p = nullptr;
+    HIP_TRY(hipMalloc(&p, host.size() * sizeof(MeasuredDev)));
+    const hipError_t e = hipMemcpy(p, host.data(), host.size() * sizeof(MeasuredDev), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(p);
+        return bsdfd_fail_(BSDFD_EHIP, std::string("hipMemcpy of the material descriptors: ") + hipGetErrorString(e));
+    }
+    *out = new bsdfd_measured_table_ctx{static_cast<MeasuredDev*>(p), n_materials, devid};
+    return BSDFD_OK;
+}
+
+void bsdfd_measured_table_destroy(bsdfd_measured_table t) {
+    if (!t) return;
+    (void)hipFree(t->dev);
+    delete t;
+}
+
+int bsdfd_measured_eval_table(bsdfd_measured_table t, const int64_t* material_id, const float* wi, const float* wo,
+                              const float* wl, int64_t n, const float* tint, float* f_o, float* f_l, void* stream) {
+    if (int rc = table_launch_checks(t, n)) return rc;
+    if (n == 0) return BSDFD_OK;
+    if ((wl == nullptr) != (f_l == nullptr)) return bsdfd_fail_(BSDFD_EINVAL, "wl and f_l are both NULL or both given");
+    if (!material_id || !wi || !wo || !f_o) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
+    const Tint c = tint ? Tint{tint[0], tint[1], tint[2]} : Tint{1.0f, 1.0f, 1.0f};
+    hipLaunchKernelGGL(measured_eval_table_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), reinterpret_cast<const MeasuredDevG*>(t->dev), (int)t->n_materials,
+                       reinterpret_cast<const long long*>(material_id), wi, wo, wl, (long long)n, c, f_o, f_l);
+    HIP_TRY(hipGetLastError());
+    return BSDFD_OK;
+}
+
+int bsdfd_measured_sample_weight_table(bsdfd_measured_table t, const int64_t* material_id, const float* wi,
+                                       const float* wo, const float* pdf_sa, const unsigned char* active, int64_t n,
+                                       const float* tint, float firefly_threshold, float* weight_out, float* pdf_out,
+                                       void* stream) {
+    if (int rc = table_launch_checks(t, n)) return rc;
+    if (n == 0) return BSDFD_OK;
+    if (!material_id || !wi || !wo || !pdf_sa || !weight_out || !pdf_out) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
+    const Tint c = tint ? Tint{tint[0], tint[1], tint[2]} : Tint{1.0f, 1.0f, 1.0f};
+    hipLaunchKernelGGL(measured_weight_table_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), reinterpret_cast<const MeasuredDevG*>(t->dev), (int)t->n_materials,
+                       reinterpret_cast<const long long*>(material_id), wi, wo, pdf_sa, active, (long long)n, c,
+                       firefly_threshold, weight_out, pdf_out);
+    HIP_TRY(hipGetLastError());
+    return BSDFD_OK;
+}
+
+}  // extern "C"

@@ -6,12 +6,15 @@ sample weight and the firefly rule.  Mitsuba has no AMD GPU variant; ``MeasuredB
 model (Dupuy & Jakob 2018) over ``libbsdfd.so`` (csrc/measured.hip) with the call shape the plugins
 use: ``eval(ctx, si, wo) -> [N,3]`` = f * cos(theta_o), zero on the lower hemispheres.  Only the
 ``*_rgb.bsdf`` flavour is supported (the one the reference's scenes name).  No CPU fallback.
+
+``MeasuredTable`` serves a wavefront whose lanes carry DIFFERENT materials (one id per lane) in one launch
+(csrc/measured_table.hip): the same numbers as ``MeasuredBSDF`` per material, bit for bit.
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
+from typing import Optional, Sequence
 
 import torch
 
@@ -101,3 +104,97 @@ class MeasuredBSDF:
     def eval(self, ctx, si, wo, active=True):
         from .plugin_base import _vec, _wi_of
         return self.eval_t(_wi_of(si), _vec(wo))
+
+
+class MeasuredTable:
+    """``eval()`` for a mixed-material wavefront: ``entries[m]`` (a ``MeasuredBSDF``, or None = no ground truth) serves the lanes
+    whose ``material_id`` is m.  One launch for the whole wavefront in LANE order (``bsdfd_measured_eval_table``), where
+    ``MeasuredBSDF.eval_t`` takes one launch per material on gathered slices; lanes with ground truth get that evaluator's
+    result bit for bit, every other lane (None entry, id negative or >= len(entries): a renderer's floor hits and misses) NaN.
+    The table keeps the entries alive: it borrows their tensor data.  The native table is created here, on the entries' device
+    (the launches then neither allocate nor synchronise); only a table without any ground truth, which the library refuses,
+    is left to fail at its first launch."""
+
+    MAX_MATERIALS = 65536
+
+    def __init__(self, entries: Sequence[Optional[MeasuredBSDF]]):
+        self.entries = list(entries)
+        if not 1 <= len(self.entries) <= self.MAX_MATERIALS:
+            raise ValueError(f"MeasuredTable: 1..{self.MAX_MATERIALS} entries")
+        if any(e is not None and not isinstance(e, MeasuredBSDF) for e in self.entries):
+            raise ValueError("MeasuredTable: entries are MeasuredBSDF objects or None")
+        self._t = C.c_void_p()
+        if any(e is not None for e in self.entries):
+            self._table()
+
+    def __len__(self):
+        return len(self.entries)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_t", None) is not None and self._t.value:
+                _lib.lib().bsdfd_measured_table_destroy(self._t)
+                self._t = C.c_void_p()
+        except Exception:
+            pass
+
+    def _table(self):
+        """The native table (created with the entries' device current — the library checks that it is)."""
+        if not self._t.value:
+            handles = (C.c_void_p * len(self.entries))(*[None if e is None else e._h.value for e in self.entries])
+            _lib.check(_lib.lib().bsdfd_measured_table_create(handles, len(self.entries), C.byref(self._t)))
+        return self._t
+
+    @staticmethod
+    def _check(material_id: torch.Tensor, **tensors):
+        """``MeasuredBSDF._check`` plus the ids: dtype and shape, then the row counts, then device and layout."""
+        if material_id.dtype != torch.int64 or material_id.dim() != 1:
+            raise ValueError("MeasuredTable: material_id must be an int64 tensor [N]")
+        n = material_id.shape[0]
+        for name, (t, cols) in tensors.items():
+            if t.dtype != torch.float32 or not ((t.dim() == 2 and t.shape[1] == cols) if cols else t.dim() == 1):
+                raise ValueError(f"MeasuredTable: {name} must be an fp32 tensor [N{',' + str(cols) if cols else ''}]")
+            if t.shape[0] != n:
+                raise ValueError(f"MeasuredTable: {name} has {t.shape[0]} rows, material_id has {n}")
+        for name, t in [("material_id", material_id)] + [(k, t) for k, (t, _) in tensors.items()]:
+            if not (t.is_cuda and t.is_contiguous() and t.device == material_id.device):
+                raise ValueError(f"MeasuredTable: {name} must be a contiguous CUDA tensor, all on one device")
+
+    def eval_t(self, material_id: torch.Tensor, wi: torch.Tensor, wo: torch.Tensor, wl: Optional[torch.Tensor] = None,
+               tint=None, out_o: Optional[torch.Tensor] = None, out_l: Optional[torch.Tensor] = None):
+        """f(wi, wo) cos(theta_o) [* tint] of each lane's material -> f_o [N,3]; with ``wl`` also f(wi, wl) cos(theta_l) ->
+        (f_o, f_l), both evaluations in the same launch.  NaN rows = no ground truth for that lane."""
+        if out_l is not None and wl is None:
+            raise ValueError("MeasuredTable.eval_t: out_l without wl")
+        given = dict(wi=(wi, 3), wo=(wo, 3))
+        given.update({k: (t, 3) for k, t in (("wl", wl), ("out_o", out_o), ("out_l", out_l)) if t is not None})
+        self._check(material_id, **given)
+        if out_o is None:
+            out_o = torch.empty_like(wi)
+        if wl is not None and out_l is None:
+            out_l = torch.empty_like(wi)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        with torch.cuda.device(wi.device):
+            stream = C.c_void_p(torch.cuda.current_stream(wi.device).cuda_stream)
+            _lib.check(_lib.lib().bsdfd_measured_eval_table(self._table(), p(material_id), p(wi), p(wo), p(wl), wi.shape[0],
+                                                            MeasuredBSDF._tint(tint), p(out_o), p(out_l), stream))
+        return out_o if wl is None else (out_o, out_l)
+
+    def sample_weight(self, material_id: torch.Tensor, wi: torch.Tensor, wo: torch.Tensor, pdf_sa: torch.Tensor, tint=None,
+                      active: Optional[torch.Tensor] = None, firefly_threshold: float = 30.0):
+        """``MeasuredBSDF.sample_weight`` of each lane's material in one launch -> (weight [N,3], pdf [N]); lanes without
+        ground truth get weight NaN and pdf = pdf_sa."""
+        self._check(material_id, wi=(wi, 3), wo=(wo, 3), pdf_sa=(pdf_sa, 0))
+        act = None
+        if active is not None:
+            if active.shape != (wi.shape[0],) or active.device != wi.device or active.dtype not in (torch.bool, torch.uint8):
+                raise ValueError("MeasuredTable.sample_weight: active must be a bool or uint8 tensor [N] on the device of wi")
+            act = active.to(torch.uint8).contiguous()
+        weight, pdf = torch.empty_like(wi), torch.empty_like(pdf_sa)
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        with torch.cuda.device(wi.device):
+            stream = C.c_void_p(torch.cuda.current_stream(wi.device).cuda_stream)
+            _lib.check(_lib.lib().bsdfd_measured_sample_weight_table(
+                self._table(), p(material_id), p(wi), p(wo), p(pdf_sa), p(act), wi.shape[0], MeasuredBSDF._tint(tint),
+                float(firefly_threshold), p(weight), p(pdf), stream))
+        return weight, pdf

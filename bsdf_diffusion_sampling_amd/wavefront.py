@@ -305,13 +305,15 @@ class ArrayRenderer(WavefrontRenderer):
     primary rays (with material ids) -> one stable bucketing of the wavefront (``bsdfd_bucket_by_material``;
     floor hits and misses sort behind the materials) -> ONE fused sample+pdf launch per kernel signature
     (``bsdfd_plugin_sample_pdf_multi``) -> shade.  ``ground_truth``: {material index: MeasuredBSDF} for the
-    balls that have an RGL tensor file; the others shade with the proxy ``f cos = albedo * pdf``.
+    balls that have an RGL tensor file; the others shade with the proxy ``f cos = albedo * pdf``.  Their ``eval()`` is ONE launch
+    on the lane-ordered wavefront (``measured.MeasuredTable``); ``fused_ground_truth=False`` keeps the earlier form — gathered
+    copies, two ``MeasuredBSDF.eval_t`` launches per material, a scatter — for A/B runs: the same film bit for bit.
     The Philox counter of a path is its row in the bucketed order, so images of different row splits agree
     statistically, not bit for bit (the single-ball renderer is split-invariant)."""
 
     def __init__(self, table, centers, radii, camera: Optional[Camera] = None, env: Optional[torch.Tensor] = None,
                  floor: bool = True, checker=(0.4, 0.2, 2.0), albedo=(1.0, 1.0, 1.0), ground_truth=None,
-                 device: Optional[torch.device] = None):
+                 device: Optional[torch.device] = None, fused_ground_truth: bool = True):
         if len(centers) != len(table) or len(radii) != len(table):
             raise ValueError("one ball per material of the table")
         if not 1 <= len(table) <= 32:
@@ -327,6 +329,11 @@ class ArrayRenderer(WavefrontRenderer):
         self.table = table
         self.ground_truth = dict(ground_truth or {})
         self.use_ground_truth = bool(self.ground_truth)   # f arrays are then filled for every path
+        self.fused_ground_truth = bool(fused_ground_truth)
+        self.measured_table = None
+        if self.use_ground_truth and self.fused_ground_truth:
+            from .measured import MeasuredTable
+            self.measured_table = MeasuredTable([self.ground_truth.get(m) for m in range(len(table))])
         self.needs_material_ids = True
         sc = self.scene
         sc.n_extra_spheres = len(centers) - 1
@@ -345,15 +352,20 @@ class ArrayRenderer(WavefrontRenderer):
         plan = self.table.bucket(b["mat"], extra_bins=2)          # floor hits and misses behind the materials
         offset = row_begin * self.camera.width * spp
         skey = (seed * 0x9E3779B97F4A7C15 + pass_idx + 1) & 0xFFFFFFFFFFFFFFFF
-        if not self.use_ground_truth:
+        if not self.use_ground_truth or self.fused_ground_truth:
             # (through the bucket permutation — no gathered copies of wi / wl, no scatter of the three results — while the pass's
             #  arrays fit the Infinity Cache: materials.WavefrontPipeline.DIRECT_MAX_LANES; the same numbers bit for bit)
             from .materials import WavefrontPipeline
             b["wo"], b["pdf_o"], b["pdf_l"] = self.table.sample_pdf(plan, b["wi"], b["wl"], seed=skey, offset=offset,
                                                                     direct=n <= WavefrontPipeline.DIRECT_MAX_LANES)
+            if self.use_ground_truth:
+                # ground truth where a tensor file exists, for both strategies, in one launch on the lane-ordered arrays; floor
+                # hits, misses and balls without a file come back NaN = "no ground truth for this path" -> the shade kernel
+                # uses the proxy
+                self.measured_table.eval_t(b["mat"], b["wi"], b["wo"], b["wl"], tint=self.plugin.albedo, out_o=b["f_o"],
+                                           out_l=b["f_l"])
         else:
-            # ground truth where a tensor file exists, evaluated on the bucket-ordered arrays (a material's rows
-            # are contiguous there); NaN = "no ground truth for this path" -> the shade kernel uses the proxy
+            # the same, one material at a time on the bucket-ordered arrays (a material's rows are contiguous there)
             b["wo"], b["pdf_o"], b["pdf_l"], s = self.table.sample_pdf(plan, b["wi"], b["wl"], seed=skey,
                                                                        offset=offset, return_bucketed=True)
             alb = self.plugin.albedo

@@ -35,7 +35,10 @@ extern "C" {
  *   5: bsdfd_desc.reserved became bsdfd_desc.tile (values other than 0 / 16 / 32 are rejected, 0 = library default).
  *   6: bsdfd_opts.row_index appended; bsdfd_abi_version() added.
  *   7: bsdfd_bucket_wide_workspace_bytes() and bsdfd_bucket_by_material_wide() added.
- *   8: bsdfd_live_workspace_bytes(), bsdfd_compact_live() and bsdfd_plugin_sample_pdf_ex() added (`active` masks). */
+ *   8: bsdfd_live_workspace_bytes(), bsdfd_compact_live() and bsdfd_plugin_sample_pdf_ex() added (`active` masks).
+ *      Added later WITHOUT a new version (no struct or existing entry point changed; a host that needs them looks the symbols
+ *      up): bsdfd_measured_table_create(), bsdfd_measured_table_destroy(), bsdfd_measured_eval_table() and
+ *      bsdfd_measured_sample_weight_table() (eval() of a mixed-material wavefront in one launch). */
 #define BSDFD_ABI_VERSION 8
 
 #define BSDFD_OK 0
@@ -365,6 +368,28 @@ int bsdfd_measured_eval(bsdfd_measured_handle h, const float* wi, const float* w
 int bsdfd_measured_sample_weight(bsdfd_measured_handle h, const float* wi, const float* wo, const float* pdf_sa,
                                  const unsigned char* active, int64_t N, const float* tint, float firefly_threshold,
                                  float* weight_out, float* pdf_out, void* hip_stream);
+
+/* eval() for a MIXED-material wavefront (csrc/measured_table.hip): one launch serves every material, where the calls above
+ * take one launch per material on gathered slices.  The rows stay in lane order with their material ids, as bsdfd_wf_primary
+ * writes them. */
+typedef struct bsdfd_measured_table_ctx* bsdfd_measured_table;
+/* handles[m] serves material id m; a NULL entry = "no ground truth for this material".  1 <= n_materials <= 65536,
+ * at least one non-NULL handle, all on the current device.  The table copies the handles' device descriptors into one
+ * device array; it borrows the handles' tensor data: the caller keeps the handles alive while the table lives. */
+int  bsdfd_measured_table_create(const bsdfd_measured_handle* handles, int32_t n_materials, bsdfd_measured_table* out);
+void bsdfd_measured_table_destroy(bsdfd_measured_table t);
+/* eval() of a whole wavefront in LANE order, one launch: row i with 0 <= material_id[i] < n_materials (the full 64-bit
+ * value) and a non-NULL handle gets f_o[i] = what bsdfd_measured_eval(handles[id], wi+3i, wo+3i, 1, tint, ...) writes, bit
+ * for bit, and likewise f_l[i] from wl; every other row (floor, miss, NULL slot, id out of range or negative) gets a quiet
+ * NaN in all three channels: the "use the proxy" value bsdfd_wf_shade reads.  wl and f_l are both NULL or both given. */
+int  bsdfd_measured_eval_table(bsdfd_measured_table t, const int64_t* material_id, const float* wi, const float* wo,
+                               const float* wl, int64_t N, const float* tint, float* f_o, float* f_l, void* hip_stream);
+/* bsdfd_measured_sample_weight per lane's material: rows with ground truth get its weight_out / pdf_out bit for bit;
+ * the others get weight_out = NaN and pdf_out = pdf_sa. */
+int  bsdfd_measured_sample_weight_table(bsdfd_measured_table t, const int64_t* material_id, const float* wi,
+                                        const float* wo, const float* pdf_sa, const unsigned char* active, int64_t N,
+                                        const float* tint, float firefly_threshold, float* weight_out, float* pdf_out,
+                                        void* hip_stream);
 
 /* ---- wavefront harness ------------------------------------
  * The reference renders through Mitsuba 3 (rendering/brdf_measured_disk.py:146-155: passes of
