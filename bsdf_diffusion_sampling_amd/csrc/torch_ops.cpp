@@ -47,6 +47,11 @@ const float* in2d(const Tensor& t, int64_t cols, const char* name, const at::Dev
 const float* opt2d(const std::optional<Tensor>& t, int64_t cols, const char* name, const at::Device& dev, int64_t n) {
     return t.has_value() ? in2d(*t, cols, name, dev, n) : nullptr;
 }
+// a caller-owned pdf output: the kernel writes n floats through its raw pointer
+void out1d(const Tensor& pdf, int64_t n, const at::Device& dev) {
+    TORCH_CHECK(pdf.device() == dev && pdf.scalar_type() == at::kFloat && pdf.dim() == 1 && pdf.size(0) == n && pdf.is_contiguous(),
+                "pdf (out) must be a contiguous float32 tensor of shape [", n, "] on ", dev);
+}
 
 struct Launch {  // device guard + current stream of the inputs' device (bindings.cpp:95-96)
     c10::hip::HIPGuardMasqueradingAsCUDA guard;
@@ -193,8 +198,7 @@ void plugin_sample_out(int64_t h, int64_t variant, const Tensor& wi, const std::
     const int64_t n = wi.size(0);
     const float* x0p = opt2d(x0, 2, "x0", dev, n);
     in2d(wo, 3, "wo (out)", dev, n);
-    TORCH_CHECK(pdf.device() == dev && pdf.scalar_type() == at::kFloat && pdf.dim() == 1 && pdf.size(0) == n && pdf.is_contiguous(),
-                "pdf (out) must be a contiguous float32 tensor of shape [", n, "] on ", dev);
+    out1d(pdf, n, dev);
     Launch L(dev);
     ok(bsdfd_plugin_sample(as_handle(h), static_cast<int32_t>(variant), wip, x0p, static_cast<uint64_t>(seed),
                            static_cast<uint64_t>(offset), n, static_cast<int32_t>(T), wo.data_ptr<float>(),
@@ -206,8 +210,7 @@ void plugin_pdf_out(int64_t h, int64_t variant, const Tensor& wi, const Tensor& 
     const float* wip = in2d(wi, 3, "wi", dev);
     const int64_t n = wi.size(0);
     const float* wop = in2d(wo, 3, "wo", dev, n);
-    TORCH_CHECK(pdf.device() == dev && pdf.scalar_type() == at::kFloat && pdf.dim() == 1 && pdf.size(0) == n && pdf.is_contiguous(),
-                "pdf (out) must be a contiguous float32 tensor of shape [", n, "] on ", dev);
+    out1d(pdf, n, dev);
     Launch L(dev);
     ok(bsdfd_plugin_pdf(as_handle(h), static_cast<int32_t>(variant), wip, wop, n, static_cast<int32_t>(T),
                         pdf.data_ptr<float>(), L.stream));
@@ -240,6 +243,14 @@ const int64_t* index_ptr(const std::optional<Tensor>& t, const char* name, const
     return r.data_ptr<int64_t>();
 }
 
+// rows a call processes: all m of the arrays, or the n <= m a row_index names (which goes into o)
+int64_t rows(const std::optional<Tensor>& row_index, int64_t m, const at::Device& dev, bsdfd_opts& o) {
+    o.row_index = index_ptr(row_index, "row_index", dev);
+    const int64_t n = row_index.has_value() ? row_index->size(0) : m;
+    TORCH_CHECK(n <= m, "row_index names ", n, " rows, wi has ", m);
+    return n;
+}
+
 void plugin_sample_ex_out(int64_t h, int64_t variant, const Tensor& wi, const std::optional<Tensor>& x0, int64_t seed,
                           int64_t offset, int64_t T, Tensor wo, Tensor pdf, const std::optional<Tensor>& ctx,
                           const std::optional<Tensor>& rng_index, bool ctx_read, const std::optional<Tensor>& row_index) {
@@ -247,13 +258,10 @@ void plugin_sample_ex_out(int64_t h, int64_t variant, const Tensor& wi, const st
     const float* wip = in2d(wi, 3, "wi", dev);
     const int64_t m = wi.size(0);
     bsdfd_opts o{};
-    o.row_index = index_ptr(row_index, "row_index", dev);
-    const int64_t n = row_index.has_value() ? row_index->size(0) : m;
-    TORCH_CHECK(n <= m, "row_index names ", n, " rows, wi has ", m);
+    const int64_t n = rows(row_index, m, dev, o);
     const float* x0p = opt2d(x0, 2, "x0", dev, m);
     in2d(wo, 3, "wo (out)", dev, m);
-    TORCH_CHECK(pdf.device() == dev && pdf.scalar_type() == at::kFloat && pdf.dim() == 1 && pdf.size(0) == m && pdf.is_contiguous(),
-                "pdf (out) must be a contiguous float32 tensor of shape [", m, "] on ", dev);
+    out1d(pdf, m, dev);
     if (ctx.has_value()) {
         if (ctx_read) o.ctx_in = ctx_ptr(*ctx, h, n, dev);
         else o.ctx_out = ctx_ptr(*ctx, h, n, dev);
@@ -271,12 +279,9 @@ void plugin_pdf_ex_out(int64_t h, int64_t variant, const Tensor& wi, const Tenso
     const float* wip = in2d(wi, 3, "wi", dev);
     const int64_t m = wi.size(0);
     bsdfd_opts o{};
-    o.row_index = index_ptr(row_index, "row_index", dev);
-    const int64_t n = row_index.has_value() ? row_index->size(0) : m;
-    TORCH_CHECK(n <= m, "row_index names ", n, " rows, wi has ", m);
+    const int64_t n = rows(row_index, m, dev, o);
     const float* wop = in2d(wo, 3, "wo", dev, m);
-    TORCH_CHECK(pdf.device() == dev && pdf.scalar_type() == at::kFloat && pdf.dim() == 1 && pdf.size(0) == m && pdf.is_contiguous(),
-                "pdf (out) must be a contiguous float32 tensor of shape [", m, "] on ", dev);
+    out1d(pdf, m, dev);
     if (ctx.has_value()) {
         if (ctx_write) o.ctx_out = ctx_ptr(*ctx, h, n, dev);
         else o.ctx_in = ctx_ptr(*ctx, h, n, dev);
@@ -294,15 +299,12 @@ void plugin_sample_pdf_ex_out(int64_t h, int64_t variant, const Tensor& wi, cons
     const float* wip = in2d(wi, 3, "wi", dev);
     const int64_t m = wi.size(0);
     bsdfd_opts o{};
-    o.row_index = index_ptr(row_index, "row_index", dev);
-    const int64_t n = row_index.has_value() ? row_index->size(0) : m;
-    TORCH_CHECK(n <= m, "row_index names ", n, " rows, wi has ", m);
+    const int64_t n = rows(row_index, m, dev, o);
     const float* wlp = in2d(wl, 3, "wl", dev, m);
     const float* x0p = opt2d(x0, 2, "x0", dev, m);
     in2d(wo, 3, "wo (out)", dev, m);
-    for (const Tensor* p : {&pdf_o, &pdf_l})
-        TORCH_CHECK(p->device() == dev && p->scalar_type() == at::kFloat && p->dim() == 1 && p->size(0) == m && p->is_contiguous(),
-                    "pdf (out) must be a contiguous float32 tensor of shape [", m, "] on ", dev);
+    out1d(pdf_o, m, dev);
+    out1d(pdf_l, m, dev);
     o.rng_index = index_ptr(rng_index, "rng_index", dev, n);
     Launch L(dev);
     ok(bsdfd_plugin_sample_pdf_ex(as_handle(h), static_cast<int32_t>(variant), wip, x0p, wlp, static_cast<uint64_t>(seed),

@@ -8,7 +8,7 @@ queries carry a material id: queries are bucketed (stable sort by id) and result
 scattered back to the callers' order.  All disk nets together are ~160 KB of fp16 fragments
 — the whole LDS — so keeping every material resident in every workgroup is not an option
 (SURVEY.md §7 "mixed-material batches").  Instead ONE segmented launch
-(``bsdfd_plugin_sample_multi``) serves all buckets whose handles share a kernel signature
+(the ``bsdfd_plugin_*_multi_ex`` entry points) serves all buckets whose handles share a kernel signature
 (domain, width, depth, precision; up to 64 per launch): workgroups are dealt to the buckets
 in proportion to their sizes and each loads only its own material's 16 KB image.  The 52
 measured materials are 2 launches (27 disk + 25 spherical) instead of 52.
@@ -17,9 +17,9 @@ reference for the segmented path).
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence, Tuple
-
 import ctypes as C
+from itertools import accumulate
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -71,9 +71,12 @@ class MaterialTable:
             groups.setdefault(key, []).append(m)
         return groups
 
-    def _multi(self, which, members, seg_end_all, T, variant, wi_s, aux_s, seed, offset, out_wo, out_pdf, ctx=None,
+    def _multi(self, which, members, seg_end_all, T, variant, ins, outs, seed, offset, ctx=None,
                gkey=None, rng_rows=None, ctx_fill=None, direct_rows=None):
-        """``direct_rows`` (int64 [n_mat], the bucket permutation): the arrays are the CALLERS' lane-ordered ones and every launch
+        """``ins`` / ``outs``: the arrays of the call as ``FlowSampler.plugin_<which>`` takes and returns them — (wi, x0 or None) ->
+        (wo, pdf), (wi, wo) -> (pdf,), (wi, wl, x0 or None) -> (wo, pdf(wo), pdf(wl)).
+
+        ``direct_rows`` (int64 [n_mat], the bucket permutation): the arrays are the CALLERS' lane-ordered ones and every launch
         reads and writes its rows through ``bsdfd_opts.row_index`` — no gathered copy, no scatter (``direct=True`` of the public
         calls).  The Philox counter is then ``offset + original lane`` by construction.
 
@@ -85,11 +88,10 @@ class MaterialTable:
 
         Segmented launch(es) for the materials `members` of one kernel signature.  The bucketed arrays
         are ordered by material id, so a group's buckets may be interleaved with other groups'; each
-        maximal run of ADJACENT buckets becomes one `bsdfd_plugin_*_multi` call on the run's row range
-        (pointers advanced to the run's first row, Philox offset advanced by the same amount)."""
+        maximal run of ADJACENT buckets becomes one segmented call on the run's row range."""
         L = _lib.lib()
         rc = 0
-        stream = C.c_void_p(torch.cuda.current_stream(wi_s.device).cuda_stream)
+        stream = C.c_void_p(torch.cuda.current_stream(ins[0].device).cuda_stream)
         # the C ABI takes cumulative ends; non-adjacent buckets are issued as separate runs
         run_h, run_end, base = [], [], None
         run_no = 0
@@ -101,8 +103,6 @@ class MaterialTable:
             k = len(run_h)
             arr_h = (C.c_void_p * k)(*run_h)
             arr_e = (C.c_int64 * k)(*[e - base for e in run_end])
-            off_rows = base
-            wi_p = C.c_void_p(wi_s.data_ptr() + off_rows * 12)
             cbuf = None
             if ctx is not None and which in ("sample", "pdf"):
                 ckey, layout = (gkey, run_no), (base, tuple(run_end))
@@ -110,8 +110,8 @@ class MaterialTable:
                 ent = ctx.get(ckey)
                 if fill:
                     nbytes = int(L.bsdfd_context_bytes(run_h[0], run_end[-1] - base, k))
-                    if ent is None or ent["buf"].numel() * 4 < nbytes or ent["buf"].device != wi_s.device:
-                        ent = ctx[ckey] = {"buf": torch.empty((nbytes // 4,), dtype=torch.float32, device=wi_s.device)}
+                    if ent is None or ent["buf"].numel() * 4 < nbytes or ent["buf"].device != ins[0].device:
+                        ent = ctx[ckey] = {"buf": torch.empty((nbytes // 4,), dtype=torch.float32, device=ins[0].device)}
                     ent["layout"] = layout
                 elif ent is None or ent.get("layout") != layout:
                     raise ValueError("a context-reading call needs the context a filling call of the SAME bucketed wavefront "
@@ -119,52 +119,28 @@ class MaterialTable:
                                      "ctx_fill=True) before sample(ctx=, ctx_fill=False)")
                 cbuf = ent["buf"]
             c_out, c_in = (cbuf, None) if fill else (None, cbuf)
+            # Where a run starts: in the INDEX array (direct: the data pointers stay at row 0 of the lane-ordered arrays) or in the
+            # bucketed arrays themselves (pointers advanced to the run's first row).  A lane index, supplied either way, carries
+            # the Philox counter (offset + ORIGINAL lane); without one the counter is offset + row in the bucketed array.
+            row0, off, o = base, offset, None
             if direct_rows is not None:
-                # the row range of this run lives in the INDEX array: data pointers stay at row 0 of the lane-ordered arrays
-                o = _lib.opts(ctx_out=c_out, ctx_in=c_in, row_index=direct_rows, byte_offset_row=off_rows * 8)
-                full = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731
-                if which == "sample":
-                    r = L.bsdfd_plugin_sample_multi_ex(arr_h, k, arr_e, variant, full(wi_s), full(aux_s), seed, offset, T,
-                                                       full(out_wo), full(out_pdf), C.byref(o), stream)
-                elif which == "pdf":
-                    r = L.bsdfd_plugin_pdf_multi_ex(arr_h, k, arr_e, variant, full(wi_s), full(aux_s), T, full(out_pdf),
-                                                    C.byref(o), stream)
-                else:   # sample_pdf: aux_s = (x0 or None, wl), out_pdf = (pdf_wo, pdf_wl)
-                    r = L.bsdfd_plugin_sample_pdf_multi_ex(arr_h, k, arr_e, variant, full(wi_s), full(aux_s[0]), full(aux_s[1]),
-                                                           seed, offset, T, full(out_wo), full(out_pdf[0]), full(out_pdf[1]),
-                                                           C.byref(o), stream)
-            elif which == "sample" and (cbuf is not None or rng_rows is not None):
-                x0_p = None if aux_s is None else C.c_void_p(aux_s.data_ptr() + off_rows * 8)
-                # rng_rows: counter of a row = offset + its ORIGINAL lane index (not its bucketed position)
-                o = _lib.opts(ctx_out=c_out, ctx_in=c_in, rng_index=rng_rows, byte_offset_rng=off_rows * 8)
-                r = L.bsdfd_plugin_sample_multi_ex(arr_h, k, arr_e, variant, wi_p, x0_p, seed,
-                                                   offset if rng_rows is not None else offset + off_rows, T,
-                                                   C.c_void_p(out_wo.data_ptr() + off_rows * 12),
-                                                   C.c_void_p(out_pdf.data_ptr() + off_rows * 4), C.byref(o), stream)
-            elif which == "pdf" and cbuf is not None:
-                o = _lib.opts(ctx_out=c_out, ctx_in=c_in)
-                r = L.bsdfd_plugin_pdf_multi_ex(arr_h, k, arr_e, variant, wi_p,
-                                                C.c_void_p(aux_s.data_ptr() + off_rows * 12), T,
-                                                C.c_void_p(out_pdf.data_ptr() + off_rows * 4), C.byref(o), stream)
-            elif which == "sample":
-                x0_p = None if aux_s is None else C.c_void_p(aux_s.data_ptr() + off_rows * 8)
-                r = L.bsdfd_plugin_sample_multi(arr_h, k, arr_e, variant, wi_p, x0_p, seed, offset + off_rows, T,
-                                                C.c_void_p(out_wo.data_ptr() + off_rows * 12),
-                                                C.c_void_p(out_pdf.data_ptr() + off_rows * 4), stream)
-            elif which == "sample_pdf":  # aux_s = (x0 or None, wl), out_pdf = (pdf_wo, pdf_wl)
-                x0_s, wl_s = aux_s
-                x0_p = None if x0_s is None else C.c_void_p(x0_s.data_ptr() + off_rows * 8)
-                o = _lib.opts(rng_index=rng_rows, byte_offset_rng=off_rows * 8)
-                r = L.bsdfd_plugin_sample_pdf_multi_ex(arr_h, k, arr_e, variant, wi_p, x0_p,
-                                                       C.c_void_p(wl_s.data_ptr() + off_rows * 12), seed,
-                                                       offset if rng_rows is not None else offset + off_rows, T,
-                                                       C.c_void_p(out_wo.data_ptr() + off_rows * 12),
-                                                       C.c_void_p(out_pdf[0].data_ptr() + off_rows * 4),
-                                                       C.c_void_p(out_pdf[1].data_ptr() + off_rows * 4), C.byref(o), stream)
+                row0, o = 0, _lib.opts(ctx_out=c_out, ctx_in=c_in, row_index=direct_rows, byte_offset_row=base * 8)
+            elif cbuf is not None or rng_rows is not None:
+                o = _lib.opts(ctx_out=c_out, ctx_in=c_in, rng_index=rng_rows, byte_offset_rng=base * 8)
+            if direct_rows is None and rng_rows is None:
+                off = offset + base
+            o = None if o is None else C.byref(o)
+
+            def at(t, row_bytes):
+                return None if t is None else C.c_void_p(t.data_ptr() + row0 * row_bytes)
+            if which == "sample":
+                r = L.bsdfd_plugin_sample_multi_ex(arr_h, k, arr_e, variant, at(ins[0], 12), at(ins[1], 8), seed, off, T,
+                                                   at(outs[0], 12), at(outs[1], 4), o, stream)
+            elif which == "pdf":
+                r = L.bsdfd_plugin_pdf_multi_ex(arr_h, k, arr_e, variant, at(ins[0], 12), at(ins[1], 12), T, at(outs[0], 4), o, stream)
             else:
-                r = L.bsdfd_plugin_pdf_multi(arr_h, k, arr_e, variant, wi_p,
-                                             C.c_void_p(aux_s.data_ptr() + off_rows * 12), T,
-                                             C.c_void_p(out_pdf.data_ptr() + off_rows * 4), stream)
+                r = L.bsdfd_plugin_sample_pdf_multi_ex(arr_h, k, arr_e, variant, at(ins[0], 12), at(ins[2], 8), at(ins[1], 12), seed,
+                                                       off, T, at(outs[0], 12), at(outs[1], 4), at(outs[2], 4), o, stream)
             run_h, run_end, base = [], [], None
             return r
         prev_end = None
@@ -195,34 +171,28 @@ class MaterialTable:
             raise ValueError(f"material ids must be in [0, {len(self) + extra_bins})")
         return perm, counts
 
-    def _plan(self, material_id, n_rows: int):
+    def _plan(self, material_id, n_rows: Optional[int] = None):
         """(rows, counts, seg_end): `rows` = the bucketed order of the lanes that carry a material (lanes of the
-        plan's extra bins sort behind them and are not evaluated), `counts` per material."""
+        plan's extra bins sort behind them and are not evaluated), `counts` per material.  ``n_rows``: the rows of the
+        lane-ordered batch the plan must cover; None for arrays that are in bucket order already, which only a plan describes."""
+        if n_rows is None and not isinstance(material_id, tuple):
+            raise ValueError("bucketed=True needs a plan from bucket()")
         perm, counts = self._buckets(material_id)
-        if perm.shape[0] != n_rows:
+        if n_rows is not None and perm.shape[0] != n_rows:
             raise ValueError(f"the bucketing plan covers {perm.shape[0]} rows, the batch has {n_rows}")
         counts = counts[: len(self)]
         n_mat = sum(counts)
-        rows = perm if n_mat == n_rows else perm[:n_mat]
-        return rows, counts, list(__import__("itertools").accumulate(counts))
+        return perm if n_mat == perm.shape[0] else perm[:n_mat], counts, list(accumulate(counts))
 
     def _chk_in(self, t, cols, name, n=None):
         return self.samplers[0]._chk(t, cols, name, n)
 
     # -- bucketed flow: a renderer keeps a wavefront in bucket order across its sample() and pdf() calls and scatters
     # once at the end, instead of gathering the inputs and scattering the outputs in every call -----------------------
-    def _plan_bucketed(self, plan):
-        if not isinstance(plan, tuple):
-            raise ValueError("bucketed=True needs a plan from bucket()")
-        perm, counts = self._buckets(plan)
-        counts = counts[: len(self)]
-        n_mat = sum(counts)
-        return perm[:n_mat] if n_mat != perm.shape[0] else perm, counts, list(__import__("itertools").accumulate(counts))
-
     def gather(self, plan, *tensors):
         """Rows of the lanes that carry a material, in bucket order (what ``bucketed=True`` calls take and return).
         A single fp32 [N,3] array (the wavefront's ``wi``) goes through the native one-pass kernel."""
-        rows, _, _ = self._plan_bucketed(plan)
+        rows, _, _ = self._plan(plan)
         if (len(tensors) == 1 and tensors[0].is_cuda and tensors[0].dtype == torch.float32 and tensors[0].dim() == 2
                 and tensors[0].shape[1] == 3 and tensors[0].is_contiguous() and rows.is_contiguous()):
             wi = tensors[0]
@@ -239,7 +209,7 @@ class MaterialTable:
         """Inverse of ``gather``: bucket-ordered results back to the callers' lane order (lanes without a material: 0).
         The usual triple of a wavefront — (wo [n,3], pdf [n], pdf [n]) or (wo, pdf) — is written in ONE native pass."""
         perm, _ = plan
-        rows, _, _ = self._plan_bucketed(plan)
+        rows, _, _ = self._plan(plan)
         n, k = perm.shape[0], rows.shape[0]
         mk = torch.empty if k == n else torch.zeros
 
@@ -269,6 +239,61 @@ class MaterialTable:
         sort behind the materials, are not evaluated, and their outputs are zero."""
         return self._buckets(material_id, extra_bins)
 
+    def _serve(self, which, material_id, ins, seed=0, offset=0, T=None, segmented=True, form="gathered", rng="lane",
+               ctx=None, ctx_fill=None):
+        """The skeleton of sample() / pdf() / sample_pdf(): ``ins`` (``wi`` first, in the order ``FlowSampler.plugin_<which>`` takes
+        them) -> (results, (bucket-ordered inputs, bucket-ordered results, rows, seg_end)).  ``form``: how the launches see the
+        arrays — "gathered": bucket-ordered copies, the results scattered back to lane order; "bucketed": the arrays are in
+        bucket order already and the results stay in it; "direct": the lane-ordered arrays themselves, read and written through
+        the bucket permutation."""
+        if ctx is not None and not segmented:
+            raise ValueError("ctx= is a feature of the segmented path (segmented=False issues one plain call per bucket)")
+        if rng not in ("lane", "bucketed"):
+            raise ValueError("rng must be 'lane' or 'bucketed'")
+        wi = ins[0]
+        n, dev = wi.shape[0], wi.device
+        rows, counts, seg_end = self._plan(material_id, None if form == "bucketed" else n)
+        if form == "bucketed" and n != rows.shape[0]:
+            raise ValueError(f"bucketed wi has {n} rows, the plan has {rows.shape[0]} material lanes")
+        rows = rows.contiguous()
+        direct, full = form == "direct", rows.shape[0] == n   # (not full: lanes without a material, their results are zeros)
+        ins_s = tuple(None if t is None else t[rows].contiguous() for t in ins) if form == "gathered" else tuple(ins)
+
+        def new(mk, k):
+            return tuple(mk((k, 3) if cols == 3 else (k,), dtype=torch.float32, device=dev)
+                         for cols in {"sample": (3, 1), "pdf": (1,), "sample_pdf": (3, 1, 1)}[which])
+        outs_s = new(torch.zeros if direct and not full else torch.empty, ins_s[0].shape[0])
+        # the Philox counter of a row: offset + its ORIGINAL lane (what the direct form draws by construction), or + its bucketed row
+        rng_rows = rows if rng == "lane" and which != "pdf" and not direct else None
+        with torch.cuda.device(dev):
+            if segmented:
+                for (dom, w, nh, prec, Tm, var), members in self._groups().items():
+                    self._multi(which, members, seg_end, Tm if T is None else T, var, ins_s, outs_s, seed, offset, ctx=ctx,
+                                gkey=(dom, w, nh, prec, var), rng_rows=rng_rows, ctx_fill=ctx_fill,
+                                direct_rows=rows if direct else None)
+            else:   # one call per bucket, same Philox keying as the segmented path
+                lo = 0
+                for m, c in enumerate(counts):
+                    if c == 0:
+                        continue
+                    sl = slice(lo, lo + c)
+                    if direct:
+                        a, o, kw = ins_s, outs_s, dict(row_index=rows[sl])
+                    else:
+                        a, o, kw = [None if t is None else t[sl] for t in ins_s], tuple(t[sl] for t in outs_s), {}
+                    if which != "pdf":
+                        kw.update(seed=seed, offset=offset if direct or rng_rows is not None else offset + lo,
+                                  rng_index=None if rng_rows is None else rng_rows[sl])
+                    getattr(self.samplers[m], "plugin_" + which)(*a, T=self.T[m] if T is None else T, variant=self.variant[m],
+                                                                 out=o[0] if which == "pdf" else o, **kw)
+                    lo += c
+        outs = outs_s
+        if form == "gathered":
+            outs = new(torch.empty if full else torch.zeros, n)
+            for t, t_s in zip(outs, outs_s):
+                t[rows] = t_s
+        return outs, (ins_s, outs_s, rows, seg_end)
+
     def sample(self, material_id: torch.Tensor, wi: torch.Tensor, seed: int = 0, offset: int = 0,
                T: Optional[int] = None, x0: Optional[torch.Tensor] = None, segmented: bool = True,
                bucketed: bool = False, ctx: Optional[dict] = None, rng: str = "lane", ctx_fill: bool = True,
@@ -287,168 +312,37 @@ class MaterialTable:
         order THROUGH the bucket permutation (``bsdfd_opts.row_index``); same results bit for bit (``rng="lane"`` only)."""
         wi = self._chk_in(wi, 3, "wi")
         x0 = self._chk_in(x0, 2, "x0", wi.shape[0])
-        if ctx is not None and not segmented:
-            raise ValueError("ctx= is a feature of the segmented path (segmented=False issues one plain call per bucket)")
-        if direct:
-            if bucketed or rng != "lane":
-                raise ValueError("direct=True takes lane-ordered arrays and draws with rng='lane'")
-            rows, counts, seg_end = self._plan(material_id, wi.shape[0])
-            rows = rows.contiguous()
-            mk = torch.empty if rows.shape[0] == wi.shape[0] else torch.zeros  # lanes without a material: zeros
-            wo = mk(wi.shape, dtype=torch.float32, device=wi.device)
-            pdf = mk(wi.shape[0], dtype=torch.float32, device=wi.device)
-            with torch.cuda.device(wi.device):
-                if segmented:
-                    for (dom, w, nh, prec, Tm, var), members in self._groups().items():
-                        self._multi("sample", members, seg_end, Tm if T is None else T, var, wi, x0, seed, offset, wo, pdf,
-                                    ctx=ctx, gkey=(dom, w, nh, prec, var), ctx_fill=ctx_fill, direct_rows=rows)
-                else:
-                    lo = 0
-                    for m, n in enumerate(counts):
-                        if n:
-                            self.samplers[m].plugin_sample(wi, x0, T=self.T[m] if T is None else T, variant=self.variant[m],
-                                                           seed=seed, offset=offset, out=(wo, pdf), row_index=rows[lo:lo + n])
-                        lo += n
-            return wo, pdf
-        if bucketed:
-            rows, counts, seg_end = self._plan_bucketed(material_id)
-            if wi.shape[0] != rows.shape[0]:
-                raise ValueError(f"bucketed wi has {wi.shape[0]} rows, the plan has {rows.shape[0]} material lanes")
-            wi_s, x0_s = wi, x0
-        else:
-            rows, counts, seg_end = self._plan(material_id, wi.shape[0])
-            wi_s = wi[rows].contiguous()
-            x0_s = None if x0 is None else x0[rows].contiguous()
-        wo_s = torch.empty_like(wi_s)
-        pdf_s = torch.empty(wi_s.shape[0], dtype=torch.float32, device=wi.device)
-        if rng not in ("lane", "bucketed"):
-            raise ValueError("rng must be 'lane' or 'bucketed'")
-        rng_rows = rows.contiguous() if rng == "lane" else None
-        if segmented:
-            with torch.cuda.device(wi.device):
-                for (dom, w, nh, prec, Tm, var), members in self._groups().items():
-                    self._multi("sample", members, seg_end, Tm if T is None else T, var, wi_s, x0_s, seed, offset,
-                                wo_s, pdf_s, ctx=ctx, gkey=(dom, w, nh, prec, var), rng_rows=rng_rows, ctx_fill=ctx_fill)
-        else:
-            lo = 0
-            for m, n in enumerate(counts):
-                if n == 0:
-                    continue
-                sl = slice(lo, lo + n)
-                # same Philox keying as the segmented path
-                self.samplers[m].plugin_sample(wi_s[sl], None if x0_s is None else x0_s[sl],
-                                               T=self.T[m] if T is None else T, variant=self.variant[m],
-                                               seed=seed, offset=offset if rng_rows is not None else offset + lo,
-                                               out=(wo_s[sl], pdf_s[sl]),
-                                               rng_index=None if rng_rows is None else rng_rows[sl])
-                lo += n
-        if bucketed:
-            return wo_s, pdf_s
-        mk = torch.empty if rows.shape[0] == wi.shape[0] else torch.zeros  # lanes without a material: zeros
-        wo = mk(wi.shape, dtype=torch.float32, device=wi.device)
-        pdf = mk(wi.shape[0], dtype=torch.float32, device=wi.device)
-        wo[rows] = wo_s
-        pdf[rows] = pdf_s
-        return wo, pdf
+        if direct and (bucketed or rng != "lane"):
+            raise ValueError("direct=True takes lane-ordered arrays and draws with rng='lane'")
+        return self._serve("sample", material_id, (wi, x0), seed, offset, T, segmented,
+                           "direct" if direct else "bucketed" if bucketed else "gathered", rng, ctx, ctx_fill)[0]
 
     def sample_pdf(self, material_id, wi: torch.Tensor, wl: torch.Tensor, seed: int = 0, offset: int = 0,
                    T: Optional[int] = None, x0: Optional[torch.Tensor] = None, return_bucketed: bool = False,
                    rng: str = "lane", direct: bool = False):
         """sample(wi) and pdf(wi, wl) for the same material-tagged intersections, one launch per kernel
-        signature (``bsdfd_plugin_sample_pdf_multi``) -> (wo [N,3], pdf(wo) [N], pdf(wl) [N]) in the callers' order."""
+        signature -> (wo [N,3], pdf(wo) [N], pdf(wl) [N]) in the callers' order."""
         wi = self._chk_in(wi, 3, "wi")
         wl = self._chk_in(wl, 3, "wl", wi.shape[0])
         x0 = self._chk_in(x0, 2, "x0", wi.shape[0])
-        rows, counts, seg_end = self._plan(material_id, wi.shape[0])  # lanes of the extra bins carry no material
-        n_mat = rows.shape[0]
-        if direct:   # through the bucket permutation: no gathered copies, results land in lane order
-            if return_bucketed or rng != "lane":
-                raise ValueError("direct=True returns lane-ordered arrays only and draws with rng='lane'")
-            mk = torch.empty if n_mat == wi.shape[0] else torch.zeros
-            wo = mk(wi.shape, dtype=torch.float32, device=wi.device)
-            po = mk(wi.shape[0], dtype=torch.float32, device=wi.device)
-            pl = mk(wi.shape[0], dtype=torch.float32, device=wi.device)
-            with torch.cuda.device(wi.device):
-                for (dom, w, nh, prec, Tm, var), members in self._groups().items():
-                    self._multi("sample_pdf", members, seg_end, Tm if T is None else T, var, wi, (x0, wl), seed, offset,
-                                wo, (po, pl), direct_rows=rows.contiguous())
-            return wo, po, pl
-        wi_s, wl_s = wi[rows].contiguous(), wl[rows].contiguous()
-        x0_s = None if x0 is None else x0[rows].contiguous()
-        wo_s = torch.empty_like(wi_s)
-        po_s = torch.empty(n_mat, dtype=torch.float32, device=wi.device)
-        pl_s = torch.empty_like(po_s)
-        with torch.cuda.device(wi.device):
-            for (dom, w, nh, prec, Tm, var), members in self._groups().items():
-                self._multi("sample_pdf", members, seg_end, Tm if T is None else T, var, wi_s, (x0_s, wl_s), seed,
-                            offset, wo_s, (po_s, pl_s), rng_rows=rows.contiguous() if rng == "lane" else None)
-        full = n_mat == wi.shape[0]
-        mk = torch.empty if full else torch.zeros
-        wo = mk(wi.shape, dtype=torch.float32, device=wi.device)
-        po = mk(wi.shape[0], dtype=torch.float32, device=wi.device)
-        pl = mk(wi.shape[0], dtype=torch.float32, device=wi.device)
-        wo[rows] = wo_s
-        po[rows] = po_s
-        pl[rows] = pl_s
+        if direct and (return_bucketed or rng != "lane"):
+            raise ValueError("direct=True returns lane-ordered arrays only and draws with rng='lane'")
+        outs, (ins_s, outs_s, rows, seg_end) = self._serve("sample_pdf", material_id, (wi, wl, x0), seed, offset, T,
+                                                           form="direct" if direct else "gathered", rng=rng)
         if return_bucketed:  # the bucket-ordered arrays too (material m = rows seg_end[m-1] .. seg_end[m]) and `rows`
-            return wo, po, pl, dict(wi=wi_s, wl=wl_s, wo=wo_s, pdf_o=po_s, pdf_l=pl_s, rows=rows, seg_end=seg_end)
-        return wo, po, pl
+            return outs + (dict(wi=ins_s[0], wl=ins_s[1], wo=outs_s[0], pdf_o=outs_s[1], pdf_l=outs_s[2], rows=rows,
+                                seg_end=seg_end),)
+        return outs
 
     def pdf(self, material_id: torch.Tensor, wi: torch.Tensor, wo: torch.Tensor, T: Optional[int] = None,
             segmented: bool = True, bucketed: bool = False, ctx: Optional[dict] = None, ctx_fill: bool = False,
             direct: bool = False):
         wi = self._chk_in(wi, 3, "wi")
         wo = self._chk_in(wo, 3, "wo", wi.shape[0])
-        if ctx is not None and not segmented:
-            raise ValueError("ctx= is a feature of the segmented path (segmented=False issues one plain call per bucket)")
-        if direct:   # lane-ordered arrays, read and written through the bucket permutation (see sample())
-            if bucketed:
-                raise ValueError("direct=True takes lane-ordered arrays")
-            rows, counts, seg_end = self._plan(material_id, wi.shape[0])
-            rows = rows.contiguous()
-            pdf = (torch.empty if rows.shape[0] == wi.shape[0] else torch.zeros)(wi.shape[0], dtype=torch.float32, device=wi.device)
-            with torch.cuda.device(wi.device):
-                if segmented:
-                    for (dom, w, nh, prec, Tm, var), members in self._groups().items():
-                        self._multi("pdf", members, seg_end, Tm if T is None else T, var, wi, wo, 0, 0, None, pdf,
-                                    ctx=ctx, gkey=(dom, w, nh, prec, var), ctx_fill=ctx_fill, direct_rows=rows)
-                else:
-                    lo = 0
-                    for m, n in enumerate(counts):
-                        if n:
-                            self.samplers[m].plugin_pdf(wi, wo, T=self.T[m] if T is None else T, variant=self.variant[m],
-                                                        out=pdf, row_index=rows[lo:lo + n])
-                        lo += n
-            return pdf
-        if bucketed:
-            rows, counts, seg_end = self._plan_bucketed(material_id)
-            if wi.shape[0] != rows.shape[0]:
-                raise ValueError(f"bucketed wi has {wi.shape[0]} rows, the plan has {rows.shape[0]} material lanes")
-            wi_s, wo_s = wi, wo
-        else:
-            rows, counts, seg_end = self._plan(material_id, wi.shape[0])
-            wi_s, wo_s = wi[rows].contiguous(), wo[rows].contiguous()
-        pdf_s = torch.empty(wi_s.shape[0], dtype=torch.float32, device=wi.device)
-        if segmented:
-            with torch.cuda.device(wi.device):
-                for (dom, w, nh, prec, Tm, var), members in self._groups().items():
-                    self._multi("pdf", members, seg_end, Tm if T is None else T, var, wi_s, wo_s, 0, 0, None, pdf_s,
-                                ctx=ctx, gkey=(dom, w, nh, prec, var), ctx_fill=ctx_fill)
-        else:
-            lo = 0
-            for m, n in enumerate(counts):
-                if n == 0:
-                    continue
-                sl = slice(lo, lo + n)
-                self.samplers[m].plugin_pdf(wi_s[sl], wo_s[sl], T=self.T[m] if T is None else T,
-                                            variant=self.variant[m], out=pdf_s[sl])
-                lo += n
-        if bucketed:
-            return pdf_s
-        pdf = (torch.empty if rows.shape[0] == wi.shape[0] else torch.zeros)(wi.shape[0], dtype=torch.float32,
-                                                                             device=wi.device)
-        pdf[rows] = pdf_s
-        return pdf
+        if direct and bucketed:
+            raise ValueError("direct=True takes lane-ordered arrays")
+        return self._serve("pdf", material_id, (wi, wo), T=T, segmented=segmented,
+                           form="direct" if direct else "bucketed" if bucketed else "gathered", ctx=ctx, ctx_fill=ctx_fill)[0][0]
 
 
 class _Wavefront:

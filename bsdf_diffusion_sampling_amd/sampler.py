@@ -239,6 +239,106 @@ class FlowSampler:
         return x
 
     # ---- plugin level (tensor core of MyBSDF.sample / MyBSDF.pdf) ----
+    # Every plain entry point of the library is its *_ex twin with no option set (opts = NULL), so each operation has ONE ctypes
+    # call site (*_ex) and one buffer-writing operator (*_ex_out); _prepare() is the one path from the arguments to either.
+    def _chk_index(self, idx, n, name="rng_index"):
+        if idx is None:
+            return None
+        if (not isinstance(idx, torch.Tensor) or idx.device != self.device or idx.dtype != torch.int64 or idx.dim() != 1
+                or (n is not None and idx.shape[0] != n) or not idx.is_contiguous()):
+            raise RuntimeError(f"{name} must be a contiguous int64 tensor" + (f" of shape [{n}]" if n is not None else "") +
+                               f" on {self.device}")
+        return idx
+
+    def _rows(self, row_index, m):
+        """Rows a call processes: all m of the arrays, or the rows a row_index names."""
+        if row_index is None:
+            return m
+        self._chk_index(row_index, None, "row_index")
+        if row_index.shape[0] > m:
+            raise RuntimeError(f"row_index names {row_index.shape[0]} rows, the arrays have {m}")
+        if row_index.numel() and os.environ.get("BSDFD_CHECK_INDEX", "0") not in ("", "0"):
+            # debugging aid (one device->host sync per call): the library cannot check this, it does not know the arrays' lengths
+            lo, hi = int(row_index.min()), int(row_index.max())
+            if lo < 0 or hi >= m:
+                raise RuntimeError(f"row_index entries span [{lo}, {hi}], the arrays have rows [0, {m})")
+            if int(torch.unique(row_index).numel()) != row_index.numel():
+                raise RuntimeError("row_index names a row more than once")
+        return row_index.shape[0]
+
+    def _outputs(self, out, m, names, row_index=None, check=True):
+        """The outputs of a call on m-row arrays, as a tuple laid out like ``names`` = (wo [m,3] or None, pdf [m], ...): fresh
+        ones (zeros under a ``row_index``: the rows it does not name stay untouched; empty otherwise) or the caller's, checked."""
+        if out is None:
+            mk = torch.empty if row_index is None else torch.zeros
+            return ((None if names[0] is None else mk((m, 3), dtype=torch.float32, device=self.device),) +
+                    tuple(mk((m,), dtype=torch.float32, device=self.device) for _ in names[1:]))
+        if check:
+            if names[0] is not None:
+                self._chk(out[0], 3, names[0], m)
+            for t, name in zip(out[1:], names[1:]):
+                self._chk1(t, m, name)
+        return tuple(out)
+
+    def _live_rows(self, active, wi, out, names, dir=None, flags=0):
+        """``active`` mask -> (outputs with their dead rows zeroed, ascending rows of the live lanes).  The mask is compacted
+        before the launch that would check ``wi``, so the row count and the outputs are settled here, for either binding.
+        ``flags``: BSDFD_LIVE_* hemisphere tests on ``wi`` and on ``dir`` = (tensor, columns, name), applied on top of the mask."""
+        from .live import live_rows
+        if self._ops is not None:
+            self._dev_chk(wi, "wi")
+            if wi.dim() != 2:
+                raise RuntimeError(f"wi must have shape [N, 3], got {tuple(wi.shape)}")
+        else:
+            self._chk(wi, 3, "wi")
+        m = wi.shape[0]
+        out = self._outputs(out, m, names)
+        if flags:   # the hemisphere tests read the direction arrays themselves
+            wi, dir = self._chk(wi, 3, "wi"), self._chk(*dir, m)
+        if (not isinstance(active, torch.Tensor) or active.device != self.device or active.dtype not in (torch.bool, torch.uint8)
+                or active.dim() != 1 or active.shape[0] != m):
+            raise RuntimeError(f"active must be a bool / uint8 tensor of shape [{m}] on {self.device}")
+        return out, live_rows(active, wi if flags else None, dir if flags else None, flags, zero=(out + (None,))[:3])
+
+    def _prepare(self, wi, ins, out, names, ctx_out=None, ctx_in=None, rng_index=None, row_index=None, active=None, cull=0):
+        """Arguments of a plugin-level call -> (n, out, opts, row_index): the rows the launch processes (None: a mask without a
+        live lane — ``out`` is the result, nothing is launched), the outputs (None: torch binding, no buffers and no option —
+        the allocating operator serves the call), the ``bsdfd_opts*`` of the ctypes call (None when no option is set) and the
+        ``row_index`` in effect.  ``ins``: the inputs besides ``wi`` as (tensor, columns, name); ``names``: see _outputs;
+        ``cull``: BSDFD_LIVE_* hemisphere tests on wi / ins[0] that a masked call applies on top of the mask."""
+        if active is not None:
+            if row_index is not None or rng_index is not None or ctx_in is not None or ctx_out is not None:
+                raise ValueError("active= cannot be combined with row_index, rng_index or a per-query context: those are indexed "
+                                 "by the call's own rows (compact the mask with live.live_rows and pass row_index instead)")
+            out, rows = self._live_rows(active, wi, out, names, ins[0], cull)
+            if rows.shape[0] == 0:
+                return None, out, None, None
+            if rows.shape[0] < wi.shape[0]:   # (every lane live: the ordinary call)
+                row_index = rows
+        if ctx_out is not None and ctx_in is not None:
+            raise RuntimeError("a call either writes a per-query context (ctx_out) or reads one (ctx_in), not both")
+        ctx = ctx_out if ctx_in is None else ctx_in
+        plain = ctx is None and rng_index is None and row_index is None
+        if self._ops is not None:   # dtype / shape / contiguity of the arrays: checked by the operator
+            self._dev_chk(wi, "wi")
+            if plain:
+                return 0, out, None, None
+            m = wi.shape[0]
+        else:
+            m = self._chk(wi, 3, "wi").shape[0]
+        n = self._rows(row_index, m)
+        if self._ops is None:
+            for t, cols, name in ins:
+                self._chk(t, cols, name, m)
+        if ctx is not None:
+            self._chk_ctx(ctx, n)
+        if rng_index is not None:
+            self._chk_index(rng_index, n)
+        out = self._outputs(out, m, names, row_index, check=self._ops is None)
+        if plain or self._ops is not None:
+            return n, out, None, row_index
+        return n, out, C.byref(_lib.opts(ctx_out=ctx_out, ctx_in=ctx_in, rng_index=rng_index, row_index=row_index)), row_index
+
     def plugin_sample(self, wi, x0=None, T: int = 4, variant: int = _lib.PLUGIN_MEASURED, seed: int = 0,
                       offset: int = 0, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
                       ctx_out: Optional[torch.Tensor] = None, rng_index: Optional[torch.Tensor] = None,
@@ -259,122 +359,20 @@ class FlowSampler:
         of the unmasked call), the dead rows of ``wo`` / ``pdf`` are 0, also in ``out=`` buffers.  One read-back of the live
         count per call.  Not together with ``row_index``, ``rng_index`` or a context (those are indexed by the call's own rows:
         whoever wants both passes ``row_index`` themselves)."""
-        if active is not None:
-            self._no_index_with_active(row_index, rng_index, ctx_in, ctx_out)
-            wi, m = self._chk_wi(wi)
-            if out is None:
-                out = (torch.empty((m, 3), dtype=torch.float32, device=self.device),
-                       torch.empty((m,), dtype=torch.float32, device=self.device))
-            else:
-                out = (self._chk(out[0], 3, "out wo", m), self._chk1(out[1], m, "out pdf"))
-            rows = self._live_rows(active, m, zero=(out[0], out[1], None))
-            if rows.shape[0] == 0:
-                return out
-            if rows.shape[0] < m:
-                return self._plugin_sample_ex(wi, x0, T, variant, seed, offset, out, None, None, row_index=rows)
-        if ctx_out is not None and ctx_in is not None:
-            raise RuntimeError("a call either writes a per-query context (ctx_out) or reads one (ctx_in), not both")
-        if ctx_out is not None or ctx_in is not None or rng_index is not None or row_index is not None:
-            return self._plugin_sample_ex(wi, x0, T, variant, seed, offset, out, ctx_out if ctx_in is None else ctx_in, rng_index,
-                                          ctx_read=ctx_in is not None, row_index=row_index)
-        if self._ops is not None:
-            self._dev_chk(wi, "wi")
-            if out is None:
-                return self._ops.plugin_sample(self._hi, variant, wi, x0, _i64(seed), _i64(offset), T)
-            self._ops.plugin_sample_out(self._hi, variant, wi, x0, _i64(seed), _i64(offset), T, out[0], out[1])
-            return out[0], out[1]
-        wi = self._chk(wi, 3, "wi")
-        n = wi.shape[0]
-        x0 = self._chk(x0, 2, "x0", n)
-        if out is None:
-            wo = torch.empty((n, 3), dtype=torch.float32, device=self.device)
-            pdf = torch.empty((n,), dtype=torch.float32, device=self.device)
+        n, out, o, row_index = self._prepare(wi, ((x0, 2, "x0"),), out, ("out wo", "out pdf"), ctx_out, ctx_in, rng_index,
+                                             row_index, active)
+        if n is None:
+            return out
+        if self._ops is None:
+            with torch.cuda.device(self.device):
+                _lib.check(self._L.bsdfd_plugin_sample_ex(self._h, variant, _ptr(wi), _ptr(x0), seed, offset, n, T,
+                                                          _ptr(out[0]), _ptr(out[1]), o, self._stream()))
+        elif out is None:
+            return self._ops.plugin_sample(self._hi, variant, wi, x0, _i64(seed), _i64(offset), T)
         else:
-            wo, pdf = self._chk(out[0], 3, "out wo", n), self._chk1(out[1], n, "out pdf")
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.bsdfd_plugin_sample(self._h, variant, _ptr(wi), _ptr(x0), seed, offset, n, T,
-                                                   _ptr(wo), _ptr(pdf), self._stream()))
-        return wo, pdf
-
-    def _chk_index(self, idx, n, name="rng_index"):
-        if idx is None:
-            return None
-        if (not isinstance(idx, torch.Tensor) or idx.device != self.device or idx.dtype != torch.int64 or idx.dim() != 1
-                or (n is not None and idx.shape[0] != n) or not idx.is_contiguous()):
-            raise RuntimeError(f"{name} must be a contiguous int64 tensor" + (f" of shape [{n}]" if n is not None else "") +
-                               f" on {self.device}")
-        return idx
-
-    def _rows(self, row_index, m):
-        """Rows a call processes: all m of the arrays, or the rows a row_index names."""
-        self._chk_index(row_index, None, "row_index")
-        if row_index is not None and row_index.shape[0] > m:
-            raise RuntimeError(f"row_index names {row_index.shape[0]} rows, the arrays have {m}")
-        if row_index is not None and row_index.numel() and os.environ.get("BSDFD_CHECK_INDEX", "0") not in ("", "0"):
-            # debugging aid (one device->host sync per call): the library cannot check this, it does not know the arrays' lengths
-            lo, hi = int(row_index.min()), int(row_index.max())
-            if lo < 0 or hi >= m:
-                raise RuntimeError(f"row_index entries span [{lo}, {hi}], the arrays have rows [0, {m})")
-            if int(torch.unique(row_index).numel()) != row_index.numel():
-                raise RuntimeError("row_index names a row more than once")
-        return m if row_index is None else row_index.shape[0]
-
-    # ---- `active` masks (live.py, csrc/live.hip) ----
-    @staticmethod
-    def _no_index_with_active(row_index, rng_index, ctx_in, ctx_out):
-        if row_index is not None or rng_index is not None or ctx_in is not None or ctx_out is not None:
-            raise ValueError("active= cannot be combined with row_index, rng_index or a per-query context: those are indexed by "
-                             "the call's own rows (compact the mask with live.live_rows and pass row_index instead)")
-
-    def _chk_wi(self, wi):
-        """(wi, rows) of a masked call: the mask is compacted before the launch that would check wi."""
-        if self._ops is not None:
-            self._dev_chk(wi, "wi")
-            if wi.dim() != 2:
-                raise RuntimeError(f"wi must have shape [N, 3], got {tuple(wi.shape)}")
-            return wi, wi.shape[0]
-        wi = self._chk(wi, 3, "wi")
-        return wi, wi.shape[0]
-
-    def _live_rows(self, active, m, wi=None, dir=None, flags=0, zero=(None, None, None)):
-        from .live import live_rows
-        if (not isinstance(active, torch.Tensor) or active.device != self.device or active.dtype not in (torch.bool, torch.uint8)
-                or active.dim() != 1 or active.shape[0] != m):
-            raise RuntimeError(f"active must be a bool / uint8 tensor of shape [{m}] on {self.device}")
-        return live_rows(active, wi, dir, flags, zero)
-
-    def _plugin_sample_ex(self, wi, x0, T, variant, seed, offset, out, ctx, rng_index, ctx_read=False, row_index=None):
-        mk = torch.empty if row_index is None else torch.zeros   # (rows a row_index does not name stay untouched)
-        if self._ops is not None:
-            self._dev_chk(wi, "wi")
-            n = self._rows(row_index, wi.shape[0])
-            if ctx is not None:
-                self._chk_ctx(ctx, n)
-            self._chk_index(rng_index, n)
-            if out is None:
-                out = (mk((wi.shape[0], 3), dtype=torch.float32, device=self.device),
-                       mk((wi.shape[0],), dtype=torch.float32, device=self.device))
-            self._ops.plugin_sample_ex_out(self._hi, variant, wi, x0, _i64(seed), _i64(offset), T, out[0], out[1], ctx, rng_index,
-                                           ctx_read, row_index)
-            return out[0], out[1]
-        wi = self._chk(wi, 3, "wi")
-        m = wi.shape[0]
-        n = self._rows(row_index, m)
-        x0 = self._chk(x0, 2, "x0", m)
-        if ctx is not None:
-            self._chk_ctx(ctx, n)
-        self._chk_index(rng_index, n)
-        if out is None:
-            wo = mk((m, 3), dtype=torch.float32, device=self.device)
-            pdf = mk((m,), dtype=torch.float32, device=self.device)
-        else:
-            wo, pdf = self._chk(out[0], 3, "out wo", m), self._chk1(out[1], m, "out pdf")
-        o = (_lib.opts(ctx_in=ctx, rng_index=rng_index, row_index=row_index) if ctx_read
-             else _lib.opts(ctx_out=ctx, rng_index=rng_index, row_index=row_index))
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.bsdfd_plugin_sample_ex(self._h, variant, _ptr(wi), _ptr(x0), seed, offset, n, T,
-                                                      _ptr(wo), _ptr(pdf), C.byref(o), self._stream()))
-        return wo, pdf
+            self._ops.plugin_sample_ex_out(self._hi, variant, wi, x0, _i64(seed), _i64(offset), T, out[0], out[1],
+                                           ctx_out if ctx_in is None else ctx_in, rng_index, ctx_in is not None, row_index)
+        return out
 
     def plugin_sample_pdf(self, wi, wl, x0=None, T: int = 4, variant: int = _lib.PLUGIN_MEASURED, seed: int = 0,
                           offset: int = 0, out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None,
@@ -382,71 +380,22 @@ class FlowSampler:
                           active: Optional[torch.Tensor] = None):
         """sample(wi) and pdf(wi, wl) of the same intersections in ONE launch (the per-query prologue is
         shared): -> (wo [N,3], pdf(wo) [N], pdf(wl) [N]), identical to plugin_sample + plugin_pdf(wi, wl).
-        ``rng_index`` / ``row_index`` / ``active``: as in ``plugin_sample`` (bsdfd_plugin_sample_pdf_ex; the fused call takes no
+        ``rng_index`` / ``row_index`` / ``active``: as in ``plugin_sample`` (the fused call takes no
         per-query context).  A masked call culls by the mask alone: ``wo`` / ``pdf(wo)`` are defined below the horizon too."""
-        if active is not None:
-            self._no_index_with_active(row_index, rng_index, None, None)
-            wi, m = self._chk_wi(wi)
-            if out is None:
-                out = (torch.empty((m, 3), dtype=torch.float32, device=self.device),
-                       torch.empty((m,), dtype=torch.float32, device=self.device),
-                       torch.empty((m,), dtype=torch.float32, device=self.device))
-            else:
-                out = (self._chk(out[0], 3, "out wo", m), self._chk1(out[1], m, "out pdf(wo)"), self._chk1(out[2], m, "out pdf(wl)"))
-            rows = self._live_rows(active, m, zero=out)
-            if rows.shape[0] == 0:
-                return out
-            if rows.shape[0] < m:
-                row_index = rows
-        if rng_index is not None or row_index is not None:
-            mk = torch.empty if row_index is None else torch.zeros   # (rows a row_index does not name stay untouched)
-            if self._ops is not None:
-                self._dev_chk(wi, "wi")
-                n = self._rows(row_index, wi.shape[0])
-                self._chk_index(rng_index, n)
-                if out is None:
-                    out = (mk((wi.shape[0], 3), dtype=torch.float32, device=self.device),
-                           mk((wi.shape[0],), dtype=torch.float32, device=self.device),
-                           mk((wi.shape[0],), dtype=torch.float32, device=self.device))
-                self._ops.plugin_sample_pdf_ex_out(self._hi, variant, wi, wl, x0, _i64(seed), _i64(offset), T, out[0], out[1], out[2],
-                                                   rng_index, row_index)
-                return out[0], out[1], out[2]
-            wi = self._chk(wi, 3, "wi")
-            m = wi.shape[0]
-            n = self._rows(row_index, m)
-            wl = self._chk(wl, 3, "wl", m)
-            x0 = self._chk(x0, 2, "x0", m)
-            self._chk_index(rng_index, n)
-            if out is None:
-                wo = mk((m, 3), dtype=torch.float32, device=self.device)
-                pdf_o = mk((m,), dtype=torch.float32, device=self.device)
-                pdf_l = mk((m,), dtype=torch.float32, device=self.device)
-            else:
-                wo, pdf_o, pdf_l = (self._chk(out[0], 3, "out wo", m), self._chk1(out[1], m, "out pdf(wo)"),
-                                    self._chk1(out[2], m, "out pdf(wl)"))
-            o = _lib.opts(rng_index=rng_index, row_index=row_index)
+        n, out, o, row_index = self._prepare(wi, ((wl, 3, "wl"), (x0, 2, "x0")), out, ("out wo", "out pdf(wo)", "out pdf(wl)"),
+                                             rng_index=rng_index, row_index=row_index, active=active)
+        if n is None:
+            return out
+        if self._ops is None:
             with torch.cuda.device(self.device):
                 _lib.check(self._L.bsdfd_plugin_sample_pdf_ex(self._h, variant, _ptr(wi), _ptr(x0), _ptr(wl), seed, offset, n, T,
-                                                              _ptr(wo), _ptr(pdf_o), _ptr(pdf_l), C.byref(o), self._stream()))
-            return wo, pdf_o, pdf_l
-        if self._ops is not None and out is None:
-            self._dev_chk(wi, "wi")
+                                                              _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), o, self._stream()))
+        elif out is None:
             return self._ops.plugin_sample_pdf(self._hi, variant, wi, wl, x0, _i64(seed), _i64(offset), T)
-        wi = self._chk(wi, 3, "wi")
-        n = wi.shape[0]
-        wl = self._chk(wl, 3, "wl", n)
-        x0 = self._chk(x0, 2, "x0", n)
-        if out is None:
-            wo = torch.empty((n, 3), dtype=torch.float32, device=self.device)
-            pdf_o = torch.empty((n,), dtype=torch.float32, device=self.device)
-            pdf_l = torch.empty((n,), dtype=torch.float32, device=self.device)
         else:
-            wo, pdf_o, pdf_l = (self._chk(out[0], 3, "out wo", n), self._chk1(out[1], n, "out pdf(wo)"),
-                                self._chk1(out[2], n, "out pdf(wl)"))
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.bsdfd_plugin_sample_pdf(self._h, variant, _ptr(wi), _ptr(x0), _ptr(wl), seed, offset,
-                                                       n, T, _ptr(wo), _ptr(pdf_o), _ptr(pdf_l), self._stream()))
-        return wo, pdf_o, pdf_l
+            self._ops.plugin_sample_pdf_ex_out(self._hi, variant, wi, wl, x0, _i64(seed), _i64(offset), T, out[0], out[1], out[2],
+                                               rng_index, row_index)
+        return out
 
     def plugin_pdf(self, wi, wo, T: int = 4, variant: int = _lib.PLUGIN_MEASURED,
                    out: Optional[torch.Tensor] = None, ctx_in: Optional[torch.Tensor] = None,
@@ -458,56 +407,18 @@ class FlowSampler:
         ``row_index``: as in ``plugin_sample`` (row i reads wi / wo at row ``row_index[i]`` and writes pdf there).
         ``active``: as in ``plugin_sample`` (rendering/brdf_measured_disk.py:112).  For ``PLUGIN_MEASURED`` the lanes with
         ``wi.z <= 0`` or ``wo.z <= 0`` are culled as well: their pdf is exactly 0 in the unmasked call too."""
-        if active is not None:
-            self._no_index_with_active(row_index, None, ctx_in, ctx_out)
-            wi, m = self._chk_wi(wi)
-            out = torch.empty((m,), dtype=torch.float32, device=self.device) if out is None else self._chk1(out, m, "out pdf")
-            if variant == _lib.PLUGIN_MEASURED:
-                rows = self._live_rows(active, m, wi=self._chk(wi, 3, "wi"), dir=self._chk(wo, 3, "wo", m),
-                                       flags=_lib.LIVE_WI_UPPER | _lib.LIVE_DIR_UPPER, zero=(None, out, None))
-            else:
-                rows = self._live_rows(active, m, zero=(None, out, None))
-            if rows.shape[0] == 0:
-                return out
-            if rows.shape[0] < m:
-                row_index = rows
-        if ctx_out is not None and ctx_in is not None:
-            raise RuntimeError("a call either writes a per-query context (ctx_out) or reads one (ctx_in), not both")
-        if ctx_in is not None or ctx_out is not None or row_index is not None:
-            ctx, write = (ctx_in, False) if ctx_out is None else (ctx_out, True)
-            mk = torch.empty if row_index is None else torch.zeros
-            if self._ops is not None:
-                self._dev_chk(wi, "wi")
-                n = self._rows(row_index, wi.shape[0])
-                if ctx is not None:
-                    self._chk_ctx(ctx, n)
-                if out is None:
-                    out = mk((wi.shape[0],), dtype=torch.float32, device=self.device)
-                self._ops.plugin_pdf_ex_out(self._hi, variant, wi, wo, T, out, ctx, write, row_index)
-                return out
-            wi = self._chk(wi, 3, "wi")
-            m = wi.shape[0]
-            n = self._rows(row_index, m)
-            wo = self._chk(wo, 3, "wo", m)
-            if ctx is not None:
-                self._chk_ctx(ctx, n)
-            pdf = mk((m,), dtype=torch.float32, device=self.device) if out is None else self._chk1(out, m, "out pdf")
-            o = _lib.opts(ctx_out=ctx, row_index=row_index) if write else _lib.opts(ctx_in=ctx, row_index=row_index)
+        n, out, o, row_index = self._prepare(wi, ((wo, 3, "wo"),), None if out is None else (None, out), (None, "out pdf"),
+                                             ctx_out, ctx_in, row_index=row_index, active=active,
+                                             cull=_lib.LIVE_WI_UPPER | _lib.LIVE_DIR_UPPER if variant == _lib.PLUGIN_MEASURED else 0)
+        if n is None:
+            return out[1]
+        if self._ops is None:
             with torch.cuda.device(self.device):
-                _lib.check(self._L.bsdfd_plugin_pdf_ex(self._h, variant, _ptr(wi), _ptr(wo), n, T, _ptr(pdf),
-                                                       C.byref(o), self._stream()))
-            return pdf
-        if self._ops is not None:
-            self._dev_chk(wi, "wi")
-            if out is None:
-                return self._ops.plugin_pdf(self._hi, variant, wi, wo, T)
-            self._ops.plugin_pdf_out(self._hi, variant, wi, wo, T, out)
-            return out
-        wi = self._chk(wi, 3, "wi")
-        n = wi.shape[0]
-        wo = self._chk(wo, 3, "wo", n)
-        pdf = torch.empty((n,), dtype=torch.float32, device=self.device) if out is None else self._chk1(out, n, "out pdf")
-        with torch.cuda.device(self.device):
-            _lib.check(self._L.bsdfd_plugin_pdf(self._h, variant, _ptr(wi), _ptr(wo), n, T, _ptr(pdf),
-                                                self._stream()))
-        return pdf
+                _lib.check(self._L.bsdfd_plugin_pdf_ex(self._h, variant, _ptr(wi), _ptr(wo), n, T, _ptr(out[1]), o,
+                                                       self._stream()))
+        elif out is None:
+            return self._ops.plugin_pdf(self._hi, variant, wi, wo, T)
+        else:
+            self._ops.plugin_pdf_ex_out(self._hi, variant, wi, wo, T, out[1], ctx_in if ctx_out is None else ctx_out,
+                                        ctx_out is not None, row_index)
+        return out[1]
