@@ -47,6 +47,8 @@ EXPORTS = (
     "bsdfd_measured_sample_weight",
     "bsdfd_measured_table_create", "bsdfd_measured_table_destroy", "bsdfd_measured_eval_table",
     "bsdfd_measured_sample_weight_table",
+    "bsdfd_measured_has_luminance", "bsdfd_measured_sample", "bsdfd_measured_pdf", "bsdfd_measured_sample_table",
+    "bsdfd_measured_pdf_table",
     "bsdfd_set_profiling", "bsdfd_profile_read", "bsdfd_profile_read_op", "bsdfd_profile_clock_mhz", "bsdfd_last_kernel_ms", "bsdfd_shader_clock_mhz",
     "bsdfd_last_error", "bsdfd_version", "bsdfd_abi_version",
 )
@@ -408,6 +410,11 @@ def lib():
     L.bsdfd_measured_table_destroy.restype = None
     L.bsdfd_measured_eval_table.argtypes = [vp, fp, fp, fp, fp, i64, C.POINTER(C.c_float), fp, fp, vp]
     L.bsdfd_measured_sample_weight_table.argtypes = [vp, fp, fp, fp, fp, fp, i64, C.POINTER(C.c_float), C.c_float, fp, fp, vp]
+    L.bsdfd_measured_has_luminance.argtypes = [vp, C.POINTER(i32)]
+    L.bsdfd_measured_sample.argtypes = [vp, fp, fp, fp, i64, C.POINTER(C.c_float), fp, fp, fp, vp]
+    L.bsdfd_measured_pdf.argtypes = [vp, fp, fp, fp, i64, fp, vp]
+    L.bsdfd_measured_sample_table.argtypes = [vp, fp, fp, fp, fp, i64, C.POINTER(C.c_float), fp, fp, fp, vp]
+    L.bsdfd_measured_pdf_table.argtypes = [vp, fp, fp, fp, fp, i64, fp, vp]
     L.bsdfd_bucket_workspace_bytes.argtypes = [i64, i32]
     L.bsdfd_bucket_workspace_bytes.restype = i64
     L.bsdfd_bucket_by_material.argtypes = [fp, i64, i32, fp, fp, fp, i64, vp]

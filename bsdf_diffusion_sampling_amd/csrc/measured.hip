@@ -14,6 +14,9 @@
 // tensor file and builds the normalised VNDF with its conditional / marginal CDFs in double;
 // the kernel is one thread per (wi, wo) pair: ~60 gathers from tables that total < 1 MB (L2-resident),
 // i.e. latency- not bandwidth-bound; it is not part of the neural hot path.
+//
+// The same files carry their own importance sampler (luminance warp, VNDF warp, reflection about the half vector):
+// bsdfd_measured_sample / bsdfd_measured_pdf below; the device side of both is measured_dev.h.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -93,6 +96,27 @@ __global__ __launch_bounds__(256) void measured_weight_kernel(MeasuredDev m, con
     weight[3 * q] = keep ? v[0] : 0.0f; weight[3 * q + 1] = keep ? v[1] : 0.0f; weight[3 * q + 2] = keep ? v[2] : 0.0f;
 }
 
+// sample(): the file's own importance sampler (measured_dev.h), one query per lane
+__global__ __launch_bounds__(256) void measured_sample_kernel(MeasuredDev m, const float* __restrict__ wi,
+                                                              const float* __restrict__ u,
+                                                              const unsigned char* __restrict__ active, long long n,
+                                                              Tint tint, float* __restrict__ wo_out,
+                                                              float* __restrict__ pdf_out, float* __restrict__ weight_out) {
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    sample_row(m, wi, u, active, q, tint, wo_out, pdf_out, weight_out);
+}
+
+// pdf(): the density of that sampler at a given wo
+__global__ __launch_bounds__(256) void measured_pdf_kernel(MeasuredDev m, const float* __restrict__ wi,
+                                                           const float* __restrict__ wo,
+                                                           const unsigned char* __restrict__ active, long long n,
+                                                           float* __restrict__ pdf_out) {
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    pdf_row(m, wi, wo, active, q, pdf_out);
+}
+
 int upload(bsdfd_measured_ctx* h, const std::vector<float>& v, const float** out) {
     void* p = nullptr;
     HIP_TRY(hipMalloc(&p, v.size() * sizeof(float)));
@@ -169,11 +193,22 @@ int bsdfd_measured_create_from_file(const char* path, bsdfd_measured_handle* out
     const Field *phi = want("phi_i", 10, 1), *theta = want("theta_i", 10, 1), *sigma = want("sigma", 10, 2),
                 *ndf = want("ndf", 10, 2), *vndf = want("vndf", 10, 4), *rgb = want("rgb", 10, 5),
                 *jac = want("jacobian", 1, 1);
+    // optional: the luminance warp of the file's own sampler (bsdfd_measured_sample); eval() does not read it
+    const Field* lum = nullptr;
+    if (auto it = fields.find("luminance"); it != fields.end()) {
+        lum = &it->second;
+        if (lum->dtype != 10 || lum->shape.size() != 4)
+            return bsdfd_fail_(BSDFD_EIO, std::string(path) + ": luminance must be an fp32 field of rank 4 [n_phi][n_theta][h][w]");
+    }
     if (!phi || !theta || !sigma || !ndf || !vndf || !rgb || !jac)
         return bsdfd_fail_(BSDFD_EIO, std::string(path) + ": expected fp32 fields phi_i, theta_i, sigma, ndf, vndf, rgb and u8 "
                                                            "jacobian (spectral files are not supported; use the *_rgb.bsdf flavour)");
     for (const Field* f : {phi, theta, sigma, ndf, vndf, rgb})  // table extents are used as int indices below
         for (auto dim : f->shape)
+            if (dim < 1 || dim > (1u << 20))
+                return bsdfd_fail_(BSDFD_EIO, std::string(path) + ": table dimension out of range [1, 2^20]");
+    if (lum)
+        for (auto dim : lum->shape)
             if (dim < 1 || dim > (1u << 20))
                 return bsdfd_fail_(BSDFD_EIO, std::string(path) + ": table dimension out of range [1, 2^20]");
     if (jac->shape[0] < 1) return bsdfd_fail_(BSDFD_EIO, std::string(path) + ": empty jacobian field");
@@ -183,6 +218,8 @@ int bsdfd_measured_create_from_file(const char* path, bsdfd_measured_handle* out
         rgb->shape[3] < 2 || rgb->shape[4] < 2 || ndf->shape[0] < 2 || ndf->shape[1] < 2 || sigma->shape[0] < 2 ||
         sigma->shape[1] < 2)
         return bsdfd_fail_(BSDFD_EIO, std::string(path) + ": inconsistent table shapes");
+    if (lum && ((int)lum->shape[0] != n_phi || (int)lum->shape[1] != n_theta || lum->shape[2] < 2 || lum->shape[3] < 2))
+        return bsdfd_fail_(BSDFD_EIO, std::string(path) + ": luminance does not match phi_i / theta_i (inconsistent table shapes)");
 
     int devid = -1;
     HIP_TRY(hipGetDevice(&devid));
@@ -204,35 +241,41 @@ int bsdfd_measured_create_from_file(const char* path, bsdfd_measured_handle* out
         d.fold_y = std::sin(mid) < 0.0 ? -1.0f : 1.0f;
     }
 
-    // VNDF: per-slice normalisation and CDFs in double.  Integrals in patch units: a linear segment
+    // Warps (VNDF, luminance): per-slice normalisation and CDFs in double.  Integrals in patch units: a linear segment
     // integrates to the mean of its end points, a row of patches to the mean of its two vertex rows.
-    const int vh = (int)vndf->shape[2], vw = (int)vndf->shape[3];
-    const std::vector<float> vraw = as_f32(*vndf);
-    std::vector<float> vdata(vraw.size()), vcond(vraw.size()), vmarg((size_t)n_phi * n_theta * vh);
-    std::vector<double> cond((size_t)vh * vw), marg(vh);
-    for (int s = 0; s < n_phi * n_theta; ++s) {
-        const float* src = vraw.data() + (size_t)s * vh * vw;
-        for (int y = 0; y < vh; ++y) {
-            double acc = 0.0;
-            cond[(size_t)y * vw] = 0.0;
-            for (int x = 1; x < vw; ++x) {
-                acc += 0.5 * ((double)src[(size_t)y * vw + x - 1] + (double)src[(size_t)y * vw + x]);
-                cond[(size_t)y * vw + x] = acc;
+    auto build_warp = [&](const Field& f, std::vector<float>& data, std::vector<float>& cdf_cond, std::vector<float>& cdf_marg) {
+        const int vh = (int)f.shape[2], vw = (int)f.shape[3];
+        const std::vector<float> vraw = as_f32(f);
+        data.resize(vraw.size()); cdf_cond.resize(vraw.size()); cdf_marg.resize((size_t)n_phi * n_theta * vh);
+        std::vector<double> cond((size_t)vh * vw), marg(vh);
+        for (int s = 0; s < n_phi * n_theta; ++s) {
+            const float* src = vraw.data() + (size_t)s * vh * vw;
+            for (int y = 0; y < vh; ++y) {
+                double acc = 0.0;
+                cond[(size_t)y * vw] = 0.0;
+                for (int x = 1; x < vw; ++x) {
+                    acc += 0.5 * ((double)src[(size_t)y * vw + x - 1] + (double)src[(size_t)y * vw + x]);
+                    cond[(size_t)y * vw + x] = acc;
+                }
             }
+            double acc = 0.0;
+            marg[0] = 0.0;
+            for (int y = 1; y < vh; ++y) {
+                acc += 0.5 * (cond[(size_t)(y - 1) * vw + vw - 1] + cond[(size_t)y * vw + vw - 1]);
+                marg[y] = acc;
+            }
+            const double scale = acc > 0.0 ? 1.0 / acc : 0.0;
+            for (size_t i = 0; i < (size_t)vh * vw; ++i) {
+                data[(size_t)s * vh * vw + i] = (float)((double)src[i] * scale);
+                cdf_cond[(size_t)s * vh * vw + i] = (float)(cond[i] * scale);
+            }
+            for (int y = 0; y < vh; ++y) cdf_marg[(size_t)s * vh + y] = (float)(marg[y] * scale);
         }
-        double acc = 0.0;
-        marg[0] = 0.0;
-        for (int y = 1; y < vh; ++y) {
-            acc += 0.5 * (cond[(size_t)(y - 1) * vw + vw - 1] + cond[(size_t)y * vw + vw - 1]);
-            marg[y] = acc;
-        }
-        const double scale = acc > 0.0 ? 1.0 / acc : 0.0;
-        for (size_t i = 0; i < (size_t)vh * vw; ++i) {
-            vdata[(size_t)s * vh * vw + i] = (float)((double)src[i] * scale);
-            vcond[(size_t)s * vh * vw + i] = (float)(cond[i] * scale);
-        }
-        for (int y = 0; y < vh; ++y) vmarg[(size_t)s * vh + y] = (float)(marg[y] * scale);
-    }
+    };
+    const int vh = (int)vndf->shape[2], vw = (int)vndf->shape[3];
+    std::vector<float> vdata, vcond, vmarg, ldata, lcond, lmarg;
+    build_warp(*vndf, vdata, vcond, vmarg);
+    if (lum) build_warp(*lum, ldata, lcond, lmarg);
     int rc = BSDFD_OK;
     auto up = [&](const std::vector<float>& v, const float** dst) {
         if (rc == BSDFD_OK) rc = upload(h, v, dst);
@@ -245,6 +288,14 @@ int bsdfd_measured_create_from_file(const char* path, bsdfd_measured_handle* out
     up(vcond, &d.vndf_cond);
     up(vmarg, &d.vndf_marg);
     up(as_f32(*rgb), &d.rgb.data);
+    d.lum = Table{nullptr, 0, 0};
+    d.lum_cond = d.lum_marg = nullptr;
+    if (lum) {
+        up(ldata, &d.lum.data);
+        up(lcond, &d.lum_cond);
+        up(lmarg, &d.lum_marg);
+        d.lum.h = (int)lum->shape[2]; d.lum.w = (int)lum->shape[3];
+    }
     d.ndf.h = (int)ndf->shape[0]; d.ndf.w = (int)ndf->shape[1];
     d.sigma.h = (int)sigma->shape[0]; d.sigma.w = (int)sigma->shape[1];
     d.vndf.h = vh; d.vndf.w = vw;
@@ -293,6 +344,35 @@ int bsdfd_measured_eval(bsdfd_measured_handle h, const float* wi, const float* w
     const Tint t = tint ? Tint{tint[0], tint[1], tint[2]} : Tint{1.0f, 1.0f, 1.0f};
     hipLaunchKernelGGL(measured_eval_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), h->dev, wi, wo, (long long)n, t, rgb_out);
+    HIP_TRY(hipGetLastError());
+    return BSDFD_OK;
+}
+
+int bsdfd_measured_has_luminance(bsdfd_measured_handle h, int32_t* has_luminance) {
+    if (!h || !has_luminance) return bsdfd_fail_(BSDFD_EINVAL, "null argument");
+    *has_luminance = h->dev.lum.data ? 1 : 0;
+    return BSDFD_OK;
+}
+
+int bsdfd_measured_sample(bsdfd_measured_handle h, const float* wi, const float* u, const unsigned char* active, int64_t n,
+                          const float* tint, float* wo_out, float* pdf_out, float* weight_out, void* stream) {
+    if (int rc = measured_launch_checks(h, n)) return rc;
+    if (n == 0) return BSDFD_OK;
+    if (!wi || !u || !wo_out || !pdf_out) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
+    const Tint t = tint ? Tint{tint[0], tint[1], tint[2]} : Tint{1.0f, 1.0f, 1.0f};
+    hipLaunchKernelGGL(measured_sample_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), h->dev, wi, u, active, (long long)n, t, wo_out, pdf_out, weight_out);
+    HIP_TRY(hipGetLastError());
+    return BSDFD_OK;
+}
+
+int bsdfd_measured_pdf(bsdfd_measured_handle h, const float* wi, const float* wo, const unsigned char* active, int64_t n,
+                       float* pdf_out, void* stream) {
+    if (int rc = measured_launch_checks(h, n)) return rc;
+    if (n == 0) return BSDFD_OK;
+    if (!wi || !wo || !pdf_out) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
+    hipLaunchKernelGGL(measured_pdf_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), h->dev, wi, wo, active, (long long)n, pdf_out);
     HIP_TRY(hipGetLastError());
     return BSDFD_OK;
 }

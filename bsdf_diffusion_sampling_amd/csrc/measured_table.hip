@@ -1,4 +1,4 @@
-// measured_table.hip — eval() of a mixed-material wavefront in one launch: the RGL evaluator of measured.hip behind a
+// measured_table.hip — eval(), sample() and pdf() of a mixed-material wavefront in one launch: the RGL evaluator of measured.hip behind a
 // table of materials.
 //
 // A renderer's wavefront carries one material id per lane (bsdfd_wf_primary writes them).  Serving eval() through
@@ -41,10 +41,13 @@ struct MeasuredDevG {
     float fold_x, fold_y;
     TableG ndf, sigma, vndf, rgb;
     gptr vndf_cond, vndf_marg;
+    TableG lum;
+    gptr lum_cond, lum_marg;
 };
 static_assert(sizeof(MeasuredDevG) == sizeof(MeasuredDev) && alignof(MeasuredDevG) == alignof(MeasuredDev) &&
               offsetof(MeasuredDevG, fold_y) == offsetof(MeasuredDev, fold_y) && offsetof(MeasuredDevG, rgb) == offsetof(MeasuredDev, rgb) &&
-              offsetof(MeasuredDevG, vndf_marg) == offsetof(MeasuredDev, vndf_marg), "MeasuredDevG mirrors MeasuredDev");
+              offsetof(MeasuredDevG, vndf_marg) == offsetof(MeasuredDev, vndf_marg) && offsetof(MeasuredDevG, lum) == offsetof(MeasuredDev, lum) &&
+              offsetof(MeasuredDevG, lum_marg) == offsetof(MeasuredDev, lum_marg), "MeasuredDevG mirrors MeasuredDev");
 
 __device__ __forceinline__ Table generic(const TableG& t) { return Table{(const float*)t.data, t.w, t.h}; }
 __device__ __forceinline__ MeasuredDev generic(const MeasuredDevG& s) {
@@ -55,6 +58,7 @@ __device__ __forceinline__ MeasuredDev generic(const MeasuredDevG& s) {
     m.fold_x = s.fold_x; m.fold_y = s.fold_y;
     m.ndf = generic(s.ndf); m.sigma = generic(s.sigma); m.vndf = generic(s.vndf); m.rgb = generic(s.rgb);
     m.vndf_cond = (const float*)s.vndf_cond; m.vndf_marg = (const float*)s.vndf_marg;
+    m.lum = generic(s.lum); m.lum_cond = (const float*)s.lum_cond; m.lum_marg = (const float*)s.lum_marg;
     return m;
 }
 
@@ -168,6 +172,57 @@ __global__ __launch_bounds__(256) void measured_weight_table_kernel(const Measur
     }
 }
 
+// sample() / pdf() of the row's material — sample_row / pdf_row (measured_dev.h), what measured_sample_kernel and
+// measured_pdf_kernel (measured.hip) run; a row without ground truth gets NaN in every output
+__device__ __forceinline__ void sample_row_nan(long long q, float* __restrict__ wo_out, float* __restrict__ pdf_out,
+                                               float* __restrict__ weight_out) {
+    const float nan = quiet_nan();
+    store3(wo_out, q, nan, nan, nan);
+    pdf_out[q] = nan;
+    if (weight_out) store3(weight_out, q, nan, nan, nan);
+}
+
+__global__ __launch_bounds__(256) void measured_sample_table_kernel(const MeasuredDevG* __restrict__ table, int n_materials,
+                                                                    const long long* __restrict__ material_id,
+                                                                    const float* __restrict__ wi, const float* __restrict__ u,
+                                                                    const unsigned char* __restrict__ active, long long n,
+                                                                    Tint tint, float* __restrict__ wo_out,
+                                                                    float* __restrict__ pdf_out,
+                                                                    float* __restrict__ weight_out) {
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    const long long id = material_id[q];
+    long long first;
+    if (wave_uniform_id(id, first)) {
+        if (first >= 0 && first < n_materials && has_ground_truth(table[first]))
+            sample_row(generic(table[first]), wi, u, active, q, tint, wo_out, pdf_out, weight_out);
+        else sample_row_nan(q, wo_out, pdf_out, weight_out);
+    } else {
+        if (id >= 0 && id < n_materials && has_ground_truth(table[id]))
+            sample_row(generic(table[id]), wi, u, active, q, tint, wo_out, pdf_out, weight_out);
+        else sample_row_nan(q, wo_out, pdf_out, weight_out);
+    }
+}
+
+__global__ __launch_bounds__(256) void measured_pdf_table_kernel(const MeasuredDevG* __restrict__ table, int n_materials,
+                                                                 const long long* __restrict__ material_id,
+                                                                 const float* __restrict__ wi, const float* __restrict__ wo,
+                                                                 const unsigned char* __restrict__ active, long long n,
+                                                                 float* __restrict__ pdf_out) {
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    const long long id = material_id[q];
+    long long first;
+    if (wave_uniform_id(id, first)) {
+        if (first >= 0 && first < n_materials && has_ground_truth(table[first]))
+            pdf_row(generic(table[first]), wi, wo, active, q, pdf_out);
+        else pdf_out[q] = quiet_nan();
+    } else {
+        if (id >= 0 && id < n_materials && has_ground_truth(table[id])) pdf_row(generic(table[id]), wi, wo, active, q, pdf_out);
+        else pdf_out[q] = quiet_nan();
+    }
+}
+
 }  // namespace
 
 struct bsdfd_measured_table_ctx {
@@ -252,6 +307,33 @@ int bsdfd_measured_sample_weight_table(bsdfd_measured_table t, const int64_t* ma
                        static_cast<hipStream_t>(stream), reinterpret_cast<const MeasuredDevG*>(t->dev), (int)t->n_materials,
                        reinterpret_cast<const long long*>(material_id), wi, wo, pdf_sa, active, (long long)n, c,
                        firefly_threshold, weight_out, pdf_out);
+    HIP_TRY(hipGetLastError());
+    return BSDFD_OK;
+}
+
+int bsdfd_measured_sample_table(bsdfd_measured_table t, const int64_t* material_id, const float* wi, const float* u,
+                                const unsigned char* active, int64_t n, const float* tint, float* wo_out, float* pdf_out,
+                                float* weight_out, void* stream) {
+    if (int rc = table_launch_checks(t, n)) return rc;
+    if (n == 0) return BSDFD_OK;
+    if (!material_id || !wi || !u || !wo_out || !pdf_out) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
+    const Tint c = tint ? Tint{tint[0], tint[1], tint[2]} : Tint{1.0f, 1.0f, 1.0f};
+    hipLaunchKernelGGL(measured_sample_table_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), reinterpret_cast<const MeasuredDevG*>(t->dev), (int)t->n_materials,
+                       reinterpret_cast<const long long*>(material_id), wi, u, active, (long long)n, c, wo_out, pdf_out,
+                       weight_out);
+    HIP_TRY(hipGetLastError());
+    return BSDFD_OK;
+}
+
+int bsdfd_measured_pdf_table(bsdfd_measured_table t, const int64_t* material_id, const float* wi, const float* wo,
+                             const unsigned char* active, int64_t n, float* pdf_out, void* stream) {
+    if (int rc = table_launch_checks(t, n)) return rc;
+    if (n == 0) return BSDFD_OK;
+    if (!material_id || !wi || !wo || !pdf_out) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
+    hipLaunchKernelGGL(measured_pdf_table_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), reinterpret_cast<const MeasuredDevG*>(t->dev), (int)t->n_materials,
+                       reinterpret_cast<const long long*>(material_id), wi, wo, active, (long long)n, pdf_out);
     HIP_TRY(hipGetLastError());
     return BSDFD_OK;
 }

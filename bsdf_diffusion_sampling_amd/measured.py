@@ -1,4 +1,4 @@
-"""Ground-truth evaluator for the plugins' ``eval()``: the RGL measured-BSDF model on the GPU.
+"""Ground-truth evaluator for the plugins' ``eval()``, and the measured BSDF's own sampler: the RGL model on the GPU.
 
 The reference builds Mitsuba's ``measured`` BSDF (``mi.load_dict({'type': 'measured', 'filename':
 'measuredbsdfs/<name>.bsdf'})``, rendering/brdf_measured_disk.py:36-42) and calls its ``eval`` for the
@@ -6,6 +6,9 @@ sample weight and the firefly rule.  Mitsuba has no AMD GPU variant; ``MeasuredB
 model (Dupuy & Jakob 2018) over ``libbsdfd.so`` (csrc/measured.hip) with the call shape the plugins
 use: ``eval(ctx, si, wo) -> [N,3]`` = f * cos(theta_o), zero on the lower hemispheres.  Only the
 ``*_rgb.bsdf`` flavour is supported (the one the reference's scenes name).  No CPU fallback.
+``sample`` / ``pdf`` / ``eval_pdf`` (``sample_t`` / ``pdf_t`` on tensors) are the importance sampler that ships inside every
+tensor file — the baseline the neural samplers compete with, and the way to sample a material that has no trained nets.  Like
+``eval`` it restates the published model and is parity-unpinned against Mitsuba.
 
 ``MeasuredTable`` serves a wavefront whose lanes carry DIFFERENT materials (one id per lane) in one launch
 (csrc/measured_table.hip): the same numbers as ``MeasuredBSDF`` per material, bit for bit.
@@ -41,6 +44,9 @@ class MeasuredBSDF:
         _lib.check(_lib.lib().bsdfd_measured_get_info(self._h, *[C.byref(i) for i in info]))
         self.n_phi, self.n_theta, iso, jac, self.reduction = (i.value for i in info)
         self.isotropic, self.jacobian = bool(iso), bool(jac)
+        lum = C.c_int32()
+        _lib.check(_lib.lib().bsdfd_measured_has_luminance(self._h, C.byref(lum)))
+        self.has_luminance = bool(lum.value)   # the file carries the sampler's luminance warp (without it that pdf is 1)
 
     def __del__(self):
         try:
@@ -100,10 +106,85 @@ class MeasuredBSDF:
                 float(firefly_threshold), C.c_void_p(weight.data_ptr()), C.c_void_p(pdf.data_ptr()), stream))
         return weight, pdf
 
-    # the call shape of ``mi.BSDF.eval`` as the reference's plugins use it (brdf_measured_disk.py:96,107)
+    @staticmethod
+    def _active(active, n: int, device, who: str):
+        """``active`` as a contiguous uint8 [N] on ``device`` (None = every lane)."""
+        if active is None:
+            return None
+        if not (isinstance(active, torch.Tensor) and active.shape == (n,) and active.device == device
+                and active.dtype in (torch.bool, torch.uint8)):
+            raise ValueError(f"{who}: active must be a bool or uint8 tensor [N] on the device of wi")
+        return active.to(torch.uint8).contiguous()
+
+    @staticmethod
+    def _sample_out(wi, out, who: str):
+        """(wo, pdf, weight) to write into: the caller's ``out`` triple, checked, or fresh tensors."""
+        if out is None:
+            return torch.empty_like(wi), torch.empty(wi.shape[0], dtype=torch.float32, device=wi.device), torch.empty_like(wi)
+        if len(out) != 3:
+            raise ValueError(f"{who}: out is a (wo [N,3], pdf [N], weight [N,3]) triple")
+        return tuple(out)
+
+    def sample_t(self, wi: torch.Tensor, u: torch.Tensor, tint=None, active: Optional[torch.Tensor] = None, out=None):
+        """The file's own importance sampler (Dupuy & Jakob: luminance warp, VNDF warp, reflection about the half vector) at the
+        variates ``u`` [N,2] in [0,1)^2 -> (wo [N,3], pdf [N], weight [N,3]), weight = f cos [* tint] / pdf.  Lanes with
+        wi.z <= 0 or ``active`` false get zeros; pdf = weight = 0 where wo leaves through the lower hemisphere (wo is still
+        written).  ``out`` = (wo, pdf, weight) buffers to write into."""
+        wo, pdf, weight = self._sample_out(wi, out, "MeasuredBSDF.sample_t")
+        self._check(wi=(wi, 3), u=(u, 2), wo=(wo, 3), pdf=(pdf, 0), weight=(weight, 3))
+        act = self._active(active, wi.shape[0], wi.device, "MeasuredBSDF.sample_t")
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        with torch.cuda.device(wi.device):
+            stream = C.c_void_p(torch.cuda.current_stream(wi.device).cuda_stream)
+            _lib.check(_lib.lib().bsdfd_measured_sample(self._h, p(wi), p(u), p(act), wi.shape[0], self._tint(tint), p(wo),
+                                                        p(pdf), p(weight), stream))
+        return wo, pdf, weight
+
+    def pdf_t(self, wi: torch.Tensor, wo: torch.Tensor, active: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Solid-angle density with which ``sample_t(wi, .)`` returns ``wo`` -> [N]; 0 on the lower hemispheres and on lanes
+        with ``active`` false."""
+        self._check(wi=(wi, 3), wo=(wo, 3))
+        if out is None:
+            out = torch.empty(wi.shape[0], dtype=torch.float32, device=wi.device)
+        self._check(wi=(wi, 3), out=(out, 0))
+        act = self._active(active, wi.shape[0], wi.device, "MeasuredBSDF.pdf_t")
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        with torch.cuda.device(wi.device):
+            stream = C.c_void_p(torch.cuda.current_stream(wi.device).cuda_stream)
+            _lib.check(_lib.lib().bsdfd_measured_pdf(self._h, p(wi), p(wo), p(act), wi.shape[0], p(out), stream))
+        return out
+
+    # the call shapes of ``mi.BSDF`` as the reference's plugins use them (brdf_measured_disk.py:59,96,107,112)
     def eval(self, ctx, si, wo, active=True):
         from .plugin_base import _vec, _wi_of
         return self.eval_t(_wi_of(si), _vec(wo))
+
+    @staticmethod
+    def _mask_of(active, wi):
+        """Mitsuba's ``active`` argument (True, a bool, or a mask) as the ``active`` of the tensor calls."""
+        if active is True or active is None:
+            return None
+        if isinstance(active, bool):
+            return torch.zeros(wi.shape[0], dtype=torch.uint8, device=wi.device)
+        if not isinstance(active, torch.Tensor):
+            active = active.torch()
+        return active.to(device=wi.device, dtype=torch.uint8).contiguous()
+
+    def sample(self, ctx, si, sample1, sample2, active=True):
+        """``mi.BSDF.sample``: -> (BSDFSample3f(wo, pdf), weight [N,3]).  ``sample1`` is ignored (one lobe)."""
+        from .plugin_base import BSDFSample3f, _vec, _wi_of
+        wi = _wi_of(si)
+        wo, pdf, weight = self.sample_t(wi, _vec(sample2), active=self._mask_of(active, wi))
+        return BSDFSample3f(wo=wo, pdf=pdf), weight
+
+    def pdf(self, ctx, si, wo, active=True):
+        from .plugin_base import _vec, _wi_of
+        wi = _wi_of(si)
+        return self.pdf_t(wi, _vec(wo), active=self._mask_of(active, wi))
+
+    def eval_pdf(self, ctx, si, wo, active=True):
+        return self.eval(ctx, si, wo, active), self.pdf(ctx, si, wo, active)
 
 
 class MeasuredTable:
@@ -198,3 +279,31 @@ class MeasuredTable:
                 self._table(), p(material_id), p(wi), p(wo), p(pdf_sa), p(act), wi.shape[0], MeasuredBSDF._tint(tint),
                 float(firefly_threshold), p(weight), p(pdf), stream))
         return weight, pdf
+
+    def sample_t(self, material_id: torch.Tensor, wi: torch.Tensor, u: torch.Tensor, tint=None,
+                 active: Optional[torch.Tensor] = None, out=None):
+        """``MeasuredBSDF.sample_t`` of each lane's material in one launch -> (wo [N,3], pdf [N], weight [N,3]); lanes without
+        ground truth get NaN in all three."""
+        wo, pdf, weight = MeasuredBSDF._sample_out(wi, out, "MeasuredTable.sample_t")
+        self._check(material_id, wi=(wi, 3), u=(u, 2), wo=(wo, 3), pdf=(pdf, 0), weight=(weight, 3))
+        act = MeasuredBSDF._active(active, wi.shape[0], wi.device, "MeasuredTable.sample_t")
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        with torch.cuda.device(wi.device):
+            stream = C.c_void_p(torch.cuda.current_stream(wi.device).cuda_stream)
+            _lib.check(_lib.lib().bsdfd_measured_sample_table(self._table(), p(material_id), p(wi), p(u), p(act), wi.shape[0],
+                                                              MeasuredBSDF._tint(tint), p(wo), p(pdf), p(weight), stream))
+        return wo, pdf, weight
+
+    def pdf_t(self, material_id: torch.Tensor, wi: torch.Tensor, wo: torch.Tensor, active: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``MeasuredBSDF.pdf_t`` of each lane's material in one launch -> [N]; NaN = no ground truth for that lane."""
+        if out is None:
+            out = torch.empty(material_id.shape[0], dtype=torch.float32, device=material_id.device)
+        self._check(material_id, wi=(wi, 3), wo=(wo, 3), out=(out, 0))
+        act = MeasuredBSDF._active(active, wi.shape[0], wi.device, "MeasuredTable.pdf_t")
+        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        with torch.cuda.device(wi.device):
+            stream = C.c_void_p(torch.cuda.current_stream(wi.device).cuda_stream)
+            _lib.check(_lib.lib().bsdfd_measured_pdf_table(self._table(), p(material_id), p(wi), p(wo), p(act), wi.shape[0],
+                                                           p(out), stream))
+        return out

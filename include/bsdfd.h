@@ -38,7 +38,9 @@ extern "C" {
  *   8: bsdfd_live_workspace_bytes(), bsdfd_compact_live() and bsdfd_plugin_sample_pdf_ex() added (`active` masks).
  *      Added later WITHOUT a new version (no struct or existing entry point changed; a host that needs them looks the symbols
  *      up): bsdfd_measured_table_create(), bsdfd_measured_table_destroy(), bsdfd_measured_eval_table() and
- *      bsdfd_measured_sample_weight_table() (eval() of a mixed-material wavefront in one launch). */
+ *      bsdfd_measured_sample_weight_table() (eval() of a mixed-material wavefront in one launch);
+ *      bsdfd_measured_sample(), bsdfd_measured_pdf(), bsdfd_measured_sample_table(), bsdfd_measured_pdf_table() and
+ *      bsdfd_measured_has_luminance() (the measured BSDF's own importance sampler). */
 #define BSDFD_ABI_VERSION 8
 
 #define BSDFD_OK 0
@@ -390,6 +392,29 @@ int  bsdfd_measured_sample_weight_table(bsdfd_measured_table t, const int64_t* m
                                         const float* wo, const float* pdf_sa, const unsigned char* active, int64_t N,
                                         const float* tint, float firefly_threshold, float* weight_out, float* pdf_out,
                                         void* hip_stream);
+
+/* ---- sample() / pdf() of the measured BSDF: the importance sampler every RGL file ships -------------------------------
+ * Mitsuba's `measured` plugin draws with the file's `luminance` warp (optional field; without it that pdf is 1), then its VNDF
+ * warp, then reflects wi about the sampled half vector (Dupuy & Jakob 2018).  Restated from the published model; PARITY-UNPINNED
+ * against Mitsuba, like eval().  u [N,2] in [0,1)^2 are the caller's variates (Mitsuba's sample2).  Per row:
+ *   wo_out [N,3]     the sampled direction (written as computed even where it leaves through the lower hemisphere),
+ *   pdf_out [N]      its solid-angle density, 0 where wo.z <= 0 (or where the density is not a positive finite number),
+ *   weight_out [N,3] f(wi, wo) cos(theta_o) * tint / pdf, 0 where pdf is 0 (may be NULL).
+ * Rows with wi.z <= 0, and rows with active[i] == 0 when a mask is given (u8 [N] or NULL), get 0 in every output.
+ * bsdfd_measured_pdf is the density of that sampler at a given wo: 0 unless wi.z > 0 and wo.z > 0.
+ * All four calls are stream-ordered, allocate nothing and do not synchronise; N = 0 is a no-op. */
+int bsdfd_measured_has_luminance(bsdfd_measured_handle h, int32_t* has_luminance);
+int bsdfd_measured_sample(bsdfd_measured_handle h, const float* wi, const float* u, const unsigned char* active, int64_t N,
+                          const float* tint, float* wo_out, float* pdf_out, float* weight_out, void* hip_stream);
+int bsdfd_measured_pdf(bsdfd_measured_handle h, const float* wi, const float* wo, const unsigned char* active, int64_t N,
+                       float* pdf_out, void* hip_stream);
+/* ... for a mixed-material wavefront in lane order: a row whose id names a non-NULL handle gets what the single-material call
+ * writes for it, bit for bit (zeros where active[i] == 0 included); every other row gets a quiet NaN in every output. */
+int bsdfd_measured_sample_table(bsdfd_measured_table t, const int64_t* material_id, const float* wi, const float* u,
+                                const unsigned char* active, int64_t N, const float* tint, float* wo_out, float* pdf_out,
+                                float* weight_out, void* hip_stream);
+int bsdfd_measured_pdf_table(bsdfd_measured_table t, const int64_t* material_id, const float* wi, const float* wo,
+                             const unsigned char* active, int64_t N, float* pdf_out, void* hip_stream);
 
 /* ---- wavefront harness ------------------------------------
  * The reference renders through Mitsuba 3 (rendering/brdf_measured_disk.py:146-155: passes of

@@ -1,5 +1,6 @@
 """Importance-sampling quality with the native ground truth: directional albedo estimated with the flow's samples
-(f / pdf) vs cosine sampling (f pi / cos), and the variance ratio of the two estimators."""
+(f / pdf), with the measured BSDF's own warp (MeasuredBSDF.sample_t: the sampler inside the tensor file) and with cosine
+sampling (f pi / cos); standard deviation of one sample and the variance ratio of each against cosine sampling."""
 import sys, os, numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from bsdf_diffusion_sampling_amd.plugin_base import SurfaceInteraction
@@ -15,6 +16,8 @@ for mod in ("brdf_measured_disk", "brdf_measured_spherical"):
         u = torch.rand(n, 2, generator=gen, device="cuda"); r, ph = torch.sqrt(u[:, 0]), 2 * np.pi * u[:, 1]
         wc = torch.stack([r * torch.cos(ph), r * torch.sin(ph), torch.sqrt((1 - u[:, 0]).clamp_min(1e-12))], 1).contiguous()
         wcos = plug.eval(None, si, wc) * (np.pi / wc[:, 2:3])
-        print(f"{mod[14:]:10s} wi={wi3}: albedo(R) neural {wn[:,0].mean():.4f} cosine {wcos[:,0].mean():.4f} | "
-              f"std of one sample: neural {wn[:,0].std():.3f} cosine {wcos[:,0].std():.2f} -> variance ratio {(wcos[:,0].var()/wn[:,0].var()).item():.0f}x, "
-              f"zero-pdf samples {(pdf<=0).float().mean().item()*100:.2f} %")
+        _, mpdf, wm = plug.bsdf.sample_t(wi, torch.rand(n, 2, generator=gen, device="cuda"))
+        print(f"{mod[14:]:10s} wi={wi3}: albedo(R) neural {wn[:,0].mean():.4f} measured-warp {wm[:,0].mean():.4f} cosine {wcos[:,0].mean():.4f} | "
+              f"std of one sample: neural {wn[:,0].std():.3f} measured-warp {wm[:,0].std():.3f} cosine {wcos[:,0].std():.2f} -> variance ratio "
+              f"over cosine: neural {(wcos[:,0].var()/wn[:,0].var()).item():.0f}x measured-warp {(wcos[:,0].var()/wm[:,0].var()).item():.0f}x, "
+              f"zero-pdf samples: neural {(pdf<=0).float().mean().item()*100:.2f} % measured-warp {(mpdf<=0).float().mean().item()*100:.2f} %")
