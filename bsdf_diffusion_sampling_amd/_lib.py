@@ -15,14 +15,15 @@ DEFAULT_LIB_PATH = os.path.join(_HERE, "libbsdfd.so")
 LIB_PATH = os.environ.get("BSDFD_LIB_PATH") or DEFAULT_LIB_PATH  # override: A/B builds
 SRC_PATH = os.path.join(_HERE, "csrc", "bsdfd.hip")
 SRC32_PATH = os.path.join(_HERE, "csrc", "flow32.hip")   # the 32-query-tile flow kernels
-SRC_PATHS = [SRC_PATH, SRC32_PATH, os.path.join(_HERE, "csrc", "wavefront.hip"), os.path.join(_HERE, "csrc", "encoding.hip"),
+SRC_PATHS = [SRC_PATH, SRC32_PATH, os.path.join(_HERE, "csrc", "wavefront.hip"), os.path.join(_HERE, "csrc", "pathtrace.hip"),
+             os.path.join(_HERE, "csrc", "encoding.hip"),
              os.path.join(_HERE, "csrc", "measured.hip"), os.path.join(_HERE, "csrc", "measured_table.hip"),
              os.path.join(_HERE, "csrc", "bucket.hip"),
              os.path.join(_HERE, "csrc", "bucket_wide.hip"), os.path.join(_HERE, "csrc", "live.hip"),
              os.path.join(_HERE, "csrc", "clock.hip")]  # translation units of libbsdfd.so
 FLOW_TUS = (SRC_PATH, SRC32_PATH)   # ... whose device assembly the build verifies (_asmcheck)
 DEP_PATHS = SRC_PATHS + [os.path.join(_HERE, "csrc", f) for f in ("common.h", "flow_dev.h", "flow32.h", "bucket_scan.h",
-                                                                     "measured_dev.h")]
+                                                                     "measured_dev.h", "wavefront_dev.h")]
 INCLUDE_DIR = os.path.join(ROOT, "include")
 ASM_CACHE_DIR = os.path.join(ROOT, "build", "asm")   # device assembly of the last product build (bsdfd.s, flow32.s)
 
@@ -39,7 +40,7 @@ EXPORTS = (
     "bsdfd_plugin_sample_pdf_multi",
     "bsdfd_context_bytes", "bsdfd_plugin_sample_ex", "bsdfd_plugin_pdf_ex", "bsdfd_plugin_sample_multi_ex",
     "bsdfd_plugin_pdf_multi_ex", "bsdfd_plugin_sample_pdf_multi_ex", "bsdfd_plugin_sample_pdf_ex",
-    "bsdfd_flow_samples_only", "bsdfd_wf_primary", "bsdfd_wf_shade",
+    "bsdfd_flow_samples_only", "bsdfd_wf_primary", "bsdfd_wf_shade", "bsdfd_wf_path_begin", "bsdfd_wf_bounce", "bsdfd_wf_resolve",
     "bsdfd_positional_encoding", "bsdfd_bucket_workspace_bytes", "bsdfd_bucket_by_material",
     "bsdfd_bucket_wide_workspace_bytes", "bsdfd_bucket_by_material_wide",
     "bsdfd_gather_lanes", "bsdfd_scatter_lanes", "bsdfd_live_workspace_bytes", "bsdfd_compact_live",
@@ -398,6 +399,9 @@ def lib():
     L.bsdfd_flow_samples_only.argtypes = [vp, fp, fp, i64, i32, fp, vp]
     L.bsdfd_wf_primary.argtypes = [C.POINTER(WfScene), i32, i32, i32, u64, u64, fp, fp, fp, fp, fp, vp]
     L.bsdfd_wf_shade.argtypes = [C.POINTER(WfScene), fp, i32, i32, i32, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, fp, vp]
+    L.bsdfd_wf_path_begin.argtypes = [C.POINTER(WfScene), fp, i64, fp, fp, fp, fp, fp, fp, vp]
+    L.bsdfd_wf_bounce.argtypes = [C.POINTER(WfScene), fp, i32, i32, i32, u64, u64, u64, i64] + [fp] * 12 + [vp]
+    L.bsdfd_wf_resolve.argtypes = [C.POINTER(WfScene), i32, i32, i32, fp, fp, vp]
     L.bsdfd_positional_encoding.argtypes = [fp, i64, i32, i32, i32, i32, fp, vp]
     L.bsdfd_measured_create_from_file.argtypes = [C.c_char_p, C.POINTER(vp)]
     L.bsdfd_measured_destroy.argtypes = [vp]

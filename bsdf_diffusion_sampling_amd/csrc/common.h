@@ -1,5 +1,5 @@
 // common.h — pieces shared by the translation units of libbsdfd.so (bsdfd.hip: the flow sampler,
-// wavefront.hip: the wavefront harness kernels): the counter-based RNG and the error plumbing.
+// wavefront.hip / pathtrace.hip: the wavefront harness kernels): the counter-based RNG and the error plumbing.
 #pragma once
 #include <hip/hip_runtime.h>
 

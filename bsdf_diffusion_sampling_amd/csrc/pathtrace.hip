@@ -1,0 +1,281 @@
+// pathtrace.hip — occlusion and further bounces for the array scene of the wavefront harness (wavefront.hip).
+//
+// The reference renders its array scenes with Mitsuba's `path` integrator at unbounded depth
+// (matpreview/disney_bsdf_array*_envmap.xml: max_depth = -1): the balls shadow the floor and each other, and every
+// further vertex calls the plugin's sample() / pdf() again.  The geometry is at most 32 analytic spheres and one plane,
+// so the secondary rays are traced here by the same brute-force loop primary_kernel runs; the path state lives in
+// lane-ordered arrays between the sampler calls:
+//
+//   path_begin : dir, nrm, material of bsdfd_wf_primary -> org (world position of the first vertex), beta = 1,
+//                rad = env(dir) for a miss, 0 otherwise
+//   bounce     : + wo, pdf(wo), pdf(wl) [, f(wo), f(wl)] of the sampler for the vertices that carry a material
+//                -> rad += beta * (MIS estimate of the environment seen from the vertex); the path moves to the vertex its
+//                BSDF sample hits (org, nrm, wi, material, beta, a fresh light sample wl) or ends (material = n_balls + 1,
+//                the "miss" id: the next bucketing sorts it behind the materials and it costs no flow evaluation)
+//   resolve    : film += mean over spp of rad
+//
+// Only the environment emits, so a BSDF sample that hits geometry adds nothing and a light sample that hits geometry is
+// shadowed.  A ray skips the surface it starts on (known from the material id; a sphere is convex, a plane flat): there
+// is no epsilon offset.  One path per lane; a lane whose path has ended returns after reading its id.  Streaming
+// kernels: ~125 B read and ~90 B written per live path, a few hundred flops.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "bsdfd.h"
+#include "common.h"
+#include "wavefront_dev.h"
+
+namespace {
+
+using namespace wf_dev;
+
+struct Hit {
+    float t;       // distance along the ray; 3e38 = nothing
+    int id;        // ball index, n_sph for the floor, -1 for nothing
+    V3 c;          // the winning ball's centre and radius, kept in registers by the loop: indexing sc.sph with the per-lane
+    float r;       // id afterwards would turn the kernel-argument array into scratch
+};
+
+// Closest hit of the ray org + t d among the balls and the floor, the surface `own` (a material id) excepted.  `sc` is a
+// kernel argument, so the loop is wave-uniform and its operands arrive through scalar loads.  Same discriminant as
+// primary_kernel: R^2 - (distance of the centre from the ray)^2.
+__device__ __forceinline__ Hit trace(const Scene& sc, V3 org, V3 d, int own) {
+    Hit h;
+    h.t = 3.0e38f; h.id = -1; h.c = v3(0.f, 0.f, 0.f); h.r = 1.0f;
+    for (int k = 0; k < sc.n_sph; ++k) {
+        const V3 c = v3(sc.sph[k][0], sc.sph[k][1], sc.sph[k][2]);
+        const float r = sc.sph[k][3];
+        const V3 oc = org - c;
+        const float b = dot(oc, d);
+        const V3 perp = oc - b * d;
+        const float disc = r * r - dot(perp, perp);
+        const float t = -b - sqrtf(fmaxf(disc, 0.0f));
+        if (k != own && disc > 0.0f && t > 0.0f && t < h.t) { h.t = t; h.id = k; h.c = c; h.r = r; }
+    }
+    if (sc.has_plane && own != sc.n_sph && d.y < 0.0f) {
+        const float t = (sc.plane_y - org.y) / d.y;
+        if (t > 0.0f && t < h.t) { h.t = t; h.id = sc.n_sph; }
+    }
+    return h;
+}
+
+__global__ __launch_bounds__(256) void path_begin_kernel(Scene sc, const float* __restrict__ env, long long n,
+                                                         const float* __restrict__ dir, const float* __restrict__ nrm,
+                                                         const long long* __restrict__ mat, float* __restrict__ org,
+                                                         float* __restrict__ beta, float* __restrict__ rad) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const long long m = mat[p];
+    V3 o = v3(0.f, 0.f, 0.f);
+    float L[3] = {0.f, 0.f, 0.f};
+    if (m >= 0 && m < sc.n_sph) {
+        V3 c = v3(0.f, 0.f, 0.f);
+        float r = 0.0f;
+        for (int k = 0; k < sc.n_sph; ++k)   // wave-uniform loop, per-lane select: no per-lane index into sc.sph
+            if (m == k) { c = v3(sc.sph[k][0], sc.sph[k][1], sc.sph[k][2]); r = sc.sph[k][3]; }
+        o = c + r * ld3(nrm + 3 * p);
+    } else if (m == sc.n_sph) {
+        const V3 d = ld3(dir + 3 * p);
+        o = sc.o + ((sc.plane_y - sc.o.y) / d.y) * d;   // the ray/plane point primary_kernel took the checker colour at
+    } else {
+        env_lookup(env, sc.env_w, sc.env_h, ld3(dir + 3 * p), L);   // the camera sees the environment
+    }
+    st3(org + 3 * p, o);
+    st3(beta + 3 * p, v3(1.f, 1.f, 1.f));
+    st3(rad + 3 * p, v3(L[0], L[1], L[2]));
+}
+
+__global__ __launch_bounds__(256) void bounce_kernel(Scene sc, const float* __restrict__ env, int bounce, int last,
+                                                     int occlusion, unsigned long long seed, unsigned long long pass,
+                                                     unsigned long long path_offset, long long n, float* __restrict__ org,
+                                                     float* __restrict__ nrm, float* __restrict__ wi, float* __restrict__ wl,
+                                                     long long* __restrict__ mat, float* __restrict__ beta,
+                                                     float* __restrict__ rad, const float* __restrict__ wo,
+                                                     const float* __restrict__ pdf_o, const float* __restrict__ pdf_l,
+                                                     const float* __restrict__ f_o, const float* __restrict__ f_l) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const long long m = mat[p];
+    if (m < 0 || m > sc.n_sph) return;   // the path has ended
+    const float inv_pi = 0.31830988618379067154f;
+    const V3 nn = ld3(nrm + 3 * p), x = ld3(org + 3 * p);
+    V3 fs, ft;
+    onb(nn, fs, ft);
+    const V3 l = ld3(wl + 3 * p);
+    const V3 lw = l.x * fs + l.y * ft + l.z * nn;
+    float L[3] = {0.f, 0.f, 0.f};   // the vertex' estimate, before the throughput
+    float thr[3] = {1.f, 1.f, 1.f};  // throughput factor of the continuing direction
+    V3 d = lw;                       // ... that direction
+    Hit h;
+    h.t = 3.0e38f; h.id = -1; h.c = v3(0.f, 0.f, 0.f); h.r = 1.0f;
+    bool go = false;                 // the path continues at `h`
+    if (m == sc.n_sph) {
+        // diffuse floor, cosine-sampled: f cos / pdf = reflectance (in the wi slot); the one direction serves both purposes
+        const float refl = wi[3 * p];
+        if (occlusion) h = trace(sc, x, lw, (int)m);
+        if (h.id < 0) {
+            float e[3];
+            env_lookup(env, sc.env_w, sc.env_h, lw, e);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) L[c] = refl * e[c];
+        } else {
+            go = true;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) thr[c] = refl;
+        }
+    } else {
+        // the two strategies of shade_kernel, same expressions in the same order
+        const bool gt_o = f_o && f_o[3 * p] == f_o[3 * p];
+        const bool gt_l = f_l && f_l[3 * p] == f_l[3 * p];
+        const V3 o = ld3(wo + 3 * p);
+        float pb = pdf_o[p];
+        if (!(pb > 0.0f) || !isfinite(pb)) pb = 0.0f;
+        if (pb > 0.0f && (!occlusion || o.z > 0.0f)) {   // (a direction below the surface is blocked by the ball itself)
+            d = o.x * fs + o.y * ft + o.z * nn;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) thr[c] = gt_o ? f_o[3 * p + c] / pb : sc.albedo[c];
+            if (occlusion) h = trace(sc, x, d, (int)m);
+            if (h.id < 0) {
+                const float w = mis_power(pb, fmaxf(o.z, 0.0f) * inv_pi);
+                float e[3];
+                env_lookup(env, sc.env_w, sc.env_h, d, e);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) L[c] += w * e[c] * (gt_o ? f_o[3 * p + c] / pb : sc.albedo[c]);
+            } else {
+                go = true;   // only the environment emits: nothing to add for this strategy
+            }
+        }
+        // light-sampled direction (cosine hemisphere, pdf cos/pi): f cos / pdf_light, unless something is in the way
+        const float pl = l.z * inv_pi;
+        float pbl = pdf_l[p];
+        if (!(pbl > 0.0f) || !isfinite(pbl)) pbl = 0.0f;
+        if (pl > 0.0f && (pbl > 0.0f || gt_l) && !(occlusion && trace(sc, x, lw, (int)m).id >= 0)) {
+            const float w = mis_power(pl, pbl) / pl;
+            float e[3];
+            env_lookup(env, sc.env_w, sc.env_h, lw, e);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) L[c] += w * e[c] * (gt_l ? f_l[3 * p + c] : sc.albedo[c] * pbl);
+        }
+    }
+    const V3 b = ld3(beta + 3 * p);
+    const V3 r0 = ld3(rad + 3 * p);
+    st3(rad + 3 * p, v3(r0.x + b.x * L[0], r0.y + b.y * L[1], r0.z + b.z * L[2]));
+    if (!go || last) {
+        mat[p] = sc.n_sph + 1;
+        return;
+    }
+    // the next vertex, written the way primary_kernel writes the first
+    V3 nv, xv, w_in;
+    if (h.id < sc.n_sph) {
+        const V3 oc = x - h.c;
+        nv = (1.0f / h.r) * (oc + h.t * d);
+        nv = (1.0f / sqrtf(dot(nv, nv))) * nv;
+        V3 gs, gt;
+        onb(nv, gs, gt);
+        w_in = v3(-dot(d, gs), -dot(d, gt), -dot(d, nv));
+        xv = h.c + h.r * nv;
+    } else {
+        xv = x + h.t * d;
+        const int cx = (int)floorf(xv.x * sc.checker_scale), cz = (int)floorf(xv.z * sc.checker_scale);
+        const float refl = ((cx + cz) & 1) ? sc.checker_c1 : sc.checker_c0;
+        nv = v3(0.f, 1.f, 0.f);
+        w_in = v3(refl, refl, refl);
+    }
+    // its light sample: primary's Philox key and counter, counter word 3 advanced by the depth of the new vertex
+    const unsigned long long gp = path_offset + (unsigned long long)p;
+    unsigned u[4];
+    philox4x32((unsigned)seed, (unsigned)(seed >> 32), (unsigned)gp, (unsigned)(gp >> 32), (unsigned)pass,
+               0x57617665u + (unsigned)(bounce + 1), u);
+    const float u2 = u01_open(u[2]), u3 = (float)(u[3] >> 8) * (1.0f / 16777216.0f);
+    const float r = sqrtf(u2);
+    float sp, cp;
+    sincosf(6.28318530717958647692f * u3, &sp, &cp);
+    st3(wl + 3 * p, v3(r * cp, r * sp, sqrtf(fmaxf(1.0f - u2, 0.0f))));
+    st3(org + 3 * p, xv);
+    st3(nrm + 3 * p, nv);
+    st3(wi + 3 * p, w_in);
+    st3(beta + 3 * p, v3(b.x * thr[0], b.y * thr[1], b.z * thr[2]));
+    mat[p] = h.id;
+}
+
+// same accumulation order as shade_kernel's tail
+__global__ __launch_bounds__(256) void resolve_kernel(long long npix, int spp, const float* __restrict__ rad,
+                                                      float* __restrict__ film) {
+    const long long pix = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (pix >= npix) return;
+    float acc[3] = {0.f, 0.f, 0.f};
+    for (int s = 0; s < spp; ++s) {
+        const V3 L = ld3(rad + 3 * (pix * spp + s));
+        acc[0] += L.x; acc[1] += L.y; acc[2] += L.z;
+    }
+    const float inv = 1.0f / (float)spp;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) film[3 * pix + c] += acc[c] * inv;
+}
+
+// scene + environment + lane count of a launch over N paths (no tile: the path kernels take N and a path offset)
+int path_scene(const bsdfd_wf_scene* s, const float* env, long long n, Scene& sc, long long& blocks) {
+    if (int rc = to_scene(s, 0, 0, 1, sc)) return rc;
+    if (sc.env_w <= 0 || sc.env_h <= 0) return bsdfd_fail_(BSDFD_EINVAL, "environment map size must be positive");
+    if (n < 0) return bsdfd_fail_(BSDFD_EINVAL, "negative path count");
+    if (n > 0 && !env) return bsdfd_fail_(BSDFD_EINVAL, "null environment map");
+    blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffLL) return bsdfd_fail_(BSDFD_EINVAL, "wavefront too large for one launch");
+    return BSDFD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bsdfd_wf_path_begin(const bsdfd_wf_scene* scene, const float* env, int64_t N, const float* dir, const float* nrm,
+                        const int64_t* material, float* org, float* beta, float* rad, void* stream) {
+    Scene sc;
+    long long blocks;
+    if (int rc = path_scene(scene, env, N, sc, blocks)) return rc;
+    if (N == 0) return BSDFD_OK;
+    if (!dir || !nrm || !material || !org || !beta || !rad) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
+    hipLaunchKernelGGL(path_begin_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), sc, env,
+                       (long long)N, dir, nrm, reinterpret_cast<const long long*>(material), org, beta, rad);
+    HIP_TRY(hipGetLastError());
+    return BSDFD_OK;
+}
+
+int bsdfd_wf_bounce(const bsdfd_wf_scene* scene, const float* env, int32_t bounce, int32_t last, int32_t occlusion,
+                    uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, float* org, float* nrm, float* wi,
+                    float* wl, int64_t* material, float* beta, float* rad, const float* wo, const float* pdf_o,
+                    const float* pdf_l, const float* f_o, const float* f_l, void* stream) {
+    Scene sc;
+    long long blocks;
+    if (int rc = path_scene(scene, env, N, sc, blocks)) return rc;
+    if (bounce < 0) return bsdfd_fail_(BSDFD_EINVAL, "bounce must be >= 0");
+    if ((f_o == nullptr) != (f_l == nullptr)) return bsdfd_fail_(BSDFD_EINVAL, "f_o and f_l are both NULL or both given");
+    if (N == 0) return BSDFD_OK;
+    if (!org || !nrm || !wi || !wl || !material || !beta || !rad || !wo || !pdf_o || !pdf_l)
+        return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
+    hipLaunchKernelGGL(bounce_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), sc, env,
+                       (int)bounce, last ? 1 : 0, occlusion ? 1 : 0, (unsigned long long)seed, (unsigned long long)pass,
+                       (unsigned long long)path_offset, (long long)N, org, nrm, wi, wl,
+                       reinterpret_cast<long long*>(material), beta, rad, wo, pdf_o, pdf_l, f_o, f_l);
+    HIP_TRY(hipGetLastError());
+    return BSDFD_OK;
+}
+
+int bsdfd_wf_resolve(const bsdfd_wf_scene* scene, int32_t row_begin, int32_t row_end, int32_t spp, const float* rad,
+                     float* film, void* stream) {
+    Scene sc;
+    if (int rc = to_scene(scene, row_begin, row_end, spp, sc)) return rc;
+    const long long npix = (long long)(row_end - row_begin) * sc.width;
+    if (npix == 0) return BSDFD_OK;
+    if (!rad || !film) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
+    const long long blocks = (npix + 255) / 256;
+    hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), npix,
+                       (int)spp, rad, film);
+    HIP_TRY(hipGetLastError());
+    return BSDFD_OK;
+}
+
+}  // extern "C"

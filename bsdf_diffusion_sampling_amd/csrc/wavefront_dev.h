@@ -1,0 +1,111 @@
+// wavefront_dev.h — the scene model of the wavefront harness, shared by the translation units that trace it: wavefront.hip
+// (primary rays, one-bounce shading) and pathtrace.hip (occlusion and further bounces).  Both inline the same vector helpers,
+// orthonormal basis, environment lookup and MIS weight, and build the kernel-argument `Scene` from the same bsdfd_wf_scene.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "bsdfd.h"
+#include "common.h"
+
+namespace wf_dev {
+
+struct V3 {
+    float x, y, z;
+};
+__host__ __device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}; }
+__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
+__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
+__device__ __forceinline__ V3 operator*(float s, V3 a) { return v3(s * a.x, s * a.y, s * a.z); }
+__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ V3 ld3(const float* p) { return v3(p[0], p[1], p[2]); }
+__device__ __forceinline__ void st3(float* p, V3 a) { p[0] = a.x; p[1] = a.y; p[2] = a.z; }
+
+// Orthonormal basis from a unit normal (Duff et al. 2017, the construction behind Mitsuba's
+// coordinate_system()): s, t with (s, t, n) right-handed.
+__device__ __forceinline__ void onb(V3 n, V3& s, V3& t) {
+    const float sign = copysignf(1.0f, n.z);
+    const float a = -1.0f / (sign + n.z);
+    const float b = n.x * n.y * a;
+    s = v3(1.0f + sign * n.x * n.x * a, sign * b, -sign * n.x);
+    t = v3(b, sign + n.y * n.y * a, -n.y);
+}
+
+constexpr int WF_MAX_SPHERES = 32;
+
+struct Scene {
+    V3 o, right, up, fwd;
+    float tan_half_fov;
+    int width, height;
+    float albedo[3];
+    int env_w, env_h;
+    int n_sph;                       // material balls; ball k carries material k
+    float sph[WF_MAX_SPHERES][4];    // centre xyz, radius
+    int has_plane;                   // diffuse checkerboard ground plane y = plane_y (the matpreview scenes' floor)
+    float plane_y, checker_scale, checker_c0, checker_c1;
+};
+
+// lat-long radiance map, y up: u = atan2(x, -z) / 2pi (wrapped), v = acos(y) / pi; bilinear
+__device__ __forceinline__ void env_lookup(const float* __restrict__ env, int w, int h, V3 d, float out[3]) {
+    float uu = atan2f(d.x, -d.z) * 0.15915494309189533577f;
+    uu -= floorf(uu);
+    const float vv = acosf(fminf(fmaxf(d.y, -1.0f), 1.0f)) * 0.31830988618379067154f;
+    const float x = uu * (float)w - 0.5f, y = vv * (float)h - 0.5f;
+    const float xf = floorf(x), yf = floorf(y);
+    const float ax = x - xf, ay = y - yf;
+    int x0 = (int)xf, y0 = (int)yf;
+    int x1 = x0 + 1, y1 = y0 + 1;
+    x0 = ((x0 % w) + w) % w; x1 = ((x1 % w) + w) % w;
+    y0 = min(max(y0, 0), h - 1); y1 = min(max(y1, 0), h - 1);
+    const float w00 = (1.f - ax) * (1.f - ay), w10 = ax * (1.f - ay), w01 = (1.f - ax) * ay, w11 = ax * ay;
+    const float* p00 = env + ((long long)y0 * w + x0) * 3;
+    const float* p10 = env + ((long long)y0 * w + x1) * 3;
+    const float* p01 = env + ((long long)y1 * w + x0) * 3;
+    const float* p11 = env + ((long long)y1 * w + x1) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[c] = w00 * p00[c] + w10 * p10[c] + w01 * p01[c] + w11 * p11[c];
+}
+
+__device__ __forceinline__ float mis_power(float pa, float pb) {  // mitsuba_helper.py:130-137
+    // pa^2 / (pa^2 + pb^2), formed as 1 / (1 + (pb/pa)^2): no overflow for the 1e9+ densities of
+    // near-specular lobes
+    if (!(pa > 0.0f)) return 0.0f;
+    const float q = pb / pa;
+    return 1.0f / fmaf(q, q, 1.0f);
+}
+
+// the kernel-argument form of a bsdfd_wf_scene, validated together with the tile [row_begin, row_end) x spp
+inline int to_scene(const bsdfd_wf_scene* s, int row_begin, int row_end, int spp, Scene& sc) {
+    if (!s) return bsdfd_fail_(BSDFD_EINVAL, "null scene");
+    if (s->width <= 0 || s->height <= 0) return bsdfd_fail_(BSDFD_EINVAL, "film size must be positive");
+    if (row_begin < 0 || row_end > s->height || row_begin > row_end)
+        return bsdfd_fail_(BSDFD_EINVAL, "row range outside the film");
+    if (spp <= 0) return bsdfd_fail_(BSDFD_EINVAL, "spp must be positive");
+    if (!(s->sphere_radius > 0.0f)) return bsdfd_fail_(BSDFD_EINVAL, "sphere radius must be positive");
+    if (s->n_extra_spheres < 0 || s->n_extra_spheres > WF_MAX_SPHERES - 1)
+        return bsdfd_fail_(BSDFD_EINVAL, "at most 31 extra spheres");
+    sc.o = v3(s->cam_origin[0], s->cam_origin[1], s->cam_origin[2]);
+    sc.right = v3(s->cam_right[0], s->cam_right[1], s->cam_right[2]);
+    sc.up = v3(s->cam_up[0], s->cam_up[1], s->cam_up[2]);
+    sc.fwd = v3(s->cam_forward[0], s->cam_forward[1], s->cam_forward[2]);
+    sc.tan_half_fov = s->tan_half_fov;
+    sc.width = s->width; sc.height = s->height;
+    for (int c = 0; c < 3; ++c) sc.albedo[c] = s->albedo[c];
+    sc.env_w = s->env_width; sc.env_h = s->env_height;
+    sc.n_sph = 1 + s->n_extra_spheres;
+    for (int c = 0; c < 3; ++c) sc.sph[0][c] = s->sphere_center[c];
+    sc.sph[0][3] = s->sphere_radius;
+    for (int k = 0; k < s->n_extra_spheres; ++k) {
+        if (!(s->extra_spheres[k][3] > 0.0f)) return bsdfd_fail_(BSDFD_EINVAL, "sphere radius must be positive");
+        for (int c = 0; c < 4; ++c) sc.sph[k + 1][c] = s->extra_spheres[k][c];
+    }
+    sc.has_plane = s->has_plane ? 1 : 0;
+    sc.plane_y = s->plane_y; sc.checker_scale = s->checker_scale;
+    sc.checker_c0 = s->checker_color0; sc.checker_c1 = s->checker_color1;
+    return BSDFD_OK;
+}
+
+}  // namespace wf_dev

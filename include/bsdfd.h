@@ -40,7 +40,8 @@ extern "C" {
  *      up): bsdfd_measured_table_create(), bsdfd_measured_table_destroy(), bsdfd_measured_eval_table() and
  *      bsdfd_measured_sample_weight_table() (eval() of a mixed-material wavefront in one launch);
  *      bsdfd_measured_sample(), bsdfd_measured_pdf(), bsdfd_measured_sample_table(), bsdfd_measured_pdf_table() and
- *      bsdfd_measured_has_luminance() (the measured BSDF's own importance sampler). */
+ *      bsdfd_measured_has_luminance() (the measured BSDF's own importance sampler);
+ *      bsdfd_wf_path_begin(), bsdfd_wf_bounce() and bsdfd_wf_resolve() (occlusion and further bounces in the array scene). */
 #define BSDFD_ABI_VERSION 8
 
 #define BSDFD_OK 0
@@ -458,6 +459,40 @@ int bsdfd_wf_shade(const bsdfd_wf_scene* scene, const float* env, int32_t row_be
                    int32_t spp, const float* wo, const float* pdf_o, const float* wl, const float* pdf_l,
                    const float* nrm, const float* dir, const float* f_o, const float* f_l, const float* wi,
                    const int64_t* material, float* film, void* hip_stream);
+
+/* ---- path tracing in the array scene: occlusion and further bounces (csrc/pathtrace.hip) ----------
+ * The reference renders its array scenes with Mitsuba's `path` integrator at unbounded depth: balls shadow the floor and
+ * each other, and every further vertex calls the plugin's sample() / pdf() again.  These three kernels keep a path's state
+ * in lane-ordered arrays between those calls; a host loops  bucket -> sample/pdf [-> eval] -> bounce  over a shrinking
+ * wavefront.  Only the environment emits.  All three are stream-ordered, allocate nothing and do not synchronise; N = 0
+ * is a no-op.  Row p of a tile is the global path  path_offset + p  (= row_begin * width * spp + p for a film tile).
+ *
+ * bsdfd_wf_path_begin: from dir / nrm / material as bsdfd_wf_primary wrote them -> org [N,3] world position of the first
+ * vertex (ball k: centre_k + r_k * nrm; floor: the ray/plane point; miss: 0), beta [N,3] = 1 (throughput), rad [N,3] =
+ * env(dir) for a miss, 0 otherwise (radiance gathered so far). */
+int bsdfd_wf_path_begin(const bsdfd_wf_scene* scene, const float* env, int64_t N, const float* dir, const float* nrm,
+                        const int64_t* material, float* org, float* beta, float* rad, void* hip_stream);
+/* One vertex of every live path (material <= n_balls).  In/out: org, nrm, wi, wl, material, beta, rad.  In: wo / pdf_o /
+ * pdf_l (and f_o / f_l, both NULL or both given; NaN = proxy) of the sampler, as bsdfd_wf_shade takes them.
+ *   ball vertex : rad += beta * (the two MIS strategies of bsdfd_wf_shade).  With `occlusion`, a light sample wl that meets
+ *                 geometry adds nothing, and the BSDF sample wo (followed only if wo.z > 0 and pdf_o is positive and finite)
+ *                 adds its environment term only if it escapes; if it hits and `last` is 0 the path moves there: org, nrm,
+ *                 wi (local incoming direction, or the checker reflectance for a floor hit — as bsdfd_wf_primary), material,
+ *                 beta *= f_o / pdf_o (proxy: albedo), and a fresh cosine-weighted wl (Philox key and counter of
+ *                 bsdfd_wf_primary with counter word 3 = 0x57617665 + bounce + 1).  Without `occlusion` no ray is traced
+ *                 and the path ends: bsdfd_wf_shade's estimate.
+ *   floor vertex: the one cosine-sampled direction wl serves both purposes — rad += beta * reflectance * env unless
+ *                 (`occlusion`) it hits a ball; then beta *= reflectance and the path moves there, or ends when `last`.
+ * A path that ends gets material = n_balls + 1 (the "miss" id: the next bucketing sorts it behind the materials); such a
+ * lane is skipped by later calls.  A ray skips the surface it starts on (known from `material`): no epsilon offset.
+ * `bounce` is the 0-based depth of the vertices being shaded. */
+int bsdfd_wf_bounce(const bsdfd_wf_scene* scene, const float* env, int32_t bounce, int32_t last, int32_t occlusion,
+                    uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, float* org, float* nrm, float* wi,
+                    float* wl, int64_t* material, float* beta, float* rad, const float* wo, const float* pdf_o,
+                    const float* pdf_l, const float* f_o, const float* f_l, void* hip_stream);
+/* film [row_end-row_begin, width, 3] += mean over the spp samples of rad [N,3] (bsdfd_wf_shade's accumulation order). */
+int bsdfd_wf_resolve(const bsdfd_wf_scene* scene, int32_t row_begin, int32_t row_end, int32_t spp, const float* rad,
+                     float* film, void* hip_stream);
 
 const char* bsdfd_last_error(void);
 const char* bsdfd_version(void);

@@ -1,0 +1,284 @@
+"""Reference for the path kernels (bsdf_diffusion_sampling_amd/csrc/pathtrace.hip): a numpy restatement of
+``bsdfd_wf_path_begin`` / ``bsdfd_wf_bounce`` / ``bsdfd_wf_resolve``, fp64 by default, fp32 on request (``dtype=np.float32``:
+the same statements in the kernels' own precision, to show which decisions the arithmetic alone can flip).
+
+Test infrastructure only.  The pieces it shares with the one-bounce harness — Philox, the orthonormal basis, the
+environment lookup, the power heuristic — are the oracle's (oracle/wavefront_oracle.py); the scene is the oracle's dict:
+``spheres`` [(centre, radius)], ``plane`` dict(y, c0, c1, scale) or absent, ``albedo``, ``origin``.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from oracle.wavefront_oracle import env_lookup, mis_power, onb, philox4x32
+
+F = np.float32
+T_NONE = 3.0e38
+
+
+def _dot(a, b):
+    return (a * b).sum(1)
+
+
+def trace(scene: dict, org, d, own, dtype=np.float64):
+    """Closest hit of the rays org + t d, the surface ``own`` (a material id per row) excepted.
+    -> (t [N], id [N]: ball index, n_balls for the floor, -1 for nothing, centre [N,3], radius [N] of the winning ball)."""
+    org, d = org.astype(dtype), d.astype(dtype)
+    n = len(org)
+    spheres = scene["spheres"]
+    t_best = np.full(n, dtype(T_NONE), dtype=dtype)
+    hit = np.full(n, -1, dtype=np.int64)
+    cen = np.zeros((n, 3), dtype=dtype)
+    rad = np.ones(n, dtype=dtype)
+    for k, (ck, rk) in enumerate(spheres):
+        c = np.asarray(ck, dtype=F).astype(dtype)   # (the scene is stored in fp32)
+        r = dtype(F(rk))
+        oc = org - c[None, :]
+        b = _dot(oc, d)
+        perp = oc - b[:, None] * d
+        disc = r * r - _dot(perp, perp)
+        t = -b - np.sqrt(np.maximum(disc, dtype(0)))
+        better = (own != k) & (disc > 0) & (t > 0) & (t < t_best)
+        t_best = np.where(better, t, t_best)
+        hit = np.where(better, k, hit)
+        cen = np.where(better[:, None], c[None, :], cen)
+        rad = np.where(better, r, rad)
+    plane = scene.get("plane")
+    if plane is not None:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tp = (dtype(F(plane["y"])) - org[:, 1]) / d[:, 1]
+        better = (own != len(spheres)) & (d[:, 1] < 0) & (tp > 0) & (tp < t_best)
+        t_best = np.where(better, tp, t_best)
+        hit = np.where(better, len(spheres), hit)
+    return t_best.astype(dtype), hit, cen, rad
+
+
+def path_begin(scene: dict, env, dir_, nrm, material, dtype=np.float64):
+    """-> org, beta, rad, each [N,3]."""
+    n_b = len(scene["spheres"])
+    d, nn = dir_.astype(dtype), nrm.astype(dtype)
+    cs = np.asarray([np.asarray(c, dtype=F) for c, _ in scene["spheres"]], dtype=F).astype(dtype)
+    rs = np.asarray([F(r) for _, r in scene["spheres"]], dtype=F).astype(dtype)
+    ball, floor = (material >= 0) & (material < n_b), material == n_b
+    k = np.where(ball, material, 0)
+    org = np.where(ball[:, None], cs[k] + rs[k][:, None] * nn, dtype(0))
+    if scene.get("plane") is not None:
+        o = np.asarray(scene["origin"], dtype=F).astype(dtype)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            t = (dtype(F(scene["plane"]["y"])) - o[1]) / d[:, 1]
+            org = np.where(floor[:, None], o[None, :] + t[:, None] * d, org)
+    rad = np.where((ball | floor)[:, None], dtype(0), env_lookup(env.astype(np.float64), dir_).astype(dtype))
+    return org.astype(dtype), np.ones((len(d), 3), dtype=dtype), rad.astype(dtype)
+
+
+def next_wl(seed: int, pass_idx: int, bounce: int, path_offset: int, n: int):
+    """The light sample of the vertex bounce + 1 of paths path_offset .. path_offset + n - 1 (fp32, primary's mapping)."""
+    gp = np.uint64(path_offset) + np.arange(n, dtype=np.uint64)
+    u = philox4x32(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, gp & np.uint64(0xFFFFFFFF), gp >> np.uint64(32),
+                   pass_idx & 0xFFFFFFFF, (0x57617665 + bounce + 1) & 0xFFFFFFFF)
+    u2 = ((u[2] >> np.uint32(8)).astype(F) + F(1.0)) * F(1.0 / 16777216.0)
+    u3 = (u[3] >> np.uint32(8)).astype(F) * F(1.0 / 16777216.0)
+    r, ang = np.sqrt(u2), F(6.28318530717958647692) * u3
+    return np.stack([r * np.cos(ang), r * np.sin(ang), np.sqrt(np.maximum(F(1.0) - u2, F(0.0)))], 1).astype(F)
+
+
+def bounce(*args, **kwargs):
+    """``_bounce`` with numpy's floating-point warnings off: rows that are masked out divide by zero on the way."""
+    with np.errstate(all="ignore"):
+        return _bounce(*args, **kwargs)
+
+
+def _bounce(scene: dict, env, bounce: int, last: bool, occlusion: bool, seed: int, pass_idx: int, path_offset: int,
+           org, nrm, wi, wl, material, beta, rad, wo, pdf_o, pdf_l, f_o=None, f_l=None, dtype=np.float64):
+    """One call of bsdfd_wf_bounce -> dict(org, nrm, wi, wl, material, beta, rad, cos_in): the arrays after the call (rows the
+    kernel does not write keep their input values); ``cos_in`` [N] = -d . n at the new vertex (nan where none), for the
+    grazing-hit bound."""
+    assert (f_o is None) == (f_l is None)
+    n_b = len(scene["spheres"])
+    n = len(material)
+    cast = lambda a: np.asarray(a).astype(dtype)
+    org, nrm, wi, wl, beta, rad, wo = (cast(a) for a in (org, nrm, wi, wl, beta, rad, wo))
+    live = (material >= 0) & (material <= n_b)
+    floor = live & (material == n_b)
+    ball = live & ~floor
+    safe_n = np.where(live[:, None], nrm, np.array([0.0, 0.0, 1.0], dtype=dtype))
+    fs, ft = onb(safe_n.astype(F))
+    fs, ft = fs.astype(dtype), ft.astype(dtype)
+    to_world = lambda v: v[:, 0:1] * fs + v[:, 1:2] * ft + v[:, 2:3] * safe_n
+    own = np.where(live, material, -2)
+    env64 = env.astype(np.float64)
+    look = lambda dw: env_lookup(env64, dw.astype(F)).astype(dtype)
+    inv_pi = dtype(0.31830988618379067154)
+    albedo = np.asarray(scene["albedo"], dtype=F).astype(dtype)[None, :]
+
+    nothing = (np.full(n, dtype(T_NONE)), np.full(n, -1), np.zeros((n, 3), dtype=dtype), np.ones(n, dtype=dtype))
+    lw = to_world(wl)
+    t_f, id_f, c_f, r_f = trace(scene, org, lw, own, dtype) if occlusion else nothing
+    hit_l = id_f >= 0
+    e_l = look(lw)
+    # ---- ball vertices: the two strategies of shade_kernel ----
+    pb = np.where(np.isfinite(pdf_o) & (pdf_o > 0), pdf_o, 0).astype(dtype)
+    gt_o = np.zeros(n, dtype=bool) if f_o is None else ~np.isnan(f_o[:, 0])
+    gt_l = np.zeros(n, dtype=bool) if f_l is None else ~np.isnan(f_l[:, 0])
+    follow = ball & (pb > 0) & ((wo[:, 2] > 0) if occlusion else np.ones(n, dtype=bool))
+    dw = to_world(wo)
+    t_o, id_o, c_o, r_o = trace(scene, org, dw, own, dtype) if occlusion else nothing
+    with np.errstate(divide="ignore", invalid="ignore"):
+        thr_o = np.where(gt_o[:, None], (np.zeros((n, 3)) if f_o is None else np.nan_to_num(f_o)).astype(dtype) / pb[:, None], albedo)
+    w_o = mis_power(pb, np.maximum(wo[:, 2], 0) * inv_pi).astype(dtype)
+    L = np.where((follow & (id_o < 0))[:, None], w_o[:, None] * look(dw) * thr_o, dtype(0))
+    pl = wl[:, 2] * inv_pi
+    pbl = np.where(np.isfinite(pdf_l) & (pdf_l > 0), pdf_l, 0).astype(dtype)
+    ok_l = ball & (pl > 0) & ((pbl > 0) | gt_l) & ~hit_l
+    with np.errstate(divide="ignore", invalid="ignore"):
+        w_l = np.where(ok_l, mis_power(pl, pbl).astype(dtype) / pl, dtype(0))
+    f_l_v = albedo * pbl[:, None] if f_l is None else np.where(gt_l[:, None], np.nan_to_num(f_l).astype(dtype), albedo * pbl[:, None])
+    L = L + np.where(ok_l[:, None], w_l[:, None] * e_l * f_l_v, dtype(0))
+    # ---- floor vertices: the one cosine-sampled direction ----
+    refl = wi[:, 0:1]
+    L = np.where(floor[:, None], np.where(hit_l[:, None], dtype(0), refl * e_l), L)
+    rad_new = np.where(live[:, None], rad + beta * L, rad)
+    # ---- where the path goes ----
+    go = (follow & (id_o >= 0)) | (floor & hit_l)
+    d = np.where(floor[:, None], lw, dw)
+    t = np.where(floor, t_f, t_o)
+    hid = np.where(floor, id_f, id_o)
+    c, r = np.where(floor[:, None], c_f, c_o), np.where(floor, r_f, r_o)
+    thr = np.where(floor[:, None], refl, thr_o)
+    cont = go & (not last)
+    mat_new = np.where(live, np.where(cont, hid, n_b + 1), material).astype(np.int64)
+    on_ball = cont & (hid < n_b)
+    tt = np.where(cont, t, dtype(0))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        nv = ((org - c) + tt[:, None] * d) / r[:, None]
+        nv = nv / np.sqrt(_dot(nv, nv))[:, None]
+    nv = np.where(on_ball[:, None], nv, np.array([0.0, 1.0, 0.0], dtype=dtype))
+    gs, gt = _onb(nv)   # (the oracle's onb rounds its input to fp32: the new basis is formed in `dtype`)
+    w_ball = np.stack([-_dot(d, gs), -_dot(d, gt), -_dot(d, nv)], 1)
+    x_ball = c + r[:, None] * nv
+    x_floor = org + tt[:, None] * d
+    plane = scene.get("plane") or dict(scale=1.0, c0=0.0, c1=0.0)
+    cx = np.floor(x_floor[:, 0] * dtype(F(plane["scale"]))).astype(np.int64)
+    cz = np.floor(x_floor[:, 2] * dtype(F(plane["scale"]))).astype(np.int64)
+    refl_new = np.where(((cx + cz) & 1) == 1, dtype(F(plane["c1"])), dtype(F(plane["c0"])))
+    out = dict(
+        org=np.where(cont[:, None], np.where(on_ball[:, None], x_ball, x_floor), org),
+        nrm=np.where(cont[:, None], nv, nrm),
+        wi=np.where(cont[:, None], np.where(on_ball[:, None], w_ball, refl_new[:, None]), wi),
+        wl=np.where(cont[:, None], next_wl(seed, pass_idx, bounce, path_offset, n).astype(dtype), wl),
+        material=mat_new,
+        beta=np.where(cont[:, None], beta * thr, beta),
+        rad=rad_new,
+        cos_in=np.where(cont, -_dot(d, nv), np.nan),
+    )
+    return out
+
+
+def _onb(n):
+    """Duff et al. 2017, in the precision of ``n``."""
+    one = n.dtype.type(1)
+    sign = np.copysign(one, n[:, 2])
+    a = -one / (sign + n[:, 2])
+    b = n[:, 0] * n[:, 1] * a
+    s = np.stack([one + sign * n[:, 0] * n[:, 0] * a, sign * b, -sign * n[:, 0]], 1)
+    t = np.stack([b, sign + n[:, 1] * n[:, 1] * a, -n[:, 1]], 1)
+    return s, t
+
+
+def resolve(rad, spp: int):
+    """-> mean over spp of rad, [npix, 3] (what bsdfd_wf_resolve adds to the film)."""
+    return rad.astype(np.float64).reshape(-1, spp, 3).mean(1)
+
+
+# ---- the synthetic wavefront the bounce kernel is checked on (tests/test_gpu_pathtrace.py) and the reference is checked against
+# itself in two precisions (tests/test_pathtrace_cpu.py) ----------------------------------------------------------------------------
+SYNTH_SCENE = dict(spheres=[((-0.7, 0.33, 0.0), 0.33), ((0.05, 0.33, 0.1), 0.33), ((0.6, 0.25, -0.45), 0.25)],
+                   plane=dict(y=0.0, c0=0.4, c1=0.2, scale=2.0), albedo=[0.9, 0.6, 0.3], origin=(0.0, 1.5, 3.0))
+
+
+def synthetic_env(h: int = 32, w: int = 64):
+    """A smooth positive lat-long map whose dependence on the azimuth vanishes at the poles (where atan2 is ill-conditioned)."""
+    v, u = (np.arange(h) + 0.5) / h, (np.arange(w) + 0.5) / w
+    s = np.sin(np.pi * v)[:, None]
+    return np.stack([0.7 + 0.4 * s * np.sin(2 * np.pi * u + c)[None, :] + 0.25 * np.cos(np.pi * v)[:, None] * (1 + 0.3 * c)
+                     for c in (0.0, 1.0, 2.0)], -1).astype(F)
+
+
+def _sphere_dirs(g, n):
+    v = g.standard_normal((n, 3))
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def _cosine_dirs(g, n):
+    u = g.random((n, 2))
+    r, a = np.sqrt(u[:, 0]), 2 * np.pi * u[:, 1]
+    return np.stack([r * np.cos(a), r * np.sin(a), np.sqrt(1 - u[:, 0])], 1)
+
+
+def _near_threshold(scene, org, nrm, own, v_local, tol=1e-4):
+    """Rows whose ray (local direction v_local at the vertex) passes within ``tol`` (relative, in the discriminant) of a ball's
+    silhouette, or lands within ``tol`` of a checker edge — the decisions fp32 rounding alone can flip — or skims the floor."""
+    s, t = _onb(nrm.astype(np.float64))
+    d = v_local[:, 0:1] * s + v_local[:, 1:2] * t + v_local[:, 2:3] * nrm
+    bad = np.zeros(len(org), dtype=bool)
+    for k, (c, r) in enumerate(scene["spheres"]):
+        oc = org - np.asarray(c, dtype=np.float64)[None, :]
+        b = _dot(oc, d)
+        perp = oc - b[:, None] * d
+        bad |= (own != k) & (np.abs(r * r - _dot(perp, perp)) < tol * r * r)
+    tt, hid, _, _ = trace(scene, org, d, own)
+    x = org + np.where(hid >= 0, tt, 0.0)[:, None] * d
+    sc = scene["plane"]["scale"]
+    edge = np.minimum(np.abs(x[:, 0] * sc - np.round(x[:, 0] * sc)), np.abs(x[:, 2] * sc - np.round(x[:, 2] * sc)))
+    far = tt > 50.0   # a ray that skims the floor lands where an fp32 position has no 2e-5 left
+    return bad | ((hid == len(scene["spheres"])) & ((edge < tol) | far))
+
+
+def synthetic_vertices(n: int = 4096, seed: int = 7, scene: dict = SYNTH_SCENE):
+    """A wavefront of ``n`` vertices as bsdfd_wf_bounce takes it: ~50 % on the balls, ~35 % on the floor, ~15 % ended paths
+    (whose state is garbage the kernel must neither read into anything nor overwrite); ``wo`` over the whole sphere (~20 % with
+    wo.z <= 0); ``pdf_o`` over six decades with zeros, infinities and NaNs; ``f_o`` / ``f_l`` with NaN rows (= proxy).  Rays that
+    graze a silhouette or land on a checker edge to within 1e-4 are redrawn: what is left decides the same way in fp32 and fp64
+    on all but a handful of rows, which is what lets the tests hold the kernel to the reference row by row.
+    -> dict of fp32 / int64 arrays."""
+    g = np.random.default_rng(seed)
+    n_b = len(scene["spheres"])
+    kind = g.random(n)
+    mat = np.where(kind < 0.5, g.integers(0, n_b, n), np.where(kind < 0.85, n_b, n_b + 1)).astype(np.int64)
+    ball, floor = mat < n_b, mat == n_b
+    cs = np.asarray([c for c, _ in scene["spheres"]], dtype=np.float64)[np.minimum(mat, n_b - 1)]
+    rs = np.asarray([r for _, r in scene["spheres"]], dtype=np.float64)[np.minimum(mat, n_b - 1)]
+    nrm = np.where(ball[:, None], _sphere_dirs(g, n), np.array([0.0, 1.0, 0.0]))
+    nrm = np.where(ball[:, None] & (cs[:, 1:2] + rs[:, None] * nrm[:, 1:2] < 0.02), nrm * [1, -1, 1], nrm)   # above the floor
+    org = np.where(ball[:, None], cs + rs[:, None] * nrm, np.stack([g.uniform(-1.5, 1.5, n), np.zeros(n), g.uniform(-1.5, 1.5, n)], 1))
+    # the kernel sees fp32 arrays: decide "near a threshold" on exactly those
+    nrm, org = nrm.astype(F).astype(np.float64), org.astype(F).astype(np.float64)
+    wl, wo = _cosine_dirs(g, n), _sphere_dirs(g, n)
+    wo[:, 2] = np.where(g.random(n) < 0.8, np.abs(wo[:, 2]), -np.abs(wo[:, 2]))
+    wo[g.random(n) < 0.01, 2] = 0.0
+    wo /= np.linalg.norm(wo, axis=1, keepdims=True)
+    for _ in range(8):
+        wl32, wo32 = wl.astype(F).astype(np.float64), wo.astype(F).astype(np.float64)
+        bad_l, bad_o = _near_threshold(scene, org, nrm, mat, wl32), _near_threshold(scene, org, nrm, mat, wo32)
+        if not (bad_l.any() or bad_o.any()):
+            break
+        wl = np.where(bad_l[:, None], _cosine_dirs(g, n), wl)
+        wo = np.where(bad_o[:, None], np.abs(_sphere_dirs(g, n)), wo)
+    wi = np.where(ball[:, None], np.abs(_sphere_dirs(g, n)), np.where(g.random(n) < 0.5, 0.4, 0.2)[:, None] * np.ones((1, 3)))
+    pdf_o = np.exp(g.uniform(np.log(1e-3), np.log(1e3), n))
+    special = g.random(n)
+    pdf_o = np.where(special < 0.03, 0.0, np.where(special < 0.06, np.inf, np.where(special < 0.09, np.nan, pdf_o)))
+    pdf_l = np.where(g.random(n) < 0.05, 0.0, np.exp(g.uniform(np.log(1e-3), np.log(1e2), n)))
+    # ground truth f cos with f / pdf <= 1 (so that the throughput stays O(1) and an absolute bound on beta means something)
+    f_o = np.where(np.isfinite(pdf_o) & (pdf_o > 0), pdf_o, 1.0)[:, None] * g.uniform(0.1, 1.0, (n, 3))
+    f_l = g.uniform(0.0, 2.0, (n, 3))
+    no_gt = g.random(n) < 0.4
+    f_o[no_gt], f_l[no_gt] = np.nan, np.nan
+    beta, rad = g.uniform(0.2, 1.0, (n, 3)), g.uniform(0.0, 1.0, (n, 3))
+    dead = ~(ball | floor)
+    for a in (org, nrm, wi, wl, beta):      # an ended path's state is garbage
+        a[dead] = np.nan
+    out = dict(org=org, nrm=nrm, wi=wi, wl=wl, beta=beta, rad=rad, wo=wo, pdf_o=pdf_o, pdf_l=pdf_l, f_o=f_o, f_l=f_l)
+    out = {k: np.ascontiguousarray(v, dtype=F) for k, v in out.items()}
+    out["material"] = mat
+    return out

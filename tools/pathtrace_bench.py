@@ -1,0 +1,101 @@
+"""Cost of the array-scene path tracer (bsdf_diffusion_sampling_amd/pathtrace.py) -> profiles/pathtrace.json.
+
+Workload: the 12-ball array scene at 683x512, 4 spp, disk nets, proxy shading.  Two measurements, each the median over
+interleaved rounds in one process (every variant is timed once per round, `--passes` passes per timing, ending in a device
+synchronise):
+  1. ArrayRenderer's pass against PathArrayRenderer(max_depth=1): the price of the state arrays (org / beta / rad written by
+     path_begin, read and written by bounce, read by resolve) and of three launches where there were two;
+  2. PathArrayRenderer(max_depth=D, occlusion) for D = 2, 4, 8, with stats["lanes_per_bounce"] and the time of each bounce
+     (device events at every bucketing) next to it: does a bounce cost what its live lanes cost, or what the wavefront costs?
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+from bsdf_diffusion_sampling_amd import wavefront as WF
+from bsdf_diffusion_sampling_amd.materials import MaterialTable
+from bsdf_diffusion_sampling_amd.pathtrace import PathArrayRenderer
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--width", type=int, default=683); ap.add_argument("--height", type=int, default=512)
+ap.add_argument("--spp", type=int, default=4); ap.add_argument("--domain", default="disk")
+ap.add_argument("--rounds", type=int, default=9); ap.add_argument("--passes", type=int, default=20)
+ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "pathtrace.json"))
+a = ap.parse_args()
+if not torch.cuda.is_available():
+    sys.exit("tools/pathtrace_bench.py measures on the GPU: no device visible")
+
+cam, centers, radii = WF.array0_scene(a.width, a.height)
+table = MaterialTable([m + "_" + a.domain for m in WF.ARRAY0_MATERIALS])
+variants = {"array": WF.ArrayRenderer(table, centers, radii, camera=cam),
+            "path_d1": PathArrayRenderer(table, centers, radii, camera=cam, max_depth=1)}
+for d in (2, 4, 8):
+    variants[f"path_d{d}_occl"] = PathArrayRenderer(table, centers, radii, camera=cam, max_depth=d)
+dev = variants["array"].device
+film = torch.zeros((a.height, a.width, 3), device=dev)
+
+
+def run(r, passes, first_pass=0):
+    for k in range(passes):
+        r.render_pass(film, 0, a.height, a.spp, 0, first_pass + k)
+    torch.cuda.synchronize(dev)
+
+
+for r in variants.values():   # every shape, every code object
+    run(r, 3)
+times = {k: [] for k in variants}
+for rnd in range(a.rounds):
+    for name, r in variants.items():
+        t0 = time.perf_counter()
+        run(r, a.passes, first_pass=rnd * a.passes)
+        times[name].append((time.perf_counter() - t0) / a.passes * 1e3)
+med = {k: float(np.median(v)) for k, v in times.items()}
+res = {"workload": f"array0_{a.width}x{a.height}_{a.spp}spp_{a.domain}_12balls", "paths_per_pass": a.width * a.height * a.spp,
+       "rounds": a.rounds, "passes_per_timing": a.passes, "device": torch.cuda.get_device_name(dev),
+       "pass_ms_median": med, "pass_ms_min": {k: float(min(v)) for k, v in times.items()},
+       "path_d1_over_array": med["path_d1"] / med["array"], "depth": {}}
+
+# per-bounce times: a device event at every bucketing (= the start of a bounce) and at the resolve
+for d in (2, 4, 8):
+    r = variants[f"path_d{d}_occl"]
+    marks, per_pass = [], []
+    bucket, resolve = r.table.bucket, r.resolve
+
+    def mark():
+        e = torch.cuda.Event(enable_timing=True)
+        e.record()
+        marks.append(e)
+
+    def bucket_marked(*args, **kw):
+        mark()
+        return bucket(*args, **kw)
+
+    def resolve_marked(*args, **kw):
+        mark()
+        return resolve(*args, **kw)
+    r.table.bucket, r.resolve = bucket_marked, resolve_marked
+    try:
+        for k in range(a.passes):
+            del marks[:]
+            r.render_pass(film, 0, a.height, a.spp, 0, 1000 + k)
+            torch.cuda.synchronize(dev)
+            per_pass.append([marks[i].elapsed_time(marks[i + 1]) for i in range(len(marks) - 1)])
+    finally:
+        r.table.bucket, r.resolve = bucket, resolve
+    n_b = min(len(p) for p in per_pass)
+    lanes = r.stats["lanes_per_bounce"]
+    bounce_ms = [float(np.median([p[i] for p in per_pass])) for i in range(n_b)]
+    res["depth"][str(d)] = {"pass_ms_median": med[f"path_d{d}_occl"], "lanes_per_bounce_last_pass": lanes,
+                            "bounce_ms_median": bounce_ms,
+                            "ns_per_material_lane": [1e6 * t / max(l, 1) for t, l in zip(bounce_ms, lanes)]}
+os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+with open(a.out, "w") as f:
+    json.dump(res, f, indent=1)
+    f.write("\n")
+print(json.dumps(res))

@@ -10,6 +10,8 @@ ap.add_argument("--width", type=int, default=683); ap.add_argument("--height", t
 ap.add_argument("--passes", type=int, default=64); ap.add_argument("--spp", type=int, default=4)
 ap.add_argument("--domain", default="disk"); ap.add_argument("--measured-dir", default=None)
 ap.add_argument("--out", default="gpurun_out/array0")
+ap.add_argument("--max-depth", type=int, default=None, help="path vertices (PathArrayRenderer; default: ArrayRenderer's one bounce)")
+ap.add_argument("--occlusion", type=int, choices=(0, 1), default=None, help="trace shadow rays (default: on when --max-depth > 1)")
 a = ap.parse_args()
 cam, centers, radii = WF.array0_scene(a.width, a.height)
 stems = [m + "_" + a.domain for m in WF.ARRAY0_MATERIALS]
@@ -20,12 +22,19 @@ if a.measured_dir:
     for i, m in enumerate(WF.ARRAY0_MATERIALS):
         p = find_measured_file(m, a.measured_dir)
         if p: gts[i] = MeasuredBSDF(p)
-r = WF.ArrayRenderer(tab, centers, radii, camera=cam, ground_truth=gts)
+if a.max_depth is None and a.occlusion is None:
+    r = WF.ArrayRenderer(tab, centers, radii, camera=cam, ground_truth=gts)
+else:
+    from bsdf_diffusion_sampling_amd.pathtrace import PathArrayRenderer
+    r = PathArrayRenderer(tab, centers, radii, camera=cam, ground_truth=gts, max_depth=1 if a.max_depth is None else a.max_depth,
+                          occlusion=None if a.occlusion is None else bool(a.occlusion))
 r.render(2, a.spp, seed=9); torch.cuda.synchronize()
 t0 = time.perf_counter(); img = r.render(a.passes, a.spp, seed=0); torch.cuda.synchronize(); dt = time.perf_counter() - t0
 b = r.primary(0, a.height, 1, 0, 0); mat = b["mat"].cpu().numpy()
 paths = a.width * a.height * a.spp * a.passes
 print(json.dumps({"workload": f"array0_{a.width}x{a.height}_{a.passes}x{a.spp}spp_{a.domain}", "materials": len(tab),
+                  "max_depth": getattr(r, "max_depth", 1), "occlusion": getattr(r, "occlusion", False),
+                  "lanes_per_bounce": getattr(r, "stats", {}).get("lanes_per_bounce"),
                   "ground_truth_materials": len(gts), "seconds": dt, "passes_per_s": a.passes / dt, "Mpaths_per_s": paths / dt / 1e6,
                   "ball_fraction": float((mat < 12).mean()), "floor_fraction": float((mat == 12).mean()), "miss_fraction": float((mat == 13).mean())}))
 img = img.cpu().numpy(); os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
