@@ -57,20 +57,17 @@ struct Field {
     }
 };
 
+// One thread per row; the rows themselves are measured_dev.h's, shared with measured_table.hip.
 // eval(): rgb_out = f cos * tint
 __global__ __launch_bounds__(256) void measured_eval_kernel(MeasuredDev m, const float* __restrict__ wi,
                                                             const float* __restrict__ wo, long long n, Tint tint,
                                                             float* __restrict__ out) {
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n) return;
-    float f[3];
-    measured_f(m, wi[3 * q], wi[3 * q + 1], wi[3 * q + 2], wo[3 * q], wo[3 * q + 1], wo[3 * q + 2], f);
-    out[3 * q] = f[0] * tint.r; out[3 * q + 1] = f[1] * tint.g; out[3 * q + 2] = f[2] * tint.b;
+    eval_row(m, wi, wo, nullptr, q, tint, out, nullptr);
 }
 
-// The tail of the plugins' sample() in one pass (rendering/brdf_measured_disk.py:89-101,
-// brdf_measured_spherical.py:97-109): value = f * albedo / pdf on active lanes with pdf > 0, firefly rule
-// pdf := 0 where lum(value) >= thr, weight = value where active, pdf > 0 and cos(theta_o) > 0, else 0.
+// the tail of the plugins' sample(): weight = f * tint / pdf with the firefly rule
 __global__ __launch_bounds__(256) void measured_weight_kernel(MeasuredDev m, const float* __restrict__ wi,
                                                               const float* __restrict__ wo,
                                                               const float* __restrict__ pdf_in,
@@ -79,24 +76,10 @@ __global__ __launch_bounds__(256) void measured_weight_kernel(MeasuredDev m, con
                                                               float* __restrict__ pdf_out) {
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n) return;
-    const float wiz = wi[3 * q + 2], woz = wo[3 * q + 2];
-    float f[3];
-    measured_f(m, wi[3 * q], wi[3 * q + 1], wiz, wo[3 * q], wo[3 * q + 1], woz, f);
-    const float pdf = pdf_in[q];
-    const bool act = wiz > 0.0f && (!active || active[q] != 0);
-    float v[3] = {0.f, 0.f, 0.f};
-    if (act && pdf > 0.0f) {
-        const float inv = 1.0f / pdf;
-        v[0] = f[0] * tint.r * inv; v[1] = f[1] * tint.g * inv; v[2] = f[2] * tint.b * inv;
-    }
-    const float lum = 0.2126f * v[0] + 0.7152f * v[1] + 0.0722f * v[2];  // rendering/utils/mitsuba_brdf_draw.py:36-38
-    const float p = lum < thr ? pdf : 0.0f;
-    const bool keep = act && p > 0.0f && woz > 0.0f;
-    pdf_out[q] = p;
-    weight[3 * q] = keep ? v[0] : 0.0f; weight[3 * q + 1] = keep ? v[1] : 0.0f; weight[3 * q + 2] = keep ? v[2] : 0.0f;
+    weight_row(m, wi, wo, pdf_in, active, q, tint, thr, weight, pdf_out);
 }
 
-// sample(): the file's own importance sampler (measured_dev.h), one query per lane
+// sample(): the file's own importance sampler, one query per lane
 __global__ __launch_bounds__(256) void measured_sample_kernel(MeasuredDev m, const float* __restrict__ wi,
                                                               const float* __restrict__ u,
                                                               const unsigned char* __restrict__ active, long long n,
@@ -130,6 +113,23 @@ std::vector<float> as_f32(const Field& f) {
     std::vector<float> v(f.count());
     std::memcpy(v.data(), f.ptr, v.size() * sizeof(float));
     return v;
+}
+
+int measured_launch_checks(bsdfd_measured_handle h, int64_t n) {
+    if (!h) return bsdfd_fail_(BSDFD_EINVAL, "null handle");
+    if (n < 0) return bsdfd_fail_(BSDFD_EINVAL, "N must be >= 0");
+    int dev = -1;
+    HIP_TRY(hipGetDevice(&dev));
+    if (dev != h->device) return bsdfd_fail_(BSDFD_EINVAL, "measured handle belongs to another device");
+    if (((long long)n + 255) / 256 > 0x7fffffffLL) return bsdfd_fail_(BSDFD_EINVAL, "N too large for one launch");
+    return BSDFD_OK;
+}
+
+// the host path of the four launchers: `kernel` over N rows of h's material, `args` behind the descriptor
+template <class... P, class... A>
+int measured_launch(bsdfd_measured_handle h, int64_t n, bool pointers_given, void (*kernel)(P...), void* stream, A... args) {
+    if (int rc = measured_launch_checks(h, n)) return rc;
+    return launch_rows(n, pointers_given ? nullptr : "null pointer", kernel, stream, h->dev, args...);
 }
 
 }  // namespace
@@ -326,26 +326,10 @@ int bsdfd_measured_get_info(bsdfd_measured_handle h, int32_t* n_phi, int32_t* n_
     return BSDFD_OK;
 }
 
-static int measured_launch_checks(bsdfd_measured_handle h, int64_t n) {
-    if (!h) return bsdfd_fail_(BSDFD_EINVAL, "null handle");
-    if (n < 0) return bsdfd_fail_(BSDFD_EINVAL, "N must be >= 0");
-    int dev = -1;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev != h->device) return bsdfd_fail_(BSDFD_EINVAL, "measured handle belongs to another device");
-    if (((long long)n + 255) / 256 > 0x7fffffffLL) return bsdfd_fail_(BSDFD_EINVAL, "N too large for one launch");
-    return BSDFD_OK;
-}
-
 int bsdfd_measured_eval(bsdfd_measured_handle h, const float* wi, const float* wo, int64_t n, const float* tint,
                         float* rgb_out, void* stream) {
-    if (int rc = measured_launch_checks(h, n)) return rc;
-    if (n == 0) return BSDFD_OK;
-    if (!wi || !wo || !rgb_out) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
-    const Tint t = tint ? Tint{tint[0], tint[1], tint[2]} : Tint{1.0f, 1.0f, 1.0f};
-    hipLaunchKernelGGL(measured_eval_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), h->dev, wi, wo, (long long)n, t, rgb_out);
-    HIP_TRY(hipGetLastError());
-    return BSDFD_OK;
+    return measured_launch(h, n, wi && wo && rgb_out, measured_eval_kernel, stream, wi, wo, (long long)n, TintArg{tint},
+                           rgb_out);
 }
 
 int bsdfd_measured_has_luminance(bsdfd_measured_handle h, int32_t* has_luminance) {
@@ -356,39 +340,20 @@ int bsdfd_measured_has_luminance(bsdfd_measured_handle h, int32_t* has_luminance
 
 int bsdfd_measured_sample(bsdfd_measured_handle h, const float* wi, const float* u, const unsigned char* active, int64_t n,
                           const float* tint, float* wo_out, float* pdf_out, float* weight_out, void* stream) {
-    if (int rc = measured_launch_checks(h, n)) return rc;
-    if (n == 0) return BSDFD_OK;
-    if (!wi || !u || !wo_out || !pdf_out) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
-    const Tint t = tint ? Tint{tint[0], tint[1], tint[2]} : Tint{1.0f, 1.0f, 1.0f};
-    hipLaunchKernelGGL(measured_sample_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), h->dev, wi, u, active, (long long)n, t, wo_out, pdf_out, weight_out);
-    HIP_TRY(hipGetLastError());
-    return BSDFD_OK;
+    return measured_launch(h, n, wi && u && wo_out && pdf_out, measured_sample_kernel, stream, wi, u, active, (long long)n,
+                           TintArg{tint}, wo_out, pdf_out, weight_out);
 }
 
 int bsdfd_measured_pdf(bsdfd_measured_handle h, const float* wi, const float* wo, const unsigned char* active, int64_t n,
                        float* pdf_out, void* stream) {
-    if (int rc = measured_launch_checks(h, n)) return rc;
-    if (n == 0) return BSDFD_OK;
-    if (!wi || !wo || !pdf_out) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
-    hipLaunchKernelGGL(measured_pdf_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), h->dev, wi, wo, active, (long long)n, pdf_out);
-    HIP_TRY(hipGetLastError());
-    return BSDFD_OK;
+    return measured_launch(h, n, wi && wo && pdf_out, measured_pdf_kernel, stream, wi, wo, active, (long long)n, pdf_out);
 }
 
 int bsdfd_measured_sample_weight(bsdfd_measured_handle h, const float* wi, const float* wo, const float* pdf_sa,
                                  const unsigned char* active, int64_t n, const float* tint, float firefly_threshold,
                                  float* weight_out, float* pdf_out, void* stream) {
-    if (int rc = measured_launch_checks(h, n)) return rc;
-    if (n == 0) return BSDFD_OK;
-    if (!wi || !wo || !pdf_sa || !weight_out || !pdf_out) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
-    const Tint t = tint ? Tint{tint[0], tint[1], tint[2]} : Tint{1.0f, 1.0f, 1.0f};
-    hipLaunchKernelGGL(measured_weight_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), h->dev, wi, wo, pdf_sa, active, (long long)n, t,
-                       firefly_threshold, weight_out, pdf_out);
-    HIP_TRY(hipGetLastError());
-    return BSDFD_OK;
+    return measured_launch(h, n, wi && wo && pdf_sa && weight_out && pdf_out, measured_weight_kernel, stream, wi, wo, pdf_sa,
+                           active, (long long)n, TintArg{tint}, firefly_threshold, weight_out, pdf_out);
 }
 
 }  // extern "C"

@@ -1,7 +1,9 @@
-// measured_dev.h — device side of the RGL measured-BSDF model (the model and the host part: measured.hip), shared by
+// measured_dev.h — device side of the RGL measured-BSDF model, and the launchers' common host path (the model and the rest
+// of the host part: measured.hip), shared by
 // the translation units that evaluate it: measured.hip (one material per launch) and measured_table.hip (a mixed-material
 // wavefront in one launch).  Both inline the same measured_f (eval), measured_sample and measured_pdf (the file's own importance
-// sampler) and compute the same bits (see the pragma below).
+// sampler), run the same row functions (eval_row, weight_row, sample_row, pdf_row) and compute the same bits (see the pragma
+// below); their launchers share launch_rows.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +11,7 @@
 #include <vector>
 
 #include "bsdfd.h"
+#include "common.h"
 
 // Fused multiply-adds are formed per source expression, by the front end, from here to the end of the including translation
 // unit — not wherever the optimiser finds a product next to a sum (hipcc's default): that choice depends on the code around an
@@ -399,7 +402,49 @@ __device__ __forceinline__ float measured_pdf(const MeasuredDev& m, float wix, f
     return p > 0.0f && p < 3.0e38f ? p : 0.0f;
 }
 
-// one row of the sample() / pdf() kernels (measured.hip, measured_table.hip): a row with active[q] == 0 gets zeros
+// ---- one row of each kernel: measured.hip runs them on its one material, measured_table.hip on the material of the row's id ----
+__device__ __forceinline__ void store3(float* __restrict__ out, long long q, float a, float b, float c) {
+    out[3 * q] = a; out[3 * q + 1] = b; out[3 * q + 2] = c;
+}
+
+// eval(): f_o = f(wi, wo) cos * tint and, with a second direction wl (null: none), f_l = f(wi, wl) cos * tint
+__device__ __forceinline__ void eval_row(const MeasuredDev& m, const float* __restrict__ wi, const float* __restrict__ wo,
+                                         const float* __restrict__ wl, long long q, Tint tint, float* __restrict__ f_o,
+                                         float* __restrict__ f_l) {
+    float f[3];
+    measured_f(m, wi[3 * q], wi[3 * q + 1], wi[3 * q + 2], wo[3 * q], wo[3 * q + 1], wo[3 * q + 2], f);
+    store3(f_o, q, f[0] * tint.r, f[1] * tint.g, f[2] * tint.b);
+    if (wl) {
+        measured_f(m, wi[3 * q], wi[3 * q + 1], wi[3 * q + 2], wl[3 * q], wl[3 * q + 1], wl[3 * q + 2], f);
+        store3(f_l, q, f[0] * tint.r, f[1] * tint.g, f[2] * tint.b);
+    }
+}
+
+// The tail of the plugins' sample() in one pass (rendering/brdf_measured_disk.py:89-101,
+// brdf_measured_spherical.py:97-109): value = f * albedo / pdf on active lanes with pdf > 0, firefly rule
+// pdf := 0 where lum(value) >= thr, weight = value where active, pdf > 0 and cos(theta_o) > 0, else 0.
+__device__ __forceinline__ void weight_row(const MeasuredDev& m, const float* __restrict__ wi, const float* __restrict__ wo,
+                                           const float* __restrict__ pdf_in, const unsigned char* __restrict__ active,
+                                           long long q, Tint tint, float thr, float* __restrict__ weight,
+                                           float* __restrict__ pdf_out) {
+    const float wiz = wi[3 * q + 2], woz = wo[3 * q + 2];
+    float f[3];
+    measured_f(m, wi[3 * q], wi[3 * q + 1], wiz, wo[3 * q], wo[3 * q + 1], woz, f);
+    const float pdf = pdf_in[q];
+    const bool act = wiz > 0.0f && (!active || active[q] != 0);
+    float v[3] = {0.f, 0.f, 0.f};
+    if (act && pdf > 0.0f) {
+        const float inv = 1.0f / pdf;
+        v[0] = f[0] * tint.r * inv; v[1] = f[1] * tint.g * inv; v[2] = f[2] * tint.b * inv;
+    }
+    const float lum = 0.2126f * v[0] + 0.7152f * v[1] + 0.0722f * v[2];  // rendering/utils/mitsuba_brdf_draw.py:36-38
+    const float p = lum < thr ? pdf : 0.0f;
+    const bool keep = act && p > 0.0f && woz > 0.0f;
+    pdf_out[q] = p;
+    store3(weight, q, keep ? v[0] : 0.0f, keep ? v[1] : 0.0f, keep ? v[2] : 0.0f);
+}
+
+// sample() / pdf(), the file's own importance sampler: a row with active[q] == 0 gets zeros
 __device__ __forceinline__ void sample_row(const MeasuredDev& m, const float* __restrict__ wi, const float* __restrict__ u,
                                            const unsigned char* __restrict__ active, long long q, Tint tint,
                                            float* __restrict__ wo_out, float* __restrict__ pdf_out,
@@ -415,6 +460,23 @@ __device__ __forceinline__ void pdf_row(const MeasuredDev& m, const float* __res
     float pdf = 0.0f;
     if (!active || active[q] != 0) pdf = measured_pdf(m, wi[3 * q], wi[3 * q + 1], wi[3 * q + 2], wo[3 * q], wo[3 * q + 1], wo[3 * q + 2]);
     pdf_out[q] = pdf;
+}
+
+// ---- host path shared by the launchers of measured.hip and measured_table.hip, after their own launch checks ----
+// a launcher's optional `tint` argument (null: white), read where it becomes the kernel's Tint: at the launch, after the checks
+struct TintArg {
+    const float* rgb;
+    operator Tint() const { return rgb ? Tint{rgb[0], rgb[1], rgb[2]} : Tint{1.0f, 1.0f, 1.0f}; }
+};
+
+// the empty call, `bad` (the first complaint about the arguments, or null), one thread per row in blocks of 256, the launch error
+template <class... P, class... A>
+int launch_rows(int64_t n, const char* bad, void (*kernel)(P...), void* stream, A... args) {
+    if (n == 0) return BSDFD_OK;
+    if (bad) return bsdfd_fail_(BSDFD_EINVAL, bad);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), args...);
+    HIP_TRY(hipGetLastError());
+    return BSDFD_OK;
 }
 
 }  // namespace measured_dev

@@ -4,8 +4,8 @@
 // A renderer's wavefront carries one material id per lane (bsdfd_wf_primary writes them).  Serving eval() through
 // bsdfd_measured_eval takes one launch per material on gathered slices; the evaluator is latency-bound (~60 dependent
 // gathers per pair from L2-resident tables), so many small launches are its worst case.  Here the lanes stay in LANE order:
-// one thread per row loads its id and evaluates the material the id names, through the same measured_f (measured_dev.h)
-// the single-material kernels inline — bit for bit what they return (measured_dev.h fixes where multiply-adds are fused).
+// one thread per row loads its id and evaluates the material the id names, through the same row functions (measured_dev.h)
+// the single-material kernels run — bit for bit what they return (measured_dev.h fixes where multiply-adds are fused).
 // Rows without ground truth get a quiet NaN, the "use the proxy" value bsdfd_wf_shade reads.
 //
 // Image-coherent lanes hit the same ball, so most waves carry ONE id: those take a wave-uniform path on which the descriptor
@@ -67,39 +67,26 @@ __device__ __forceinline__ bool has_ground_truth(const MeasuredDevG& m) { return
 
 __device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7fc00000); }
 
-// true when every live lane of the wave carries the id of its first live lane, which `first` then holds as a scalar.
-// Call with the dead lanes (rows past N) already retired.
-__device__ __forceinline__ bool wave_uniform_id(long long id, long long& first) {
+// The row's material, once: a wave whose live lanes all carry one id (the first live lane's, held as a scalar) addresses the
+// descriptor with that scalar, any other wave per lane; `row(m)` serves a row whose id names a material with ground truth,
+// `none()` every other.  Call with the dead lanes (rows past N) already retired.
+template <class Row, class None>
+__device__ __forceinline__ void with_material(const MeasuredDevG* __restrict__ table, int n_materials, long long id, Row row,
+                                              None none) {
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)id & 0xffffffffull));
     const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)id >> 32));
-    first = (long long)(((unsigned long long)hi << 32) | lo);
-    return __ballot(id != first) == 0ull;
-}
-
-__device__ __forceinline__ void store3(float* __restrict__ out, long long q, float a, float b, float c) {
-    out[3 * q] = a; out[3 * q + 1] = b; out[3 * q + 2] = c;
-}
-
-// one row of eval(): f_o = f(wi, wo) cos * tint and, with a light direction, f_l = f(wi, wl) cos * tint — what
-// measured_eval_kernel (measured.hip) computes for each pair
-__device__ __forceinline__ void eval_row(const MeasuredDev& m, const float* __restrict__ wi, const float* __restrict__ wo,
-                                         const float* __restrict__ wl, long long q, Tint tint, float* __restrict__ f_o,
-                                         float* __restrict__ f_l) {
-    float f[3];
-    measured_f(m, wi[3 * q], wi[3 * q + 1], wi[3 * q + 2], wo[3 * q], wo[3 * q + 1], wo[3 * q + 2], f);
-    store3(f_o, q, f[0] * tint.r, f[1] * tint.g, f[2] * tint.b);
-    if (wl) {
-        measured_f(m, wi[3 * q], wi[3 * q + 1], wi[3 * q + 2], wl[3 * q], wl[3 * q + 1], wl[3 * q + 2], f);
-        store3(f_l, q, f[0] * tint.r, f[1] * tint.g, f[2] * tint.b);
+    const long long first = (long long)(((unsigned long long)hi << 32) | lo);
+    if (__ballot(id != first) == 0ull) {
+        if (first >= 0 && first < n_materials && has_ground_truth(table[first])) row(generic(table[first]));
+        else none();
+    } else {
+        if (id >= 0 && id < n_materials && has_ground_truth(table[id])) row(generic(table[id]));
+        else none();
     }
 }
 
-__device__ __forceinline__ void eval_row_nan(long long q, float* __restrict__ f_o, float* __restrict__ f_l) {
-    const float nan = quiet_nan();
-    store3(f_o, q, nan, nan, nan);
-    if (f_l) store3(f_l, q, nan, nan, nan);
-}
-
+// The four kernels: the rows of measured_dev.h, which the single-material kernels (measured.hip) run too; a row without
+// ground truth gets NaN in every output (the weight kernel passes its pdf through).
 __global__ __launch_bounds__(256) void measured_eval_table_kernel(const MeasuredDevG* __restrict__ table, int n_materials,
                                                                   const long long* __restrict__ material_id,
                                                                   const float* __restrict__ wi,
@@ -108,45 +95,10 @@ __global__ __launch_bounds__(256) void measured_eval_table_kernel(const Measured
                                                                   float* __restrict__ f_o, float* __restrict__ f_l) {
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n) return;
-    const long long id = material_id[q];
-    long long first;
-    if (wave_uniform_id(id, first)) {
-        if (first >= 0 && first < n_materials && has_ground_truth(table[first]))
-            eval_row(generic(table[first]), wi, wo, wl, q, tint, f_o, f_l);
-        else eval_row_nan(q, f_o, f_l);
-    } else {
-        if (id >= 0 && id < n_materials && has_ground_truth(table[id])) eval_row(generic(table[id]), wi, wo, wl, q, tint, f_o, f_l);
-        else eval_row_nan(q, f_o, f_l);
-    }
-}
-
-// one row of the plugins' sample() tail — measured_weight_kernel (measured.hip) for the row's material
-__device__ __forceinline__ void weight_row(const MeasuredDev& m, const float* __restrict__ wi, const float* __restrict__ wo,
-                                           const float* __restrict__ pdf_in, const unsigned char* __restrict__ active,
-                                           long long q, Tint tint, float thr, float* __restrict__ weight,
-                                           float* __restrict__ pdf_out) {
-    const float wiz = wi[3 * q + 2], woz = wo[3 * q + 2];
-    float f[3];
-    measured_f(m, wi[3 * q], wi[3 * q + 1], wiz, wo[3 * q], wo[3 * q + 1], woz, f);
-    const float pdf = pdf_in[q];
-    const bool act = wiz > 0.0f && (!active || active[q] != 0);
-    float v[3] = {0.f, 0.f, 0.f};
-    if (act && pdf > 0.0f) {
-        const float inv = 1.0f / pdf;
-        v[0] = f[0] * tint.r * inv; v[1] = f[1] * tint.g * inv; v[2] = f[2] * tint.b * inv;
-    }
-    const float lum = 0.2126f * v[0] + 0.7152f * v[1] + 0.0722f * v[2];
-    const float p = lum < thr ? pdf : 0.0f;
-    const bool keep = act && p > 0.0f && woz > 0.0f;
-    pdf_out[q] = p;
-    store3(weight, q, keep ? v[0] : 0.0f, keep ? v[1] : 0.0f, keep ? v[2] : 0.0f);
-}
-
-__device__ __forceinline__ void weight_row_nan(const float* __restrict__ pdf_in, long long q, float* __restrict__ weight,
-                                               float* __restrict__ pdf_out) {
     const float nan = quiet_nan();
-    pdf_out[q] = pdf_in[q];
-    store3(weight, q, nan, nan, nan);
+    with_material(table, n_materials, material_id[q],
+                  [&](const MeasuredDev& m) { eval_row(m, wi, wo, wl, q, tint, f_o, f_l); },
+                  [&] { store3(f_o, q, nan, nan, nan); if (f_l) store3(f_l, q, nan, nan, nan); });
 }
 
 __global__ __launch_bounds__(256) void measured_weight_table_kernel(const MeasuredDevG* __restrict__ table, int n_materials,
@@ -159,27 +111,10 @@ __global__ __launch_bounds__(256) void measured_weight_table_kernel(const Measur
                                                                     float* __restrict__ pdf_out) {
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n) return;
-    const long long id = material_id[q];
-    long long first;
-    if (wave_uniform_id(id, first)) {
-        if (first >= 0 && first < n_materials && has_ground_truth(table[first]))
-            weight_row(generic(table[first]), wi, wo, pdf_in, active, q, tint, thr, weight, pdf_out);
-        else weight_row_nan(pdf_in, q, weight, pdf_out);
-    } else {
-        if (id >= 0 && id < n_materials && has_ground_truth(table[id]))
-            weight_row(generic(table[id]), wi, wo, pdf_in, active, q, tint, thr, weight, pdf_out);
-        else weight_row_nan(pdf_in, q, weight, pdf_out);
-    }
-}
-
-// sample() / pdf() of the row's material — sample_row / pdf_row (measured_dev.h), what measured_sample_kernel and
-// measured_pdf_kernel (measured.hip) run; a row without ground truth gets NaN in every output
-__device__ __forceinline__ void sample_row_nan(long long q, float* __restrict__ wo_out, float* __restrict__ pdf_out,
-                                               float* __restrict__ weight_out) {
     const float nan = quiet_nan();
-    store3(wo_out, q, nan, nan, nan);
-    pdf_out[q] = nan;
-    if (weight_out) store3(weight_out, q, nan, nan, nan);
+    with_material(table, n_materials, material_id[q],
+                  [&](const MeasuredDev& m) { weight_row(m, wi, wo, pdf_in, active, q, tint, thr, weight, pdf_out); },
+                  [&] { pdf_out[q] = pdf_in[q]; store3(weight, q, nan, nan, nan); });
 }
 
 __global__ __launch_bounds__(256) void measured_sample_table_kernel(const MeasuredDevG* __restrict__ table, int n_materials,
@@ -191,17 +126,10 @@ __global__ __launch_bounds__(256) void measured_sample_table_kernel(const Measur
                                                                     float* __restrict__ weight_out) {
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n) return;
-    const long long id = material_id[q];
-    long long first;
-    if (wave_uniform_id(id, first)) {
-        if (first >= 0 && first < n_materials && has_ground_truth(table[first]))
-            sample_row(generic(table[first]), wi, u, active, q, tint, wo_out, pdf_out, weight_out);
-        else sample_row_nan(q, wo_out, pdf_out, weight_out);
-    } else {
-        if (id >= 0 && id < n_materials && has_ground_truth(table[id]))
-            sample_row(generic(table[id]), wi, u, active, q, tint, wo_out, pdf_out, weight_out);
-        else sample_row_nan(q, wo_out, pdf_out, weight_out);
-    }
+    const float nan = quiet_nan();
+    with_material(table, n_materials, material_id[q],
+                  [&](const MeasuredDev& m) { sample_row(m, wi, u, active, q, tint, wo_out, pdf_out, weight_out); },
+                  [&] { store3(wo_out, q, nan, nan, nan); pdf_out[q] = nan; if (weight_out) store3(weight_out, q, nan, nan, nan); });
 }
 
 __global__ __launch_bounds__(256) void measured_pdf_table_kernel(const MeasuredDevG* __restrict__ table, int n_materials,
@@ -211,16 +139,8 @@ __global__ __launch_bounds__(256) void measured_pdf_table_kernel(const MeasuredD
                                                                  float* __restrict__ pdf_out) {
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n) return;
-    const long long id = material_id[q];
-    long long first;
-    if (wave_uniform_id(id, first)) {
-        if (first >= 0 && first < n_materials && has_ground_truth(table[first]))
-            pdf_row(generic(table[first]), wi, wo, active, q, pdf_out);
-        else pdf_out[q] = quiet_nan();
-    } else {
-        if (id >= 0 && id < n_materials && has_ground_truth(table[id])) pdf_row(generic(table[id]), wi, wo, active, q, pdf_out);
-        else pdf_out[q] = quiet_nan();
-    }
+    with_material(table, n_materials, material_id[q], [&](const MeasuredDev& m) { pdf_row(m, wi, wo, active, q, pdf_out); },
+                  [&] { pdf_out[q] = quiet_nan(); });
 }
 
 }  // namespace
@@ -241,6 +161,15 @@ int table_launch_checks(bsdfd_measured_table t, int64_t n) {
     if (dev != t->device) return bsdfd_fail_(BSDFD_EINVAL, "measured table belongs to another device");
     if ((long long)n > 0xffffffffLL - 255) return bsdfd_fail_(BSDFD_EINVAL, "N too large for one launch");   // grid * block < 2^32
     return BSDFD_OK;
+}
+
+// the host path of the four launchers: `kernel` over N rows with their ids, `args` behind the table and the ids
+template <class... P, class... A>
+int table_launch(bsdfd_measured_table t, int64_t n, const int64_t* material_id, const char* bad, void (*kernel)(P...),
+                 void* stream, A... args) {
+    if (int rc = table_launch_checks(t, n)) return rc;
+    return launch_rows(n, bad, kernel, stream, reinterpret_cast<const MeasuredDevG*>(t->dev), (int)t->n_materials,
+                       reinterpret_cast<const long long*>(material_id), args...);
 }
 
 }  // namespace
@@ -283,59 +212,34 @@ void bsdfd_measured_table_destroy(bsdfd_measured_table t) {
 
 int bsdfd_measured_eval_table(bsdfd_measured_table t, const int64_t* material_id, const float* wi, const float* wo,
                               const float* wl, int64_t n, const float* tint, float* f_o, float* f_l, void* stream) {
-    if (int rc = table_launch_checks(t, n)) return rc;
-    if (n == 0) return BSDFD_OK;
-    if ((wl == nullptr) != (f_l == nullptr)) return bsdfd_fail_(BSDFD_EINVAL, "wl and f_l are both NULL or both given");
-    if (!material_id || !wi || !wo || !f_o) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
-    const Tint c = tint ? Tint{tint[0], tint[1], tint[2]} : Tint{1.0f, 1.0f, 1.0f};
-    hipLaunchKernelGGL(measured_eval_table_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), reinterpret_cast<const MeasuredDevG*>(t->dev), (int)t->n_materials,
-                       reinterpret_cast<const long long*>(material_id), wi, wo, wl, (long long)n, c, f_o, f_l);
-    HIP_TRY(hipGetLastError());
-    return BSDFD_OK;
+    const char* bad = (wl == nullptr) != (f_l == nullptr) ? "wl and f_l are both NULL or both given"
+                      : !material_id || !wi || !wo || !f_o ? "null pointer" : nullptr;
+    return table_launch(t, n, material_id, bad, measured_eval_table_kernel, stream, wi, wo, wl, (long long)n, TintArg{tint},
+                        f_o, f_l);
 }
 
 int bsdfd_measured_sample_weight_table(bsdfd_measured_table t, const int64_t* material_id, const float* wi,
                                        const float* wo, const float* pdf_sa, const unsigned char* active, int64_t n,
                                        const float* tint, float firefly_threshold, float* weight_out, float* pdf_out,
                                        void* stream) {
-    if (int rc = table_launch_checks(t, n)) return rc;
-    if (n == 0) return BSDFD_OK;
-    if (!material_id || !wi || !wo || !pdf_sa || !weight_out || !pdf_out) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
-    const Tint c = tint ? Tint{tint[0], tint[1], tint[2]} : Tint{1.0f, 1.0f, 1.0f};
-    hipLaunchKernelGGL(measured_weight_table_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), reinterpret_cast<const MeasuredDevG*>(t->dev), (int)t->n_materials,
-                       reinterpret_cast<const long long*>(material_id), wi, wo, pdf_sa, active, (long long)n, c,
-                       firefly_threshold, weight_out, pdf_out);
-    HIP_TRY(hipGetLastError());
-    return BSDFD_OK;
+    const bool given = material_id && wi && wo && pdf_sa && weight_out && pdf_out;
+    return table_launch(t, n, material_id, given ? nullptr : "null pointer", measured_weight_table_kernel, stream, wi, wo, pdf_sa,
+                        active, (long long)n, TintArg{tint}, firefly_threshold, weight_out, pdf_out);
 }
 
 int bsdfd_measured_sample_table(bsdfd_measured_table t, const int64_t* material_id, const float* wi, const float* u,
                                 const unsigned char* active, int64_t n, const float* tint, float* wo_out, float* pdf_out,
                                 float* weight_out, void* stream) {
-    if (int rc = table_launch_checks(t, n)) return rc;
-    if (n == 0) return BSDFD_OK;
-    if (!material_id || !wi || !u || !wo_out || !pdf_out) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
-    const Tint c = tint ? Tint{tint[0], tint[1], tint[2]} : Tint{1.0f, 1.0f, 1.0f};
-    hipLaunchKernelGGL(measured_sample_table_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), reinterpret_cast<const MeasuredDevG*>(t->dev), (int)t->n_materials,
-                       reinterpret_cast<const long long*>(material_id), wi, u, active, (long long)n, c, wo_out, pdf_out,
-                       weight_out);
-    HIP_TRY(hipGetLastError());
-    return BSDFD_OK;
+    const bool given = material_id && wi && u && wo_out && pdf_out;
+    return table_launch(t, n, material_id, given ? nullptr : "null pointer", measured_sample_table_kernel, stream, wi, u, active,
+                        (long long)n, TintArg{tint}, wo_out, pdf_out, weight_out);
 }
 
 int bsdfd_measured_pdf_table(bsdfd_measured_table t, const int64_t* material_id, const float* wi, const float* wo,
                              const unsigned char* active, int64_t n, float* pdf_out, void* stream) {
-    if (int rc = table_launch_checks(t, n)) return rc;
-    if (n == 0) return BSDFD_OK;
-    if (!material_id || !wi || !wo || !pdf_out) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
-    hipLaunchKernelGGL(measured_pdf_table_kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0,
-                       static_cast<hipStream_t>(stream), reinterpret_cast<const MeasuredDevG*>(t->dev), (int)t->n_materials,
-                       reinterpret_cast<const long long*>(material_id), wi, wo, active, (long long)n, pdf_out);
-    HIP_TRY(hipGetLastError());
-    return BSDFD_OK;
+    const bool given = material_id && wi && wo && pdf_out;
+    return table_launch(t, n, material_id, given ? nullptr : "null pointer", measured_pdf_table_kernel, stream, wi, wo, active,
+                        (long long)n, pdf_out);
 }
 
 }  // extern "C"

@@ -117,22 +117,18 @@ __global__ __launch_bounds__(256) void bounce_kernel(Scene sc, const float* __re
         const float refl = wi[3 * p];
         if (occlusion) h = trace(sc, x, lw, (int)m);
         if (h.id < 0) {
-            float e[3];
-            env_lookup(env, sc.env_w, sc.env_h, lw, e);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) L[c] = refl * e[c];
+            floor_term(sc, env, lw, refl, L);
         } else {
             go = true;
 #pragma unroll
             for (int c = 0; c < 3; ++c) thr[c] = refl;
         }
     } else {
-        // the two strategies of shade_kernel, same expressions in the same order
-        const bool gt_o = f_o && f_o[3 * p] == f_o[3 * p];
-        const bool gt_l = f_l && f_l[3 * p] == f_l[3 * p];
+        // the two strategies of shade_kernel, same expressions in the same order: a copy, because the shared form of these two
+        // terms rounded differently (the compiler fuses and packs their multiply-adds by the code around them)
+        const bool gt_o = has_ground_truth(f_o, p), gt_l = has_ground_truth(f_l, p);
         const V3 o = ld3(wo + 3 * p);
-        float pb = pdf_o[p];
-        if (!(pb > 0.0f) || !isfinite(pb)) pb = 0.0f;
+        const float pb = usable_pdf(pdf_o[p]);
         if (pb > 0.0f && (!occlusion || o.z > 0.0f)) {   // (a direction below the surface is blocked by the ball itself)
             d = o.x * fs + o.y * ft + o.z * nn;
 #pragma unroll
@@ -150,8 +146,7 @@ __global__ __launch_bounds__(256) void bounce_kernel(Scene sc, const float* __re
         }
         // light-sampled direction (cosine hemisphere, pdf cos/pi): f cos / pdf_light, unless something is in the way
         const float pl = l.z * inv_pi;
-        float pbl = pdf_l[p];
-        if (!(pbl > 0.0f) || !isfinite(pbl)) pbl = 0.0f;
+        const float pbl = usable_pdf(pdf_l[p]);
         if (pl > 0.0f && (pbl > 0.0f || gt_l) && !(occlusion && trace(sc, x, lw, (int)m).id >= 0)) {
             const float w = mis_power(pl, pbl) / pl;
             float e[3];
@@ -189,11 +184,7 @@ __global__ __launch_bounds__(256) void bounce_kernel(Scene sc, const float* __re
     unsigned u[4];
     philox4x32((unsigned)seed, (unsigned)(seed >> 32), (unsigned)gp, (unsigned)(gp >> 32), (unsigned)pass,
                0x57617665u + (unsigned)(bounce + 1), u);
-    const float u2 = u01_open(u[2]), u3 = (float)(u[3] >> 8) * (1.0f / 16777216.0f);
-    const float r = sqrtf(u2);
-    float sp, cp;
-    sincosf(6.28318530717958647692f * u3, &sp, &cp);
-    st3(wl + 3 * p, v3(r * cp, r * sp, sqrtf(fmaxf(1.0f - u2, 0.0f))));
+    st3(wl + 3 * p, cosine_sample(u[2], u[3]));
     st3(org + 3 * p, xv);
     st3(nrm + 3 * p, nv);
     st3(wi + 3 * p, w_in);
@@ -201,29 +192,20 @@ __global__ __launch_bounds__(256) void bounce_kernel(Scene sc, const float* __re
     mat[p] = h.id;
 }
 
-// same accumulation order as shade_kernel's tail
 __global__ __launch_bounds__(256) void resolve_kernel(long long npix, int spp, const float* __restrict__ rad,
                                                       float* __restrict__ film) {
     const long long pix = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= npix) return;
-    float acc[3] = {0.f, 0.f, 0.f};
-    for (int s = 0; s < spp; ++s) {
-        const V3 L = ld3(rad + 3 * (pix * spp + s));
-        acc[0] += L.x; acc[1] += L.y; acc[2] += L.z;
-    }
-    const float inv = 1.0f / (float)spp;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) film[3 * pix + c] += acc[c] * inv;
+    add_pixel_mean(film, pix, spp, [&](long long p, float L[3]) { L[0] = rad[3 * p]; L[1] = rad[3 * p + 1]; L[2] = rad[3 * p + 2]; });
 }
 
 // scene + environment + lane count of a launch over N paths (no tile: the path kernels take N and a path offset)
-int path_scene(const bsdfd_wf_scene* s, const float* env, long long n, Scene& sc, long long& blocks) {
+int path_scene(const bsdfd_wf_scene* s, const float* env, long long n, Scene& sc) {
     if (int rc = to_scene(s, 0, 0, 1, sc)) return rc;
     if (sc.env_w <= 0 || sc.env_h <= 0) return bsdfd_fail_(BSDFD_EINVAL, "environment map size must be positive");
     if (n < 0) return bsdfd_fail_(BSDFD_EINVAL, "negative path count");
     if (n > 0 && !env) return bsdfd_fail_(BSDFD_EINVAL, "null environment map");
-    blocks = (n + 255) / 256;
-    if (blocks > 0x7fffffffLL) return bsdfd_fail_(BSDFD_EINVAL, "wavefront too large for one launch");
+    if ((n + 255) / 256 > 0x7fffffffLL) return bsdfd_fail_(BSDFD_EINVAL, "wavefront too large for one launch");
     return BSDFD_OK;
 }
 
@@ -234,14 +216,11 @@ extern "C" {
 int bsdfd_wf_path_begin(const bsdfd_wf_scene* scene, const float* env, int64_t N, const float* dir, const float* nrm,
                         const int64_t* material, float* org, float* beta, float* rad, void* stream) {
     Scene sc;
-    long long blocks;
-    if (int rc = path_scene(scene, env, N, sc, blocks)) return rc;
+    if (int rc = path_scene(scene, env, N, sc)) return rc;
     if (N == 0) return BSDFD_OK;
     if (!dir || !nrm || !material || !org || !beta || !rad) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
-    hipLaunchKernelGGL(path_begin_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), sc, env,
-                       (long long)N, dir, nrm, reinterpret_cast<const long long*>(material), org, beta, rad);
-    HIP_TRY(hipGetLastError());
-    return BSDFD_OK;
+    return launch_lanes(N, path_begin_kernel, stream, sc, env, (long long)N, dir, nrm, reinterpret_cast<const long long*>(material),
+                        org, beta, rad);
 }
 
 int bsdfd_wf_bounce(const bsdfd_wf_scene* scene, const float* env, int32_t bounce, int32_t last, int32_t occlusion,
@@ -249,19 +228,15 @@ int bsdfd_wf_bounce(const bsdfd_wf_scene* scene, const float* env, int32_t bounc
                     float* wl, int64_t* material, float* beta, float* rad, const float* wo, const float* pdf_o,
                     const float* pdf_l, const float* f_o, const float* f_l, void* stream) {
     Scene sc;
-    long long blocks;
-    if (int rc = path_scene(scene, env, N, sc, blocks)) return rc;
+    if (int rc = path_scene(scene, env, N, sc)) return rc;
     if (bounce < 0) return bsdfd_fail_(BSDFD_EINVAL, "bounce must be >= 0");
     if ((f_o == nullptr) != (f_l == nullptr)) return bsdfd_fail_(BSDFD_EINVAL, "f_o and f_l are both NULL or both given");
     if (N == 0) return BSDFD_OK;
     if (!org || !nrm || !wi || !wl || !material || !beta || !rad || !wo || !pdf_o || !pdf_l)
         return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
-    hipLaunchKernelGGL(bounce_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), sc, env,
-                       (int)bounce, last ? 1 : 0, occlusion ? 1 : 0, (unsigned long long)seed, (unsigned long long)pass,
-                       (unsigned long long)path_offset, (long long)N, org, nrm, wi, wl,
-                       reinterpret_cast<long long*>(material), beta, rad, wo, pdf_o, pdf_l, f_o, f_l);
-    HIP_TRY(hipGetLastError());
-    return BSDFD_OK;
+    return launch_lanes(N, bounce_kernel, stream, sc, env, (int)bounce, last ? 1 : 0, occlusion ? 1 : 0, (unsigned long long)seed,
+                        (unsigned long long)pass, (unsigned long long)path_offset, (long long)N, org, nrm, wi, wl,
+                        reinterpret_cast<long long*>(material), beta, rad, wo, pdf_o, pdf_l, f_o, f_l);
 }
 
 int bsdfd_wf_resolve(const bsdfd_wf_scene* scene, int32_t row_begin, int32_t row_end, int32_t spp, const float* rad,
@@ -271,11 +246,7 @@ int bsdfd_wf_resolve(const bsdfd_wf_scene* scene, int32_t row_begin, int32_t row
     const long long npix = (long long)(row_end - row_begin) * sc.width;
     if (npix == 0) return BSDFD_OK;
     if (!rad || !film) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
-    const long long blocks = (npix + 255) / 256;
-    hipLaunchKernelGGL(resolve_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), npix,
-                       (int)spp, rad, film);
-    HIP_TRY(hipGetLastError());
-    return BSDFD_OK;
+    return launch_lanes(npix, resolve_kernel, stream, npix, (int)spp, rad, film);
 }
 
 }  // extern "C"

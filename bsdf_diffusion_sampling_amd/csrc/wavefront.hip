@@ -90,11 +90,7 @@ __global__ __launch_bounds__(256) void primary_kernel(Scene sc, int row_begin, i
         material = sc.n_sph;
     }
     // cosine-weighted light-sample direction in the local frame
-    const float u2 = u01_open(u[2]), u3 = (float)(u[3] >> 8) * (1.0f / 16777216.0f);
-    const float r = sqrtf(u2);
-    float sp, cp;
-    sincosf(6.28318530717958647692f * u3, &sp, &cp);
-    const V3 w_l = v3(r * cp, r * sp, sqrtf(fmaxf(1.0f - u2, 0.0f)));
+    const V3 w_l = cosine_sample(u[2], u[3]);
     st3(wi + 3 * p, w_in);
     st3(wl + 3 * p, w_l);
     st3(nrm + 3 * p, nn);
@@ -112,23 +108,16 @@ __global__ __launch_bounds__(256) void shade_kernel(Scene sc, const float* __res
     const long long npix = (long long)(row_end - row_begin) * sc.width;
     const long long pix = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= npix) return;
-    float acc[3] = {0.f, 0.f, 0.f};
     const float inv_pi = 0.31830988618379067154f;
-    for (int s = 0; s < spp; ++s) {
-        const long long p = pix * spp + s;
+    add_pixel_mean(film, pix, spp, [&](long long p, float L[3]) {
         const V3 n = ld3(nrm + 3 * p);
-        float L[3];
         if (n.x == 0.0f && n.y == 0.0f && n.z == 0.0f) {  // miss: the camera sees the environment
             env_lookup(env, sc.env_w, sc.env_h, ld3(dir + 3 * p), L);
         } else if (mat && mat[p] == sc.n_sph) {  // diffuse floor, cosine-sampled: f cos / pdf = reflectance
             V3 fs, ft;
             onb(n, fs, ft);
             const V3 l = ld3(wl + 3 * p);
-            float e[3];
-            env_lookup(env, sc.env_w, sc.env_h, l.x * fs + l.y * ft + l.z * n, e);
-            const float refl = wi[3 * p];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) L[c] = refl * e[c];
+            floor_term(sc, env, l.x * fs + l.y * ft + l.z * n, wi[3 * p], L);
         } else {
             V3 fs, ft;
             onb(n, fs, ft);
@@ -138,11 +127,9 @@ __global__ __launch_bounds__(256) void shade_kernel(Scene sc, const float* __res
             // (the nets model pdf ∝ lum(f cos)) gives weight = albedo.
             // per-path opt-out: a NaN in the f arrays selects the proxy for that path (array scenes mix materials
             // with and without a ground-truth file)
-            const bool gt_o = f_o && f_o[3 * p] == f_o[3 * p];
-            const bool gt_l = f_l && f_l[3 * p] == f_l[3 * p];
+            const bool gt_o = has_ground_truth(f_o, p), gt_l = has_ground_truth(f_l, p);
             const V3 o = ld3(wo + 3 * p);
-            float pb = pdf_o[p];
-            if (!(pb > 0.0f) || !isfinite(pb)) pb = 0.0f;
+            const float pb = usable_pdf(pdf_o[p]);
             if (pb > 0.0f) {
                 const float w = mis_power(pb, fmaxf(o.z, 0.0f) * inv_pi);
                 float e[3];
@@ -153,8 +140,7 @@ __global__ __launch_bounds__(256) void shade_kernel(Scene sc, const float* __res
             // light-sampled direction (cosine hemisphere, pdf cos/pi): f cos / pdf_light
             const V3 l = ld3(wl + 3 * p);
             const float pl = l.z * inv_pi;
-            float pbl = pdf_l[p];
-            if (!(pbl > 0.0f) || !isfinite(pbl)) pbl = 0.0f;
+            const float pbl = usable_pdf(pdf_l[p]);
             if (pl > 0.0f && (pbl > 0.0f || gt_l)) {
                 const float w = mis_power(pl, pbl) / pl;
                 float e[3];
@@ -163,12 +149,7 @@ __global__ __launch_bounds__(256) void shade_kernel(Scene sc, const float* __res
                 for (int c = 0; c < 3; ++c) L[c] += w * e[c] * (gt_l ? f_l[3 * p + c] : sc.albedo[c] * pbl);
             }
         }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) acc[c] += L[c];
-    }
-    const float inv = 1.0f / (float)spp;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) film[3 * pix + c] += acc[c] * inv;
+    });
 }
 
 }  // namespace
@@ -182,13 +163,9 @@ int bsdfd_wf_primary(const bsdfd_wf_scene* scene, int32_t row_begin, int32_t row
     const long long n = (long long)(row_end - row_begin) * sc.width * spp;
     if (n == 0) return BSDFD_OK;
     if (!wi || !wl || !nrm || !dir) return bsdfd_fail_(BSDFD_EINVAL, "null output pointer");
-    const long long blocks = (n + 255) / 256;
-    if (blocks > 0x7fffffffLL) return bsdfd_fail_(BSDFD_EINVAL, "tile too large for one launch");
-    hipLaunchKernelGGL(primary_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), sc,
-                       row_begin, row_end, spp, (unsigned long long)seed, (unsigned long long)pass, wi, wl, nrm, dir,
-                       reinterpret_cast<long long*>(material));
-    HIP_TRY(hipGetLastError());
-    return BSDFD_OK;
+    if ((n + 255) / 256 > 0x7fffffffLL) return bsdfd_fail_(BSDFD_EINVAL, "tile too large for one launch");
+    return launch_lanes(n, primary_kernel, stream, sc, row_begin, row_end, spp, (unsigned long long)seed,
+                        (unsigned long long)pass, wi, wl, nrm, dir, reinterpret_cast<long long*>(material));
 }
 
 int bsdfd_wf_shade(const bsdfd_wf_scene* scene, const float* env, int32_t row_begin, int32_t row_end, int32_t spp,
@@ -204,12 +181,8 @@ int bsdfd_wf_shade(const bsdfd_wf_scene* scene, const float* env, int32_t row_be
         return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
     if (material && !wi) return bsdfd_fail_(BSDFD_EINVAL, "the material ids need the wi array (floor reflectance)");
     if (sc.has_plane && !material) return bsdfd_fail_(BSDFD_EINVAL, "a scene with a floor needs the material ids");
-    const long long blocks = (npix + 255) / 256;
-    hipLaunchKernelGGL(shade_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), sc, env,
-                       row_begin, row_end, spp, wo, pdf_o, wl, pdf_l, nrm, dir, f_o, f_l, wi,
-                       reinterpret_cast<const long long*>(material), film);
-    HIP_TRY(hipGetLastError());
-    return BSDFD_OK;
+    return launch_lanes(npix, shade_kernel, stream, sc, env, row_begin, row_end, spp, wo, pdf_o, wl, pdf_l, nrm, dir, f_o, f_l,
+                        wi, reinterpret_cast<const long long*>(material), film);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // wavefront_dev.h — the scene model of the wavefront harness, shared by the translation units that trace it: wavefront.hip
 // (primary rays, one-bounce shading) and pathtrace.hip (occlusion and further bounces).  Both inline the same vector helpers,
-// orthonormal basis, environment lookup and MIS weight, and build the kernel-argument `Scene` from the same bsdfd_wf_scene.
+// orthonormal basis, environment lookup and MIS weight, the same light sample, floor term and pixel mean, and build the
+// kernel-argument `Scene` from the same bsdfd_wf_scene.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -75,6 +76,55 @@ __device__ __forceinline__ float mis_power(float pa, float pb) {  // mitsuba_hel
     if (!(pa > 0.0f)) return 0.0f;
     const float q = pb / pa;
     return 1.0f / fmaf(q, q, 1.0f);
+}
+
+// cosine-weighted light-sample direction in the local frame, from two Philox words
+__device__ __forceinline__ V3 cosine_sample(unsigned a, unsigned b) {
+    const float u2 = u01_open(a), u3 = (float)(b >> 8) * (1.0f / 16777216.0f);
+    const float r = sqrtf(u2);
+    float sp, cp;
+    sincosf(6.28318530717958647692f * u3, &sp, &cp);
+    return v3(r * cp, r * sp, sqrtf(fmaxf(1.0f - u2, 0.0f)));
+}
+
+// ---- pieces of the radiance estimate at a vertex that shade_kernel and bounce_kernel share ----
+// a sampler's pdf as the estimate uses it: anything but a positive finite number is 0
+__device__ __forceinline__ float usable_pdf(float p) { return !(p > 0.0f) || !isfinite(p) ? 0.0f : p; }
+
+// per-path opt-out of the ground truth: a NaN in an f array selects the proxy for that path (array scenes mix materials with
+// and without a ground-truth file); so does a null array
+__device__ __forceinline__ bool has_ground_truth(const float* f, long long p) { return f && f[3 * p] == f[3 * p]; }
+
+// diffuse floor, cosine-sampled towards lw: f cos / pdf = reflectance
+__device__ __forceinline__ void floor_term(const Scene& sc, const float* __restrict__ env, V3 lw, float refl, float L[3]) {
+    float e[3];
+    env_lookup(env, sc.env_w, sc.env_h, lw, e);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) L[c] = refl * e[c];
+}
+
+// film[pix] += the mean over the pixel's spp paths of radiance(path, L)
+template <class Radiance>
+__device__ __forceinline__ void add_pixel_mean(float* __restrict__ film, long long pix, int spp, Radiance radiance) {
+    float acc[3] = {0.f, 0.f, 0.f};
+    for (int s = 0; s < spp; ++s) {
+        float L[3];
+        radiance(pix * spp + s, L);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] += L[c];
+    }
+    const float inv = 1.0f / (float)spp;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) film[3 * pix + c] += acc[c] * inv;
+}
+
+// ---- host side ----
+// one thread per lane in blocks of 256 on `stream`, and the launch error
+template <class... P, class... A>
+int launch_lanes(long long n, void (*kernel)(P...), void* stream, A... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), args...);
+    HIP_TRY(hipGetLastError());
+    return BSDFD_OK;
 }
 
 // the kernel-argument form of a bsdfd_wf_scene, validated together with the tile [row_begin, row_end) x spp

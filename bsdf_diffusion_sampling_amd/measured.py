@@ -35,6 +35,15 @@ def find_measured_file(material: str, directory: Optional[str] = None) -> Option
     return None
 
 
+def _launch(name: str, device, *args):
+    """One launch of the library's ``name`` on ``device``'s current stream, with that device current: tensors go as their data
+    pointers, None as NULL, everything else as it is; the stream is the last argument."""
+    with torch.cuda.device(device):
+        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        _lib.check(getattr(_lib.lib(), name)(*[C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args],
+                                             stream))
+
+
 class MeasuredBSDF:
     def __init__(self, path: str):
         self.path = path
@@ -80,10 +89,7 @@ class MeasuredBSDF:
         self._check(wi=(wi, 3), wo=(wo, 3))
         if out is None:
             out = torch.empty_like(wi)
-        with torch.cuda.device(wi.device):
-            stream = C.c_void_p(torch.cuda.current_stream(wi.device).cuda_stream)
-            _lib.check(_lib.lib().bsdfd_measured_eval(self._h, C.c_void_p(wi.data_ptr()), C.c_void_p(wo.data_ptr()),
-                                                      wi.shape[0], self._tint(tint), C.c_void_p(out.data_ptr()), stream))
+        _launch("bsdfd_measured_eval", wi.device, self._h, wi, wo, wi.shape[0], self._tint(tint), out)
         return out
 
     def sample_weight(self, wi: torch.Tensor, wo: torch.Tensor, pdf_sa: torch.Tensor, tint=None,
@@ -98,12 +104,8 @@ class MeasuredBSDF:
             if act.shape != (wi.shape[0],):
                 raise ValueError("MeasuredBSDF.sample_weight: active must be [N]")
         weight, pdf = torch.empty_like(wi), torch.empty_like(pdf_sa)
-        with torch.cuda.device(wi.device):
-            stream = C.c_void_p(torch.cuda.current_stream(wi.device).cuda_stream)
-            _lib.check(_lib.lib().bsdfd_measured_sample_weight(
-                self._h, C.c_void_p(wi.data_ptr()), C.c_void_p(wo.data_ptr()), C.c_void_p(pdf_sa.data_ptr()),
-                None if act is None else C.c_void_p(act.data_ptr()), wi.shape[0], self._tint(tint),
-                float(firefly_threshold), C.c_void_p(weight.data_ptr()), C.c_void_p(pdf.data_ptr()), stream))
+        _launch("bsdfd_measured_sample_weight", wi.device, self._h, wi, wo, pdf_sa, act, wi.shape[0], self._tint(tint),
+                float(firefly_threshold), weight, pdf)
         return weight, pdf
 
     @staticmethod
@@ -133,26 +135,18 @@ class MeasuredBSDF:
         wo, pdf, weight = self._sample_out(wi, out, "MeasuredBSDF.sample_t")
         self._check(wi=(wi, 3), u=(u, 2), wo=(wo, 3), pdf=(pdf, 0), weight=(weight, 3))
         act = self._active(active, wi.shape[0], wi.device, "MeasuredBSDF.sample_t")
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        with torch.cuda.device(wi.device):
-            stream = C.c_void_p(torch.cuda.current_stream(wi.device).cuda_stream)
-            _lib.check(_lib.lib().bsdfd_measured_sample(self._h, p(wi), p(u), p(act), wi.shape[0], self._tint(tint), p(wo),
-                                                        p(pdf), p(weight), stream))
+        _launch("bsdfd_measured_sample", wi.device, self._h, wi, u, act, wi.shape[0], self._tint(tint), wo, pdf, weight)
         return wo, pdf, weight
 
     def pdf_t(self, wi: torch.Tensor, wo: torch.Tensor, active: Optional[torch.Tensor] = None,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Solid-angle density with which ``sample_t(wi, .)`` returns ``wo`` -> [N]; 0 on the lower hemispheres and on lanes
         with ``active`` false."""
-        self._check(wi=(wi, 3), wo=(wo, 3))
         if out is None:
             out = torch.empty(wi.shape[0], dtype=torch.float32, device=wi.device)
-        self._check(wi=(wi, 3), out=(out, 0))
+        self._check(wi=(wi, 3), wo=(wo, 3), out=(out, 0))
         act = self._active(active, wi.shape[0], wi.device, "MeasuredBSDF.pdf_t")
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        with torch.cuda.device(wi.device):
-            stream = C.c_void_p(torch.cuda.current_stream(wi.device).cuda_stream)
-            _lib.check(_lib.lib().bsdfd_measured_pdf(self._h, p(wi), p(wo), p(act), wi.shape[0], p(out), stream))
+        _launch("bsdfd_measured_pdf", wi.device, self._h, wi, wo, act, wi.shape[0], out)
         return out
 
     # the call shapes of ``mi.BSDF`` as the reference's plugins use them (brdf_measured_disk.py:59,96,107,112)
@@ -254,11 +248,8 @@ class MeasuredTable:
             out_o = torch.empty_like(wi)
         if wl is not None and out_l is None:
             out_l = torch.empty_like(wi)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        with torch.cuda.device(wi.device):
-            stream = C.c_void_p(torch.cuda.current_stream(wi.device).cuda_stream)
-            _lib.check(_lib.lib().bsdfd_measured_eval_table(self._table(), p(material_id), p(wi), p(wo), p(wl), wi.shape[0],
-                                                            MeasuredBSDF._tint(tint), p(out_o), p(out_l), stream))
+        _launch("bsdfd_measured_eval_table", wi.device, self._table(), material_id, wi, wo, wl, wi.shape[0],
+                MeasuredBSDF._tint(tint), out_o, out_l)
         return out_o if wl is None else (out_o, out_l)
 
     def sample_weight(self, material_id: torch.Tensor, wi: torch.Tensor, wo: torch.Tensor, pdf_sa: torch.Tensor, tint=None,
@@ -272,12 +263,8 @@ class MeasuredTable:
                 raise ValueError("MeasuredTable.sample_weight: active must be a bool or uint8 tensor [N] on the device of wi")
             act = active.to(torch.uint8).contiguous()
         weight, pdf = torch.empty_like(wi), torch.empty_like(pdf_sa)
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        with torch.cuda.device(wi.device):
-            stream = C.c_void_p(torch.cuda.current_stream(wi.device).cuda_stream)
-            _lib.check(_lib.lib().bsdfd_measured_sample_weight_table(
-                self._table(), p(material_id), p(wi), p(wo), p(pdf_sa), p(act), wi.shape[0], MeasuredBSDF._tint(tint),
-                float(firefly_threshold), p(weight), p(pdf), stream))
+        _launch("bsdfd_measured_sample_weight_table", wi.device, self._table(), material_id, wi, wo, pdf_sa, act, wi.shape[0],
+                MeasuredBSDF._tint(tint), float(firefly_threshold), weight, pdf)
         return weight, pdf
 
     def sample_t(self, material_id: torch.Tensor, wi: torch.Tensor, u: torch.Tensor, tint=None,
@@ -287,11 +274,8 @@ class MeasuredTable:
         wo, pdf, weight = MeasuredBSDF._sample_out(wi, out, "MeasuredTable.sample_t")
         self._check(material_id, wi=(wi, 3), u=(u, 2), wo=(wo, 3), pdf=(pdf, 0), weight=(weight, 3))
         act = MeasuredBSDF._active(active, wi.shape[0], wi.device, "MeasuredTable.sample_t")
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        with torch.cuda.device(wi.device):
-            stream = C.c_void_p(torch.cuda.current_stream(wi.device).cuda_stream)
-            _lib.check(_lib.lib().bsdfd_measured_sample_table(self._table(), p(material_id), p(wi), p(u), p(act), wi.shape[0],
-                                                              MeasuredBSDF._tint(tint), p(wo), p(pdf), p(weight), stream))
+        _launch("bsdfd_measured_sample_table", wi.device, self._table(), material_id, wi, u, act, wi.shape[0],
+                MeasuredBSDF._tint(tint), wo, pdf, weight)
         return wo, pdf, weight
 
     def pdf_t(self, material_id: torch.Tensor, wi: torch.Tensor, wo: torch.Tensor, active: Optional[torch.Tensor] = None,
@@ -301,9 +285,5 @@ class MeasuredTable:
             out = torch.empty(material_id.shape[0], dtype=torch.float32, device=material_id.device)
         self._check(material_id, wi=(wi, 3), wo=(wo, 3), out=(out, 0))
         act = MeasuredBSDF._active(active, wi.shape[0], wi.device, "MeasuredTable.pdf_t")
-        p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        with torch.cuda.device(wi.device):
-            stream = C.c_void_p(torch.cuda.current_stream(wi.device).cuda_stream)
-            _lib.check(_lib.lib().bsdfd_measured_pdf_table(self._table(), p(material_id), p(wi), p(wo), p(act), wi.shape[0],
-                                                           p(out), stream))
+        _launch("bsdfd_measured_pdf_table", wi.device, self._table(), material_id, wi, wo, act, wi.shape[0], out)
         return out

@@ -132,6 +132,23 @@ def test_bounce_kernel_matches_reference(synth, occlusion, last, bounce, with_f)
     assert np.isfinite(got["rad"][live]).all() and p999 < 2e-4 and worst < 5e-3
 
 
+@pytest.mark.parametrize("occlusion,last,bounce,keys", [(1, 0, 2, ("org", "nrm", "wi", "wl", "material", "beta", "rad")),
+                                                        (0, 1, 0, ("material", "rad"))])
+def test_bounce_kernel_is_bit_identical_to_the_recording(synth, occlusion, last, bounce, keys):
+    """The synthetic vertices (f_o and f_l given, the arguments of test_bounce_kernel_matches_reference) through ONE
+    bsdfd_wf_bounce call: every output array is, bit for bit, what the kernel wrote before it shared its light sample, floor
+    term and pdf / ground-truth tests with primary_kernel and shade_kernel (tests/golden/bounce_kernel_before_sharing.npz)."""
+    v, env = synth
+    r = _scene_renderer(R.SYNTH_SCENE, env)
+    b = _to_device(r, v)
+    r.bounce(b, bounce, bool(last), 0x1234567890ABCDEF, 3, (1 << 32) - 2000, occlusion=bool(occlusion))
+    torch.cuda.synchronize()
+    before = np.load(os.path.join(ROOT, "tests", "golden", "bounce_kernel_before_sharing.npz"))
+    for k in keys:
+        got = b["mat" if k == "material" else k].cpu().numpy()
+        assert np.array_equal(got, before[f"occlusion{occlusion}_last{last}_bounce{bounce}_{k}"], equal_nan=True), k
+
+
 def test_path_begin_and_resolve_match_reference():
     """The two small kernels on a real primary wavefront of the 5-ball scene (an odd tile: rows 5..57 of 64, 3 spp)."""
     from bsdf_diffusion_sampling_amd.wavefront import make_sky
