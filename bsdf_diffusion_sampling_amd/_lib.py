@@ -16,7 +16,7 @@ LIB_PATH = os.environ.get("BSDFD_LIB_PATH") or DEFAULT_LIB_PATH  # override: A/B
 SRC_PATH = os.path.join(_HERE, "csrc", "bsdfd.hip")
 SRC32_PATH = os.path.join(_HERE, "csrc", "flow32.hip")   # the 32-query-tile flow kernels
 SRC_PATHS = [SRC_PATH, SRC32_PATH, os.path.join(_HERE, "csrc", "wavefront.hip"), os.path.join(_HERE, "csrc", "pathtrace.hip"),
-             os.path.join(_HERE, "csrc", "encoding.hip"),
+             os.path.join(_HERE, "csrc", "pathlights.hip"), os.path.join(_HERE, "csrc", "encoding.hip"),
              os.path.join(_HERE, "csrc", "measured.hip"), os.path.join(_HERE, "csrc", "measured_table.hip"),
              os.path.join(_HERE, "csrc", "bucket.hip"),
              os.path.join(_HERE, "csrc", "bucket_wide.hip"), os.path.join(_HERE, "csrc", "live.hip"),
@@ -41,6 +41,7 @@ EXPORTS = (
     "bsdfd_context_bytes", "bsdfd_plugin_sample_ex", "bsdfd_plugin_pdf_ex", "bsdfd_plugin_sample_multi_ex",
     "bsdfd_plugin_pdf_multi_ex", "bsdfd_plugin_sample_pdf_multi_ex", "bsdfd_plugin_sample_pdf_ex",
     "bsdfd_flow_samples_only", "bsdfd_wf_primary", "bsdfd_wf_shade", "bsdfd_wf_path_begin", "bsdfd_wf_bounce", "bsdfd_wf_resolve",
+    "bsdfd_wf_sample_emitter", "bsdfd_wf_bounce_lit",
     "bsdfd_positional_encoding", "bsdfd_bucket_workspace_bytes", "bsdfd_bucket_by_material",
     "bsdfd_bucket_wide_workspace_bytes", "bsdfd_bucket_by_material_wide",
     "bsdfd_gather_lanes", "bsdfd_scatter_lanes", "bsdfd_live_workspace_bytes", "bsdfd_compact_live",
@@ -65,6 +66,15 @@ class WfScene(C.Structure):
                 ("n_extra_spheres", C.c_int32), ("extra_spheres", (C.c_float * 4) * 31), ("has_plane", C.c_int32),
                 ("plane_y", C.c_float), ("checker_scale", C.c_float), ("checker_color0", C.c_float),
                 ("checker_color1", C.c_float)]
+
+
+WF_MAX_LIGHTS = 8   # BSDFD_WF_MAX_LIGHTS
+
+
+class WfLights(C.Structure):
+    """bsdfd_wf_lights (include/bsdfd.h)."""
+    _fields_ = [("n_lights", C.c_int32), ("has_env", C.c_int32), ("position", (C.c_float * 3) * WF_MAX_LIGHTS),
+                ("intensity", (C.c_float * 3) * WF_MAX_LIGHTS)]
 
 
 class Opts(C.Structure):
@@ -402,6 +412,8 @@ def lib():
     L.bsdfd_wf_path_begin.argtypes = [C.POINTER(WfScene), fp, i64, fp, fp, fp, fp, fp, fp, vp]
     L.bsdfd_wf_bounce.argtypes = [C.POINTER(WfScene), fp, i32, i32, i32, u64, u64, u64, i64] + [fp] * 12 + [vp]
     L.bsdfd_wf_resolve.argtypes = [C.POINTER(WfScene), i32, i32, i32, fp, fp, vp]
+    L.bsdfd_wf_sample_emitter.argtypes = [C.POINTER(WfScene), C.POINTER(WfLights), i32, i32, u64, u64, u64, i64] + [fp] * 7 + [vp]
+    L.bsdfd_wf_bounce_lit.argtypes = L.bsdfd_wf_bounce.argtypes[:-1] + [C.POINTER(WfLights), fp, fp, vp]
     L.bsdfd_positional_encoding.argtypes = [fp, i64, i32, i32, i32, i32, fp, vp]
     L.bsdfd_measured_create_from_file.argtypes = [C.c_char_p, C.POINTER(vp)]
     L.bsdfd_measured_destroy.argtypes = [vp]

@@ -14,10 +14,11 @@
 //                the "miss" id: the next bucketing sorts it behind the materials and it costs no flow evaluation)
 //   resolve    : film += mean over spp of rad
 //
-// Only the environment emits, so a BSDF sample that hits geometry adds nothing and a light sample that hits geometry is
-// shadowed.  A ray skips the surface it starts on (known from the material id; a sphere is convex, a plane flat): there
-// is no epsilon offset.  One path per lane; a lane whose path has ended returns after reading its id.  Streaming
-// kernels: ~125 B read and ~90 B written per live path, a few hundred flops.
+// Only the environment emits here (point emitters: pathlights.hip, whose bounce_lit_kernel stands in for bounce_kernel), so a
+// BSDF sample that hits geometry adds nothing and a light sample that hits geometry is shadowed.  A ray skips the surface it
+// starts on (known from the material id; a sphere is convex, a plane flat): there is no epsilon offset.  One path per lane; a
+// lane whose path has ended returns after reading its id.  Streaming kernels: ~125 B read and ~90 B written per live path, a
+// few hundred flops.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -31,36 +32,6 @@
 namespace {
 
 using namespace wf_dev;
-
-struct Hit {
-    float t;       // distance along the ray; 3e38 = nothing
-    int id;        // ball index, n_sph for the floor, -1 for nothing
-    V3 c;          // the winning ball's centre and radius, kept in registers by the loop: indexing sc.sph with the per-lane
-    float r;       // id afterwards would turn the kernel-argument array into scratch
-};
-
-// Closest hit of the ray org + t d among the balls and the floor, the surface `own` (a material id) excepted.  `sc` is a
-// kernel argument, so the loop is wave-uniform and its operands arrive through scalar loads.  Same discriminant as
-// primary_kernel: R^2 - (distance of the centre from the ray)^2.
-__device__ __forceinline__ Hit trace(const Scene& sc, V3 org, V3 d, int own) {
-    Hit h;
-    h.t = 3.0e38f; h.id = -1; h.c = v3(0.f, 0.f, 0.f); h.r = 1.0f;
-    for (int k = 0; k < sc.n_sph; ++k) {
-        const V3 c = v3(sc.sph[k][0], sc.sph[k][1], sc.sph[k][2]);
-        const float r = sc.sph[k][3];
-        const V3 oc = org - c;
-        const float b = dot(oc, d);
-        const V3 perp = oc - b * d;
-        const float disc = r * r - dot(perp, perp);
-        const float t = -b - sqrtf(fmaxf(disc, 0.0f));
-        if (k != own && disc > 0.0f && t > 0.0f && t < h.t) { h.t = t; h.id = k; h.c = c; h.r = r; }
-    }
-    if (sc.has_plane && own != sc.n_sph && d.y < 0.0f) {
-        const float t = (sc.plane_y - org.y) / d.y;
-        if (t > 0.0f && t < h.t) { h.t = t; h.id = sc.n_sph; }
-    }
-    return h;
-}
 
 __global__ __launch_bounds__(256) void path_begin_kernel(Scene sc, const float* __restrict__ env, long long n,
                                                          const float* __restrict__ dir, const float* __restrict__ nrm,
@@ -162,34 +133,7 @@ __global__ __launch_bounds__(256) void bounce_kernel(Scene sc, const float* __re
         mat[p] = sc.n_sph + 1;
         return;
     }
-    // the next vertex, written the way primary_kernel writes the first
-    V3 nv, xv, w_in;
-    if (h.id < sc.n_sph) {
-        const V3 oc = x - h.c;
-        nv = (1.0f / h.r) * (oc + h.t * d);
-        nv = (1.0f / sqrtf(dot(nv, nv))) * nv;
-        V3 gs, gt;
-        onb(nv, gs, gt);
-        w_in = v3(-dot(d, gs), -dot(d, gt), -dot(d, nv));
-        xv = h.c + h.r * nv;
-    } else {
-        xv = x + h.t * d;
-        const int cx = (int)floorf(xv.x * sc.checker_scale), cz = (int)floorf(xv.z * sc.checker_scale);
-        const float refl = ((cx + cz) & 1) ? sc.checker_c1 : sc.checker_c0;
-        nv = v3(0.f, 1.f, 0.f);
-        w_in = v3(refl, refl, refl);
-    }
-    // its light sample: primary's Philox key and counter, counter word 3 advanced by the depth of the new vertex
-    const unsigned long long gp = path_offset + (unsigned long long)p;
-    unsigned u[4];
-    philox4x32((unsigned)seed, (unsigned)(seed >> 32), (unsigned)gp, (unsigned)(gp >> 32), (unsigned)pass,
-               0x57617665u + (unsigned)(bounce + 1), u);
-    st3(wl + 3 * p, cosine_sample(u[2], u[3]));
-    st3(org + 3 * p, xv);
-    st3(nrm + 3 * p, nv);
-    st3(wi + 3 * p, w_in);
-    st3(beta + 3 * p, v3(b.x * thr[0], b.y * thr[1], b.z * thr[2]));
-    mat[p] = h.id;
+    continue_path(sc, h, x, d, b, thr, seed, pass, path_offset, bounce, p, org, nrm, wi, wl, mat, beta);
 }
 
 __global__ __launch_bounds__(256) void resolve_kernel(long long npix, int spp, const float* __restrict__ rad,
@@ -197,16 +141,6 @@ __global__ __launch_bounds__(256) void resolve_kernel(long long npix, int spp, c
     const long long pix = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= npix) return;
     add_pixel_mean(film, pix, spp, [&](long long p, float L[3]) { L[0] = rad[3 * p]; L[1] = rad[3 * p + 1]; L[2] = rad[3 * p + 2]; });
-}
-
-// scene + environment + lane count of a launch over N paths (no tile: the path kernels take N and a path offset)
-int path_scene(const bsdfd_wf_scene* s, const float* env, long long n, Scene& sc) {
-    if (int rc = to_scene(s, 0, 0, 1, sc)) return rc;
-    if (sc.env_w <= 0 || sc.env_h <= 0) return bsdfd_fail_(BSDFD_EINVAL, "environment map size must be positive");
-    if (n < 0) return bsdfd_fail_(BSDFD_EINVAL, "negative path count");
-    if (n > 0 && !env) return bsdfd_fail_(BSDFD_EINVAL, "null environment map");
-    if ((n + 255) / 256 > 0x7fffffffLL) return bsdfd_fail_(BSDFD_EINVAL, "wavefront too large for one launch");
-    return BSDFD_OK;
 }
 
 }  // namespace

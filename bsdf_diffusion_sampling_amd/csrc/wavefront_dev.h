@@ -1,7 +1,7 @@
 // wavefront_dev.h — the scene model of the wavefront harness, shared by the translation units that trace it: wavefront.hip
-// (primary rays, one-bounce shading) and pathtrace.hip (occlusion and further bounces).  Both inline the same vector helpers,
-// orthonormal basis, environment lookup and MIS weight, the same light sample, floor term and pixel mean, and build the
-// kernel-argument `Scene` from the same bsdfd_wf_scene.
+// (primary rays, one-bounce shading), pathtrace.hip (occlusion and further bounces) and pathlights.hip (point emitters).  They
+// inline the same vector helpers, orthonormal basis, environment lookup and MIS weight, the same light sample, floor term and
+// pixel mean, the same secondary ray and path continuation, and build the kernel-argument `Scene` from the same bsdfd_wf_scene.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -118,6 +118,74 @@ __device__ __forceinline__ void add_pixel_mean(float* __restrict__ film, long lo
     for (int c = 0; c < 3; ++c) film[3 * pix + c] += acc[c] * inv;
 }
 
+// ---- rays between the vertices of a path (pathtrace.hip, pathlights.hip) ----
+struct Hit {
+    float t;       // distance along the ray; 3e38 = nothing
+    int id;        // ball index, n_sph for the floor, -1 for nothing
+    V3 c;          // the winning ball's centre and radius, kept in registers by the loop: indexing sc.sph with the per-lane
+    float r;       // id afterwards would turn the kernel-argument array into scratch
+};
+
+// Closest hit of the ray org + t d among the balls and the floor, the surface `own` (a material id) excepted.  `sc` is a
+// kernel argument, so the loop is wave-uniform and its operands arrive through scalar loads.  Same discriminant as
+// primary_kernel: R^2 - (distance of the centre from the ray)^2.
+__device__ __forceinline__ Hit trace(const Scene& sc, V3 org, V3 d, int own) {
+    Hit h;
+    h.t = 3.0e38f; h.id = -1; h.c = v3(0.f, 0.f, 0.f); h.r = 1.0f;
+    for (int k = 0; k < sc.n_sph; ++k) {
+        const V3 c = v3(sc.sph[k][0], sc.sph[k][1], sc.sph[k][2]);
+        const float r = sc.sph[k][3];
+        const V3 oc = org - c;
+        const float b = dot(oc, d);
+        const V3 perp = oc - b * d;
+        const float disc = r * r - dot(perp, perp);
+        const float t = -b - sqrtf(fmaxf(disc, 0.0f));
+        if (k != own && disc > 0.0f && t > 0.0f && t < h.t) { h.t = t; h.id = k; h.c = c; h.r = r; }
+    }
+    if (sc.has_plane && own != sc.n_sph && d.y < 0.0f) {
+        const float t = (sc.plane_y - org.y) / d.y;
+        if (t > 0.0f && t < h.t) { h.t = t; h.id = sc.n_sph; }
+    }
+    return h;
+}
+
+// The path of lane p moves on to the hit `h` of the ray x + t d: the next vertex, written the way primary_kernel writes the first,
+// the throughput b * thr, and the vertex' light sample.
+__device__ __forceinline__ void continue_path(const Scene& sc, const Hit& h, V3 x, V3 d, V3 b, const float thr[3],
+                                              unsigned long long seed, unsigned long long pass, unsigned long long path_offset,
+                                              int bounce, long long p, float* __restrict__ org, float* __restrict__ nrm,
+                                              float* __restrict__ wi, float* __restrict__ wl, long long* __restrict__ mat,
+                                              float* __restrict__ beta) {
+    V3 nv, xv, w_in;
+    if (h.id < sc.n_sph) {
+        const V3 oc = x - h.c;
+        nv = (1.0f / h.r) * (oc + h.t * d);
+        nv = (1.0f / sqrtf(dot(nv, nv))) * nv;
+        V3 gs, gt;
+        onb(nv, gs, gt);
+        w_in = v3(-dot(d, gs), -dot(d, gt), -dot(d, nv));
+        xv = h.c + h.r * nv;
+    } else {
+        xv = x + h.t * d;
+        const int cx = (int)floorf(xv.x * sc.checker_scale), cz = (int)floorf(xv.z * sc.checker_scale);
+        const float c0 = sc.checker_c0, c1 = sc.checker_c1;   // (both read: a select between the two argument loads goes per lane)
+        const float refl = ((cx + cz) & 1) ? c1 : c0;
+        nv = v3(0.f, 1.f, 0.f);
+        w_in = v3(refl, refl, refl);
+    }
+    // its light sample: primary's Philox key and counter, counter word 3 advanced by the depth of the new vertex
+    const unsigned long long gp = path_offset + (unsigned long long)p;
+    unsigned u[4];
+    philox4x32((unsigned)seed, (unsigned)(seed >> 32), (unsigned)gp, (unsigned)(gp >> 32), (unsigned)pass,
+               0x57617665u + (unsigned)(bounce + 1), u);
+    st3(wl + 3 * p, cosine_sample(u[2], u[3]));
+    st3(org + 3 * p, xv);
+    st3(nrm + 3 * p, nv);
+    st3(wi + 3 * p, w_in);
+    st3(beta + 3 * p, v3(b.x * thr[0], b.y * thr[1], b.z * thr[2]));
+    mat[p] = h.id;
+}
+
 // ---- host side ----
 // one thread per lane in blocks of 256 on `stream`, and the launch error
 template <class... P, class... A>
@@ -155,6 +223,16 @@ inline int to_scene(const bsdfd_wf_scene* s, int row_begin, int row_end, int spp
     sc.has_plane = s->has_plane ? 1 : 0;
     sc.plane_y = s->plane_y; sc.checker_scale = s->checker_scale;
     sc.checker_c0 = s->checker_color0; sc.checker_c1 = s->checker_color1;
+    return BSDFD_OK;
+}
+
+// scene + environment + lane count of a launch over N paths (no tile: the path kernels take N and a path offset)
+inline int path_scene(const bsdfd_wf_scene* s, const float* env, long long n, Scene& sc) {
+    if (int rc = to_scene(s, 0, 0, 1, sc)) return rc;
+    if (sc.env_w <= 0 || sc.env_h <= 0) return bsdfd_fail_(BSDFD_EINVAL, "environment map size must be positive");
+    if (n < 0) return bsdfd_fail_(BSDFD_EINVAL, "negative path count");
+    if (n > 0 && !env) return bsdfd_fail_(BSDFD_EINVAL, "null environment map");
+    if ((n + 255) / 256 > 0x7fffffffLL) return bsdfd_fail_(BSDFD_EINVAL, "wavefront too large for one launch");
     return BSDFD_OK;
 }
 

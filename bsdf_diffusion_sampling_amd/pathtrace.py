@@ -1,5 +1,6 @@
-"""Path tracer for the array scene: occlusion and further bounces (csrc/pathtrace.hip, C ABI ``bsdfd_wf_path_begin`` /
-``bsdfd_wf_bounce`` / ``bsdfd_wf_resolve``).
+"""Path tracer for the array scene: occlusion, further bounces (csrc/pathtrace.hip, C ABI ``bsdfd_wf_path_begin`` /
+``bsdfd_wf_bounce`` / ``bsdfd_wf_resolve``) and point emitters (csrc/pathlights.hip, ``bsdfd_wf_sample_emitter`` /
+``bsdfd_wf_bounce_lit``).
 
 The reference renders its 12-ball array scenes with Mitsuba's ``path`` integrator at unbounded depth
 (matpreview/disney_bsdf_array*_envmap.xml, scene_measured.xml: ``max_depth = -1``): balls shadow the floor and each
@@ -14,14 +15,25 @@ the loop that feeds a shrinking wavefront through the same pieces bounce after b
                    bounce(k, last = k == max_depth - 1)
     resolve -> film tile += mean_spp of rad
 
-The geometry is at most 32 analytic spheres and one plane, intersected by brute force like the primary rays.  Only the
-environment emits.  There is no Russian roulette: a path ends when it escapes, when its BSDF sample is invalid, or at
-``max_depth``.  There is no CPU fallback.
+The geometry is at most 32 analytic spheres and one plane, intersected by brute force like the primary rays.  Without
+``lights`` only the environment emits.  With ``lights`` (up to 8 ``PointLight``, the emitter of the reference's
+matpreview/disney_bsdf_array*_pointlight*.xml scenes) every vertex takes one emitter sample, the emitter chosen uniformly
+as Mitsuba's ``sample_emitter_direction`` does, and a depth becomes
+
+    sample_emitter(k) -> bucket -> sample_pdf -> eval_t -> bounce_lit(k)
+
+where ``sample_emitter`` puts the direction to a picked point light into ``wl`` — so the sampler's ``pdf()`` and the
+evaluator answer for that direction — and what arrives from it (visibility, 1 / d^2, the selection's factor) into ``emit``.
+A point light is a delta: its term has no MIS weight.  There is no Russian roulette: a path ends when it escapes, when its
+BSDF sample is invalid, or at ``max_depth`` (the reference's unbounded depth is a finite ``max_depth`` here).  There are no
+area or spot emitters, and the environment strategy stays cosine-weighted.  There is no CPU fallback.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional
+import math
+from collections import namedtuple
+from typing import Optional, Sequence
 
 import torch
 
@@ -29,6 +41,52 @@ from . import _lib
 from .wavefront import ArrayRenderer
 
 _M64 = 0xFFFFFFFFFFFFFFFF
+
+# a Mitsuba `point` emitter: world position (y up) and radiant intensity, a scalar or an RGB triple
+PointLight = namedtuple("PointLight", "position intensity")
+
+
+def wf_lights(lights: Sequence[PointLight], has_env: bool) -> _lib.WfLights:
+    """The ``bsdfd_wf_lights`` of 1..8 point lights; ``ValueError`` for anything the kernels should not see."""
+    lights = list(lights)
+    if not 1 <= len(lights) <= _lib.WF_MAX_LIGHTS:
+        raise ValueError(f"1..{_lib.WF_MAX_LIGHTS} point lights, got {len(lights)}")
+    out = _lib.WfLights()
+    out.n_lights, out.has_env = len(lights), int(bool(has_env))
+    for k, (position, intensity) in enumerate(lights):
+        pos = [float(v) for v in position]
+        rgb = [float(v) for v in intensity] if hasattr(intensity, "__len__") else [float(intensity)] * 3
+        if len(pos) != 3 or not all(math.isfinite(v) for v in pos):
+            raise ValueError(f"light {k}: the position must be three finite numbers")
+        if len(rgb) != 3 or not all(math.isfinite(v) and v >= 0.0 for v in rgb):
+            raise ValueError(f"light {k}: the intensity must be finite and non-negative (a scalar or an RGB triple)")
+        out.position[k] = (C.c_float * 3)(*pos)
+        out.intensity[k] = (C.c_float * 3)(*rgb)
+    return out
+
+
+def lights_from_matpreview_xml(path: str):
+    """The ``<emitter type="point">`` elements of a reference scene file (rendering/matpreview/disney_bsdf_array*_pointlight*.xml)
+    as ``PointLight``s: the z-up position (x, y, z) becomes (x, z, -y), the mapping ``scene_from_matpreview_xml`` applies to the
+    balls; the intensity is a scalar or an RGB triple.  [] for a file without point emitters."""
+    import xml.etree.ElementTree as ET
+    numbers = lambda text: [float(v) for v in text.replace(",", " ").split()]
+    out = []
+    for em in ET.parse(path).getroot().iter("emitter"):
+        if em.get("type") != "point":
+            continue
+        pos, inten = (0.0, 0.0, 0.0), 1.0   # Mitsuba's defaults
+        for child in em:
+            if child.get("name") == "position":
+                pos = numbers(child.get("value")) if child.get("value") is not None else \
+                    [float(child.get(a, 0.0)) for a in ("x", "y", "z")]
+            elif child.get("name") == "intensity":
+                v = numbers(child.get("value"))
+                inten = v[0] if len(v) == 1 else tuple(v)
+        if len(pos) != 3:
+            raise ValueError(f"{path}: a point emitter's position needs three numbers")
+        out.append(PointLight((pos[0], pos[2], -pos[1]), inten))
+    return out
 
 
 class PathArrayRenderer(ArrayRenderer):
@@ -39,16 +97,25 @@ class PathArrayRenderer(ArrayRenderer):
     ``occlusion=False`` is refused (it would count the environment through the balls at every depth).
     Bounce 0 draws with ``ArrayRenderer.render_pass``'s sampler key; bounce k > 0 with ``key ^ (k * 0xD1B54A32D192ED03)``.
     ``stats["lanes_per_bounce"]``: the material lanes served at each bounce of the last pass — the compaction is the
-    bucketing itself, no mask machinery."""
+    bucketing itself, no mask machinery.
 
-    def __init__(self, *args, max_depth: int = 1, occlusion: Optional[bool] = None, **kwargs):
+    ``lights``: up to 8 ``PointLight``.  None or [] is the renderer without the argument, bit for bit.  With lights and
+    ``env=None`` the environment is black and is no emitter (camera misses are 0); with an explicit ``env`` both emit."""
+
+    def __init__(self, table, centers, radii, camera=None, env: Optional[torch.Tensor] = None, *args, max_depth: int = 1,
+                 occlusion: Optional[bool] = None, lights: Optional[Sequence[PointLight]] = None, **kwargs):
         max_depth = int(max_depth)
         if max_depth < 1:
             raise ValueError("max_depth must be >= 1")
         occlusion = max_depth > 1 if occlusion is None else bool(occlusion)
         if max_depth > 1 and not occlusion:
             raise ValueError("max_depth > 1 needs occlusion: without it every vertex would see the environment through the balls")
-        super().__init__(*args, **kwargs)
+        self.lights = None
+        if lights is not None and len(lights):
+            self.lights = wf_lights(lights, has_env=env is not None)
+            if env is None:
+                env = torch.zeros((2, 4, 3), dtype=torch.float32)   # black: path_begin and the lookups stay valid
+        super().__init__(table, centers, radii, camera, env, *args, **kwargs)
         if self.use_ground_truth and self.measured_table is None:
             raise ValueError("PathArrayRenderer evaluates the ground truth on the lane-ordered wavefront (fused_ground_truth=True)")
         self.max_depth, self.occlusion = max_depth, occlusion
@@ -59,9 +126,12 @@ class PathArrayRenderer(ArrayRenderer):
         if "org" not in b:
             for name in ("org", "beta", "rad"):
                 b[name] = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+            if self.lights is not None:
+                b["lsel"] = torch.empty((n,), dtype=torch.int32, device=self.device)
+                b["emit"] = torch.empty((n, 3), dtype=torch.float32, device=self.device)
         return b
 
-    # -- the three path kernels ----------------------------------------------------------------------
+    # -- the path kernels ----------------------------------------------------------------------------
     def path_begin(self, b):
         """org, beta, rad of the first vertices from what ``primary`` wrote into ``b``."""
         p = lambda t: C.c_void_p(t.data_ptr())
@@ -70,16 +140,34 @@ class PathArrayRenderer(ArrayRenderer):
                                                       p(b["nrm"]), p(b["mat"]), p(b["org"]), p(b["beta"]), p(b["rad"]),
                                                       self._stream()))
 
-    def bounce(self, b, bounce: int, last: bool, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None):
-        """Shade the vertices in ``b`` (``wo``, ``pdf_o``, ``pdf_l`` [, ``f_o``, ``f_l``] from the sampler) and move the paths on."""
+    def sample_emitter(self, b, bounce: int, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
+                       lights: Optional[_lib.WfLights] = None):
+        """The emitter sample of the vertices in ``b``: ``lsel``, ``emit``, and ``wl`` towards a picked point light."""
         p = lambda t: C.c_void_p(t.data_ptr())
         occlusion = self.occlusion if occlusion is None else occlusion
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().bsdfd_wf_bounce(
-                C.byref(self.scene), p(self.env), bounce, int(bool(last)), int(bool(occlusion)), seed, pass_idx, path_offset,
+            _lib.check(_lib.lib().bsdfd_wf_sample_emitter(
+                C.byref(self.scene), C.byref(self.lights if lights is None else lights), bounce, int(bool(occlusion)), seed,
+                pass_idx, path_offset, b["mat"].shape[0], p(b["org"]), p(b["nrm"]), p(b["wi"]), p(b["mat"]), p(b["wl"]),
+                p(b["lsel"]), p(b["emit"]), self._stream()))
+        torch.autograd.graph.increment_version([b["wl"], b["lsel"], b["emit"]])
+
+    def bounce(self, b, bounce: int, last: bool, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
+               lights: Optional[_lib.WfLights] = None):
+        """Shade the vertices in ``b`` (``wo``, ``pdf_o``, ``pdf_l`` [, ``f_o``, ``f_l``] from the sampler; with lights also
+        ``lsel`` and ``emit`` from ``sample_emitter``) and move the paths on."""
+        p = lambda t: C.c_void_p(t.data_ptr())
+        occlusion = self.occlusion if occlusion is None else occlusion
+        lights = self.lights if lights is None else lights
+        args = [C.byref(self.scene), p(self.env), bounce, int(bool(last)), int(bool(occlusion)), seed, pass_idx, path_offset,
                 b["mat"].shape[0], p(b["org"]), p(b["nrm"]), p(b["wi"]), p(b["wl"]), p(b["mat"]), p(b["beta"]), p(b["rad"]),
                 p(b["wo"]), p(b["pdf_o"]), p(b["pdf_l"]), p(b["f_o"]) if "f_o" in b else None,
-                p(b["f_l"]) if "f_l" in b else None, self._stream()))
+                p(b["f_l"]) if "f_l" in b else None]
+        with torch.cuda.device(self.device):
+            if lights is None:
+                _lib.check(_lib.lib().bsdfd_wf_bounce(*args, self._stream()))
+            else:
+                _lib.check(_lib.lib().bsdfd_wf_bounce_lit(*args, C.byref(lights), p(b["lsel"]), p(b["emit"]), self._stream()))
         # written through raw pointers: tell torch (the plugin cores key their per-query context cache on wi._version)
         torch.autograd.graph.increment_version([b["wi"], b["wl"], b["nrm"], b["org"], b["mat"], b["beta"], b["rad"]])
 
@@ -106,6 +194,8 @@ class PathArrayRenderer(ArrayRenderer):
         n_balls = len(self.table)
         lanes = []
         for k in range(self.max_depth):
+            if self.lights is not None:
+                self.sample_emitter(b, k, seed, pass_idx, offset)
             plan = self.table.bucket(b["mat"], extra_bins=2)      # floor vertices and ended paths behind the materials
             counts = plan[1]                                      # (already on the host)
             n_mat = sum(counts[:n_balls])

@@ -41,7 +41,9 @@ extern "C" {
  *      bsdfd_measured_sample_weight_table() (eval() of a mixed-material wavefront in one launch);
  *      bsdfd_measured_sample(), bsdfd_measured_pdf(), bsdfd_measured_sample_table(), bsdfd_measured_pdf_table() and
  *      bsdfd_measured_has_luminance() (the measured BSDF's own importance sampler);
- *      bsdfd_wf_path_begin(), bsdfd_wf_bounce() and bsdfd_wf_resolve() (occlusion and further bounces in the array scene). */
+ *      bsdfd_wf_path_begin(), bsdfd_wf_bounce() and bsdfd_wf_resolve() (occlusion and further bounces in the array scene);
+ *      bsdfd_wf_sample_emitter() and bsdfd_wf_bounce_lit(), which take a struct of their own, bsdfd_wf_lights: point emitters
+ *      in the array scene. */
 #define BSDFD_ABI_VERSION 8
 
 #define BSDFD_OK 0
@@ -464,8 +466,9 @@ int bsdfd_wf_shade(const bsdfd_wf_scene* scene, const float* env, int32_t row_be
  * The reference renders its array scenes with Mitsuba's `path` integrator at unbounded depth: balls shadow the floor and
  * each other, and every further vertex calls the plugin's sample() / pdf() again.  These three kernels keep a path's state
  * in lane-ordered arrays between those calls; a host loops  bucket -> sample/pdf [-> eval] -> bounce  over a shrinking
- * wavefront.  Only the environment emits.  All three are stream-ordered, allocate nothing and do not synchronise; N = 0
- * is a no-op.  Row p of a tile is the global path  path_offset + p  (= row_begin * width * spp + p for a film tile).
+ * wavefront.  Only the environment emits (point emitters: the section below).  All three are stream-ordered, allocate
+ * nothing and do not synchronise; N = 0 is a no-op.  Row p of a tile is the global path  path_offset + p
+ * (= row_begin * width * spp + p for a film tile).
  *
  * bsdfd_wf_path_begin: from dir / nrm / material as bsdfd_wf_primary wrote them -> org [N,3] world position of the first
  * vertex (ball k: centre_k + r_k * nrm; floor: the ray/plane point; miss: 0), beta [N,3] = 1 (throughput), rad [N,3] =
@@ -493,6 +496,45 @@ int bsdfd_wf_bounce(const bsdfd_wf_scene* scene, const float* env, int32_t bounc
 /* film [row_end-row_begin, width, 3] += mean over the spp samples of rad [N,3] (bsdfd_wf_shade's accumulation order). */
 int bsdfd_wf_resolve(const bsdfd_wf_scene* scene, int32_t row_begin, int32_t row_end, int32_t spp, const float* rad,
                      float* film, void* hip_stream);
+
+/* ---- point emitters in the array scene (csrc/pathlights.hip) ---------------------------------------
+ * Five of the reference's array scenes are lit by a Mitsuba `point` emitter (matpreview/disney_bsdf_array*_pointlight*.xml).
+ * Every vertex takes ONE emitter sample, the emitter chosen uniformly among the n_e = n_lights + has_env emitters as
+ * Mitsuba's sample_emitter_direction does:  pick = (u0 * n_e) >> 32  with u0 the first word of
+ * philox4x32(key = seed, counter = (global path index lo, hi, pass, 0x4C697465 + bounce));  pick == n_lights is the
+ * environment.  A host with lights runs, per depth,  sample_emitter -> bucket -> sample/pdf [-> eval] -> bounce_lit  in place
+ * of  bucket -> sample/pdf [-> eval] -> bounce.  Both calls are stream-ordered, allocate nothing and do not synchronise; N = 0
+ * is a no-op; a lane whose path has ended (material outside 0..n_balls) is not read into anything and not a byte of its
+ * wl, lsel, emit or state moves. */
+#define BSDFD_WF_MAX_LIGHTS 8
+typedef struct bsdfd_wf_lights {
+    int32_t n_lights;            /* 1..8 point emitters */
+    int32_t has_env;             /* the environment map emits too and counts as one more emitter */
+    float position[8][3];        /* world, y up like the rest of bsdfd_wf_scene */
+    float intensity[8][3];       /* radiant intensity per channel (Mitsuba `point`: radiance f cos * I / d^2) */
+} bsdfd_wf_lights;               /* 200 bytes */
+
+/* The emitter sample of the vertices at depth `bounce` (org, nrm, wi, material as bsdfd_wf_path_begin / bsdfd_wf_bounce left
+ * them) -> lsel [N] (the picked point emitter, -1 for the environment), emit [N,3], and wl [N,3] in/out:
+ *   environment picked   : wl stays the cosine sample bsdfd_wf_primary / bsdfd_wf_bounce wrote; emit = 0.
+ *   point k, ball vertex : wl = the local direction to the light in the vertex' frame (the sampler's pdf() and the evaluator
+ *                          are asked about it next); emit = n_e * I_k / d^2, 0 where wl.z <= 0 and, with `occlusion`, where the
+ *                          ray towards the light meets another surface before it (the vertex' own surface is skipped by id).
+ *   point k, floor vertex: wl stays (the path continues along it); emit = n_e * (reflectance / pi) * cos * I_k / d^2, the whole
+ *                          term, shadowed the same way. */
+int bsdfd_wf_sample_emitter(const bsdfd_wf_scene* scene, const bsdfd_wf_lights* lights, int32_t bounce, int32_t occlusion,
+                            uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, const float* org, const float* nrm,
+                            const float* wi, const int64_t* material, float* wl, int32_t* lsel, float* emit, void* hip_stream);
+/* bsdfd_wf_bounce for vertices whose emitter sample is lsel / emit.  The path moves on exactly as there.  The estimate:
+ *   ball vertex : a picked point adds emit * f cos(wl) (f_l, or the proxy albedo * pdf_l; a delta light has no MIS weight);
+ *                 a picked environment adds bsdfd_wf_bounce's light term with the density (wl.z / pi) / n_e.  A BSDF sample that
+ *                 escapes adds the environment weighted against (wo.z / pi) / n_e if has_env, else nothing.
+ *   floor vertex: the environment along wl at full weight if has_env and the ray escapes, plus emit. */
+int bsdfd_wf_bounce_lit(const bsdfd_wf_scene* scene, const float* env, int32_t bounce, int32_t last, int32_t occlusion,
+                        uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, float* org, float* nrm, float* wi,
+                        float* wl, int64_t* material, float* beta, float* rad, const float* wo, const float* pdf_o,
+                        const float* pdf_l, const float* f_o, const float* f_l, const bsdfd_wf_lights* lights,
+                        const int32_t* lsel, const float* emit, void* hip_stream);
 
 const char* bsdfd_last_error(void);
 const char* bsdfd_version(void);

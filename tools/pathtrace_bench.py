@@ -7,6 +7,11 @@ synchronise):
      path_begin, read and written by bounce, read by resolve) and of three launches where there were two;
   2. PathArrayRenderer(max_depth=D, occlusion) for D = 2, 4, 8, with stats["lanes_per_bounce"] and the time of each bounce
      (device events at every bucketing) next to it: does a bounce cost what its live lanes cost, or what the wavefront costs?
+
+``--lights N`` measures the point emitters instead -> profiles/pathtrace_lights.json: PathArrayRenderer with N point lights and a
+black environment at depths 1 / 2 / 4 (occlusion on), interleaved with the unlit renderer at the same depths and occlusion.  A
+path goes where it goes whatever emits, so both trace the same vertices and serve the same lanes: the difference per depth is
+the sample_emitter launch plus what bounce_lit costs over bounce.  The launch itself is also timed with device events.
 """
 import argparse
 import json
@@ -26,18 +31,32 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--width", type=int, default=683); ap.add_argument("--height", type=int, default=512)
 ap.add_argument("--spp", type=int, default=4); ap.add_argument("--domain", default="disk")
 ap.add_argument("--rounds", type=int, default=9); ap.add_argument("--passes", type=int, default=20)
-ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "pathtrace.json"))
+ap.add_argument("--lights", type=int, default=0, help="measure N point lights against the unlit renderer instead")
+ap.add_argument("--out", default=None, help="default: profiles/pathtrace.json, or profiles/pathtrace_lights.json with --lights")
 a = ap.parse_args()
+a.out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
+                              "pathtrace_lights.json" if a.lights else "pathtrace.json")
 if not torch.cuda.is_available():
     sys.exit("tools/pathtrace_bench.py measures on the GPU: no device visible")
 
 cam, centers, radii = WF.array0_scene(a.width, a.height)
 table = MaterialTable([m + "_" + a.domain for m in WF.ARRAY0_MATERIALS])
-variants = {"array": WF.ArrayRenderer(table, centers, radii, camera=cam),
-            "path_d1": PathArrayRenderer(table, centers, radii, camera=cam, max_depth=1)}
-for d in (2, 4, 8):
-    variants[f"path_d{d}_occl"] = PathArrayRenderer(table, centers, radii, camera=cam, max_depth=d)
-dev = variants["array"].device
+LIT_DEPTHS = (1, 2, 4)
+if a.lights:
+    from bsdf_diffusion_sampling_amd.pathtrace import PointLight
+    # the reference's emitter (position 0, 4, 5 in its z-up frame, intensity 200), further ones on a circle at the same height
+    lights = [PointLight((4.0 * np.sin(2 * np.pi * k / a.lights), 5.0, -4.0 * np.cos(2 * np.pi * k / a.lights)), 200.0)
+              for k in range(a.lights)]
+    variants = {}
+    for d in LIT_DEPTHS:
+        variants[f"unlit_d{d}"] = PathArrayRenderer(table, centers, radii, camera=cam, max_depth=d, occlusion=True)
+        variants[f"lit_d{d}"] = PathArrayRenderer(table, centers, radii, camera=cam, max_depth=d, occlusion=True, lights=lights)
+else:
+    variants = {"array": WF.ArrayRenderer(table, centers, radii, camera=cam),
+                "path_d1": PathArrayRenderer(table, centers, radii, camera=cam, max_depth=1)}
+    for d in (2, 4, 8):
+        variants[f"path_d{d}_occl"] = PathArrayRenderer(table, centers, radii, camera=cam, max_depth=d)
+dev = next(iter(variants.values())).device
 film = torch.zeros((a.height, a.width, 3), device=dev)
 
 
@@ -58,8 +77,48 @@ for rnd in range(a.rounds):
 med = {k: float(np.median(v)) for k, v in times.items()}
 res = {"workload": f"array0_{a.width}x{a.height}_{a.spp}spp_{a.domain}_12balls", "paths_per_pass": a.width * a.height * a.spp,
        "rounds": a.rounds, "passes_per_timing": a.passes, "device": torch.cuda.get_device_name(dev),
-       "pass_ms_median": med, "pass_ms_min": {k: float(min(v)) for k, v in times.items()},
-       "path_d1_over_array": med["path_d1"] / med["array"], "depth": {}}
+       "pass_ms_median": med, "pass_ms_min": {k: float(min(v)) for k, v in times.items()}}
+
+
+def write(res):
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(res, f, indent=1)
+        f.write("\n")
+    print(json.dumps(res))
+
+
+if a.lights:
+    res.update(point_lights=a.lights, environment="black, no emitter", occlusion=True, depth={})
+    for d in LIT_DEPTHS:
+        r = variants[f"lit_d{d}"]
+        marks, per_pass = [], []
+        sample_emitter = r.sample_emitter
+
+        def sample_emitter_timed(*args, **kw):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            sample_emitter(*args, **kw)
+            e1.record()
+            marks.append((e0, e1))
+        r.sample_emitter = sample_emitter_timed
+        try:
+            for k in range(a.passes):
+                del marks[:]
+                r.render_pass(film, 0, a.height, a.spp, 0, 1000 + k)
+                torch.cuda.synchronize(dev)
+                per_pass.append([e0.elapsed_time(e1) for e0, e1 in marks])
+        finally:
+            del r.sample_emitter
+        extra = med[f"lit_d{d}"] - med[f"unlit_d{d}"]
+        res["depth"][str(d)] = {"lit_pass_ms_median": med[f"lit_d{d}"], "unlit_pass_ms_median": med[f"unlit_d{d}"],
+                                "extra_ms": extra, "extra_ms_per_depth": extra / d,
+                                "lanes_per_bounce_last_pass": r.stats["lanes_per_bounce"],
+                                "sample_emitter_ms_median_per_depth":
+                                    [float(np.median([p[i] for p in per_pass])) for i in range(min(len(p) for p in per_pass))]}
+    write(res)
+    sys.exit(0)
+res.update(path_d1_over_array=med["path_d1"] / med["array"], depth={})
 
 # per-bounce times: a device event at every bucketing (= the start of a bounce) and at the resolve
 for d in (2, 4, 8):
@@ -94,8 +153,4 @@ for d in (2, 4, 8):
     res["depth"][str(d)] = {"pass_ms_median": med[f"path_d{d}_occl"], "lanes_per_bounce_last_pass": lanes,
                             "bounce_ms_median": bounce_ms,
                             "ns_per_material_lane": [1e6 * t / max(l, 1) for t, l in zip(bounce_ms, lanes)]}
-os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-with open(a.out, "w") as f:
-    json.dump(res, f, indent=1)
-    f.write("\n")
-print(json.dumps(res))
+write(res)
