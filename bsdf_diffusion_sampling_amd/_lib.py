@@ -16,14 +16,15 @@ LIB_PATH = os.environ.get("BSDFD_LIB_PATH") or DEFAULT_LIB_PATH  # override: A/B
 SRC_PATH = os.path.join(_HERE, "csrc", "bsdfd.hip")
 SRC32_PATH = os.path.join(_HERE, "csrc", "flow32.hip")   # the 32-query-tile flow kernels
 SRC_PATHS = [SRC_PATH, SRC32_PATH, os.path.join(_HERE, "csrc", "wavefront.hip"), os.path.join(_HERE, "csrc", "pathtrace.hip"),
-             os.path.join(_HERE, "csrc", "pathlights.hip"), os.path.join(_HERE, "csrc", "encoding.hip"),
+             os.path.join(_HERE, "csrc", "pathlights.hip"), os.path.join(_HERE, "csrc", "pathenv.hip"),
+             os.path.join(_HERE, "csrc", "encoding.hip"),
              os.path.join(_HERE, "csrc", "measured.hip"), os.path.join(_HERE, "csrc", "measured_table.hip"),
              os.path.join(_HERE, "csrc", "bucket.hip"),
              os.path.join(_HERE, "csrc", "bucket_wide.hip"), os.path.join(_HERE, "csrc", "live.hip"),
              os.path.join(_HERE, "csrc", "clock.hip")]  # translation units of libbsdfd.so
 FLOW_TUS = (SRC_PATH, SRC32_PATH)   # ... whose device assembly the build verifies (_asmcheck)
 DEP_PATHS = SRC_PATHS + [os.path.join(_HERE, "csrc", f) for f in ("common.h", "flow_dev.h", "flow32.h", "bucket_scan.h",
-                                                                     "measured_dev.h", "wavefront_dev.h")]
+                                                                     "measured_dev.h", "wavefront_dev.h", "env_dev.h")]
 INCLUDE_DIR = os.path.join(ROOT, "include")
 ASM_CACHE_DIR = os.path.join(ROOT, "build", "asm")   # device assembly of the last product build (bsdfd.s, flow32.s)
 
@@ -42,6 +43,7 @@ EXPORTS = (
     "bsdfd_plugin_pdf_multi_ex", "bsdfd_plugin_sample_pdf_multi_ex", "bsdfd_plugin_sample_pdf_ex",
     "bsdfd_flow_samples_only", "bsdfd_wf_primary", "bsdfd_wf_shade", "bsdfd_wf_path_begin", "bsdfd_wf_bounce", "bsdfd_wf_resolve",
     "bsdfd_wf_sample_emitter", "bsdfd_wf_bounce_lit",
+    "bsdfd_env_sample", "bsdfd_env_pdf", "bsdfd_wf_sample_env", "bsdfd_wf_bounce_env",
     "bsdfd_positional_encoding", "bsdfd_bucket_workspace_bytes", "bsdfd_bucket_by_material",
     "bsdfd_bucket_wide_workspace_bytes", "bsdfd_bucket_by_material_wide",
     "bsdfd_gather_lanes", "bsdfd_scatter_lanes", "bsdfd_live_workspace_bytes", "bsdfd_compact_live",
@@ -75,6 +77,12 @@ class WfLights(C.Structure):
     """bsdfd_wf_lights (include/bsdfd.h)."""
     _fields_ = [("n_lights", C.c_int32), ("has_env", C.c_int32), ("position", (C.c_float * 3) * WF_MAX_LIGHTS),
                 ("intensity", (C.c_float * 3) * WF_MAX_LIGHTS)]
+
+
+class EnvDist(C.Structure):
+    """bsdfd_env_dist (include/bsdfd.h)."""
+    _fields_ = [("marginal", C.c_void_p), ("conditional", C.c_void_p), ("pdf_uv", C.c_void_p), ("width", C.c_int32),
+                ("height", C.c_int32)]
 
 
 class Opts(C.Structure):
@@ -414,6 +422,10 @@ def lib():
     L.bsdfd_wf_resolve.argtypes = [C.POINTER(WfScene), i32, i32, i32, fp, fp, vp]
     L.bsdfd_wf_sample_emitter.argtypes = [C.POINTER(WfScene), C.POINTER(WfLights), i32, i32, u64, u64, u64, i64] + [fp] * 7 + [vp]
     L.bsdfd_wf_bounce_lit.argtypes = L.bsdfd_wf_bounce.argtypes[:-1] + [C.POINTER(WfLights), fp, fp, vp]
+    L.bsdfd_env_sample.argtypes = [C.POINTER(EnvDist), i64, fp, fp, fp, vp]
+    L.bsdfd_env_pdf.argtypes = [C.POINTER(EnvDist), i64, fp, fp, vp]
+    L.bsdfd_wf_sample_env.argtypes = [C.POINTER(WfScene), fp, C.POINTER(EnvDist), i32, i32, i32, u64, u64, u64, i64] + [fp] * 8 + [vp]
+    L.bsdfd_wf_bounce_env.argtypes = L.bsdfd_wf_bounce_lit.argtypes[:-1] + [fp, C.POINTER(EnvDist), vp]
     L.bsdfd_positional_encoding.argtypes = [fp, i64, i32, i32, i32, i32, fp, vp]
     L.bsdfd_measured_create_from_file.argtypes = [C.c_char_p, C.POINTER(vp)]
     L.bsdfd_measured_destroy.argtypes = [vp]

@@ -1,6 +1,7 @@
 """Path tracer for the array scene: occlusion, further bounces (csrc/pathtrace.hip, C ABI ``bsdfd_wf_path_begin`` /
-``bsdfd_wf_bounce`` / ``bsdfd_wf_resolve``) and point emitters (csrc/pathlights.hip, ``bsdfd_wf_sample_emitter`` /
-``bsdfd_wf_bounce_lit``).
+``bsdfd_wf_bounce`` / ``bsdfd_wf_resolve``), point emitters (csrc/pathlights.hip, ``bsdfd_wf_sample_emitter`` /
+``bsdfd_wf_bounce_lit``) and importance sampling of the environment map (csrc/pathenv.hip, ``bsdfd_wf_sample_env`` /
+``bsdfd_wf_bounce_env``; the distribution: ``envmap.EnvDistribution``).
 
 The reference renders its 12-ball array scenes with Mitsuba's ``path`` integrator at unbounded depth
 (matpreview/disney_bsdf_array*_envmap.xml, scene_measured.xml: ``max_depth = -1``): balls shadow the floor and each
@@ -24,9 +25,23 @@ as Mitsuba's ``sample_emitter_direction`` does, and a depth becomes
 
 where ``sample_emitter`` puts the direction to a picked point light into ``wl`` — so the sampler's ``pdf()`` and the
 evaluator answer for that direction — and what arrives from it (visibility, 1 / d^2, the selection's factor) into ``emit``.
-A point light is a delta: its term has no MIS weight.  There is no Russian roulette: a path ends when it escapes, when its
-BSDF sample is invalid, or at ``max_depth`` (the reference's unbounded depth is a finite ``max_depth`` here).  There are no
-area or spot emitters, and the environment strategy stays cosine-weighted.  There is no CPU fallback.
+A point light is a delta: its term has no MIS weight.
+
+The light strategy towards the environment is a cosine-weighted hemisphere draw by default.  ``env_sampling="importance"``
+draws it in proportion to the map's luminance instead, as the ``envmap`` emitter of the reference's
+matpreview/disney_bsdf_array*_envmap.xml and scene_measured.xml does (``sample_direction`` / ``pdf_direction``), and a depth becomes
+
+    [sample_emitter(k)] -> sample_env(k) -> bucket -> sample_pdf -> eval_t -> bounce_env(k)
+
+``sample_env`` overwrites ``wl`` on the ball vertices that picked the environment with a direction drawn from
+``envmap.EnvDistribution`` — a piecewise-constant density over the map's own texel grid, built from the 3x3 maximum of the
+luminance times the row's solid angle; Mitsuba's is a bilinear ``Hierarchical2D`` over luminance x sin(theta), and this one is
+parity-unpinned against it like the evaluator — and leaves its density in ``lpdf`` and radiance x visibility / density in
+``emit``; ``bounce_env`` weights both strategies against that density.  The floor keeps its cosine direction as BSDF sample and
+way on, so where a path goes does not depend on ``env_sampling``.
+
+There is no Russian roulette: a path ends when it escapes, when its BSDF sample is invalid, or at ``max_depth`` (the
+reference's unbounded depth is a finite ``max_depth`` here).  There are no area or spot emitters.  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -100,18 +115,27 @@ class PathArrayRenderer(ArrayRenderer):
     bucketing itself, no mask machinery.
 
     ``lights``: up to 8 ``PointLight``.  None or [] is the renderer without the argument, bit for bit.  With lights and
-    ``env=None`` the environment is black and is no emitter (camera misses are 0); with an explicit ``env`` both emit."""
+    ``env=None`` the environment is black and is no emitter (camera misses are 0); with an explicit ``env`` both emit.
+
+    ``env_sampling``: ``"cosine"`` (the default: the renderer without the argument, bit for bit) or ``"importance"``, which
+    samples the environment in proportion to its luminance (``envmap.EnvDistribution``, built once here).  ``"importance"``
+    needs an emitting environment: with lights and ``env=None`` it is refused."""
 
     def __init__(self, table, centers, radii, camera=None, env: Optional[torch.Tensor] = None, *args, max_depth: int = 1,
-                 occlusion: Optional[bool] = None, lights: Optional[Sequence[PointLight]] = None, **kwargs):
+                 occlusion: Optional[bool] = None, lights: Optional[Sequence[PointLight]] = None, env_sampling: str = "cosine",
+                 **kwargs):
         max_depth = int(max_depth)
         if max_depth < 1:
             raise ValueError("max_depth must be >= 1")
         occlusion = max_depth > 1 if occlusion is None else bool(occlusion)
         if max_depth > 1 and not occlusion:
             raise ValueError("max_depth > 1 needs occlusion: without it every vertex would see the environment through the balls")
+        if env_sampling not in ("cosine", "importance"):
+            raise ValueError(f'env_sampling must be "cosine" or "importance", got {env_sampling!r}')
         self.lights = None
         if lights is not None and len(lights):
+            if env_sampling == "importance" and env is None:
+                raise ValueError('env_sampling="importance" needs an emitting environment: with lights, pass env')
             self.lights = wf_lights(lights, has_env=env is not None)
             if env is None:
                 env = torch.zeros((2, 4, 3), dtype=torch.float32)   # black: path_begin and the lookups stay valid
@@ -119,6 +143,11 @@ class PathArrayRenderer(ArrayRenderer):
         if self.use_ground_truth and self.measured_table is None:
             raise ValueError("PathArrayRenderer evaluates the ground truth on the lane-ordered wavefront (fused_ground_truth=True)")
         self.max_depth, self.occlusion = max_depth, occlusion
+        self.env_sampling = env_sampling
+        self.env_dist = None
+        if env_sampling == "importance":
+            from .envmap import EnvDistribution
+            self.env_dist = EnvDistribution(self.env)
         self.stats = {"lanes_per_bounce": []}
 
     def _buffers(self, n: int):
@@ -128,7 +157,10 @@ class PathArrayRenderer(ArrayRenderer):
                 b[name] = torch.empty((n, 3), dtype=torch.float32, device=self.device)
             if self.lights is not None:
                 b["lsel"] = torch.empty((n,), dtype=torch.int32, device=self.device)
+            if self.lights is not None or self.env_dist is not None:
                 b["emit"] = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+            if self.env_dist is not None:
+                b["lpdf"] = torch.empty((n,), dtype=torch.float32, device=self.device)
         return b
 
     # -- the path kernels ----------------------------------------------------------------------------
@@ -152,19 +184,40 @@ class PathArrayRenderer(ArrayRenderer):
                 p(b["lsel"]), p(b["emit"]), self._stream()))
         torch.autograd.graph.increment_version([b["wl"], b["lsel"], b["emit"]])
 
-    def bounce(self, b, bounce: int, last: bool, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
-               lights: Optional[_lib.WfLights] = None):
-        """Shade the vertices in ``b`` (``wo``, ``pdf_o``, ``pdf_l`` [, ``f_o``, ``f_l``] from the sampler; with lights also
-        ``lsel`` and ``emit`` from ``sample_emitter``) and move the paths on."""
+    def sample_env(self, b, bounce: int, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
+                   lights: Optional[_lib.WfLights] = None, env_dist=None):
+        """The environment's emitter sample of the vertices in ``b`` that picked it (``lsel == -1``; all live ones without
+        lights): ``lpdf``, ``emit``, and ``wl`` on the balls, drawn from the ``EnvDistribution``."""
         p = lambda t: C.c_void_p(t.data_ptr())
         occlusion = self.occlusion if occlusion is None else occlusion
         lights = self.lights if lights is None else lights
+        env_dist = self.env_dist if env_dist is None else env_dist
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().bsdfd_wf_sample_env(
+                C.byref(self.scene), p(self.env), C.byref(env_dist.struct(self.device)), 1 if lights is None else lights.n_lights + 1,
+                bounce, int(bool(occlusion)), seed, pass_idx, path_offset, b["mat"].shape[0], p(b["org"]), p(b["nrm"]), p(b["wi"]),
+                p(b["mat"]), None if lights is None else p(b["lsel"]), p(b["wl"]), p(b["lpdf"]), p(b["emit"]), self._stream()))
+        torch.autograd.graph.increment_version([b["wl"], b["lpdf"], b["emit"]])
+
+    def bounce(self, b, bounce: int, last: bool, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
+               lights: Optional[_lib.WfLights] = None, env_dist=None):
+        """Shade the vertices in ``b`` (``wo``, ``pdf_o``, ``pdf_l`` [, ``f_o``, ``f_l``] from the sampler; with lights also
+        ``lsel`` and ``emit`` from ``sample_emitter``; with an ``EnvDistribution`` also ``lpdf`` and ``emit`` from ``sample_env``)
+        and move the paths on."""
+        p = lambda t: C.c_void_p(t.data_ptr())
+        occlusion = self.occlusion if occlusion is None else occlusion
+        lights = self.lights if lights is None else lights
+        env_dist = self.env_dist if env_dist is None else env_dist
         args = [C.byref(self.scene), p(self.env), bounce, int(bool(last)), int(bool(occlusion)), seed, pass_idx, path_offset,
                 b["mat"].shape[0], p(b["org"]), p(b["nrm"]), p(b["wi"]), p(b["wl"]), p(b["mat"]), p(b["beta"]), p(b["rad"]),
                 p(b["wo"]), p(b["pdf_o"]), p(b["pdf_l"]), p(b["f_o"]) if "f_o" in b else None,
                 p(b["f_l"]) if "f_l" in b else None]
         with torch.cuda.device(self.device):
-            if lights is None:
+            if env_dist is not None:
+                _lib.check(_lib.lib().bsdfd_wf_bounce_env(
+                    *args, None if lights is None else C.byref(lights), None if lights is None else p(b["lsel"]), p(b["emit"]),
+                    p(b["lpdf"]), C.byref(env_dist.struct(self.device)), self._stream()))
+            elif lights is None:
                 _lib.check(_lib.lib().bsdfd_wf_bounce(*args, self._stream()))
             else:
                 _lib.check(_lib.lib().bsdfd_wf_bounce_lit(*args, C.byref(lights), p(b["lsel"]), p(b["emit"]), self._stream()))
@@ -196,6 +249,8 @@ class PathArrayRenderer(ArrayRenderer):
         for k in range(self.max_depth):
             if self.lights is not None:
                 self.sample_emitter(b, k, seed, pass_idx, offset)
+            if self.env_dist is not None:
+                self.sample_env(b, k, seed, pass_idx, offset)
             plan = self.table.bucket(b["mat"], extra_bins=2)      # floor vertices and ended paths behind the materials
             counts = plan[1]                                      # (already on the host)
             n_mat = sum(counts[:n_balls])

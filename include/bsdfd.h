@@ -43,7 +43,9 @@ extern "C" {
  *      bsdfd_measured_has_luminance() (the measured BSDF's own importance sampler);
  *      bsdfd_wf_path_begin(), bsdfd_wf_bounce() and bsdfd_wf_resolve() (occlusion and further bounces in the array scene);
  *      bsdfd_wf_sample_emitter() and bsdfd_wf_bounce_lit(), which take a struct of their own, bsdfd_wf_lights: point emitters
- *      in the array scene. */
+ *      in the array scene;
+ *      bsdfd_env_sample(), bsdfd_env_pdf(), bsdfd_wf_sample_env() and bsdfd_wf_bounce_env(), which take a struct of their own,
+ *      bsdfd_env_dist: importance sampling of the environment map in the array scene. */
 #define BSDFD_ABI_VERSION 8
 
 #define BSDFD_OK 0
@@ -535,6 +537,54 @@ int bsdfd_wf_bounce_lit(const bsdfd_wf_scene* scene, const float* env, int32_t b
                         float* wl, int64_t* material, float* beta, float* rad, const float* wo, const float* pdf_o,
                         const float* pdf_l, const float* f_o, const float* f_l, const bsdfd_wf_lights* lights,
                         const int32_t* lsel, const float* emit, void* hip_stream);
+
+/* ---- importance sampling of the environment map in the array scene (csrc/pathenv.hip) ---------------
+ * Four of the reference's array scenes (matpreview/disney_bsdf_array{0,1}_envmap.xml, disney_bsdf_array2_spherical_envmap.xml,
+ * scene_measured.xml) are lit by a Mitsuba `envmap` emitter, whose sample_direction / pdf_direction draw directions in
+ * proportion to the map's luminance (a bilinear Hierarchical2D over luminance x sin theta).  The distribution here is piecewise
+ * constant over the unit square of the lookup's own parameterisation,  u = atan2(x, -z) / 2pi (wrapped),  v = theta / pi,  cell
+ * (j, i) = [i/W, (i+1)/W) x [j/H, (j+1)/H), built by the host from the 3x3 maximum of the texel luminances (so that the density is
+ * positive wherever the bilinear lookup is) times the row's solid angle; it is NOT pinned to Mitsuba's.  All tables are fp32 on
+ * the device; first entries of the CDFs are 0, last entries 1.  A cell is the one with cdf[k] <= t < cdf[k+1] (a cell of zero
+ * width is never chosen); inside it both coordinates are uniform with offset (t - cdf[k]) / (cdf[k+1] - cdf[k]).  The density of a
+ * direction per solid angle is  pdf_uv[cell] / (2 pi^2 max(sin theta, 1e-6)). */
+typedef struct bsdfd_env_dist {
+    const float* marginal;       /* [height + 1]         CDF over the rows */
+    const float* conditional;    /* [height][width + 1]  CDF over the columns of each row */
+    const float* pdf_uv;         /* [height][width]      density per unit area of the (u, v) square: averages to 1 */
+    int32_t width, height;
+} bsdfd_env_dist;
+
+/* Row-level access (Mitsuba envmap: sample_direction / pdf_direction).  u [N,2] in [0,1): u[.,0] picks the row, u[.,1] the
+ * column -> dir [N,3] (world, y up, unit) and its density pdf [N];  dir [N,3] unit -> pdf [N].  N = 0 is a no-op. */
+int bsdfd_env_sample(const bsdfd_env_dist* dist, int64_t N, const float* u, float* dir, float* pdf, void* hip_stream);
+int bsdfd_env_pdf(const bsdfd_env_dist* dist, int64_t N, const float* dir, float* pdf, void* hip_stream);
+
+/* The environment's emitter sample of the vertices at depth `bounce`, drawn from `dist` (of the environment map's size) instead
+ * of the cosine-weighted wl: runs after bsdfd_wf_sample_emitter (if there are lights) and before the bucketing.  For every live
+ * vertex with lsel == -1 — lsel NULL: every live vertex, and n_e must be 1 — a direction d from
+ * philox4x32(key = seed, counter = (global path index lo, hi, pass, 0x456E766D + bounce)): word 0 >> 8 picks the row, word 1 >> 8
+ * the column (times 2^-24).  With p_l = pdf(d) / n_e, E the bilinear lookup and V the visibility (`occlusion`: no surface along d;
+ * the vertex' own is skipped by id):
+ *   ball vertex : wl = d in the vertex' frame (it may be below the horizon), lpdf = p_l, emit = E V / p_l, 0 where wl.z <= 0.
+ *   floor vertex: wl stays (the cosine direction is the floor's BSDF sample and the way on), lpdf = p_l,
+ *                 emit = mis(p_l, cos / pi) (reflectance / pi) cos E V / p_l, the finished term.
+ * Vertices that picked a point light, and ended paths: not a byte of their wl, lpdf or emit moves. */
+int bsdfd_wf_sample_env(const bsdfd_wf_scene* scene, const float* env, const bsdfd_env_dist* dist, int32_t n_e, int32_t bounce,
+                        int32_t occlusion, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, const float* org,
+                        const float* nrm, const float* wi, const int64_t* material, const int32_t* lsel, float* wl, float* lpdf,
+                        float* emit, void* hip_stream);
+/* bsdfd_wf_bounce_lit for vertices whose environment sample is bsdfd_wf_sample_env's.  `lights` and `lsel` are both NULL (the
+ * environment is the only emitter) or both given (has_env must be set; n_e = n_lights + 1).  The path moves on exactly as in
+ * bsdfd_wf_bounce.  The estimate differs from bsdfd_wf_bounce_lit's in three places:
+ *   ball vertex, environment picked: adds mis(lpdf, pdf_l) * emit * f cos(wl) (f_l, or the proxy albedo * pdf_l);
+ *   a BSDF sample wo that escapes  : weighted mis(pdf_o, pdf(d) / n_e);
+ *   floor vertex                   : its escaping cosine sample is weighted mis(cos / pi, pdf(d) / n_e), and emit is added. */
+int bsdfd_wf_bounce_env(const bsdfd_wf_scene* scene, const float* env, int32_t bounce, int32_t last, int32_t occlusion,
+                        uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, float* org, float* nrm, float* wi,
+                        float* wl, int64_t* material, float* beta, float* rad, const float* wo, const float* pdf_o,
+                        const float* pdf_l, const float* f_o, const float* f_l, const bsdfd_wf_lights* lights,
+                        const int32_t* lsel, const float* emit, const float* lpdf, const bsdfd_env_dist* dist, void* hip_stream);
 
 const char* bsdfd_last_error(void);
 const char* bsdfd_version(void);

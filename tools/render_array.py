@@ -20,6 +20,9 @@ ap.add_argument("--lights-from", default=None, metavar="scene.xml",
                      "Its maxDepth = 2 (direct light only) is --max-depth 1 --occlusion 1 here: Mitsuba counts segments, this "
                      "renderer counts vertices; its unbounded depth is a finite --max-depth (no Russian roulette)")
 ap.add_argument("--no-env", action="store_true", help="with lights: a black environment that is no emitter (default: the sky emits too)")
+ap.add_argument("--env-sampling", choices=("cosine", "importance"), default="cosine",
+                help="the light strategy towards the environment: a cosine-weighted draw (default), or in proportion to the map's "
+                     "luminance, as the reference's envmap emitter draws (PathArrayRenderer)")
 a = ap.parse_args()
 lights = []
 if a.lights_from or a.point_light:
@@ -40,12 +43,14 @@ if a.measured_dir:
     for i, m in enumerate(WF.ARRAY0_MATERIALS):
         p = find_measured_file(m, a.measured_dir)
         if p: gts[i] = MeasuredBSDF(p)
-if a.max_depth is None and a.occlusion is None and not lights:
+if a.env_sampling == "importance" and a.no_env:
+    ap.error("--env-sampling importance needs an emitting environment: drop --no-env")
+if a.max_depth is None and a.occlusion is None and not lights and a.env_sampling == "cosine":
     r = WF.ArrayRenderer(tab, centers, radii, camera=cam, ground_truth=gts)
 else:
     from bsdf_diffusion_sampling_amd.pathtrace import PathArrayRenderer
     r = PathArrayRenderer(tab, centers, radii, camera=cam, ground_truth=gts, max_depth=1 if a.max_depth is None else a.max_depth,
-                          occlusion=None if a.occlusion is None else bool(a.occlusion), lights=lights,
+                          occlusion=None if a.occlusion is None else bool(a.occlusion), lights=lights, env_sampling=a.env_sampling,
                           env=None if a.no_env or not lights else WF.make_sky())
 r.render(2, a.spp, seed=9); torch.cuda.synchronize()
 t0 = time.perf_counter(); img = r.render(a.passes, a.spp, seed=0); torch.cuda.synchronize(); dt = time.perf_counter() - t0
@@ -53,6 +58,7 @@ b = r.primary(0, a.height, 1, 0, 0); mat = b["mat"].cpu().numpy()
 paths = a.width * a.height * a.spp * a.passes
 print(json.dumps({"workload": f"array0_{a.width}x{a.height}_{a.passes}x{a.spp}spp_{a.domain}", "materials": len(tab),
                   "max_depth": getattr(r, "max_depth", 1), "occlusion": getattr(r, "occlusion", False), "point_lights": len(lights),
+                  "env_sampling": a.env_sampling,
                   "lanes_per_bounce": getattr(r, "stats", {}).get("lanes_per_bounce"),
                   "ground_truth_materials": len(gts), "seconds": dt, "passes_per_s": a.passes / dt, "Mpaths_per_s": paths / dt / 1e6,
                   "ball_fraction": float((mat < 12).mean()), "floor_fraction": float((mat == 12).mean()), "miss_fraction": float((mat == 13).mean())}))
