@@ -24,7 +24,7 @@ SRC_PATHS = [SRC_PATH, SRC32_PATH, os.path.join(_HERE, "csrc", "wavefront.hip"),
              os.path.join(_HERE, "csrc", "clock.hip")]  # translation units of libbsdfd.so
 FLOW_TUS = (SRC_PATH, SRC32_PATH)   # ... whose device assembly the build verifies (_asmcheck)
 DEP_PATHS = SRC_PATHS + [os.path.join(_HERE, "csrc", f) for f in ("common.h", "flow_dev.h", "flow32.h", "bucket_scan.h",
-                                                                     "measured_dev.h", "wavefront_dev.h", "env_dev.h")]
+                                                                     "measured_dev.h", "wavefront_dev.h", "env_dev.h", "bounce_dev.h")]
 INCLUDE_DIR = os.path.join(ROOT, "include")
 ASM_CACHE_DIR = os.path.join(ROOT, "build", "asm")   # device assembly of the last product build (bsdfd.s, flow32.s)
 

@@ -1,0 +1,210 @@
+// bounce_dev.h — the one bounce of the array-scene path tracer, and what its kernels' launchers and the two emitter samplers
+// share.  pathtrace.hip, pathlights.hip and pathenv.hip each instantiate bounce_vertex<Mode> in a thin __global__ stub:
+//
+//   COSINE : only the environment emits; the light strategy is the cosine-weighted direction primary / bounce left in wl
+//   LIT    : one emitter sample per vertex, uniform among n_e = point lights [+ the environment] (sample_emitter: lsel, emit)
+//   ENV    : LIT, or no point lights at all, with the environment's sample drawn from its own distribution (sample_env: lpdf, emit)
+//
+// Where the path goes — the floor's cosine direction, the ball's BSDF sample, the trace, continue_path — is written once and
+// does not depend on the mode, so the three kernels' continuation states are equal bit for bit by construction.  The modes
+// differ, under `if constexpr`, in where the emitter sample comes from, in how the floor's environment term is gated or
+// weighted, in the light-strategy density the escaping BSDF sample is weighted against, and in the light strategy's own term.
+// Each instantiation is straight-line code of its own.
+//
+// The arrays travel in small structs passed by value (kernel arguments: scalar loads); no struct is indexed per lane.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "env_dev.h"
+#include "wavefront_dev.h"
+
+namespace bounce_dev {
+
+using namespace wf_dev;
+using env_dev::EnvDist;
+
+enum Mode { COSINE, LIT, ENV };
+
+struct PathState {    // the path at its vertex, lane-ordered; the bounce moves it on
+    float *org, *nrm, *wi, *wl;
+    long long* mat;
+    float *beta, *rad;
+};
+struct SamplerAnswer {   // of the sampler (and, f: of the ground-truth evaluator) for the vertices that carry a material
+    const float *wo, *pdf_o, *pdf_l, *f_o, *f_l;
+};
+struct EmitterSample {   // of sample_emitter (lsel, emit) and sample_env (lpdf, emit)
+    const int* lsel;
+    const float *lpdf, *emit;
+};
+struct Step {
+    int bounce, last, occlusion;
+    unsigned long long seed, pass, path_offset;
+    long long n;
+};
+
+// this thread's lane and its material id; false beyond the wavefront and for a path that has ended
+__device__ __forceinline__ bool live_lane(const Scene& sc, long long n, const long long* __restrict__ mat, long long& p, long long& m) {
+    p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return false;
+    m = mat[p];
+    return m >= 0 && m <= sc.n_sph;
+}
+
+// a Philox draw of lane p's own: primary's key and counter, counter word 3 = a four-letter tag + the depth of the vertex
+__device__ __forceinline__ void tagged_draw(unsigned long long seed, unsigned long long pass, unsigned long long path_offset,
+                                            long long p, unsigned tag, int bounce, unsigned u[4]) {
+    const unsigned long long gp = path_offset + (unsigned long long)p;
+    philox4x32((unsigned)seed, (unsigned)(seed >> 32), (unsigned)gp, (unsigned)(gp >> 32), (unsigned)pass, tag + (unsigned)bounce, u);
+}
+
+// An emitter sample along the world direction `dir` from the vertex (x, nn) of surface m: its cosine, and whether it arrives —
+// above the horizon and (occlusion) nothing nearer than `dist` in the way.
+__device__ __forceinline__ bool emitter_arrives(const Scene& sc, V3 x, V3 nn, V3 dir, long long m, int occlusion, float dist,
+                                                bool valid, float& cosl) {
+    cosl = dot(dir, nn);
+    bool lit = valid && cosl > 0.0f;
+    if (lit && occlusion) {
+        const Hit h = trace(sc, x, dir, (int)m);
+        lit = !(h.id >= 0 && h.t < dist);
+    }
+    return lit;
+}
+
+// A ball vertex is asked about its emitter sample in its own frame: wl = the local direction.  (The floor keeps the cosine
+// sample in wl: it is its BSDF sample and the way on.)
+__device__ __forceinline__ void store_local_direction(float* __restrict__ wl, V3 nn, V3 dir, float cosl) {
+    V3 fs, ft;
+    onb(nn, fs, ft);
+    st3(wl, v3(dot(dir, fs), dot(dir, ft), cosl));
+}
+
+// One bounce of lane p's path: rad += beta * (the vertex' estimate), then the path moves to what its BSDF sample hits or ends.
+// `e`, `n_e` and `has_env` are read by the modes that have them (ENV; LIT and ENV; LIT).
+template <int M>
+__device__ __forceinline__ void bounce_vertex(const Scene& sc, const float* __restrict__ env, const EnvDist& e, int n_e, int has_env,
+                                              const Step& st, const PathState& ps, const SamplerAnswer& sa,
+                                              const EmitterSample& es) {
+    long long p, m;
+    if (!live_lane(sc, st.n, ps.mat, p, m)) return;
+    const int occlusion = st.occlusion;
+    const float inv_pi = 0.31830988618379067154f;
+    // probability with which the one emitter sample went to the environment
+    const float sel_p = M == COSINE ? 1.0f : 1.0f / (float)n_e;
+    const bool env_emits = M != LIT || has_env;
+    const V3 nn = ld3(ps.nrm + 3 * p), x = ld3(ps.org + 3 * p);
+    V3 fs, ft;
+    onb(nn, fs, ft);
+    const V3 l = ld3(ps.wl + 3 * p);
+    const V3 lw = l.x * fs + l.y * ft + l.z * nn;
+    // the emitter sample: what arrives from a picked point light (LIT, ENV) or the environment's own draw (ENV), ready-made in emit
+    bool point = false;
+    V3 em = v3(0.f, 0.f, 0.f);
+    if constexpr (M != COSINE) {
+        point = (M == LIT || es.lsel) && es.lsel[p] >= 0;
+        if (M == ENV || point) em = ld3(es.emit + 3 * p);
+    }
+    float L[3] = {0.f, 0.f, 0.f};   // the vertex' estimate, before the throughput
+    float thr[3] = {1.f, 1.f, 1.f};  // throughput factor of the continuing direction
+    V3 d = lw;                       // ... that direction
+    Hit h;
+    h.t = 3.0e38f; h.id = -1; h.c = v3(0.f, 0.f, 0.f); h.r = 1.0f;
+    bool go = false;                 // the path continues at `h`
+    if (m == sc.n_sph) {
+        // diffuse floor, cosine-sampled: f cos / pdf = reflectance (in the wi slot); the direction in wl is its BSDF sample — at
+        // full weight towards the environment, or (ENV) weighted against the environment's own density — and the way on
+        const float refl = ps.wi[3 * p];
+        if (occlusion) h = trace(sc, x, lw, (int)m);
+        if (h.id < 0) {
+            if (env_emits) floor_term(sc, env, lw, refl, L);
+            if constexpr (M == ENV) {
+                const float w = mis_power(l.z * inv_pi, env_dev::env_pdf(e, lw) * sel_p);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) L[c] *= w;
+            }
+        } else {
+            go = true;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) thr[c] = refl;
+        }
+        if constexpr (M != COSINE) { L[0] += em.x; L[1] += em.y; L[2] += em.z; }
+    } else {
+        // the two strategies of shade_kernel
+        const bool gt_o = has_ground_truth(sa.f_o, p), gt_l = has_ground_truth(sa.f_l, p);
+        const V3 o = ld3(sa.wo + 3 * p);
+        const float pb = usable_pdf(sa.pdf_o[p]);
+        if (pb > 0.0f && (!occlusion || o.z > 0.0f)) {   // (a direction below the surface is blocked by the ball itself)
+            d = o.x * fs + o.y * ft + o.z * nn;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) thr[c] = gt_o ? sa.f_o[3 * p + c] / pb : sc.albedo[c];
+            if (occlusion) h = trace(sc, x, d, (int)m);
+            if (h.id >= 0) {
+                go = true;   // geometry does not emit, and a BSDF sample cannot hit a point
+            } else if (env_emits) {
+                // the BSDF sample escapes: the environment, weighted against the light strategy's density for this direction
+                const float p_light = (M == ENV ? env_dev::env_pdf(e, d) : fmaxf(o.z, 0.0f) * inv_pi) * sel_p;
+                const float w = mis_power(pb, p_light);
+                float ev[3];
+                env_lookup(env, sc.env_w, sc.env_h, d, ev);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    // COSINE keeps shade_kernel's expression: the compiler fuses and packs these multiply-adds by the code around
+                    // them, and with thr[c] this instantiation rounds differently from the recording
+                    if constexpr (M == COSINE) L[c] += w * ev[c] * (gt_o ? sa.f_o[3 * p + c] / pb : sc.albedo[c]);
+                    else L[c] += w * ev[c] * thr[c];
+                }
+            }
+        }
+        // the light strategy: f cos towards the emitter sample times what arrives
+        const float pbl = usable_pdf(sa.pdf_l[p]);
+        if (pbl > 0.0f || gt_l) {
+            if (M == ENV || point) {
+                // visibility and the density are in emit; a point is a delta and has no MIS weight, the environment's draw is
+                // weighted against the sampler's density for its direction
+                const float w = M == LIT || point ? 1.0f : mis_power(es.lpdf[p], pbl);
+                const float ev[3] = {em.x, em.y, em.z};
+#pragma unroll
+                for (int c = 0; c < 3; ++c) L[c] += w * ev[c] * (gt_l ? sa.f_l[3 * p + c] : sc.albedo[c] * pbl);
+            } else {
+                // the environment along the cosine sample (pdf cos/pi, chosen with probability sel_p), unless something is in the way
+                const float pl = l.z * inv_pi * sel_p;
+                if (pl > 0.0f && !(occlusion && trace(sc, x, lw, (int)m).id >= 0)) {
+                    const float w = mis_power(pl, pbl) / pl;
+                    float ev[3];
+                    env_lookup(env, sc.env_w, sc.env_h, lw, ev);
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) L[c] += w * ev[c] * (gt_l ? sa.f_l[3 * p + c] : sc.albedo[c] * pbl);
+                }
+            }
+        }
+    }
+    const V3 b = ld3(ps.beta + 3 * p);
+    const V3 r0 = ld3(ps.rad + 3 * p);
+    st3(ps.rad + 3 * p, v3(r0.x + b.x * L[0], r0.y + b.y * L[1], r0.z + b.z * L[2]));
+    if (!go || st.last) {
+        ps.mat[p] = sc.n_sph + 1;
+        return;
+    }
+    continue_path(sc, h, x, d, b, thr, st.seed, st.pass, st.path_offset, st.bounce, p, ps.org, ps.nrm, ps.wi, ps.wl, ps.mat, ps.beta);
+}
+
+// ---- host side ----
+inline Step make_step(int32_t bounce, int32_t last, int32_t occlusion, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N) {
+    return Step{(int)bounce, last ? 1 : 0, occlusion ? 1 : 0, (unsigned long long)seed, (unsigned long long)pass,
+                (unsigned long long)path_offset, (long long)N};
+}
+
+// The arguments bsdfd_wf_bounce, _lit and _env share, in the structs the kernels take, checked after the launcher's own scene
+// and emitter arguments; then `launch`, unless there is nothing to do.  `emitter_arrays`: the mode's own arrays are all given.
+template <class Launch>
+int checked_bounce(int32_t bounce, int32_t last, int32_t occlusion, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N,
+                   const PathState& ps, const SamplerAnswer& sa, bool emitter_arrays, Launch launch) {
+    if (bounce < 0) return bsdfd_fail_(BSDFD_EINVAL, "bounce must be >= 0");
+    if ((sa.f_o == nullptr) != (sa.f_l == nullptr)) return bsdfd_fail_(BSDFD_EINVAL, "f_o and f_l are both NULL or both given");
+    if (N == 0) return BSDFD_OK;
+    if (!ps.org || !ps.nrm || !ps.wi || !ps.wl || !ps.mat || !ps.beta || !ps.rad || !sa.wo || !sa.pdf_o || !sa.pdf_l || !emitter_arrays)
+        return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
+    return launch(make_step(bounce, last, occlusion, seed, pass, path_offset, N));
+}
+
+}  // namespace bounce_dev

@@ -1,6 +1,6 @@
 // wavefront_dev.h — the scene model of the wavefront harness, shared by the translation units that trace it: wavefront.hip
 // (primary rays, one-bounce shading), pathtrace.hip (occlusion and further bounces), pathlights.hip (point emitters) and
-// pathenv.hip (importance sampling of the environment map).  They
+// pathenv.hip (importance sampling of the environment map) — the last three through bounce_dev.h, their one bounce.  They
 // inline the same vector helpers, orthonormal basis, environment lookup and MIS weight, the same light sample, floor term and
 // pixel mean, the same secondary ray and path continuation, and build the kernel-argument `Scene` from the same bsdfd_wf_scene.
 #pragma once

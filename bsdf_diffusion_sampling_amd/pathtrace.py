@@ -61,6 +61,11 @@ _M64 = 0xFFFFFFFFFFFFFFFF
 PointLight = namedtuple("PointLight", "position intensity")
 
 
+def _p(t: Optional[torch.Tensor]):
+    """The device pointer of a tensor as a C argument (None stays NULL)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 def wf_lights(lights: Sequence[PointLight], has_env: bool) -> _lib.WfLights:
     """The ``bsdfd_wf_lights`` of 1..8 point lights; ``ValueError`` for anything the kernels should not see."""
     lights = list(lights)
@@ -166,37 +171,34 @@ class PathArrayRenderer(ArrayRenderer):
     # -- the path kernels ----------------------------------------------------------------------------
     def path_begin(self, b):
         """org, beta, rad of the first vertices from what ``primary`` wrote into ``b``."""
-        p = lambda t: C.c_void_p(t.data_ptr())
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().bsdfd_wf_path_begin(C.byref(self.scene), p(self.env), b["mat"].shape[0], p(b["dir"]),
-                                                      p(b["nrm"]), p(b["mat"]), p(b["org"]), p(b["beta"]), p(b["rad"]),
+            _lib.check(_lib.lib().bsdfd_wf_path_begin(C.byref(self.scene), _p(self.env), b["mat"].shape[0], _p(b["dir"]),
+                                                      _p(b["nrm"]), _p(b["mat"]), _p(b["org"]), _p(b["beta"]), _p(b["rad"]),
                                                       self._stream()))
 
     def sample_emitter(self, b, bounce: int, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
                        lights: Optional[_lib.WfLights] = None):
         """The emitter sample of the vertices in ``b``: ``lsel``, ``emit``, and ``wl`` towards a picked point light."""
-        p = lambda t: C.c_void_p(t.data_ptr())
         occlusion = self.occlusion if occlusion is None else occlusion
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().bsdfd_wf_sample_emitter(
                 C.byref(self.scene), C.byref(self.lights if lights is None else lights), bounce, int(bool(occlusion)), seed,
-                pass_idx, path_offset, b["mat"].shape[0], p(b["org"]), p(b["nrm"]), p(b["wi"]), p(b["mat"]), p(b["wl"]),
-                p(b["lsel"]), p(b["emit"]), self._stream()))
+                pass_idx, path_offset, b["mat"].shape[0], _p(b["org"]), _p(b["nrm"]), _p(b["wi"]), _p(b["mat"]), _p(b["wl"]),
+                _p(b["lsel"]), _p(b["emit"]), self._stream()))
         torch.autograd.graph.increment_version([b["wl"], b["lsel"], b["emit"]])
 
     def sample_env(self, b, bounce: int, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
                    lights: Optional[_lib.WfLights] = None, env_dist=None):
         """The environment's emitter sample of the vertices in ``b`` that picked it (``lsel == -1``; all live ones without
         lights): ``lpdf``, ``emit``, and ``wl`` on the balls, drawn from the ``EnvDistribution``."""
-        p = lambda t: C.c_void_p(t.data_ptr())
         occlusion = self.occlusion if occlusion is None else occlusion
         lights = self.lights if lights is None else lights
         env_dist = self.env_dist if env_dist is None else env_dist
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().bsdfd_wf_sample_env(
-                C.byref(self.scene), p(self.env), C.byref(env_dist.struct(self.device)), 1 if lights is None else lights.n_lights + 1,
-                bounce, int(bool(occlusion)), seed, pass_idx, path_offset, b["mat"].shape[0], p(b["org"]), p(b["nrm"]), p(b["wi"]),
-                p(b["mat"]), None if lights is None else p(b["lsel"]), p(b["wl"]), p(b["lpdf"]), p(b["emit"]), self._stream()))
+                C.byref(self.scene), _p(self.env), C.byref(env_dist.struct(self.device)), 1 if lights is None else lights.n_lights + 1,
+                bounce, int(bool(occlusion)), seed, pass_idx, path_offset, b["mat"].shape[0], _p(b["org"]), _p(b["nrm"]), _p(b["wi"]),
+                _p(b["mat"]), None if lights is None else _p(b["lsel"]), _p(b["wl"]), _p(b["lpdf"]), _p(b["emit"]), self._stream()))
         torch.autograd.graph.increment_version([b["wl"], b["lpdf"], b["emit"]])
 
     def bounce(self, b, bounce: int, last: bool, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
@@ -204,23 +206,21 @@ class PathArrayRenderer(ArrayRenderer):
         """Shade the vertices in ``b`` (``wo``, ``pdf_o``, ``pdf_l`` [, ``f_o``, ``f_l``] from the sampler; with lights also
         ``lsel`` and ``emit`` from ``sample_emitter``; with an ``EnvDistribution`` also ``lpdf`` and ``emit`` from ``sample_env``)
         and move the paths on."""
-        p = lambda t: C.c_void_p(t.data_ptr())
         occlusion = self.occlusion if occlusion is None else occlusion
         lights = self.lights if lights is None else lights
         env_dist = self.env_dist if env_dist is None else env_dist
-        args = [C.byref(self.scene), p(self.env), bounce, int(bool(last)), int(bool(occlusion)), seed, pass_idx, path_offset,
-                b["mat"].shape[0], p(b["org"]), p(b["nrm"]), p(b["wi"]), p(b["wl"]), p(b["mat"]), p(b["beta"]), p(b["rad"]),
-                p(b["wo"]), p(b["pdf_o"]), p(b["pdf_l"]), p(b["f_o"]) if "f_o" in b else None,
-                p(b["f_l"]) if "f_l" in b else None]
         with torch.cuda.device(self.device):
-            if env_dist is not None:
-                _lib.check(_lib.lib().bsdfd_wf_bounce_env(
-                    *args, None if lights is None else C.byref(lights), None if lights is None else p(b["lsel"]), p(b["emit"]),
-                    p(b["lpdf"]), C.byref(env_dist.struct(self.device)), self._stream()))
-            elif lights is None:
-                _lib.check(_lib.lib().bsdfd_wf_bounce(*args, self._stream()))
-            else:
-                _lib.check(_lib.lib().bsdfd_wf_bounce_lit(*args, C.byref(lights), p(b["lsel"]), p(b["emit"]), self._stream()))
+            fn, args = _lib.lib().bsdfd_wf_bounce, [
+                C.byref(self.scene), _p(self.env), bounce, int(bool(last)), int(bool(occlusion)), seed, pass_idx, path_offset,
+                b["mat"].shape[0], _p(b["org"]), _p(b["nrm"]), _p(b["wi"]), _p(b["wl"]), _p(b["mat"]), _p(b["beta"]), _p(b["rad"]),
+                _p(b["wo"]), _p(b["pdf_o"]), _p(b["pdf_l"]), _p(b.get("f_o")), _p(b.get("f_l"))]
+            if lights is not None or env_dist is not None:   # bounce_lit's arguments follow bounce's ...
+                fn = _lib.lib().bsdfd_wf_bounce_lit
+                args += [None if lights is None else C.byref(lights), None if lights is None else _p(b["lsel"]), _p(b["emit"])]
+            if env_dist is not None:                         # ... and bounce_env's follow bounce_lit's
+                fn = _lib.lib().bsdfd_wf_bounce_env
+                args += [_p(b["lpdf"]), C.byref(env_dist.struct(self.device))]
+            _lib.check(fn(*args, self._stream()))
         # written through raw pointers: tell torch (the plugin cores key their per-query context cache on wi._version)
         torch.autograd.graph.increment_version([b["wi"], b["wl"], b["nrm"], b["org"], b["mat"], b["beta"], b["rad"]])
 
@@ -230,8 +230,8 @@ class PathArrayRenderer(ArrayRenderer):
                 or not film.is_contiguous() or film.device != self.device:
             raise ValueError("film must be a contiguous fp32 [rows, width, 3] tensor on the renderer's device")
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().bsdfd_wf_resolve(C.byref(self.scene), row_begin, row_end, spp, C.c_void_p(b["rad"].data_ptr()),
-                                                   C.c_void_p(film.data_ptr()), self._stream()))
+            _lib.check(_lib.lib().bsdfd_wf_resolve(C.byref(self.scene), row_begin, row_end, spp, _p(b["rad"]), _p(film),
+                                                   self._stream()))
 
     # -- one pass over a tile ------------------------------------------------------------------------
     def render_pass(self, film: torch.Tensor, row_begin: int, row_end: int, spp: int, seed: int, pass_idx: int,

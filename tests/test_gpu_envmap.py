@@ -3,6 +3,7 @@
 ``PathArrayRenderer(..., env_sampling="importance")`` at the level of images — cosine is the renderer as it was, the film scales
 exactly with the map, the mean is the cosine renderer's, and the variance is several times smaller."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -13,7 +14,7 @@ torch = pytest.importorskip("torch")
 import envmap_ref as ER  # noqa: E402
 import pathtrace_lights_ref as LR  # noqa: E402
 import pathtrace_ref as R  # noqa: E402
-from test_gpu_pathtrace import _array, _gpu, _scene_renderer, _shade_bound, _to_device  # noqa: E402
+from test_gpu_pathtrace import ROOT, _array, _gpu, _scene_renderer, _shade_bound, _to_device  # noqa: E402
 from test_gpu_pathtrace_lights import _device_lights  # noqa: E402
 from test_pathtrace_cpu import STATE  # noqa: E402
 
@@ -117,8 +118,7 @@ def test_env_pdf_rows_match_reference(name):
 
 
 # ---- the path kernels on the synthetic wavefront -----------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def synth():
+def synthetic_inputs():
     env = R.synthetic_env()
     t = ER.build_tables(env)
     v, lights = ER.synthetic_env_vertices(env.shape[:2]), LR.synthetic_lights()
@@ -130,6 +130,11 @@ def synth():
             sampled[(with_lights, occ)] = ER.sample_env(R.SYNTH_SCENE, env, t, 4 if with_lights else 1, BOUNCE, bool(occ), SEED, PASS,
                                                         OFFSET, *[v[k] for k in VERTEX], point["lsel"] if with_lights else None, wl)
     return v, lights, env, t, point, sampled
+
+
+@pytest.fixture(scope="module")
+def synth():
+    return synthetic_inputs()
 
 
 def _emitter_inputs(v, point, with_lights):
@@ -194,14 +199,9 @@ def test_sample_env_kernel_matches_reference(synth, with_lights, occlusion):
     assert np.isfinite(emit[picked]).all() and p999 < 2e-4 and worst < 5e-3
 
 
-@pytest.mark.parametrize("with_f", [True, False])
-@pytest.mark.parametrize("last", [0, 1])
-@pytest.mark.parametrize("occlusion", [0, 1])
-@pytest.mark.parametrize("with_lights", [0, 1])
-def test_bounce_env_kernel_matches_reference(synth, with_lights, occlusion, last, with_f):
-    """The same vertices with the reference's emitter samples (rounded to fp32) through ONE bsdfd_wf_bounce_env call: the
-    assertions of test_bounce_lit_kernel_matches_reference on rad and on the continuation state, which is bsdfd_wf_bounce's on
-    the same inputs bit for bit."""
+def _bounce_inputs(synth, with_lights, occlusion, with_f):
+    """The vertices, lsel, emit, lpdf and picked rows of one bsdfd_wf_bounce_env call: the reference's emitter samples, rounded to
+    fp32."""
     v, lights, env, t, point, sampled = synth
     s = sampled[(with_lights, occlusion)]
     wl_in, lsel, emit_in, lpdf_in = _emitter_inputs(v, point, with_lights)
@@ -211,6 +211,19 @@ def test_bounce_env_kernel_matches_reference(synth, with_lights, occlusion, last
         v = {k: a for k, a in v.items() if k not in ("f_o", "f_l")}
     emit = np.where(picked[:, None], s["emit"], np.where(emit_in == EMIT_SENTINEL, 0.0, emit_in)).astype(np.float32)
     lpdf = np.where(picked, s["lpdf"], 0.0).astype(np.float32)
+    return v, lsel, emit, lpdf, picked
+
+
+@pytest.mark.parametrize("with_f", [True, False])
+@pytest.mark.parametrize("last", [0, 1])
+@pytest.mark.parametrize("occlusion", [0, 1])
+@pytest.mark.parametrize("with_lights", [0, 1])
+def test_bounce_env_kernel_matches_reference(synth, with_lights, occlusion, last, with_f):
+    """The same vertices with the reference's emitter samples (rounded to fp32) through ONE bsdfd_wf_bounce_env call: the
+    assertions of test_bounce_lit_kernel_matches_reference on rad and on the continuation state, which is bsdfd_wf_bounce's on
+    the same inputs bit for bit."""
+    v, lights, env, t, point, sampled = synth
+    v, lsel, emit, lpdf, picked = _bounce_inputs(synth, with_lights, occlusion, with_f)
     scene = R.SYNTH_SCENE
     n_b, n = len(scene["spheres"]), len(v["material"])
     n_e = 4 if with_lights else 1
@@ -260,6 +273,42 @@ def test_bounce_env_kernel_matches_reference(synth, with_lights, occlusion, last
     lit_rows = same & picked & (emit > 0).any(1)     # (not vacuous: the environment's draw arrives)
     assert lit_rows.sum() > (100 if with_lights else 500)
     assert (np.abs(want["rad"][lit_rows] - v["rad"][lit_rows]) > 0).any(1).mean() > 0.5
+
+
+def recorded_arrays(synth):
+    """What tests/golden/bounce_kernels_before_merge.npz holds of this file's kernels (tests/golden/make_bounce_merge_golden.py):
+    wl, lsel, emit, lpdf after ONE bsdfd_wf_sample_env call (occlusion = 1; without and with lights) on the inputs of
+    test_sample_env_kernel_matches_reference, and rad of ONE bsdfd_wf_bounce_env call (last = 0) on those of
+    test_bounce_env_kernel_matches_reference, as {key: array}."""
+    v, lights, env, t, point, sampled = synth
+    r = _scene_renderer(R.SYNTH_SCENE, env)
+    dist = _dist(env)
+    device_lights = lambda with_lights: _device_lights(lights, 1) if with_lights else None
+    out = {}
+    for with_lights in (0, 1):
+        wl_in, lsel, emit_in, lpdf_in = _emitter_inputs(v, point, with_lights)
+        b = _to_device(r, dict(v, wl=wl_in, emit=emit_in, lpdf=lpdf_in, **({"lsel": lsel} if with_lights else {})))
+        r.sample_env(b, BOUNCE, SEED, PASS, OFFSET, occlusion=True, lights=device_lights(with_lights), env_dist=dist)
+        out.update({f"sample_env_lights{with_lights}_{k}": b[k].cpu().numpy() for k in ("wl", "lsel", "emit", "lpdf") if k in b})
+    cases = [(wl, occ, True) for wl in (0, 1) for occ in (0, 1)] + [(0, 1, False), (1, 1, False)]
+    for with_lights, occlusion, with_f in cases:
+        v_in, lsel, emit, lpdf, picked = _bounce_inputs(synth, with_lights, occlusion, with_f)
+        b = _to_device(r, dict(v_in, emit=emit, lpdf=lpdf, **({"lsel": lsel} if with_lights else {})))
+        r.bounce(b, BOUNCE, False, SEED, PASS, OFFSET, occlusion=bool(occlusion), lights=device_lights(with_lights), env_dist=dist)
+        out[f"bounce_env_lights{with_lights}_occlusion{occlusion}_f{int(with_f)}_rad"] = b["rad"].cpu().numpy()
+    return out
+
+
+def test_env_kernels_are_bit_identical_to_the_recording(synth):
+    """Every array bsdfd_wf_sample_env and bsdfd_wf_bounce_env wrote before the three bounce kernels became one templated body
+    (tests/golden/bounce_kernels_before_merge.npz), bit for bit.  The continuation state is pinned by
+    test_bounce_kernel_is_bit_identical_to_the_recording through test_bounce_env_kernel_matches_reference's "equal to
+    bsdfd_wf_bounce's" assertions."""
+    before = np.load(os.path.join(ROOT, "tests", "golden", "bounce_kernels_before_merge.npz"))
+    got = recorded_arrays(synth)
+    assert len(got) == 3 + 4 + 6
+    for k, a in got.items():
+        assert np.array_equal(a, before[k], equal_nan=True), k
 
 
 def test_errors(synth):

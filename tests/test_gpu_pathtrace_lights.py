@@ -2,6 +2,7 @@
 (csrc/pathlights.hip) row by row against tests/pathtrace_lights_ref.py, and ``PathArrayRenderer(..., lights=...)`` at the level
 of images — no lights is the renderer as it was, intensity scales the film exactly, a ball casts its shadow, depth only adds."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -11,7 +12,7 @@ torch = pytest.importorskip("torch")
 
 import pathtrace_lights_ref as LR  # noqa: E402
 import pathtrace_ref as R  # noqa: E402
-from test_gpu_pathtrace import _array, _scene_renderer, _shade_bound, _to_device  # noqa: E402
+from test_gpu_pathtrace import ROOT, _array, _scene_renderer, _shade_bound, _to_device  # noqa: E402
 from test_pathtrace_cpu import STATE  # noqa: E402
 
 VERTEX = ("org", "nrm", "wi", "material", "wl")
@@ -25,12 +26,16 @@ def _device_lights(lights, has_env):
                      has_env)
 
 
-@pytest.fixture(scope="module")
-def synth():
+def synthetic_inputs():
     v, lights, env = LR.synthetic_lit_vertices(), LR.synthetic_lights(), R.synthetic_env()
     sampled = {(occ, he): LR.sample_emitter(R.SYNTH_SCENE, lights, bool(he), BOUNCE, bool(occ), SEED, PASS, OFFSET,
                                             *[v[k] for k in VERTEX]) for occ in (0, 1) for he in (0, 1)}
     return v, lights, env, sampled
+
+
+@pytest.fixture(scope="module")
+def synth():
+    return synthetic_inputs()
 
 
 def _with_emitter_arrays(r, b, n):
@@ -82,6 +87,17 @@ def test_sample_emitter_kernel_matches_reference(synth, occlusion, has_env):
     assert np.isfinite(emit[live]).all() and p999 < 2e-4 and worst < 5e-3
 
 
+def _lit_inputs(synth, has_env, with_f):
+    """The vertices, lsel and emit of one bsdfd_wf_bounce_lit call: the reference's emitter samples at occlusion = 1, rounded to
+    fp32."""
+    v, lights, env, sampled = synth
+    s = sampled[(1, has_env)]
+    v = dict(v, wl=s["wl"].astype(np.float32))
+    if not with_f:
+        v = {k: a for k, a in v.items() if k not in ("f_o", "f_l")}
+    return v, s["lsel"], s["emit"].astype(np.float32)
+
+
 @pytest.mark.parametrize("with_f", [True, False])
 @pytest.mark.parametrize("last", [0, 1])
 @pytest.mark.parametrize("has_env", [0, 1])
@@ -89,11 +105,7 @@ def test_bounce_lit_kernel_matches_reference(synth, has_env, last, with_f):
     """The same vertices with the reference's emitter samples (rounded to fp32) through ONE bsdfd_wf_bounce_lit call, occlusion on:
     the assertions of test_bounce_kernel_matches_reference on the continuation state and on rad."""
     v, lights, env, sampled = synth
-    s = sampled[(1, has_env)]
-    v = dict(v, wl=s["wl"].astype(np.float32))
-    if not with_f:
-        v = {k: a for k, a in v.items() if k not in ("f_o", "f_l")}
-    lsel, emit = s["lsel"], s["emit"].astype(np.float32)
+    v, lsel, emit = _lit_inputs(synth, has_env, with_f)
     scene = R.SYNTH_SCENE
     n_b, n = len(scene["spheres"]), len(v["material"])
     want = LR.bounce_lit(scene, env, 3 + has_env, bool(has_env), BOUNCE, bool(last), True, SEED, PASS, OFFSET,
@@ -139,6 +151,50 @@ def test_bounce_lit_kernel_matches_reference(synth, has_env, last, with_f):
     assert np.isfinite(got["rad"][live]).all() and p999 < 2e-4 and worst < 5e-3
     lit_rows = same & (lsel >= 0) & (emit > 0).any(1)
     assert lit_rows.sum() > 500 and (np.abs(want["rad"][lit_rows] - v["rad"][lit_rows]) > 0).any(1).mean() > 0.5   # (not vacuous)
+
+
+def recorded_arrays(synth):
+    """What tests/golden/bounce_kernels_before_merge.npz holds of this file's kernels (tests/golden/make_bounce_merge_golden.py):
+    wl, lsel, emit of ONE bsdfd_wf_sample_emitter call (occlusion = 1, has_env = 1) on the inputs of
+    test_sample_emitter_kernel_matches_reference, and rad of ONE bsdfd_wf_bounce_lit call (occlusion = 1, last = 0) on those of
+    test_bounce_lit_kernel_matches_reference, as {key: array}."""
+    v, lights, env, sampled = synth
+    r = _scene_renderer(R.SYNTH_SCENE, env)
+    out = {}
+    b = _with_emitter_arrays(r, _to_device(r, v), len(v["material"]))
+    r.sample_emitter(b, BOUNCE, SEED, PASS, OFFSET, occlusion=True, lights=_device_lights(lights, 1))
+    out.update({f"sample_emitter_{k}": b[k].cpu().numpy() for k in ("wl", "lsel", "emit")})
+    for has_env in (0, 1):
+        for with_f in (True, False):
+            v_in, lsel, emit = _lit_inputs(synth, has_env, with_f)
+            b = _to_device(r, v_in)
+            b["lsel"], b["emit"] = torch.from_numpy(lsel).to(r.device), torch.from_numpy(emit).to(r.device)
+            r.bounce(b, BOUNCE, False, SEED, PASS, OFFSET, occlusion=True, lights=_device_lights(lights, has_env))
+            out[f"bounce_lit_env{has_env}_f{int(with_f)}_rad"] = b["rad"].cpu().numpy()
+    return out
+
+
+def test_lit_kernels_are_bit_identical_to_the_recording(synth):
+    """Every array bsdfd_wf_sample_emitter and bsdfd_wf_bounce_lit wrote before the three bounce kernels became one templated body
+    (tests/golden/bounce_kernels_before_merge.npz), bit for bit.  The continuation state is pinned by
+    test_bounce_kernel_is_bit_identical_to_the_recording through the "equal to bsdfd_wf_bounce's" assertions."""
+    before = np.load(os.path.join(ROOT, "tests", "golden", "bounce_kernels_before_merge.npz"))
+    got = recorded_arrays(synth)
+    assert len(got) == 7
+    for k, a in got.items():
+        assert np.array_equal(a, before[k], equal_nan=True), k
+    # ... and where a path goes is bsdfd_wf_bounce's on the same inputs, bit for bit
+    v, lights, env, sampled = synth
+    r = _scene_renderer(R.SYNTH_SCENE, env)
+    for has_env in (0, 1):
+        v_in, lsel, emit = _lit_inputs(synth, has_env, True)
+        b, unlit = _to_device(r, v_in), _to_device(r, v_in)
+        b["lsel"], b["emit"] = torch.from_numpy(lsel).to(r.device), torch.from_numpy(emit).to(r.device)
+        r.bounce(b, BOUNCE, False, SEED, PASS, OFFSET, occlusion=True, lights=_device_lights(lights, has_env))
+        r.bounce(unlit, BOUNCE, False, SEED, PASS, OFFSET, occlusion=True)
+        for k in ("org", "nrm", "wi", "wl", "beta"):
+            assert torch.equal(b[k].view(torch.int32), unlit[k].view(torch.int32)), k
+        assert torch.equal(b["mat"], unlit["mat"])
 
 
 def test_errors(synth):

@@ -27,6 +27,8 @@ def test_library_exports_the_path_kernels_without_a_new_abi():
     assert C.sizeof(_lib.WfScene) == 4 * (13 + 2 + 7 + 3 + 124 + 1 + 4) == 616
     src = os.path.join(ROOT, "bsdf_diffusion_sampling_amd", "csrc", "pathtrace.hip")
     assert src in _lib.SRC_PATHS and src in _lib.DEP_PATHS and os.path.exists(src)
+    body = os.path.join(os.path.dirname(src), "bounce_dev.h")   # the bounce the three path translation units instantiate
+    assert body in _lib.DEP_PATHS and body not in _lib.SRC_PATHS and os.path.exists(body)
 
 
 def test_renderer_argument_checks():
