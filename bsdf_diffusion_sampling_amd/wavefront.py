@@ -308,8 +308,8 @@ class ArrayRenderer(WavefrontRenderer):
     balls that have an RGL tensor file; the others shade with the proxy ``f cos = albedo * pdf``.  Their ``eval()`` is ONE launch
     on the lane-ordered wavefront (``measured.MeasuredTable``); ``fused_ground_truth=False`` keeps the earlier form — gathered
     copies, two ``MeasuredBSDF.eval_t`` launches per material, a scatter — for A/B runs: the same film bit for bit.
-    The Philox counter of a path is its row in the bucketed order, so images of different row splits agree
-    statistically, not bit for bit (the single-ball renderer is split-invariant)."""
+    The Philox counter of a path is its global index in the film — primary's, and the sampler's too (``rng="lane"`` with the
+    tile's first path as ``offset``) — so a tile is the rows of the whole film bit for bit, like the single-ball renderer's."""
 
     def __init__(self, table, centers, radii, camera: Optional[Camera] = None, env: Optional[torch.Tensor] = None,
                  floor: bool = True, checker=(0.4, 0.2, 2.0), albedo=(1.0, 1.0, 1.0), ground_truth=None,

@@ -209,11 +209,11 @@ def bounce_env(scene: dict, env, tables: dict, n_e: int, bounce: int, last: bool
 
 
 # ---- the synthetic wavefront of tests/test_gpu_envmap.py ---------------------------------------------------------------------
-def synthetic_env_vertices(shape, n: int = 4096, seed: int = 7, scene: dict = R.SYNTH_SCENE, tol: float = 1e-3):
+def synthetic_env_vertices(shape, n: int = 4096, seed: int = 7, scene: dict = R.SYNTH_SCENE, tol: float = 1e-3, lights: dict = None):
     """``pathtrace_lights_ref.synthetic_lit_vertices`` with new directions for every vertex whose wl or wo, in the world, lies
     within ``tol`` cells of a cell boundary of a map of ``shape`` — where the fp32 kernel may look its density up in the
     neighbouring cell — until those graze no silhouette either."""
-    v = LR.synthetic_lit_vertices(n, seed, scene)
+    v = LR.synthetic_lit_vertices(n, seed, scene, lights)
     g = np.random.default_rng(seed + 2000)
     n_b, mat = len(scene["spheres"]), v["material"]
     live = mat <= n_b

@@ -1,0 +1,550 @@
+"""GPU tests of ``PathArrayRenderer.render_pass`` as a WHOLE: one recorded pass per case (tests/pass_replay.py ``Recorder``), held
+stage by stage to the fp64 references of the kernel tests and, end to end, to ``pass_replay.reference_pass``.
+
+The kernel tests run every path kernel alone on one synthetic wavefront; the loop that strings them together was only held by
+statements about images.  Here the loop itself is on the bench: the order of the stages, the arguments it hands them (bounce,
+last, seed, pass, path offset, the sampler's key per bounce), that nothing writes the state between two stages, each stage on the
+REAL mid-path wavefront it meets (tens of lanes at depth, floor vertices 1e3 away, ``wi`` out of the continuation, ``wl`` below
+the horizon), the sampler's rows bit for bit against the single-material call with the documented key, the evaluator on the
+``wl`` the emitter stages left, the film.  And tiles: every draw is keyed by the global path index, so a tile is the rows of the
+whole film bit for bit.
+
+All cases: the 5-ball scene of tests/test_gpu_pathtrace.py seen from the low camera (the reference scene's own camera looks down
+on the array and none of its primary rays reaches the sky, so "miss" could not occur at bounce 0), 96x64, 2 spp, seed 4, a film
+pre-filled with 0.25.
+"""
+import functools
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+import envmap_ref as ER  # noqa: E402
+import pass_replay as PR  # noqa: E402
+import pathtrace_lights_ref as LR  # noqa: E402
+import pathtrace_ref as R  # noqa: E402
+from oracle import bsdf_oracle as O  # noqa: E402
+from oracle import measured_oracle as M  # noqa: E402
+from oracle import wavefront_oracle as WO  # noqa: E402
+from test_gpu_pathtrace import ROOT, _array, _shade_bound  # noqa: E402
+from test_pass_replay_cpu import five_ball_lights  # noqa: E402
+
+W, H, SPP, SEED, FILL = 96, 64, 2, 4, 0.25
+TILE = (5, 57)
+#            mode          lights  env    ground truth  depth  rows   pass
+CASES = {"a": ("cosine", False, True, False, 4, None, 0),
+         "b": ("cosine", False, True, True, 4, TILE, 1),
+         "c": ("cosine", True, True, True, 3, None, 1),
+         "d": ("cosine", True, False, False, 3, TILE, 0),
+         "e": ("importance", False, True, False, 3, None, 0),
+         "f": ("importance", True, True, True, 3, TILE, 1)}
+FIXTURE = os.path.join(ROOT, "tests", "golden", "chm_orange_rgb.bsdf")
+VERTEX = ("org", "nrm", "wi", "mat")
+STATE = ("org", "nrm", "wi", "wl", "mat", "beta", "rad", "wo", "pdf_o", "pdf_l")
+
+
+def _sky():
+    from bsdf_diffusion_sampling_amd.wavefront import make_sky
+    return make_sky(64, 128, seed=5)
+
+
+def _renderer(case, **more):
+    """The case's renderer.  Lights: the three of pathtrace_lights_ref.synthetic_lights() at (-1.7, 2.5, -1.0) over the middle of
+    the balls, (-3.2, 1.2, -0.5) to their side and (-0.3, 0.45, -0.6), low between them (test_pass_replay_cpu.LIGHT_POSITIONS)."""
+    from bsdf_diffusion_sampling_amd.pathtrace import PointLight
+    mode, lit, with_env, gt, depth, rows, pass_idx = CASES[case]
+    kw = dict(max_depth=depth, **more)
+    if mode == "importance":
+        kw["env_sampling"] = "importance"
+    if lit:
+        lights = five_ball_lights()
+        kw["lights"] = [PointLight(tuple(p), tuple(i)) for p, i in zip(lights["position"].tolist(), lights["intensity"].tolist())]
+    return _array(kw, w=W, h=H, gt=gt, env=_sky() if with_env else None, low_camera=True)
+
+
+def _record_pass(r, rows, pass_idx):
+    r0, r1 = rows
+    film = torch.full((r1 - r0, W, 3), FILL, dtype=torch.float32, device=r.device)
+    with PR.Recorder(r) as rec:
+        r.render_pass(film, r0, r1, SPP, SEED, pass_idx)
+    torch.cuda.synchronize()
+    k = 0
+    for s in rec.stages:          # the bounce a stage belongs to: the bounces that ran before it
+        s["k"] = k
+        k += s["name"] == "bounce"
+    return rec.stages, list(r.stats["lanes_per_bounce"])
+
+
+@functools.lru_cache(maxsize=None)
+def _recorded(case):
+    """ONE recorded render_pass of the case, shared by its tests (nobody changes it)."""
+    mode, lit, with_env, gt, depth, rows, pass_idx = CASES[case]
+    r = _renderer(case)
+    rows = rows or (0, H)
+    stages, lanes = _record_pass(r, rows, pass_idx)
+    env = _sky().numpy() if with_env else None
+    return dict(r=r, stages=stages, lanes=lanes, rows=rows, offset=rows[0] * W * SPP, scene=PR.scene_of(r), env=env,
+                tables=ER.build_tables(env) if mode == "importance" else None, lights=five_ball_lights() if lit else None,
+                n_b=len(r.table), n=(rows[1] - rows[0]) * W * SPP)
+
+
+def _named(rec, name):
+    return [s for s in rec["stages"] if s["name"] == name]
+
+
+def _codes(rec, snap):
+    return PR.decision_code(rec["scene"], snap["mat"], snap["wi"])
+
+
+# ---- the order of the stages and what they are handed ----------------------------------------------------------------------------
+@pytest.mark.parametrize("case", list(CASES))
+def test_stages_come_in_the_documented_order_with_the_documented_arguments(case):
+    mode, lit, with_env, gt, depth, _, pass_idx = CASES[case]
+    rec = _recorded(case)
+    r, n_b, offset = rec["r"], rec["n_b"], rec["offset"]
+    buckets = _named(rec, "bucket")
+    want, lanes = ["primary", "path_begin"], []
+    for k in range(depth):
+        want += ["sample_emitter"] * lit + ["sample_env"] * (mode == "importance") + ["bucket"]
+        if k >= len(buckets):
+            break
+        counts = buckets[k]["counts"]
+        n_mat = sum(counts[:n_b])
+        if n_mat + counts[n_b] == 0:                 # the loop stops where no live lane is left
+            break
+        lanes.append(n_mat)
+        want += (["sample_pdf"] + ["eval_t"] * gt) * (n_mat > 0) + ["bounce"]
+    want.append("resolve")
+    got = [s["name"] for s in rec["stages"]]
+    print(f"case {case}: {' '.join(f'{s}' for s in got)}; material lanes per bounce {rec['lanes']}")
+    assert got == want
+    # the ids the bucketing saw are the state's, and its counts are theirs
+    for s in buckets:
+        assert s["args"] == dict(extra_bins=2, ids_are_state=True)
+        assert s["counts"] == np.bincount(s["before"]["mat"], minlength=n_b + 2).tolist()
+    bounces = _named(rec, "bounce")
+    assert rec["lanes"] == lanes == [int((s["before"]["mat"] < n_b).sum()) for s in bounces]
+    assert len(bounces) == depth and lanes[-1] >= 20           # (not vacuous: material lanes are served at the last bounce)
+    # the scalars
+    rows = rec["rows"]
+    tile = dict(row_begin=rows[0], row_end=rows[1], spp=SPP)
+    assert _named(rec, "primary")[0]["args"] == dict(tile, seed=SEED, pass_idx=pass_idx)
+    assert _named(rec, "resolve")[0]["args"] == tile
+    assert offset == rows[0] * W * SPP and r.occlusion is True
+    for name in ("sample_emitter", "sample_env", "bounce"):
+        for s in _named(rec, name):
+            a = dict(bounce=s["k"], seed=SEED, pass_idx=pass_idx, path_offset=offset, occlusion=r.occlusion)
+            if name == "bounce":
+                a["last"] = s["k"] == depth - 1
+            assert s["args"] == a, (name, s["k"], s["args"])
+    keys = {(p, k): PR.sampler_key(SEED, p, k) for p in (0, 1) for k in range(depth)}
+    assert len(set(keys.values())) == 2 * depth                # pairwise distinct across the bounces of passes 0 and 1
+    for s in _named(rec, "sample_pdf"):
+        a = s["args"]
+        assert a["seed"] == keys[(pass_idx, s["k"])] and a["offset"] == offset, (s["k"], hex(a["seed"]))
+        assert a["wi_is_state"] and a["wl_is_state"] and a["counts"] == buckets[s["k"]]["counts"]
+    for s in _named(rec, "eval_t"):
+        assert s["args"] == dict(tint=[1.0, 1.0, 1.0], reads_state=True, writes_state=True)
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_nothing_writes_the_state_between_two_stages(case):
+    """What a stage left is, byte for byte, what the next one finds — every array of the buffer dict, the ones nobody has
+    written yet included."""
+    stages = _recorded(case)["stages"]
+    for s, t in zip(stages, stages[1:]):
+        assert set(s["after"]) == set(t["before"]), (s["name"], t["name"])
+        for key, a in s["after"].items():
+            assert a.dtype == t["before"][key].dtype and a.tobytes() == t["before"][key].tobytes(), (s["name"], t["name"], key)
+
+
+# ---- every stage against its reference, on the device's own input ---------------------------------------------------------------
+def _near_cell(rec, snap):
+    """Live rows of a bounce's input whose environment-density lookup — of the world-space ``wl`` on the floor, of the BSDF sample
+    on a ball — lies within 1e-3 cells of a cell boundary (envmap_ref.synthetic_env_vertices' tolerance): the fp32 kernel may
+    read the neighbouring cell's density there."""
+    n_b = rec["n_b"]
+    mat = snap["mat"]
+    live = (mat >= 0) & (mat <= n_b)
+    fs, ft, nn = LR._frames(snap["nrm"].astype(np.float64), live, np.float64)
+    local = np.where((mat == n_b)[:, None], snap["wl"], snap["wo"]).astype(np.float64)
+    world = local[:, 0:1] * fs + local[:, 1:2] * ft + local[:, 2:3] * nn
+    with np.errstate(invalid="ignore"):
+        edge = ER.cell_of(rec["tables"]["pdf_uv"].shape, world)[3]
+    return live & ~(edge >= 1e-3)
+
+
+def _reference_bounce(rec, s, case):
+    mode, lit, with_env, gt, depth, _, pass_idx = CASES[case]
+    b = s["before"]
+    env = rec["env"] if with_env else np.zeros((2, 4, 3), np.float32)
+    args = (s["k"], s["k"] == depth - 1, True, SEED, pass_idx, rec["offset"], *[b[k] for k in STATE],
+            b["f_o"] if gt else None, b["f_l"] if gt else None)
+    n_e = (3 if lit else 0) + int(with_env)
+    if mode == "importance":
+        return ER.bounce_env(rec["scene"], env, rec["tables"], n_e, *args, lsel=b["lsel"] if lit else None, emit=b["emit"],
+                             lpdf=b["lpdf"])
+    if lit:
+        return LR.bounce_lit(rec["scene"], env, n_e, with_env, *args, lsel=b["lsel"], emit=b["emit"])
+    return R.bounce(rec["scene"], env, *args)
+
+
+def _check_bounce(rec, s, case):
+    """The assertions of test_bounce_kernel_matches_reference on one recorded bounce.  Two things a real wavefront has and the
+    synthetic one redraws: a floor vertex's checker colour is a decision (pass_replay.decision_code), counted with the ids; and
+    a ray that lands on the floor further than 50 away (the synthetic generator's limit) is held to what fp32 can know of the
+    landing point: the five roundings of the world direction's y (2^-25 each) over cos_in move t, and with it the point, by
+    t 2^-25 5 / cos_in — 2^-22 t / cos_in allowed, which at the generator's limit (t = 50, from a ball's height) is the
+    grazing bound 2e-3 of the kernel test."""
+    mode = CASES[case][0]
+    n_b, scene = rec["n_b"], rec["scene"]
+    v, got = s["before"], s["after"]
+    want = _reference_bounce(rec, s, case)
+    live = (v["mat"] >= 0) & (v["mat"] <= n_b)
+    for k in ("org", "nrm", "wi", "wl", "mat", "beta", "rad"):      # ended paths: not a byte of their state moves
+        assert got[k][~live].tobytes() == v[k][~live].tobytes(), k
+    for k in got:                                                     # and the bounce writes nothing but the state
+        if k not in ("org", "nrm", "wi", "wl", "mat", "beta", "rad"):
+            assert got[k].tobytes() == v[k].tobytes(), k
+    differ = live & (_codes(rec, got) != PR.decision_code(scene, want["material"], want["wi"]))
+    assert differ.sum() <= live.sum() // 1000, (s["k"], int(differ.sum()), int(live.sum()))
+    same = live & ~differ
+    cont = same & (want["material"] <= n_b)
+    out = f"  bounce {s['k']}: {int(live.sum())} live rows, {int(differ.sum())} decide differently, {int(cont.sum())} continue"
+    if s["args"]["last"]:
+        assert not cont.any() and (got["mat"][live] == n_b + 1).all()
+    elif cont.any():
+        t = np.linalg.norm(want["org"] - v["org"].astype(np.float64), axis=1)
+        far = cont & (want["material"] == n_b) & (t > 50.0)
+        graze = cont & (want["cos_in"] < 0.1)
+        ok = cont & ~graze
+        assert not (far & ~graze).any()
+        for k in ("org", "nrm", "wi", "beta"):
+            err = np.abs(got[k] - want[k]).max(1)
+            rows = cont & ~far if k == "org" else cont
+            e_ok, e_all = err[ok].max(initial=0.0), err[rows].max(initial=0.0)
+            out += f"; {k} {e_ok:.1e} ({e_all:.1e} grazing)"
+            assert e_ok < 2e-5 and e_all < 2e-3, (s["k"], k, e_ok, e_all)
+        if far.any():
+            err = np.abs(got["org"] - want["org"]).max(1)[far]
+            bound = 2e-5 + 2.0 ** -22 * t[far] / want["cos_in"][far]
+            out += f"; {int(far.sum())} land {t[far].min():.3g}..{t[far].max():.3g} away, error / bound {(err / bound).max():.2f}"
+            assert (err <= bound).all()
+        e_wl = np.abs(got["wl"][cont] - R.next_wl(SEED, s["args"]["pass_idx"], s["k"], rec["offset"], rec["n"])[cont]).max()
+        assert e_wl < 2e-6, (s["k"], e_wl)
+    ended = same & ~cont                                              # rows that end keep the rest of their state
+    for k in ("org", "nrm", "wi", "wl", "beta"):
+        assert got[k][ended].tobytes() == v[k][ended].tobytes(), k
+    assert np.isfinite(got["rad"][live]).all()
+    rows = same
+    if mode == "importance":
+        near = _near_cell(rec, v)
+        rows = same & ~near
+        out += f"; {int((same & near).sum())} of {int(same.sum())} rows near a cell boundary left out"
+        assert (same & near).sum() <= 0.02 * rows.sum()
+    p999, worst = _shade_bound(got["rad"][rows], want["rad"][rows])
+    print(out + f"; rad p99.9 {p999:.1e} max {worst:.1e}")
+    assert p999 < 2e-4 and worst < 5e-3, (s["k"], p999, worst)
+    return differ
+
+
+def _check_primary_and_path_begin(rec, case):
+    """test_array_scene_matches_oracle's assertions on primary, test_path_begin_and_resolve_match_reference's on path_begin."""
+    with_env, pass_idx = CASES[case][2], CASES[case][6]
+    n_b, scene, rows = rec["n_b"], rec["scene"], rec["rows"]
+    b = _named(rec, "primary")[0]["after"]
+    wi_o, wl_o, n_o, d_o, mat_o = WO.primary(scene, rows[0], rows[1], SPP, SEED, pass_idx, with_material=True)
+    differ = _codes(rec, b) != PR.decision_code(scene, mat_o, wi_o)
+    assert differ.sum() <= rec["n"] // 1000
+    same = ~differ
+    assert np.abs(b["dir"] - d_o).max() < 1e-6 and np.abs(b["wl"] - wl_o).max() < 2e-6
+    floor = same & (mat_o == n_b)
+    assert (b["wi"][floor] == wi_o[floor]).all() and (b["nrm"][floor] == [0, 1, 0]).all()
+    ball = same & (mat_o < n_b) & (-(d_o * n_o).sum(1) > 0.1)
+    assert np.abs(b["wi"][ball] - wi_o[ball]).max() < 5e-5
+    s = _named(rec, "path_begin")[0]
+    v, h = s["before"], s["after"]
+    for k in h:
+        if k not in ("org", "beta", "rad"):
+            assert h[k].tobytes() == v[k].tobytes(), k
+    env = rec["env"] if with_env else np.zeros((2, 4, 3), np.float32)
+    org, beta, rad = R.path_begin(scene, env, v["dir"], v["nrm"], v["mat"])
+    hit = v["mat"] <= n_b
+    assert (h["beta"] == 1).all() and np.isfinite(h["org"]).all()
+    err, size = np.abs(h["org"][hit] - org[hit]).max(1), np.abs(org[hit]).max(1)
+    assert (err < 2e-5 + 4e-7 * size).all()
+    assert (h["rad"][hit] == 0).all()
+    p999, worst = _shade_bound(h["rad"], rad)
+    print(f"  primary: {int(differ.sum())} of {rec['n']} rows decide differently; path_begin: farthest floor point {size.max():.3g}, "
+          f"rad p99.9 {p999:.1e} max {worst:.1e}")
+    assert p999 < 2e-4 and worst < 5e-3
+    if not with_env:
+        assert (h["rad"] == 0).all()
+
+
+def _check_sample_emitter(rec, s, case):
+    """test_sample_emitter_kernel_matches_reference's assertions on one recorded call."""
+    with_env, pass_idx = CASES[case][2], CASES[case][6]
+    n_b = rec["n_b"]
+    v, got = s["before"], s["after"]
+    want = LR.sample_emitter(rec["scene"], rec["lights"], with_env, s["k"], True, SEED, pass_idx, rec["offset"],
+                             *[v[k] for k in VERTEX], v["wl"])
+    live, floor = (v["mat"] >= 0) & (v["mat"] <= n_b), v["mat"] == n_b
+    point = live & (want["lsel"] >= 0)
+    assert np.array_equal(got["lsel"][live], want["lsel"][live])                       # exact
+    for k in got:                                                                      # ended paths: not a byte moves; nor
+        rows = ~live if k in ("wl", "lsel", "emit") else slice(None)                   # does anything but wl, lsel, emit
+        assert got[k][rows].tobytes() == v[k][rows].tobytes(), k
+    keep = live & (floor | ~point)     # floor rows and rows that picked the environment keep their cosine sample bit for bit
+    assert np.array_equal(got["wl"][keep], v["wl"][keep]) and (got["emit"][live & ~point] == 0).all()
+    lit = (got["emit"] > 0).any(1)                                                     # (every intensity and reflectance is positive)
+    differ = point & (lit != want["lit"])
+    assert differ.sum() <= live.sum() // 1000, (s["k"], int(differ.sum()), int(live.sum()))
+    same = point & ~differ
+    turned = same & ~floor
+    e_wl = np.abs(got["wl"][turned] - want["wl"][turned]).max(initial=0.0)
+    p999, worst = _shade_bound(got["emit"][same], want["emit"][same])
+    print(f"  sample_emitter {s['k']}: {int(live.sum())} live rows, {int(differ.sum())} decide visibility differently, "
+          f"{int((turned & (want['wl'][:, 2] <= 0)).sum())} see their light below the horizon; wl {e_wl:.1e}; emit p99.9 {p999:.1e} "
+          f"max {worst:.1e}")
+    assert e_wl < 2e-5
+    assert np.isfinite(got["emit"][live]).all() and p999 < 2e-4 and worst < 5e-3
+    return differ, want
+
+
+def _check_sample_env(rec, s, case):
+    """test_sample_env_kernel_matches_reference's assertions on one recorded call."""
+    lit_case, pass_idx = CASES[case][1], CASES[case][6]
+    n_b = rec["n_b"]
+    v, got = s["before"], s["after"]
+    want = ER.sample_env(rec["scene"], rec["env"], rec["tables"], 4 if lit_case else 1, s["k"], True, SEED, pass_idx, rec["offset"],
+                         *[v[k] for k in VERTEX], v["lsel"] if lit_case else None, v["wl"])
+    live, floor, picked = (v["mat"] >= 0) & (v["mat"] <= n_b), v["mat"] == n_b, want["picked"]
+    for k in got:   # ended paths and vertices that picked a point light: not a byte moves; nor does anything but wl, lpdf, emit
+        rows = ~picked if k in ("wl", "lpdf", "emit") else slice(None)
+        assert got[k][rows].tobytes() == v[k][rows].tobytes(), k
+    assert np.array_equal(got["wl"][floor], v["wl"][floor])            # the floor keeps its cosine direction bit for bit
+    lit = (got["emit"] > 0).any(1)                                     # (the sky is positive everywhere)
+    differ = picked & (lit != want["lit"])
+    assert differ.sum() <= live.sum() // 1000, (s["k"], int(differ.sum()), int(live.sum()))
+    assert (got["emit"][picked & ~lit] == 0).all()
+    same = picked & ~differ
+    e_wl = np.abs(got["wl"][same & ~floor] - want["wl"][same & ~floor]).max(initial=0.0)
+    e_pdf = np.abs(got["lpdf"][picked] / want["lpdf"][picked] - 1).max(initial=0.0)
+    p999, worst = _shade_bound(got["emit"][same], want["emit"][same])
+    print(f"  sample_env {s['k']}: {int(picked.sum())} rows picked the environment, {int(differ.sum())} decide visibility differently; "
+          f"wl {e_wl:.1e}; lpdf {e_pdf:.1e}; emit p99.9 {p999:.1e} max {worst:.1e}")
+    assert e_wl < 2e-5 and e_pdf < 1e-5 and (got["lpdf"][picked] > 0).all()
+    assert np.isfinite(got["emit"][picked]).all() and p999 < 2e-4 and worst < 5e-3
+    return differ, want
+
+
+@pytest.mark.parametrize("case", list(CASES))
+def test_every_stage_matches_its_reference_on_the_device_input(case):
+    mode, lit, with_env, gt, depth, _, pass_idx = CASES[case]
+    rec = _recorded(case)
+    n_b = rec["n_b"]
+    print(f"case {case}:")
+    _check_primary_and_path_begin(rec, case)
+    for s in _named(rec, "sample_emitter"):
+        _, want = _check_sample_emitter(rec, s, case)
+        if s["k"] == 0:   # (not vacuous) every light is picked, lit and shadowed rows occur
+            point = want["lsel"] >= 0
+            assert all((want["lsel"] == j).sum() >= 50 for j in range(3))
+            assert (point & want["lit"]).sum() >= 50 and (point & ~want["lit"]).sum() >= 50
+    for s in _named(rec, "sample_env"):
+        _, want = _check_sample_env(rec, s, case)
+        if s["k"] == 0:
+            assert (want["picked"] & (s["after"]["emit"] > 0).any(1)).sum() >= 500
+    for s in _named(rec, "bounce"):
+        _check_bounce(rec, s, case)
+    # (not vacuous) every ball, the floor and the sky at bounce 0; floor -> ball and ball -> ball at bounce 1
+    first, second = _named(rec, "bounce")[0]["before"]["mat"], _named(rec, "bounce")[1]["before"]["mat"]
+    assert set(np.unique(first).tolist()) == set(range(n_b + 2))
+    assert ((first == n_b) & (second < n_b)).any() and ((first < n_b) & (second < n_b)).any()
+
+
+# ---- the sampler and the evaluator ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", list(CASES))
+def test_sampler_rows_are_the_single_material_call_with_the_documented_key(case):
+    pass_idx = CASES[case][6]
+    rec = _recorded(case)
+    r, n_b = rec["r"], rec["n_b"]
+    table = r.table
+    for s in _named(rec, "sample_pdf"):
+        v, got = s["before"], s["after"]
+        nomat = ~((v["mat"] >= 0) & (v["mat"] < n_b))
+        assert nomat.any() and (got["wo"][nomat] == 0).all() and (got["pdf_o"][nomat] == 0).all() and (got["pdf_l"][nomat] == 0).all()
+        key = PR.sampler_key(SEED, pass_idx, s["k"])
+        for m in range(n_b):
+            rows = np.flatnonzero(v["mat"] == m)
+            if not len(rows):
+                continue
+            dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(r.device)
+            wo, pdf_o, pdf_l = table.samplers[m].plugin_sample_pdf(dev(v["wi"][rows]), dev(v["wl"][rows]), None, T=table.T[m],
+                                                                   variant=table.variant[m], seed=key, offset=rec["offset"],
+                                                                   rng_index=dev(rows.astype(np.int64)))
+            for name, t in (("wo", wo), ("pdf_o", pdf_o), ("pdf_l", pdf_l)):
+                assert np.array_equal(t.cpu().numpy(), got[name][rows], equal_nan=True), (s["k"], m, name)
+    assert len(_named(rec, "sample_pdf")) == CASES[case][4]
+
+
+def _resolved(ref, acc):
+    """tests/test_gpu_architectures.py::_resolved."""
+    det_ok = (np.abs(acc) > 1e-3) & (np.abs(acc) < 1e3)
+    scale = np.percentile(np.abs(ref[det_ok]), 99)
+    return det_ok & (np.abs(ref) > 1e-6 * scale)
+
+
+def test_sampler_density_of_the_light_direction_matches_the_oracle():
+    """Case (a), where ``wl`` is a cosine direction in every row: ``pdf_l`` at (wi, wl) of the material rows of all bounces, per
+    material, against the fp64 oracle, with the bound of tests/test_gpu_architectures.py::_check_density — on the resolved rows
+    p99 <= max(1e-4, 4 x the fp32 oracle's p99), max <= max(2e-3, 4 x its max), signs equal.  The resolved share is >= 0.9 per
+    material; the near-specular aniso_miro_7_rgb_spherical resolves 24-30 % of cosine directions in the fp64 oracle itself:
+    >= 0.15 there.
+
+    ``pdf_o`` is not compared with ``plugin_pdf_*`` at (wi, wo): it is the density the FORWARD flow accumulates, the oracle's
+    ``plugin_pdf_*`` integrates the reverse flow, and at the plugins' T = 4 / 8 Euler steps the two differ by a median of 5-40 %
+    in the fp64 oracle itself (chm_orange 25 %, vch_silk_blue 5 %, aniso_copper_sheet 41 %).  ``pdf_o`` and ``wo`` are held bit
+    for bit by test_sampler_rows_are_the_single_material_call_with_the_documented_key."""
+    rec = _recorded("a")
+    table = rec["r"].table
+    stages = _named(rec, "sample_pdf")
+    for m, stem in enumerate(table.stems):
+        rows = [np.flatnonzero(s["before"]["mat"] == m) for s in stages]
+        wi = np.concatenate([s["before"]["wi"][q] for s, q in zip(stages, rows)])
+        wl = np.concatenate([s["before"]["wl"][q] for s, q in zip(stages, rows)])
+        p = np.concatenate([s["after"]["pdf_l"][q] for s, q in zip(stages, rows)]).astype(np.float64)
+        fw = table.samplers[m].weights
+        fn = O.plugin_pdf_disk if stem.endswith("_disk") else O.plugin_pdf_spherical
+        with np.errstate(all="ignore"):
+            po, acc = fn(O.Oracle(fw), wi, wl, T=table.T[m], return_acc=True)
+            p32 = fn(O.Oracle(fw, dtype=np.float32), wi, wl, T=table.T[m]).astype(np.float64)
+        ok = _resolved(po, acc) & np.isfinite(p32)
+        rel = lambda a: np.abs(a - po)[ok] / np.maximum(np.abs(po[ok]), 1e-30)
+        e, e32 = rel(p), rel(p32)
+        b99, bmax = max(1e-4, 4.0 * float(np.percentile(e32, 99))), max(2e-3, 4.0 * float(e32.max()))
+        print(f"{stem}: {len(p)} rows, resolved {ok.mean():.3f}; pdf_l p99 {np.percentile(e, 99):.2e} (bound {b99:.2e}) max {e.max():.2e} "
+              f"(bound {bmax:.2e}); fp32 oracle p99 {np.percentile(e32, 99):.2e} max {e32.max():.2e}")
+        assert len(p) >= 50 and np.isfinite(p).all()
+        assert ok.mean() >= (0.15 if stem == "aniso_miro_7_rgb_spherical" else 0.9), (stem, ok.mean())
+        assert np.percentile(e, 99) <= b99 and e.max() <= bmax, stem
+        assert np.array_equal(np.sign(p[ok]), np.sign(po[ok])), stem
+
+
+@pytest.mark.parametrize("case", [c for c in CASES if CASES[c][3]])
+def test_evaluator_answers_for_the_light_direction_the_emitter_stages_left(case):
+    """f_o at (wi, wo) and f_l at (wi, wl) of ball 0, as the bounce finds them, against oracle.measured_oracle with the bound of
+    tests/test_gpu_measured.py::test_eval_matches_oracle; NaN on every other row.  ``wl`` is the one in the state when the
+    evaluator ran: with lights or importance sampling that is the emitter stages' direction, not primary's."""
+    rec = _recorded(case)
+    orc = M.MeasuredBSDF(FIXTURE)
+    assert len(_named(rec, "eval_t")) == CASES[case][4]
+    moved = 0
+    for s in _named(rec, "bounce"):                            # (what the bounce finds is what it shades with)
+        b = s["before"]
+        rows = b["mat"] == 0
+        assert np.isnan(b["f_o"][~rows]).all() and np.isnan(b["f_l"][~rows]).all()
+        assert rows.sum() >= (50 if s["k"] == 0 else 0)
+        if not rows.any():
+            continue
+        wi = b["wi"][rows].astype(np.float64)
+        for name, d in (("f_o", b["wo"]), ("f_l", b["wl"])):
+            got = b[name][rows].astype(np.float64)
+            want = orc.eval(wi, d[rows].astype(np.float64))
+            assert np.isfinite(got).all() and ((got == 0).all(1) == (want == 0).all(1)).all(), (s["k"], name)
+            err = np.abs(got - want) / (np.abs(want).max(1, keepdims=True) + 1e-3)
+            print(f"case {case} bounce {s['k']} {name}: {int(rows.sum())} rows of ball 0, p99 {np.percentile(err, 99):.1e} max {err.max():.1e}")
+            assert np.percentile(err, 99) < 2e-4 and err.max() < 5e-3, (s["k"], name)
+        if s["k"] == 0:
+            first = _named(rec, "primary")[0]["after"]["wl"]
+            moved = int((np.abs(first[rows] - b["wl"][rows]).max(1) > 1e-3).sum())
+    if CASES[case][0] == "importance" or CASES[case][1]:      # (not vacuous: the emitter stages did move ball 0's wl)
+        assert moved >= 50
+
+
+# ---- end to end --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", list(CASES))
+def test_pass_matches_the_free_running_reference_pass(case):
+    """``reference_pass`` in fp64 from the oracle's primary, with the recorded answers of the sampler and the evaluator: the same
+    decision history on all but 0.1 % of the paths; on the others the final ``rad``, and on the pixels all of whose paths agree the
+    film, inside the shade bound.  In the importance cases the paths that met a row near a cell boundary
+    (test_every_stage_matches_its_reference_on_the_device_input leaves those rows out of its rad comparison) are left out here
+    too."""
+    mode, lit, with_env, gt, depth, _, pass_idx = CASES[case]
+    rec = _recorded(case)
+    n, n_b, rows = rec["n"], rec["n_b"], rec["rows"]
+    bounces = _named(rec, "bounce")
+    names = ("wo", "pdf_o", "pdf_l") + (("f_o", "f_l") if gt else ())
+    answers = [{k: s["before"][k] for k in names} for s in bounces]
+    ref = PR.reference_pass(rec["scene"], rec["env"], mode, rec["lights"], rec["tables"], rows[0], rows[1], SPP, SEED, pass_idx, depth,
+                            True, answers)
+    history = [_codes(rec, _named(rec, "primary")[0]["after"])] + [_codes(rec, s["after"]) for s in bounces]
+    differ = PR.histories_differ(history, ref["history"])
+    assert differ.sum() <= n // 1000
+    final = _named(rec, "resolve")[0]
+    rad = final["before"]["rad"]
+    agree = ~differ
+    if mode == "importance":
+        near = np.any([_near_cell(rec, s["before"]) for s in bounces], axis=0)
+        agree &= ~near
+    p999, worst = _shade_bound(rad[agree], ref["rad"][agree])
+    film = final["film_after"].astype(np.float64)
+    assert (final["film_before"] == FILL).all()
+    px = agree.reshape(-1, SPP).all(1)
+    f999, fworst = _shade_bound((film - FILL).reshape(-1, 3)[px], ref["film"].reshape(-1, 3)[px])
+    print(f"case {case}: histories differ on {int(differ.sum())} of {n} paths, {int(agree.sum())} compared; rad p99.9 {p999:.1e} "
+          f"max {worst:.1e}; film on {int(px.sum())} pixels p99.9 {f999:.1e} max {fworst:.1e}")
+    assert np.isfinite(rad).all() and p999 < 2e-4 and worst < 5e-3
+    assert f999 < 2e-4 and fworst < 5e-3
+    want = FILL + R.resolve(rad, SPP)
+    assert np.abs(film.reshape(-1, 3) - want).max() < 1e-5 * max(1.0, want.max())
+    # (not vacuous) the kinds of path the case is about
+    first, second = PR.ids_of(ref["history"][0]), PR.ids_of(ref["history"][1])
+    assert set(np.unique(first).tolist()) == set(range(n_b + 2))
+    assert ((first == n_b) & (second < n_b) & agree).any() and ((first < n_b) & (second < n_b) & agree).any()
+
+
+@pytest.mark.parametrize("case", ["a", "f"])
+def test_render_is_the_mean_of_its_passes(case):
+    """render(passes=2) = (pass 0 + pass 1) / 2 of two recorded passes, bit for bit: the second pass is added to the film the
+    first one left (resolve is ``film +=``), with pass indices 0 and 1 and nothing else changed."""
+    rows = CASES[case][5] or (0, H)
+    r = _renderer(case)
+    film = torch.zeros((rows[1] - rows[0], W, 3), dtype=torch.float32, device=r.device)
+    ends = []
+    for pass_idx in (0, 1):
+        with PR.Recorder(r) as rec:
+            r.render_pass(film, rows[0], rows[1], SPP, SEED, pass_idx)
+        ends.append(rec.named("resolve")[0])
+        assert rec.named("primary")[0]["args"]["pass_idx"] == pass_idx
+    assert (ends[0]["film_before"] == 0).all() and np.array_equal(ends[0]["film_after"], ends[1]["film_before"])
+    want = ends[1]["film_before"] + R.resolve(ends[1]["before"]["rad"], SPP).reshape(ends[1]["film_before"].shape)
+    assert np.abs(ends[1]["film_after"] - want).max() < 1e-5 * max(1.0, want.max())
+    assert not np.array_equal(ends[0]["before"]["rad"], ends[1]["before"]["rad"])
+    both = r.render(2, spp=SPP, seed=SEED, rows=rows)
+    assert torch.equal(both, film / 2) and float(both.mean()) > 0
+
+
+# ---- tiles -------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("gt", [False, True])
+@pytest.mark.parametrize("mode", ["cosine", "lights + env", "importance + lights"])
+def test_tiles_are_the_rows_of_the_whole_film_bit_for_bit(mode, gt):
+    """Every draw of a pass is keyed by the global path index — primary's, the sampler's (rng = "lane", offset = the tile's first
+    path), the path kernels' (path_offset) — so rows (0, 1), (1, 30), (30, 64) of a depth-3 render, concatenated, ARE the whole
+    render."""
+    from bsdf_diffusion_sampling_amd.pathtrace import PointLight
+    kw = dict(max_depth=3)
+    if "lights" in mode:
+        lights = five_ball_lights()
+        kw["lights"] = [PointLight(tuple(p), tuple(i)) for p, i in zip(lights["position"].tolist(), lights["intensity"].tolist())]
+    if "importance" in mode:
+        kw["env_sampling"] = "importance"
+    r = _array(kw, w=W, h=H, gt=gt, env=_sky(), low_camera=True)
+    whole = r.render(2, spp=SPP, seed=SEED)
+    parts = torch.cat([r.render(2, spp=SPP, seed=SEED, rows=rows) for rows in ((0, 1), (1, 30), (30, 64))], 0)
+    assert torch.isfinite(whole).all() and float(whole.mean()) > 0
+    assert torch.equal(parts, whole)

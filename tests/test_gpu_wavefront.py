@@ -259,7 +259,7 @@ def test_array_scene_renders_and_shards():
     r = _array_renderer(w=96, h=64)
     a = r.render(passes=4, spp=2, seed=1)
     assert torch.isfinite(a).all() and float(a.mean()) > 0.05
-    # statistically the same image whatever the row split (bucketed Philox counters differ: not bit-identical)
+    # the same image whatever the row split (bit for bit, in fact: test_array_scene_tiles_are_the_rows_of_the_whole_film_bit_for_bit)
     parts = torch.cat([r.render(passes=4, spp=2, seed=1, rows=(0, 30)), r.render(passes=4, spp=2, seed=1, rows=(30, 64))], 0)
     assert abs(float(parts.mean()) - float(a.mean())) < 0.05 * float(a.mean())
     # floor pixels (no BSDF sampling noise source but the light sample) are independent of the split
@@ -267,3 +267,15 @@ def test_array_scene_renders_and_shards():
     floor = (b["mat"] == len(r.table)).reshape(64, 96)
     close = torch.isclose(parts, a, rtol=1e-5, atol=1e-6).all(-1)
     assert float(close[floor].float().mean()) > 0.97     # all but pixels on a ball's silhouette
+
+
+@pytest.mark.parametrize("gt", [False, True])
+def test_array_scene_tiles_are_the_rows_of_the_whole_film_bit_for_bit(gt):
+    """Every draw of a pass is keyed by the global path index — primary's Philox counter, and the sampler's through rng = "lane"
+    with the tile's first path as offset — so rows (0, 1), (1, 30), (30, 64), concatenated, ARE the whole render."""
+    from bsdf_diffusion_sampling_amd.wavefront import make_sky
+    r = _array_renderer(w=96, h=64, gt=gt, env=make_sky(64, 128, seed=5))
+    whole = r.render(passes=2, spp=2, seed=1)
+    parts = torch.cat([r.render(passes=2, spp=2, seed=1, rows=rows) for rows in ((0, 1), (1, 30), (30, 64))], 0)
+    assert torch.isfinite(whole).all() and float(whole.mean()) > 0.05
+    assert torch.equal(parts, whole)

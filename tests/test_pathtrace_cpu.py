@@ -95,6 +95,39 @@ def test_reference_decides_the_same_in_fp32_and_fp64(occlusion):
         assert (a["material"] > len(R.SYNTH_SCENE["spheres"])).all()
 
 
+def test_reference_decides_the_same_in_fp32_and_fp64_at_the_kernels_capacity():
+    """The same at the stated capacity of the kernels — 32 balls (ids to 33) and 8 lights (pass_replay.capacity_scene /
+    capacity_lights): the generators reach all 34 ids and all 8 lights, and the fp32 and fp64 references disagree on at most 0.1 %
+    of the rows of ``bounce`` (with and without occlusion) and of the ``lit`` decisions of ``sample_emitter`` (has_env 0 and 1)."""
+    import pass_replay as PR
+    import pathtrace_lights_ref as LR
+    scene, lights, env = PR.capacity_scene(), PR.capacity_lights(), R.synthetic_env()
+    n_b = len(scene["spheres"])
+    assert n_b == 32 and len(lights["position"]) == 8
+    v = R.synthetic_vertices(scene=scene)
+    n = len(v["material"])
+    assert set(np.unique(v["material"]).tolist()) == set(range(n_b + 2))
+    for occlusion in (False, True):
+        a, b = (R.bounce(scene, env, 0, False, occlusion, 0x1234567890, 3, 1000, *[v[k] for k in STATE], dtype=dt)
+                for dt in (np.float64, np.float32))
+        differ = int((a["material"] != b["material"]).sum())
+        print(f"32 balls, occlusion = {occlusion}: {differ} of {n} rows decide differently in fp32")
+        assert differ <= n // 1000
+        if occlusion:
+            live = v["material"] <= n_b
+            assert len(np.unique(a["material"][live])) >= n_b and (a["material"][live] == n_b).sum() > 30
+    v = LR.synthetic_lit_vertices(scene=scene, lights=lights)
+    vertex = [v[k] for k in ("org", "nrm", "wi", "material", "wl")]
+    for has_env in (False, True):
+        s64, s32 = (LR.sample_emitter(scene, lights, has_env, 1, True, 0x1234567890, 3, 1000, *vertex, dtype=dt)
+                    for dt in (np.float64, np.float32))
+        assert np.array_equal(s64["lsel"], s32["lsel"])
+        differ = int((s64["lit"] != s32["lit"]).sum())
+        picks = [int((s64["lsel"] == k).sum()) for k in range(8)]
+        print(f"8 lights, has_env = {has_env}: {differ} of {n} lit decisions differ in fp32; picks per light {picks}")
+        assert differ <= n // 1000 and min(picks) >= 200 and s64["lsel"].max() == 7
+
+
 def test_reference_leaves_ended_paths_alone_and_replays_philox():
     v = R.synthetic_vertices()
     out = R.bounce(R.SYNTH_SCENE, R.synthetic_env(), 2, False, True, 9, 1, 77, *[v[k] for k in STATE])
