@@ -280,13 +280,22 @@ def expected_flow_kernels(variant: str = "async") -> Dict[str, Dict[str, int]]:
                             spec = dict(spec, sel=max(nh, 1) * (nm // 2) * 8)
                         out[f"flow_kernelILi{dom}ELi{nm}ELi{prec}ELb{jac}ELi{nh}ELb{fused}EE"] = spec
     for dom in (0, 1):                                    # csrc/flow32.hip, compiler-managed LDS reads
-        for jac, fused, split in ((0, 0, 1), (1, 0, 1), (1, 1, 1), (0, 0, 0)):   # <DOMAIN, JAC, FUSED, SPLIT>; (0, 0, 0): precision f16, samples-only
+        for jac, fused, split in ((0, 0, 1), (1, 0, 1), (1, 1, 1), (0, 0, 0)):   # <DOMAIN, JAC, FUSED, SPLIT, ROP = -1>; (0, 0, 0): precision f16, samples-only
             # "sel": destination-select writes (the packed-fp16 sigmoids' SDWA halves, BSDFD_PK4_TRANS: 2 x 4 per fragment, one
             # fragment per 8 units) the forwarding-hazard check must see: 2 (3) hidden layers in front of the last one x 2 fragments
-            out[f"flow_kernel32ILi{dom}ELb{jac}ELb{fused}ELb{split}EE"] = {"async": 0, "waits": 0, "sel": 0 if split else (32, 48)[dom]}
+            out[f"flow_kernel32ILi{dom}ELb{jac}ELb{fused}ELb{split}ELin1EE"] = {"async": 0, "waits": 0, "sel": 0 if split else (32, 48)[dom]}
     out["flow_kernel32wE"] = {"async": 0, "waits": 0, "sel": 160}   # the 64 x 6 fp16 teacher on 32-query tiles: 5 layers x 4 fragments
     out["flow_kernel32cE"] = {"async": 0, "waits": 0}               # the 64 x 6 split3 net with the Jacobian on 32-query tiles (round 6)
     return out
+
+
+RESIDENT_OF = "flow_kernel32ILi0ELb1ELb0ELb1ELin1EE"   # the general disk kernel with the Jacobian ...
+
+
+def resident_flow_kernels() -> Dict[str, Dict[str, int]]:
+    """... and its two register-resident fast-path instantiations (ROP = OP_SAMPLE, OP_PDF; csrc/flow32.hip): they come out of the
+    same template in the same translation unit, so the census holds them to the same terms wherever it finds RESIDENT_OF."""
+    return {f"flow_kernel32ILi0ELb1ELb0ELb1ELi{rop}EE": {"async": 0, "waits": 0, "sel": 0} for rop in (0, 1)}
 
 
 def census_lines(lines: List[str], fragment: str = "flow_kernel") -> Dict[str, Dict[str, int]]:
@@ -331,6 +340,8 @@ def verify_census(asm_paths: List[str], variant: str = "async", allow_scratch: b
     for path in asm_paths:
         found.update(census_lines(open(path).read().splitlines()))
     expected = {f: v for f, v in expected_flow_kernels(variant).items() if only is None or f.startswith(only)}
+    if any(RESIDENT_OF in k for k in found):
+        expected.update({f: v for f, v in resident_flow_kernels().items() if only is None or f.startswith(only)})
     problems = []
     by_frag = {}
     for k, c in found.items():

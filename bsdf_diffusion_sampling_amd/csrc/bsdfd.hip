@@ -1202,19 +1202,23 @@ int bsdfd_fail_(int code, const std::string& msg) {
 struct bsdfd_ctx {
     int domain, width, n_hidden, precision, state_dim, in_dim;
     int device, num_cu;
-    int per_cu[3];  // resident blocks per CU of the (no-Jacobian, Jacobian, Jacobian + fused sample/pdf) kernels
-    const void* kfun[3];
+    // launch slots: 0 .. 2 = the (no-Jacobian, Jacobian, Jacobian + fused sample/pdf) kernels of every call form; KF_RESIDENT + op =
+    // the register-resident fast path of the plain plugin sample / pdf call (flow32.hip, flow_kernel32<.., ROP>; kfun = nullptr
+    // where the net has none), chosen per call by run()
+    static constexpr int KF_RESIDENT = 3, NKF = 5;
+    int per_cu[NKF];  // resident blocks per CU
+    const void* kfun[NKF];
     ImgLayout L;
     char* d_img;
     // 32-query-tile kernels (flow32.hip): which modes run them, and their weight image.  tile[m] = queries per wave tile of
     // mode m's kernel (16 | 32), img_of[m] / img_bytes[m] = the image that kernel reads (= its dynamic LDS)
     char* d_img32;
     int ctx_v4_32;   // f32x4 records per 32-query tile of the per-query context (bsdfd_tile32_context_v4)
-    int tile[3];
-    const char* img_of[3];
-    int img_bytes[3];
-    int lds_bytes[3];   // dynamic LDS of mode m's kernel (>= img_bytes[m])
-    int threads[3];     // workgroup size of mode m's kernel
+    int tile[NKF];
+    const char* img_of[NKF];
+    int img_bytes[NKF];
+    int lds_bytes[NKF];   // dynamic LDS of slot m's kernel (>= img_bytes[m])
+    int threads[NKF];     // workgroup size of slot m's kernel
     // profiling: a ring of HIP event pairs recorded on the launch stream around every launch.  Everything
     // above this line is immutable after create; the profiling state below is guarded by `prof_mu`, so the
     // handle stays re-entrant across host threads / streams with profiling on (launches that are being timed
@@ -1228,9 +1232,9 @@ struct bsdfd_ctx {
     long long n_done;      // launches harvested
     double total_ms;
     float last_ms;
-    int op_of[RING];       // which operation a recorded launch ran (OP_*): the per-operation totals of bsdfd_profile_read_op
-    long long n_op[4];
-    double ms_op[4];
+    int op_of[RING];       // which operation a recorded launch ran (OP_*, + BSDFD_OP_RESIDENT on the fast path): the per-operation
+    long long n_op[8];     // totals of bsdfd_profile_read_op ([op]: every launch of the operation, [BSDFD_OP_RESIDENT + op]: the
+    double ms_op[8];       // fast-path launches among them)
     unsigned long long* d_clk;  // CLK_SLOTS x 8 cumulative counters (KParams::clk), zeroed by bsdfd_set_profiling — NOT per launch: a memset in
                                 // front of every profiled launch would put an inter-kernel boundary inside the event bracket
     double wall_khz;            // rate of the wall clock (hipDeviceAttributeWallClockRate)
@@ -1491,8 +1495,16 @@ hipError_t harvest(bsdfd_handle h, int slot) {
     h->n_done++;
     h->n_op[h->op_of[slot] & 3]++;
     h->ms_op[h->op_of[slot] & 3] += ms;
+    if (h->op_of[slot] & BSDFD_OP_RESIDENT) {
+        h->n_op[h->op_of[slot] & 7]++;
+        h->ms_op[h->op_of[slot] & 7] += ms;
+    }
     return hipSuccess;
 }
+
+#ifndef BSDFD_T32_RESIDENT_MIN_T
+#define BSDFD_T32_RESIDENT_MIN_T 8   // least T at which run() takes the register-resident fast path (A/B builds: 0 = never)
+#endif
 
 struct SegHost {
     bsdfd_handle h;
@@ -1561,15 +1573,24 @@ int run(bsdfd_handle h, int op, int io, const float* in_a, const float* in_b, ui
     // all four are rejected for OP_SAMPLES_ONLY above and below — keep it that way if that validation is ever relaxed
     if (mode == 0 && (segs || ctx.out || ctx.in || ctx.rng_index || ctx.row_index))
         return fail(BSDFD_EINVAL, "flow_samples_only takes no segments, per-query context, rng_index or row_index");
-    const int threads = h->threads[mode];
+    // The register-resident fast path (flow32.hip) serves exactly one call form: a single-material plugin sample / pdf of the
+    // measured variant with nothing optional — no context, no index arrays (an `active` mask arrives as a row_index), no injected
+    // base point — at T a power of two >= BSDFD_T32_RESIDENT_MIN_T, the step counts it is tested bit for bit against the general
+    // kernel at (measurements: DESIGN.md §4.3, profiles/r07_ab/disk_resident_path.txt).  Everything else: the general kernel.
+    int kf = mode;
+    if (BSDFD_T32_RESIDENT_MIN_T > 0 && mode == 1 && (op == OP_SAMPLE || op == OP_PDF) && h->kfun[bsdfd_ctx::KF_RESIDENT + op] &&
+        io == IO_PLUGIN && !segs && !ctx.out && !ctx.in && !ctx.rng_index && !ctx.row_index && (op == OP_PDF || !in_b) &&
+        T >= BSDFD_T32_RESIDENT_MIN_T && (T & (T - 1)) == 0)
+        kf = bsdfd_ctx::KF_RESIDENT + op;
+    const int threads = h->threads[kf];
     const int waves = threads / 64;
     // grid: 4 rounds of the resident capacity (blocks per CU from the occupancy query of the
     // instantiated kernel: VGPR- or LDS-limited); block-granular dynamic balancing measured ~4 %
     // faster than an exactly-resident persistent grid (tools/tscan.py sweep)
-    kp.img = h->img_of[mode];
-    kp.L.total = h->img_bytes[mode];
-    const int tile = h->tile[mode];
-    int per_cu = h->per_cu[mode];
+    kp.img = h->img_of[kf];
+    kp.L.total = h->img_bytes[kf];
+    const int tile = h->tile[kf];
+    int per_cu = h->per_cu[kf];
     if (per_cu < 1) per_cu = 1;
     // grid-shape overrides of the tools builds (tools/tuning_knobs.h, force-included by tools/ab_build.sh for tools/tscan.py
     // and tools/nscan.py); the product build has none
@@ -1633,13 +1654,13 @@ int run(bsdfd_handle h, int op, int io, const float* in_a, const float* in_b, ui
             HIP_TRY(hipEventRecord(h->ev0[slot], s));
         }
     }
-    hipError_t e = hipLaunchKernel(h->kfun[mode], grid, block, args, (size_t)h->lds_bytes[mode] + lds_pad(), s);
+    hipError_t e = hipLaunchKernel(h->kfun[kf], grid, block, args, (size_t)h->lds_bytes[kf] + lds_pad(), s);
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return fail(BSDFD_EHIP, std::string("kernel launch: ") + hipGetErrorString(e));
     if (slot >= 0) {
         HIP_TRY(hipEventRecord(h->ev1[slot], s));
         h->pending[slot] = true;
-        h->op_of[slot] = op;
+        h->op_of[slot] = op | (kf >= bsdfd_ctx::KF_RESIDENT ? BSDFD_OP_RESIDENT : 0);
         h->n_rec++;
     }
     return BSDFD_OK;
@@ -1714,7 +1735,7 @@ int bsdfd_create(const bsdfd_desc* d, bsdfd_handle* out) {
     h->device = dev; h->num_cu = prop.multiProcessorCount;
     h->profiling = false; h->d_img = nullptr; h->d_img32 = nullptr; h->d_clk = nullptr;
     h->n_rec = h->n_done = 0; h->total_ms = 0.0; h->last_ms = -1.0f;
-    for (int i = 0; i < 4; ++i) { h->n_op[i] = 0; h->ms_op[i] = 0.0; }
+    for (int i = 0; i < 8; ++i) { h->n_op[i] = 0; h->ms_op[i] = 0.0; }
     {
         int khz = 0;
         h->wall_khz = hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) == hipSuccess ? (double)khz : 0.0;
@@ -1738,9 +1759,10 @@ int bsdfd_create(const bsdfd_desc* d, bsdfd_handle* out) {
     const int want_tile = d->tile == 0 ? kDefaultTile : d->tile;
     const bool t32 = want_tile == 32 && bsdfd_tile32_supported(*d, prec);
     h->ctx_v4_32 = bsdfd_tile32_context_v4(*d, prec);
-    for (int m = 0; m < 3; ++m) {
+    for (int m = 0; m < bsdfd_ctx::NKF; ++m) {
         h->tile[m] = 16; h->img_of[m] = h->d_img; h->img_bytes[m] = h->lds_bytes[m] = h->L.total;
         h->threads[m] = threads_for(h->width / 16);
+        h->kfun[m] = nullptr; h->per_cu[m] = 0;
     }
     if (t32 && e == hipSuccess) {
         const std::vector<char> img32 = bsdfd_build_image32(*d, prec);
@@ -1752,6 +1774,13 @@ int bsdfd_create(const bsdfd_desc* d, bsdfd_handle* out) {
                 h->lds_bytes[m] = bsdfd_kernel32_lds_bytes(*d, prec, m);
                 h->threads[m] = bsdfd_kernel32_threads(*d, prec, m);
             }
+        // the fast path rides on mode 1's 32-query tiling: same image, same LDS, same workgroup size — its own kernel and occupancy
+        for (int op = OP_SAMPLE; op <= OP_PDF && h->tile[1] == 32; ++op)
+            if (const void* kr = bsdfd_kernel32_resident(*d, prec, op)) {
+                const int m = bsdfd_ctx::KF_RESIDENT + op;
+                h->kfun[m] = kr; h->tile[m] = 32; h->img_of[m] = h->d_img32; h->img_bytes[m] = (int)img32.size();
+                h->lds_bytes[m] = h->lds_bytes[1]; h->threads[m] = h->threads[1];
+            }
     }
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&h->d_clk), (size_t)CLK_SLOTS * 8 * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemset(h->d_clk, 0, (size_t)CLK_SLOTS * 8 * sizeof(unsigned long long));
@@ -1759,8 +1788,9 @@ int bsdfd_create(const bsdfd_desc* d, bsdfd_handle* out) {
         e = hipEventCreate(&h->ev0[i]);
         if (e == hipSuccess) e = hipEventCreate(&h->ev1[i]);
     }
-    for (int jac = 0; jac < 3 && e == hipSuccess; ++jac) {
-        h->kfun[jac] = h->tile[jac] == 32 ? bsdfd_kernel32(*d, prec, jac) : kernel_ptr(h->domain, h->width / 16, h->n_hidden, prec, jac);
+    for (int jac = 0; jac < bsdfd_ctx::NKF && e == hipSuccess; ++jac) {
+        if (jac < 3) h->kfun[jac] = h->tile[jac] == 32 ? bsdfd_kernel32(*d, prec, jac) : kernel_ptr(h->domain, h->width / 16, h->n_hidden, prec, jac);
+        else if (!h->kfun[jac]) continue;
         // dynamic LDS above the default cap needs the attribute (per function and device)
         e = hipFuncSetAttribute(h->kfun[jac], hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes[jac] + (int)lds_pad());
         int nb = 0;
@@ -1993,7 +2023,7 @@ int bsdfd_set_profiling(bsdfd_handle h, int32_t enable) {
     h->n_rec = h->n_done = 0;
     h->total_ms = 0.0;
     h->last_ms = -1.0f;
-    for (int i = 0; i < 4; ++i) { h->n_op[i] = 0; h->ms_op[i] = 0.0; }
+    for (int i = 0; i < 8; ++i) { h->n_op[i] = 0; h->ms_op[i] = 0.0; }
     HIP_TRY(hipMemset(h->d_clk, 0, (size_t)CLK_SLOTS * 8 * sizeof(unsigned long long)));  // (every pending launch was harvested above: nothing is in flight)
     // the memset runs on the legacy stream and is asynchronous to the host: a profiled launch issued right behind this call on a
     // NON-BLOCKING stream (torch side streams, the WavefrontPipeline streams) is not ordered behind it and its counters could be
@@ -2016,7 +2046,8 @@ int bsdfd_profile_read(bsdfd_handle h, int64_t* n_launches, double* total_ms) {
 }
 
 int bsdfd_profile_read_op(bsdfd_handle h, int32_t op, int64_t* n_launches, double* total_ms) {
-    if (op < 0 || op > 3) return fail(BSDFD_EINVAL, "op must be one of BSDFD_OP_SAMPLE, _PDF, _SAMPLES_ONLY, _SAMPLE_PDF");
+    if (op < 0 || op > BSDFD_OP_RESIDENT + OP_PDF)
+        return fail(BSDFD_EINVAL, "op must be one of BSDFD_OP_SAMPLE, _PDF, _SAMPLES_ONLY, _SAMPLE_PDF, or BSDFD_OP_RESIDENT + _SAMPLE / _PDF");
     int rc = bsdfd_profile_read(h, nullptr, nullptr);
     if (rc != BSDFD_OK) return rc;
     std::lock_guard<std::mutex> lock(h->prof_mu);

@@ -13,6 +13,9 @@ std::vector<char> bsdfd_build_image32(const bsdfd_desc& d, int prec);
 // mode 0: no Jacobian (flow_samples_only), 1: Jacobian (network_sampling / network_pdf / plugin sample / plugin pdf), 2: fused
 // sample+pdf; nullptr = no such kernel for this net / precision (the 16-query-tile kernel of csrc/bsdfd.hip serves the mode)
 const void* bsdfd_kernel32(const bsdfd_desc& d, int prec, int mode);
+// the register-resident fast path of the plain plugin sample / pdf call (op = OP_SAMPLE | OP_PDF) of this net, or nullptr: the disk
+// 25-32x3-2 net in split3.  Same image, LDS bytes and workgroup size as bsdfd_kernel32(d, prec, 1); 2 waves per SIMD.
+const void* bsdfd_kernel32_resident(const bsdfd_desc& d, int prec, int op);
 // true for a kernel that serves the mode only when the caller asked for 32-query tiles EXPLICITLY (bsdfd_desc.tile = 32), not under
 // the library's default: the 64 x 6 Jacobian kernel, which measured slower than its 16-query counterpart
 bool bsdfd_kernel32_opt_in(const bsdfd_desc& d, int prec, int mode);

@@ -24,7 +24,8 @@
 //   * per-tile prologue: lane h encodes dimension h of omega_i (5 sincos), the conditioning term is 6 split-fp16 MFMAs (disk) or
 //     11 exact-fp32 v_mfma_f32_32x32x2_f32 (spherical), the base net's first layer 4 split-fp16 MFMAs (all four products), its
 //     second layer fp32 VALU.
-//   * 3 waves per SIMD (2 for the fused spherical kernel); no kernel uses scratch: the lane number is re-derived per tile and the
+//   * 3 waves per SIMD (2 for the fused spherical kernel and for the register-resident fast path of the disk net's plain plugin
+//     sample / pdf call, which keeps the step's weight fragments in registers: flow_kernel32<.., ROP>); no kernel uses scratch: the lane number is re-derived per tile and the
 //     query's row after the Euler loop instead of being carried across it.
 // Same operators, same plugin variants, same context / rng_index / segmented-launch semantics as the 16-query kernels; the base
 // draws are bit-identical to theirs (same Philox counters, same arithmetic).
@@ -161,6 +162,13 @@ __device__ __forceinline__ void act_pack16(const f32x16& z, Frag (&hi)[2]) {
     }
 }
 
+// a a + b b with both squares rounded (no fma contraction)
+__device__ __forceinline__ float sum_sq_unfused(float a, float b) {
+#pragma clang fp contract(off)
+    const float aa = a * a, bb = b * b;
+    return aa + bb;
+}
+
 // one 32 x 32 matrix = 4 fragments (hi chunk 0, hi chunk 1, lo chunk 0, lo chunk 1)
 struct Mat32 {
     f16x8 h0, h1, l0, l1;
@@ -257,10 +265,20 @@ __device__ __forceinline__ float von_mises_sample32(float mu, float kappa, unsig
 // contractions (precision split3) — false: single fp16 products (precision f16; instantiated without the Jacobian only: the reflow
 // teacher sampling of the 32-wide nets, learning_repo_cleanup/disk_domain_sampling.py:93-110).
 // Per lane the step keeps 16-register vectors where the 16-query kernels keep 8; BSDFD_T32_WAVES = 3 waves per SIMD (168 VGPRs).
+//
+// ROP >= 0: the REGISTER-RESIDENT fast path — the same statements for the one call form the
+// plugins make: the disk net, split3 with the Jacobian, op = ROP (OP_SAMPLE | OP_PDF) and io = IO_PLUGIN as compile-time constants,
+// no segments, no context, no row_index / rng_index, no injected base point, T a power of two.  At 2 waves per SIMD (256 VGPRs) the
+// 24 hidden-layer fragments and the layer-1 fragment are read from LDS ONCE per workgroup and stay in registers across every tile and
+// Euler step; WOUT, the conditioning matrix and the base net stay in LDS.  The host (bsdfd.hip, run()) selects it; every other call
+// form runs the general kernel (ROP = -1), whose code this parameter does not touch.
 // ---------------------------------------------------------------------------------------------
-template <int DOMAIN, bool JAC, bool FUSED, bool SPLIT>
-__global__ __launch_bounds__(256, (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? BSDFD_T32_FUSED_SPH_WAVES : BSDFD_T32_WAVES) void flow_kernel32(const KParams p) {
+template <int DOMAIN, bool JAC, bool FUSED, bool SPLIT, int ROP = -1>
+__global__ __launch_bounds__(256, ROP >= 0 ? 2 : (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? BSDFD_T32_FUSED_SPH_WAVES : BSDFD_T32_WAVES) void flow_kernel32(const KParams p) {
     static_assert(SPLIT || !JAC, "the single-product (f16) instantiations exist without the Jacobian only");
+    constexpr bool RES = ROP >= 0;
+    static_assert(!RES || (DOMAIN == BSDFD_DOMAIN_DISK && JAC && !FUSED && SPLIT && (ROP == OP_SAMPLE || ROP == OP_PDF)),
+                  "the resident fast path serves the disk net's plugin sample / pdf calls only");
     using LY = L32<DOMAIN>;
     constexpr bool SPH = DOMAIN == BSDFD_DOMAIN_SPHERICAL;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -270,7 +288,7 @@ __global__ __launch_bounds__(256, (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? 
     long long q_begin = 0, q_end = p.N;
     int blk = blockIdx.x, nblk = gridDim.x, cl = p.chunk_log2;
     int sidx = 0;
-    if (p.nseg > 0) {
+    if (!RES && p.nseg > 0) {
         for (int i = 1; i < p.nseg; ++i)
             if ((int)blockIdx.x >= p.seg[i].blk_begin) sidx = i;
         img = p.seg[sidx].img;
@@ -288,6 +306,21 @@ __global__ __launch_bounds__(256, (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? 
     __syncthreads();
 
     const int lane0 = threadIdx.x & 63;
+    // what the general kernel reads from the launch parameters per call, the fast path knows at compile time
+    auto kop = [&]() -> int { if constexpr (RES) return ROP; else return p.op; };
+    auto kio = [&]() -> int { if constexpr (RES) return IO_PLUGIN; else return p.io; };
+    // RES: the step's weight fragments, read once per workgroup (W2, W3, F0, F1, G0, G1 and the layer-1 state fragment)
+    Mat32 rW2, rW3, rF0, rF1, rG0, rG1;
+    f16x8 rA1;
+    if constexpr (RES) {
+        rA1 = *(reinterpret_cast<const f16x8*>(smem + LY::A1) + lane0);
+        rW2 = load_mat(smem, LY::WH, lane0);
+        rW3 = load_mat(smem, LY::WH + 4 * FR32, lane0);
+        rF0 = load_mat(smem, LY::WF, lane0);
+        rF1 = load_mat(smem, LY::WF + 4 * FR32, lane0);
+        rG0 = load_mat(smem, LY::WG, lane0);
+        rG1 = load_mat(smem, LY::WG + 4 * FR32, lane0);
+    }
     const int wave = threadIdx.x >> 6;
     const int waves_per_block = blockDim.x >> 6;
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -301,10 +334,10 @@ __global__ __launch_bounds__(256, (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? 
         return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
     };
     const double invT_d = uniform_d(1.0 / (double)p.T);
-    const bool t_pow2 = (p.T & (p.T - 1)) == 0;
+    const bool t_pow2 = RES || (p.T & (p.T - 1)) == 0;
     const float invT = uniform_f((float)invT_d);
     const int nphase = FUSED ? 2 : 1;
-    const bool reverse1 = (p.op == OP_PDF);
+    const bool reverse1 = (kop() == OP_PDF);
     const float cstep1 = reverse1 ? -invT : invT;
     const long long ntiles = (q_end - q_begin + 31) / 32;
 
@@ -335,7 +368,7 @@ __global__ __launch_bounds__(256, (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? 
         const long long qi = row_of(n, in_range0);
         // row of the callers' arrays this query reads and writes (bsdfd_opts.row_index: a bucketed wavefront hands over the bucket
         // permutation instead of gathered copies); re-read in the epilogue rather than carried across the Euler loop
-        auto user_row = [&](long long r) -> long long { return p.row_index ? p.row_index[r] : r; };
+        auto user_row = [&](long long r) -> long long { return (!RES && p.row_index) ? p.row_index[r] : r; };
         const long long qu = user_row(qi);
 
         // ---------------- inputs ---------------------------------------------------------------------
@@ -346,7 +379,7 @@ __global__ __launch_bounds__(256, (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? 
         float xo0 = 0.f, xo1 = 0.f;   // both coordinates of an injected / asked point (base density, epilogue)
         bool wo_pole = false;
         float xi0 = 0.f, xi1 = 0.f;   // FUSED: injected x0
-        const bool have_ctx = !FUSED && p.ctx_in != nullptr;
+        const bool have_ctx = !RES && !FUSED && p.ctx_in != nullptr;
         auto load_dir = [&](const float* dir, long long qi) {   // plugin io: the direction whose pdf is asked -> start point of the reverse flow
             const float ox = dir[qi * 3 + 0], oy = dir[qi * 3 + 1], oz = dir[qi * 3 + 2];
             wo_z = oz;
@@ -362,10 +395,10 @@ __global__ __launch_bounds__(256, (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? 
 #endif
             }
         };
-        if (p.io == IO_OPERATOR) {
+        if (kio() == IO_OPERATOR) {
             const float2 c2 = reinterpret_cast<const float2*>(p.in_a)[qi];
             yh = h ? c2.y : c2.x;
-            if (p.op == OP_PDF || p.in_b != nullptr) {
+            if (kop() == OP_PDF || p.in_b != nullptr) {
                 const float2 b2 = reinterpret_cast<const float2*>(p.in_b)[qi];
                 xs = h ? b2.y : b2.x;
                 xo0 = b2.x; xo1 = b2.y;
@@ -382,8 +415,8 @@ __global__ __launch_bounds__(256, (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? 
                 if (!h) yh = ai.theta_ref;
 #endif
             }
-            if (!FUSED && p.op == OP_PDF) load_dir(p.in_b, qu);
-            if ((FUSED || p.op != OP_PDF) && p.in_b != nullptr) {  // injected base sample
+            if (!FUSED && kop() == OP_PDF) load_dir(p.in_b, qu);
+            if (!RES && (FUSED || kop() != OP_PDF) && p.in_b != nullptr) {  // injected base sample
                 const float2 b2 = reinterpret_cast<const float2*>(p.in_b)[qu];
                 if (FUSED) { xi0 = b2.x; xi1 = b2.y; } else { xs = h ? b2.y : b2.x; xo0 = b2.x; xo1 = b2.y; }
             }
@@ -474,7 +507,7 @@ __global__ __launch_bounds__(256, (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? 
                 const f32x4 b2 = *reinterpret_cast<const f32x4*>(smem + LY::BB2);
                 bo = (f32x4){a0 + b2[0], a1 + b2[1], a2 + b2[2], a3 + b2[3]};
             }
-            if (!FUSED && p.ctx_out != nullptr) {
+            if (!RES && !FUSED && p.ctx_out != nullptr) {
                 f32x4* c = reinterpret_cast<f32x4*>(p.ctx_out) + ctx_slot * CTX_V4;
 #pragma unroll
                 for (int k = 0; k < 4; ++k) c[k * 64 + lane] = (f32x4){cacc[4 * k], cacc[4 * k + 1], cacc[4 * k + 2], cacc[4 * k + 3]};
@@ -492,7 +525,7 @@ __global__ __launch_bounds__(256, (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? 
         int ph = 0;
     next_phase:
         {
-        const int op = FUSED ? (ph ? OP_PDF : OP_SAMPLE) : p.op;
+        const int op = FUSED ? (ph ? OP_PDF : OP_SAMPLE) : kop();
         const bool reverse = FUSED ? (ph != 0) : reverse1;
         const float cstep = FUSED ? (ph ? -invT : invT) : cstep1;
         float* const out_pdf = (FUSED && ph) ? p.out_pdf2 : p.out_pdf;
@@ -503,8 +536,8 @@ __global__ __launch_bounds__(256, (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? 
         if (FUSED && !ph) { xs = h ? xi1 : xi0; xo0 = xi0; xo1 = xi1; }
         // ---------------- initial state ------------------------------------------------------------
         auto fexp = [](float x) -> float { return __builtin_amdgcn_exp2f(x * kLog2e); };
-        if (op == OP_SAMPLE && p.in_b == nullptr) {  // draw x0 ~ D_base(. | omega_i): same counters and arithmetic as bsdfd.hip
-            const unsigned long long ctr = p.offset + (unsigned long long)(p.rng_index ? p.rng_index[qi] : qu);
+        if (op == OP_SAMPLE && (RES || p.in_b == nullptr)) {  // draw x0 ~ D_base(. | omega_i): same counters and arithmetic as bsdfd.hip
+            const unsigned long long ctr = p.offset + (unsigned long long)((!RES && p.rng_index) ? p.rng_index[qi] : qu);
             const unsigned k0 = (unsigned)p.seed, k1 = (unsigned)(p.seed >> 32);
             unsigned u[4];
             philox4x32(k0, k1, (unsigned)ctr, (unsigned)(ctr >> 32), 0u, 0x476175u, u);  // "Gau"
@@ -525,6 +558,9 @@ __global__ __launch_bounds__(256, (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? 
             if (!SPH) {  // model.py:393-398
                 const float e0 = (a0 - bo[0]) * fexp(-bo[2]);
                 const float e1 = (a1 - bo[1]) * fexp(-bo[3]);
+                // (which products of this expression are fused is the compiler's choice per instantiation; the fast path spells out
+                //  the general kernel's: two rounded squares, their sum, one fma — its results are held to that kernel's bit for bit)
+                if constexpr (RES) return fexp(__builtin_fmaf(-0.5f, sum_sq_unfused(e0, e1), -log2pi - (bo[2] + bo[3])));
                 return fexp(-log2pi - (bo[2] + bo[3]) - 0.5f * (e0 * e0 + e1 * e1));
             } else {     // model.py:308-317
                 const float e = (a0 - bo[0]) * __builtin_amdgcn_rcpf(fexp(bo[1]) + 1e-3f);
@@ -563,7 +599,14 @@ __global__ __launch_bounds__(256, (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? 
             const f16x2 vp = {(_Float16)vh, (_Float16)(vin - vh)}, wp = {(_Float16)wh, (_Float16)(win - wh)};
             Frag b1;
             b1.p[0] = vp; b1.p[1] = vp; b1.p[2] = wp; b1.p[3] = wp;
-            const f16x8 a1 = *(reinterpret_cast<const f16x8*>(smem + LY::A1) + lane);
+            // a step's matrix: the resident copy (RES) or a fresh read of the image in LDS
+            auto mat = [&](const Mat32& r, int off) -> Mat32 {
+                if constexpr (RES) return r;
+                else return load_mat(smem, off, lane);
+            };
+            f16x8 a1;
+            if constexpr (RES) a1 = rA1;
+            else a1 = *(reinterpret_cast<const f16x8*>(smem + LY::A1) + lane);
             f32x16 cin = cacc;
             if constexpr (CaccLds<DOMAIN, FUSED>::on) {
 #pragma unroll
@@ -587,15 +630,15 @@ __global__ __launch_bounds__(256, (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? 
                 // ---- MIM, disk 25-32-32-32-2: U_i = F_i g1, R_j = G_j g3, J_ji = sum_k R_j[k] g2[k] U_i[k] (bsdfd.hip, block MIM)
                 if constexpr (SPLIT) { act16<JAC>(z, hv, gv); split16(hv, bh, bl); }
                 else act_pack16(z, bh);
-                z = mm6<SPLIT>(load_mat(smem, LY::WH, lane), bh, bl);
+                z = mm6<SPLIT>(mat(rW2, LY::WH), bh, bl);
                 if constexpr (JAC) {
                     split16_jac(gv, gh, gl);
-                    mm6x2(load_mat(smem, LY::WF, lane), gh, gl, load_mat(smem, LY::WF + 4 * FR32, lane), gh, gl, U0, U1);
+                    mm6x2(mat(rF0, LY::WF), gh, gl, mat(rF1, LY::WF + 4 * FR32), gh, gl, U0, U1);
                 }
                 // hidden layer 2 (its silu' stays in fp32)
                 if constexpr (SPLIT) { act16<JAC>(z, hv, gm); if constexpr (JAC) premul(); split16(hv, bh, bl); }
                 else act_pack16(z, bh);
-                z = mm6<SPLIT>(load_mat(smem, LY::WH + 4 * FR32, lane), bh, bl);
+                z = mm6<SPLIT>(mat(rW3, LY::WH + 4 * FR32), bh, bl);
             } else {
                 // ---- MIMS, spherical 26-32-32-32-32-2: two forward-mode tangent layers, then the output fold (bsdfd.hip, block MIMS)
                 f32x16 zt0, zt1;
@@ -648,7 +691,7 @@ __global__ __launch_bounds__(256, (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? 
             f32x16 R0, R1;
             if constexpr (JAC) {
                 split16_jac(gv, gh, gl);
-                mm6x2(load_mat(smem, LY::WG, lane), gh, gl, load_mat(smem, LY::WG + 4 * FR32, lane), gh, gl, R0, R1);
+                mm6x2(mat(rG0, LY::WG), gh, gl, mat(rG1, LY::WG + 4 * FR32), gh, gl, R0, R1);
             }
             {
                 const f32x4* Lwo = reinterpret_cast<const f32x4*>(smem + LY::WOUT + h * 128);
@@ -699,9 +742,9 @@ __global__ __launch_bounds__(256, (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? 
 
         bool valid_e;
         const long long qe_tile = row_of(opaque(n), valid_e);
-        const long long qe = p.io == IO_OPERATOR ? qe_tile : user_row(qe_tile);
+        const long long qe = kio() == IO_OPERATOR ? qe_tile : user_row(qe_tile);
         const bool writer = valid_e && h == 0;
-        if (p.io == IO_OPERATOR) {
+        if (kio() == IO_OPERATOR) {
             if (writer) {
                 if (op != OP_PDF) reinterpret_cast<float2*>(p.out_x)[qe] = make_float2(x0, x1);
                 if (op != OP_SAMPLES_ONLY) out_pdf[qe] = pdf;
@@ -719,7 +762,7 @@ __global__ __launch_bounds__(256, (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? 
                 sincos_enc(x0, st, ct);
                 sincos_enc(x1, sp, cp);
                 if (!(st > 0.00005f)) pdf = 0.0f;
-                if (p.io == IO_PLUGIN && !(ct > 0.0f)) pdf = 0.0f;
+                if (kio() == IO_PLUGIN && !(ct > 0.0f)) pdf = 0.0f;
                 ox = cp * st; oy = sp * st; oz = ct;
                 const float inv = fminf(fmaxf(1.0f / sqrtf(ox * ox + oy * oy), 1.0f), 3.402823466e+38f);
                 pdf_sa = pdf * inv;
@@ -734,7 +777,7 @@ __global__ __launch_bounds__(256, (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? 
                 pdf_sa = (wi_z > 0.0f && wo_z > 0.0f) ? pdf * wo_z : 0.0f;
             } else {
                 const float inv = fminf(fmaxf(1.0f / wo_sin, 1.0f), 3.402823466e+38f);
-                if (p.io == IO_PLUGIN) {  // rendering/brdf_measured_spherical.py:122-137
+                if (kio() == IO_PLUGIN) {  // rendering/brdf_measured_spherical.py:122-137
                     if (wo_pole) pdf = 0.0f;
                     pdf_sa = (wi_z > 0.0f && wo_z > 0.0f) ? pdf * inv : 0.0f;
                 } else {                  // rendering/bsdf_myresult.py:115-133
@@ -1558,6 +1601,13 @@ int bsdfd_kernel32_lds_bytes(const bsdfd_desc& d, int prec, int mode) {
 int bsdfd_kernel32_threads(const bsdfd_desc& d, int prec, int mode) {
     const int kind = kind32(d, prec, mode);
     return (kind == 2 || kind == 4) ? 512 : 256;
+}
+
+const void* bsdfd_kernel32_resident(const bsdfd_desc& d, int prec, int op) {
+    if (kind32(d, prec, 1) != 1 || d.domain != BSDFD_DOMAIN_DISK) return nullptr;
+    if (op == OP_SAMPLE) return reinterpret_cast<const void*>(flow_kernel32<BSDFD_DOMAIN_DISK, true, false, true, OP_SAMPLE>);
+    if (op == OP_PDF) return reinterpret_cast<const void*>(flow_kernel32<BSDFD_DOMAIN_DISK, true, false, true, OP_PDF>);
+    return nullptr;
 }
 
 const void* bsdfd_kernel32(const bsdfd_desc& d, int prec, int mode) {

@@ -180,9 +180,10 @@ class FlowSampler:
 
     def profile_read_op(self, op: str):
         """(launches, total kernel ms) of ONE kind of launch since ``set_profiling(True)``: ``op`` is "sample", "pdf",
-        "samples_only" or "sample_pdf" (bsdfd_profile_read_op)."""
+        "samples_only" or "sample_pdf" (bsdfd_profile_read_op); "sample_resident" / "pdf_resident": those of the sample / pdf
+        launches that ran the register-resident fast-path kernel."""
         n, ms = C.c_int64(), C.c_double()
-        code = {"sample": 0, "pdf": 1, "samples_only": 2, "sample_pdf": 3}[op]
+        code = {"sample": 0, "pdf": 1, "samples_only": 2, "sample_pdf": 3, "sample_resident": 4, "pdf_resident": 5}[op]
         _lib.check(self._L.bsdfd_profile_read_op(self._h, code, C.byref(n), C.byref(ms)))
         return n.value, ms.value
 

@@ -84,6 +84,9 @@ typedef struct bsdfd_ctx* bsdfd_handle;
 #define BSDFD_OP_PDF 1           /* network_pdf, plugin_pdf              */
 #define BSDFD_OP_SAMPLES_ONLY 2  /* flow_samples_only                    */
 #define BSDFD_OP_SAMPLE_PDF 3    /* plugin_sample_pdf                    */
+/* bsdfd_profile_read_op only: BSDFD_OP_RESIDENT + BSDFD_OP_SAMPLE / _PDF = those launches of the operation that ran the
+ * register-resident fast-path kernel (plain single-material plugin sample / pdf of the disk net at T = 8, 16, 32, ...). */
+#define BSDFD_OP_RESIDENT 4
 
 /* Host pointers to fp32 row-major [out, in] matrices exactly as nn.Linear.weight
  * stores them (reference checkpoints: rendering/checkpoints_new/.../brdf_rectify_network*.pth
@@ -279,7 +282,8 @@ int bsdfd_profile_read(bsdfd_handle h, int64_t* n_launches, double* total_ms);
 float bsdfd_last_kernel_ms(bsdfd_handle h);
 /* The same totals for ONE kind of launch (bench.py's sample / pdf split of the timed region itself): `op` is
  * BSDFD_OP_SAMPLE (network_sampling, plugin_sample), BSDFD_OP_PDF (network_pdf, plugin_pdf), BSDFD_OP_SAMPLES_ONLY
- * (flow_samples_only) or BSDFD_OP_SAMPLE_PDF (plugin_sample_pdf).  No counterpart in the reference. */
+ * (flow_samples_only) or BSDFD_OP_SAMPLE_PDF (plugin_sample_pdf); BSDFD_OP_RESIDENT + BSDFD_OP_SAMPLE / _PDF: the part of that
+ * operation's launches which took the fast-path kernel (which kernel a call ran).  No counterpart in the reference. */
 int bsdfd_profile_read_op(bsdfd_handle h, int32_t op, int64_t* n_launches, double* total_ms);
 /* Shader clock (MHz) the chip sustained UNDER THE PROFILED LAUNCHES THEMSELVES: while profiling is enabled every wave adds its
  * lifetime in shader cycles (s_memtime) and in ticks of the constant-rate wall clock (s_memrealtime,

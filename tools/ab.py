@@ -126,6 +126,8 @@ def main():
         plug("disk8", "aniso_miro_7_rgb", "disk", None, 1 << 20, 8)
     if "disk4" in only:
         plug("disk4", "aniso_miro_7_rgb", "disk", None, 1 << 20, 4)
+    if "disk16" in only:
+        plug("disk16", "aniso_miro_7_rgb", "disk", None, 1 << 20, 16)
     if "fused4" in only:  # sample(wi) + pdf(wi, wl) in one launch (the renderer's call pattern), disk T = 4
         fw = W.load(W.shipped_path("aniso_miro_7_rgb", "disk"))
         smp = FlowSampler(fw)

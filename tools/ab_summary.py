@@ -4,7 +4,7 @@ import collections, json, sys
 import numpy as np
 rows = [json.loads(l) for l in open(sys.argv[1]) if l.strip().startswith("{")]
 tags = list(dict.fromkeys(r["tag"] for r in rows))
-keys = [("disk8", "sample_ms"), ("disk8", "pdf_ms"), ("disk4", "sample_ms"), ("disk4", "pdf_ms"), ("sph8", "sample_ms"),
+keys = [("disk8", "sample_ms"), ("disk8", "pdf_ms"), ("disk4", "sample_ms"), ("disk4", "pdf_ms"), ("disk16", "sample_ms"), ("disk16", "pdf_ms"), ("sph8", "sample_ms"),
         ("sph8", "pdf_ms"), ("cplx8", "sample_ms"), ("cplx8", "pdf_ms"), ("teacher", "ms"), ("fused4", "ms"), ("fusedsph8", "ms")]
 keys = [wk for wk in keys if any(wk[0] in r for r in rows)]
 med = collections.defaultdict(dict)

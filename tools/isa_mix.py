@@ -53,9 +53,9 @@ from bsdf_diffusion_sampling_amd._asmcheck import check_async_lines, check_file_
 
 
 KERNEL_OF_WORKLOAD = {  # bench.py workload -> mangled-name fragment of its flow kernel (split3, Jacobian; the library's default tile)
-    "disk_1Mi_T8": "flow_kernel32ILi0ELb1ELb0E",
-    "disk_1Mi_T4": "flow_kernel32ILi0ELb1ELb0E",
-    "spherical_16Mi_T8": "flow_kernel32ILi1ELb1ELb0E",
+    "disk_1Mi_T8": "flow_kernel32ILi0ELb1ELb0ELb1ELi0E",     # T >= 8: the register-resident fast path (ROP = OP_SAMPLE)
+    "disk_1Mi_T4": "flow_kernel32ILi0ELb1ELb0ELb1ELin1E",    # the general kernel (ROP = -1)
+    "spherical_16Mi_T8": "flow_kernel32ILi1ELb1ELb0ELb1ELin1E",
     "teacher_64x6_4Mi_T128": "flow_kernel32wE",
     "teacher_64x6_4Mi_T128@tile16": "flow_kernelILi1ELi4ELi3ELb0ELi6ELb0E",
     "complex64_1Mi_T8": "flow_kernelILi1ELi4ELi2ELb1ELi6ELb0E",
@@ -155,22 +155,30 @@ def main():
             for m in problems[:8]:
                 print("  ", m)
             rc |= bool(problems)
+            # (the two register-resident fast-path instantiations of csrc/flow32.hip are reported on lines of their own)
+            from bsdf_diffusion_sampling_amd._asmcheck import resident_flow_kernels
+            def split_resident(d):
+                res = {k: v for k, v in d.items() if any(f in k for f in resident_flow_kernels())}
+                return {k: v for k, v in d.items() if k not in res}, res
             hz = check_file_mfma(asm)
             hz.update(check_file_mfma(paths["flow32"]))
+            hz, hz_res = split_resident(hz)
             n_bad = sum(1 for _, b in hz.values() if b)
             print(f"MFMA results consumed before their wait states: {n_bad} of {len(hz)} kernels, {sum(n for n, _ in hz.values())} MFMAs checked")
-            for k, (_, b) in hz.items():
+            n_bad_res = sum(1 for _, b in hz_res.values() if b)
+            print(f"  ... and in the resident fast-path kernels: {n_bad_res} of {len(hz_res)}, {sum(n for n, _ in hz_res.values())} MFMAs checked")
+            for k, (_, b) in list(hz.items()) + list(hz_res.items()):
                 for x in b[:2]:
                     print("  ", k, x)
-            rc |= bool(n_bad)
+            rc |= bool(n_bad) or bool(n_bad_res) or len(hz_res) != len(resident_flow_kernels())
             # occupancy of the kernels behind the tracked workloads (waves/SIMD the VGPR allocation allows): a prologue edit shared
             # by all instantiations once took the teacher sampler from 4 to 3 waves unnoticed (round 4, -4 %)
             from bsdf_diffusion_sampling_amd._asmcheck import kernel_meta
             lines = open(asm).read().splitlines() + open(paths["flow32"]).read().splitlines()
-            for name, key, want in (("disk 32x3 split3, 32-query tiles (disk_1Mi_T8 / T4)", "flow_kernel32ILi0ELb1ELb0E", 3),
-                                    ("spherical 32x4 split3, 32-query tiles (spherical_16Mi_T8)", "flow_kernel32ILi1ELb1ELb0E", 3),
-                                    ("disk 32x3 fused sample+pdf, 32-query tiles", "flow_kernel32ILi0ELb1ELb1E", 3),
-                                    ("spherical 32x4 fused sample+pdf, 32-query tiles", "flow_kernel32ILi1ELb1ELb1E", 2),
+            for name, key, want in (("disk 32x3 split3, 32-query tiles, general kernel (disk_1Mi_T4)", "flow_kernel32ILi0ELb1ELb0ELb1ELin1E", 3),
+                                    ("spherical 32x4 split3, 32-query tiles (spherical_16Mi_T8)", "flow_kernel32ILi1ELb1ELb0ELb1ELin1E", 3),
+                                    ("disk 32x3 fused sample+pdf, 32-query tiles", "flow_kernel32ILi0ELb1ELb1ELb1ELin1E", 3),
+                                    ("spherical 32x4 fused sample+pdf, 32-query tiles", "flow_kernel32ILi1ELb1ELb1ELb1ELin1E", 2),
                                     ("disk 32x3 split3, 16-query tiles", "flow_kernelILi0ELi2ELi2ELb1ELi3ELb0E", 3),
                                     ("spherical 32x4 split3, 16-query tiles", "flow_kernelILi1ELi2ELi2ELb1ELi4ELb0E", 3),
                                     ("teacher 64x6 f16, no Jacobian, 32-query tiles", "flow_kernel32wE", 4),
@@ -180,12 +188,20 @@ def main():
                 waves = 8 if v <= 64 else 512 // ((v + 7) // 8 * 8)
                 print(f"occupancy {name}: {v} VGPRs = {waves} waves/SIMD (wanted {want}){'' if waves >= want else '  <-- LOST'}")
                 rc |= waves < want
+            for op, key in (("sample", "flow_kernel32ILi0ELb1ELb0ELb1ELi0E"), ("pdf", "flow_kernel32ILi0ELb1ELb0ELb1ELi1E")):   # disk_1Mi_T8
+                m = kernel_meta(lines, key)
+                v, spill = m.get("vgpr_count", 0), m.get("vgpr_spill_count", -1) + m.get("private_segment_fixed_size", -1)
+                print(f"resident fast path, disk 32x3 plugin {op}: {v} VGPRs (2 waves/SIMD: <= 256), spills + scratch {spill}{'' if 0 < v <= 256 and spill == 0 else '  <-- LOST'}")
+                rc |= not (0 < v <= 256 and spill == 0)
             from bsdf_diffusion_sampling_amd._asmcheck import check_file_swap
             sw = check_file_swap(asm)
             sw.update(check_file_swap(paths["flow32"]))
+            sw, sw_res = split_resident(sw)
             n_bad = sum(1 for _, b in sw.values() if b)
             print(f"lane swaps of a register written fewer than 2 wait states earlier: {n_bad} of {len(sw)} kernels, {sum(n for n, _ in sw.values())} swaps checked")
-            rc |= bool(n_bad)
+            n_bad_res = sum(1 for _, b in sw_res.values() if b)
+            print(f"  ... and in the resident fast-path kernels: {n_bad_res} of {len(sw_res)}, {sum(n for n, _ in sw_res.values())} swaps checked")
+            rc |= bool(n_bad) or bool(n_bad_res)
         return rc
     print(json.dumps(model(sys.argv[1], sys.argv[2]), indent=1))
 
