@@ -15,7 +15,8 @@ DEFAULT_LIB_PATH = os.path.join(_HERE, "libbsdfd.so")
 LIB_PATH = os.environ.get("BSDFD_LIB_PATH") or DEFAULT_LIB_PATH  # override: A/B builds
 SRC_PATH = os.path.join(_HERE, "csrc", "bsdfd.hip")
 SRC32_PATH = os.path.join(_HERE, "csrc", "flow32.hip")   # the 32-query-tile flow kernels
-SRC_PATHS = [SRC_PATH, SRC32_PATH, os.path.join(_HERE, "csrc", "wavefront.hip"), os.path.join(_HERE, "csrc", "pathtrace.hip"),
+HOST_PATH = os.path.join(_HERE, "csrc", "host.hip")      # handle, launch routine and entry points of both kernel families
+SRC_PATHS = [SRC_PATH, SRC32_PATH, HOST_PATH, os.path.join(_HERE, "csrc", "wavefront.hip"), os.path.join(_HERE, "csrc", "pathtrace.hip"),
              os.path.join(_HERE, "csrc", "pathlights.hip"), os.path.join(_HERE, "csrc", "pathenv.hip"),
              os.path.join(_HERE, "csrc", "encoding.hip"),
              os.path.join(_HERE, "csrc", "measured.hip"), os.path.join(_HERE, "csrc", "measured_table.hip"),
@@ -23,7 +24,7 @@ SRC_PATHS = [SRC_PATH, SRC32_PATH, os.path.join(_HERE, "csrc", "wavefront.hip"),
              os.path.join(_HERE, "csrc", "bucket_wide.hip"), os.path.join(_HERE, "csrc", "live.hip"),
              os.path.join(_HERE, "csrc", "clock.hip")]  # translation units of libbsdfd.so
 FLOW_TUS = (SRC_PATH, SRC32_PATH)   # ... whose device assembly the build verifies (_asmcheck)
-DEP_PATHS = SRC_PATHS + [os.path.join(_HERE, "csrc", f) for f in ("common.h", "flow_dev.h", "flow32.h", "bucket_scan.h",
+DEP_PATHS = SRC_PATHS + [os.path.join(_HERE, "csrc", f) for f in ("common.h", "flow_dev.h", "flow_kernels.h", "bucket_scan.h",
                                                                      "measured_dev.h", "wavefront_dev.h", "env_dev.h", "bounce_dev.h")]
 INCLUDE_DIR = os.path.join(ROOT, "include")
 ASM_CACHE_DIR = os.path.join(ROOT, "build", "asm")   # device assembly of the last product build (bsdfd.s, flow32.s)
@@ -111,9 +112,9 @@ KERNEL_SOURCES = (SRC_PATH, SRC32_PATH, os.path.join(_HERE, "csrc", "flow_dev.h"
 
 
 def kernel_source_sha256() -> str:
-    """Fingerprint of the flow kernels' source (csrc/bsdfd.hip, csrc/flow32.hip, csrc/flow_dev.h): the committed profile summaries
-    (HBM traffic from the PMC passes, the instruction-issue model from the ISA) record it; bench.py withholds them and a CPU test
-    fails when the kernels have changed since."""
+    """Fingerprint of the flow kernels' source (csrc/bsdfd.hip, csrc/flow32.hip, csrc/flow_dev.h — they hold no host entry point:
+    that is csrc/host.hip): the committed profile summaries (HBM traffic from the PMC passes, the instruction-issue model from the
+    ISA) record it; bench.py withholds them and a CPU test fails when the kernels have changed since."""
     import hashlib
     h = hashlib.sha256()
     for f in KERNEL_SOURCES:
@@ -226,7 +227,7 @@ def build(force: bool = False, verbose: bool = False, lib_path: str = None) -> s
     info = {"variant": "async", "violations": {}, "hipcc": None, "unverified": False, "compiler_only": False}
     allow_unverified = os.environ.get("BSDFD_ALLOW_UNVERIFIED_BUILD") == "1"
     compiler_only = os.environ.get("BSDFD_COMPILER_ONLY_BUILD") == "1"
-    CO_FLAGS = ["-DBSDFD_NO_ASYNC_LDS", "-DBSDFD_NO_SDWA_PACK", "-DBSDFD_COMPILER_ONLY_BUILD"]
+    CO_FLAGS = ["-DBSDFD_NO_ASYNC_LDS", "-DBSDFD_NO_SDWA_PACK"]   # the flow-kernel units; csrc/host.hip gets the marker
     try:
         v = subprocess.run(["hipcc", "--version"], capture_output=True, text=True)
         info["hipcc"] = next((l.strip() for l in v.stdout.splitlines() if "version" in l.lower()), None)
@@ -234,10 +235,15 @@ def build(force: bool = False, verbose: bool = False, lib_path: str = None) -> s
         pass
     with tempfile.TemporaryDirectory(prefix="bsdfd_build_") as td:
         side, procs = [], []
+
+        def host_cmd(marker):   # csrc/host.hip: bsdfd_version() carries the build's markers — no kernel is recompiled for one
+            return ["hipcc", *HIPCC_FLAGS, *marker, "-I", INCLUDE_DIR, "-c", HOST_PATH, "-o", os.path.join(td, "host.o")]
+
         for src in SRC_PATHS[1:]:   # the other translation units in parallel with csrc/bsdfd.hip (the long one)
             obj = os.path.join(td, os.path.basename(src)[:-4] + ".o")
             side.append(obj)
             cmd = (_flow_tu_cmd(td, src, CO_FLAGS if compiler_only else []) if src in FLOW_TUS
+                   else host_cmd(["-DBSDFD_COMPILER_ONLY_BUILD"] if compiler_only else []) if src == HOST_PATH
                    else ["hipcc", *HIPCC_FLAGS, "-I", INCLUDE_DIR, "-c", src, "-o", obj])
             if verbose:
                 print(" ".join(cmd), flush=True)
@@ -316,8 +322,7 @@ def build(force: bool = False, verbose: bool = False, lib_path: str = None) -> s
                                          "build info and in bsdfd_version()).")
             print("=" * 100 + "\n" + msg + "\nBSDFD_ALLOW_UNVERIFIED_BUILD=1: SHIPPING IT ANYWAY, marked UNVERIFIED\n" + "=" * 100, flush=True)
             info["unverified"] = True
-            extra = ["-DBSDFD_UNVERIFIED_BUILD"] + (["-DBSDFD_NO_ASYNC_LDS"] if info["variant"] == "plain" else [])
-            _compile_flow_tu(td, extra, verbose)   # the marker goes into bsdfd_version()
+            subprocess.run(host_cmd(["-DBSDFD_UNVERIFIED_BUILD"]), check=True, cwd=td)   # the marker goes into bsdfd_version()
         cmd = ["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", os.path.join(td, "bsdfd.o"), *side, "-o", tmp]
         if verbose:
             print(" ".join(cmd), flush=True)

@@ -1,5 +1,5 @@
-// common.h — pieces shared by the translation units of libbsdfd.so (bsdfd.hip: the flow sampler,
-// wavefront.hip / pathtrace.hip: the wavefront harness kernels): the counter-based RNG and the error plumbing.
+// common.h — pieces shared by the translation units of libbsdfd.so (bsdfd.hip / flow32.hip: the flow kernels, host.hip: their host
+// side, wavefront.hip / pathtrace.hip: the wavefront harness kernels): the counter-based RNG and the error plumbing.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,7 +24,7 @@ __device__ __forceinline__ float u01_open(unsigned x) {  // (0, 1]
     return ((float)(x >> 8) + 1.0f) * (1.0f / 16777216.0f);
 }
 
-// records the thread-local message behind bsdfd_last_error() and returns `code` (defined in bsdfd.hip)
+// records the thread-local message behind bsdfd_last_error() and returns `code` (defined in host.hip)
 int bsdfd_fail_(int code, const std::string& msg);
 
 #define HIP_TRY(expr)                                                                               \

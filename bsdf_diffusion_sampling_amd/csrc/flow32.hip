@@ -39,7 +39,7 @@
 #include "bsdfd.h"
 #include "common.h"
 #include "flow_dev.h"
-#include "flow32.h"
+#include "flow_kernels.h"
 
 namespace {
 
@@ -270,7 +270,7 @@ __device__ __forceinline__ float von_mises_sample32(float mu, float kappa, unsig
 // plugins make: the disk net, split3 with the Jacobian, op = ROP (OP_SAMPLE | OP_PDF) and io = IO_PLUGIN as compile-time constants,
 // no segments, no context, no row_index / rng_index, no injected base point, T a power of two.  At 2 waves per SIMD (256 VGPRs) the
 // 24 hidden-layer fragments and the layer-1 fragment are read from LDS ONCE per workgroup and stay in registers across every tile and
-// Euler step; WOUT, the conditioning matrix and the base net stay in LDS.  The host (bsdfd.hip, run()) selects it; every other call
+// Euler step; WOUT, the conditioning matrix and the base net stay in LDS.  The host (host.hip, run()) selects it; every other call
 // form runs the general kernel (ROP = -1), whose code this parameter does not touch.
 // ---------------------------------------------------------------------------------------------
 template <int DOMAIN, bool JAC, bool FUSED, bool SPLIT, int ROP = -1>
@@ -1549,7 +1549,7 @@ std::vector<char> build_image32c(const bsdfd_desc& d) {
 
 // which 32-query-tile kernel serves (net, precision, mode): 0 none, 1 flow_kernel32 (split3), 2 flow_kernel32w, 3 flow_kernel32 (f16),
 // 4 flow_kernel32c (the 64 x 6 spherical net in split3 with the Jacobian: mode 1 only — its samples-only and fused calls stay on
-// 16-query tiles).  Kind 4 is OPT-IN (bsdfd_desc.tile = 32 explicitly; bsdfd_kernel32_opt_in): measured 4 % slower than the 16-query
+// 16-query tiles).  Kind 4 is OPT-IN (bsdfd_desc.tile = 32 explicitly; FlowKernel::opt_in): measured 4 % slower than the 16-query
 // kernel — 4 % fewer shader cycles at a 7.5 % lower clock, +2.5 % J/query (profiles/r06_ab/ab32c_64x6_jacobian.txt) — the library's
 // default for this net stays the 16-query kernel.
 #ifndef BSDFD_T32_WIDE_JAC
@@ -1568,53 +1568,15 @@ int kind32(const bsdfd_desc& d, int prec, int mode) {
     return 0;
 }
 
-}  // namespace
-
-bool bsdfd_tile32_supported(const bsdfd_desc& d, int prec) {
-    return kind32(d, prec, 0) != 0 || kind32(d, prec, 1) != 0;
-}
-
-bool bsdfd_kernel32_opt_in(const bsdfd_desc& d, int prec, int mode) { return kind32(d, prec, mode) == 4; }
-
-int bsdfd_tile32_context_v4(const bsdfd_desc& d, int prec) {   // f32x4 records per 32-query tile of the per-query context (mode 1)
-    return kind32(d, prec, 1) == 4 ? 8 * 64 + 32 : 4 * 64 + 32;
-}
-
-
-std::vector<char> bsdfd_build_image32(const bsdfd_desc& d, int prec) {
-    if (kind32(d, prec, 1) == 4) return build_image32c(d);
-    if (kind32(d, prec, 0) == 2) return build_image32w(d);
-    return d.domain == BSDFD_DOMAIN_DISK ? build_image32_t<BSDFD_DOMAIN_DISK>(d) : build_image32_t<BSDFD_DOMAIN_SPHERICAL>(d);
-}
-
-int bsdfd_kernel32_lds_bytes(const bsdfd_desc& d, int prec, int mode) {
-    if (kind32(d, prec, mode) == 4) return L32C::TOTAL + L32C::WAVES * L32C::SLAB;
-    if (kind32(d, prec, mode) == 2) return L32W::TOTAL;
-    const int domain = d.domain;   // (kind 3 = mode 0 of the same kernel template: same image, same slab)
-    if (mode == 2)
-        return domain == BSDFD_DOMAIN_DISK ? L32<BSDFD_DOMAIN_DISK>::TOTAL + 4 * CaccLds<BSDFD_DOMAIN_DISK, true>::slab
-                                           : L32<BSDFD_DOMAIN_SPHERICAL>::TOTAL + 4 * CaccLds<BSDFD_DOMAIN_SPHERICAL, true>::slab;
-    return domain == BSDFD_DOMAIN_DISK ? L32<BSDFD_DOMAIN_DISK>::TOTAL + 4 * CaccLds<BSDFD_DOMAIN_DISK, false>::slab
-                                       : L32<BSDFD_DOMAIN_SPHERICAL>::TOTAL + 4 * CaccLds<BSDFD_DOMAIN_SPHERICAL, false>::slab;
-}
-
-int bsdfd_kernel32_threads(const bsdfd_desc& d, int prec, int mode) {
-    const int kind = kind32(d, prec, mode);
-    return (kind == 2 || kind == 4) ? 512 : 256;
-}
-
-const void* bsdfd_kernel32_resident(const bsdfd_desc& d, int prec, int op) {
-    if (kind32(d, prec, 1) != 1 || d.domain != BSDFD_DOMAIN_DISK) return nullptr;
+const void* resident32_fn(int op) {   // (disk, split3)
     if (op == OP_SAMPLE) return reinterpret_cast<const void*>(flow_kernel32<BSDFD_DOMAIN_DISK, true, false, true, OP_SAMPLE>);
     if (op == OP_PDF) return reinterpret_cast<const void*>(flow_kernel32<BSDFD_DOMAIN_DISK, true, false, true, OP_PDF>);
     return nullptr;
 }
 
-const void* bsdfd_kernel32(const bsdfd_desc& d, int prec, int mode) {
-    const int kind = kind32(d, prec, mode);
+const void* kernel32_fn(int kind, bool disk, int mode) {
     if (kind == 4) return reinterpret_cast<const void*>(flow_kernel32c);
     if (kind == 2) return reinterpret_cast<const void*>(flow_kernel32w);
-    const bool disk = d.domain == BSDFD_DOMAIN_DISK;
     if (kind == 3)
         return disk ? reinterpret_cast<const void*>(flow_kernel32<BSDFD_DOMAIN_DISK, false, false, false>)
                     : reinterpret_cast<const void*>(flow_kernel32<BSDFD_DOMAIN_SPHERICAL, false, false, false>);
@@ -1628,4 +1590,42 @@ const void* bsdfd_kernel32(const bsdfd_desc& d, int prec, int mode) {
                             : reinterpret_cast<const void*>(flow_kernel32<BSDFD_DOMAIN_SPHERICAL, true, true, true>);
     }
     return nullptr;
+}
+
+// dynamic LDS of that kernel: the image + per-wave scratch
+int lds_bytes32(int kind, bool disk, int mode) {
+    if (kind == 4) return L32C::TOTAL + L32C::WAVES * L32C::SLAB;
+    if (kind == 2) return L32W::TOTAL;
+    // (kind 3 = mode 0 of the same kernel template: same image, same slab)
+    if (mode == 2)
+        return disk ? L32<BSDFD_DOMAIN_DISK>::TOTAL + 4 * CaccLds<BSDFD_DOMAIN_DISK, true>::slab
+                    : L32<BSDFD_DOMAIN_SPHERICAL>::TOTAL + 4 * CaccLds<BSDFD_DOMAIN_SPHERICAL, true>::slab;
+    return disk ? L32<BSDFD_DOMAIN_DISK>::TOTAL + 4 * CaccLds<BSDFD_DOMAIN_DISK, false>::slab
+                : L32<BSDFD_DOMAIN_SPHERICAL>::TOTAL + 4 * CaccLds<BSDFD_DOMAIN_SPHERICAL, false>::slab;
+}
+
+}  // namespace
+
+bool bsdfd_tile32_supported(const bsdfd_desc& d, int prec) { return kind32(d, prec, 0) != 0 || kind32(d, prec, 1) != 0; }
+
+int bsdfd_tile32_context_v4(const bsdfd_desc& d, int prec) {   // f32x4 records per 32-query tile of the per-query context (mode 1)
+    return kind32(d, prec, 1) == 4 ? 8 * 64 + 32 : 4 * 64 + 32;
+}
+
+std::vector<char> bsdfd_build_image32(const bsdfd_desc& d, int prec) {
+    if (kind32(d, prec, 1) == 4) return build_image32c(d);
+    if (kind32(d, prec, 0) == 2) return build_image32w(d);
+    return d.domain == BSDFD_DOMAIN_DISK ? build_image32_t<BSDFD_DOMAIN_DISK>(d) : build_image32_t<BSDFD_DOMAIN_SPHERICAL>(d);
+}
+
+FlowKernel bsdfd_kernel32(const bsdfd_desc& d, int prec, int mode) {
+    const int kind = kind32(d, prec, mode);
+    const bool disk = d.domain == BSDFD_DOMAIN_DISK;
+    return {kernel32_fn(kind, disk, mode), 32, (kind == 2 || kind == 4) ? 512 : 256, lds_bytes32(kind, disk, mode), kind == 4};
+}
+
+FlowKernel bsdfd_kernel32_resident(const bsdfd_desc& d, int prec, int op) {
+    FlowKernel k = bsdfd_kernel32(d, prec, 1);   // the fast path rides on mode 1's tiling: same image, LDS and workgroup size
+    k.fn = kind32(d, prec, 1) == 1 && d.domain == BSDFD_DOMAIN_DISK ? resident32_fn(op) : nullptr;
+    return k;
 }

@@ -1,6 +1,7 @@
 // flow_dev.h — device helpers, kernel-parameter block and constants shared by the flow-kernel translation units
-// (bsdfd.hip: 16-query tiles on the 16x16 MFMA shapes + the host side; flow32.hip: 32-query tiles on v_mfma_f32_32x32x16_f16).
-// Everything lives in an unnamed namespace: each translation unit gets its own copy, nothing is exported.
+// (bsdfd.hip: 16-query tiles on the 16x16 MFMA shapes; flow32.hip: 32-query tiles on v_mfma_f32_32x32x16_f16) and by host.hip,
+// which fills the parameter block.  Everything but ImgLayout (it crosses translation units: flow_kernels.h) lives in an unnamed
+// namespace: each translation unit gets its own copy, nothing is exported.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +9,10 @@
 
 #include "bsdfd.h"
 #include "common.h"
+
+struct ImgLayout {  // byte offsets into the weight image (identical in global memory and LDS)
+    int win, wc, wh, wh_lo, wo, wf, wf_lo, wg, wg_lo, bw1, bb1, bw2, bb2, wcs, wcs_lo, wt0, total;
+};
 
 namespace {
 
@@ -33,10 +38,6 @@ constexpr int kTangentPrec = 3;
 constexpr int CLK_SLOTS = 256;  // counter pairs of the in-kernel clock measurement, 8 u64 (one 64-B line) apart
 constexpr int MAX_SEG = 64;  // materials per segmented launch (the descriptors travel in the kernel arguments)
 enum { IO_OPERATOR = 0, IO_PLUGIN = 1, IO_PLUGIN_FULLSPHERE = 2 };
-
-struct ImgLayout {  // byte offsets into the weight image (identical in global memory and LDS)
-    int win, wc, wh, wh_lo, wo, wf, wf_lo, wg, wg_lo, bw1, bb1, bw2, bb2, wcs, wcs_lo, wt0, total;
-};
 
 struct KParams {
     const char* img;

@@ -756,6 +756,20 @@ def test_build_falls_back_to_compiler_managed_lds_reads_when_the_asm_check_fails
     assert _lib.build_info().get("variant") == "async" and b"asynchronous LDS reads" in _lib.lib().bsdfd_version()
 
 
+def test_host_code_is_a_translation_unit_outside_the_kernel_fingerprint():
+    """The handle, run() and every entry point live in csrc/host.hip: built and tracked as a dependency like every translation
+    unit, but not hashed by `kernel_source_sha256()` — an edit to an error message or an entry point cannot change an instruction
+    of a kernel and must not invalidate the committed profiles.  The fingerprinted files hold no host entry point at all."""
+    from bsdf_diffusion_sampling_amd import _lib
+    csrc = os.path.join(ROOT, "bsdf_diffusion_sampling_amd", "csrc")
+    host, hdr = os.path.join(csrc, "host.hip"), os.path.join(csrc, "flow_kernels.h")
+    assert host in _lib.SRC_PATHS and host in _lib.DEP_PATHS and host not in _lib.KERNEL_SOURCES and os.path.exists(host)
+    assert hdr in _lib.DEP_PATHS and hdr not in _lib.SRC_PATHS and os.path.exists(hdr)
+    assert len(_lib.KERNEL_SOURCES) == 3
+    for f in _lib.KERNEL_SOURCES:
+        assert 'extern "C"' not in open(f).read(), f
+
+
 def test_committed_profiles_match_the_kernel_source():
     """bench.py looks `roofline.traffic` (PMC passes) and the instruction-issue model (ISA of the build) up in profiles/*.json
     and withholds them when csrc/bsdfd.hip has changed since they were taken ("a kernel change without a profile

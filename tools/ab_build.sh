@@ -1,7 +1,8 @@
 #!/bin/bash
 # Build A/B variants of libbsdfd.so into build_ab/ (travels to the GPU box, git-ignored):
 #   tools/ab_build.sh NAME "EXTRA HIPCC FLAGS" [NAME2 "FLAGS2" ...]
-# The side translation units (csrc/flow32.hip included) are compiled once; only csrc/bsdfd.hip is rebuilt per variant.
+# The side translation units (csrc/flow32.hip included) are compiled once; csrc/bsdfd.hip and csrc/host.hip are rebuilt per variant
+# (the knobs live on both sides: the kernel's in the one, run()'s — BSDFD_T32_RESIDENT_MIN_T, tools/tuning_knobs.h — in the other).
 set -e
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT="$ROOT/build_ab"; mkdir -p "$OUT"
@@ -9,7 +10,7 @@ CS="$ROOT/bsdf_diffusion_sampling_amd/csrc"
 COMMON="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value -Wno-pass-failed -I $ROOT/include"
 SIDE="flow32 wavefront pathtrace pathlights pathenv encoding measured measured_table bucket bucket_wide live clock"
 for tu in $SIDE; do
-  if [ ! -f "$OUT/$tu.o" ] || [ "$CS/$tu.hip" -nt "$OUT/$tu.o" ] || [ "$CS/flow_dev.h" -nt "$OUT/$tu.o" ] || [ "$CS/flow32.h" -nt "$OUT/$tu.o" ] || [ "$ROOT/include/bsdfd.h" -nt "$OUT/$tu.o" ]; then
+  if [ ! -f "$OUT/$tu.o" ] || [ "$CS/$tu.hip" -nt "$OUT/$tu.o" ] || [ "$CS/flow_dev.h" -nt "$OUT/$tu.o" ] || [ "$CS/flow_kernels.h" -nt "$OUT/$tu.o" ] || [ "$ROOT/include/bsdfd.h" -nt "$OUT/$tu.o" ]; then
     hipcc $COMMON -c "$CS/$tu.hip" -o "$OUT/$tu.o" &
     if (( $(jobs -r | wc -l) >= 8 )); then wait -n; fi
   fi
@@ -17,8 +18,8 @@ done
 wait
 while [ $# -gt 0 ]; do
   name="$1"; flags="$2"; shift 2
-  ( hipcc $COMMON $flags -c "$CS/bsdfd.hip" -o "$OUT/bsdfd_$name.o" && \
-    hipcc --offload-arch=gfx950 -shared -fPIC "$OUT/bsdfd_$name.o" $(for tu in $SIDE; do echo "$OUT/$tu.o"; done) -o "$OUT/lib_$name.so" && echo "built $name ($flags)" ) &
+  ( hipcc $COMMON $flags -c "$CS/bsdfd.hip" -o "$OUT/bsdfd_$name.o" && hipcc $COMMON $flags -c "$CS/host.hip" -o "$OUT/host_$name.o" && \
+    hipcc --offload-arch=gfx950 -shared -fPIC "$OUT/bsdfd_$name.o" "$OUT/host_$name.o" $(for tu in $SIDE; do echo "$OUT/$tu.o"; done) -o "$OUT/lib_$name.so" && echo "built $name ($flags)" ) &
   if (( $(jobs -r | wc -l) >= 4 )); then wait -n; fi
 done
 wait

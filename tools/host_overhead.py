@@ -1,11 +1,14 @@
-"""Host-side cost of one call through the Python wrapper vs the kernel time (small wavefronts)."""
+"""Host-side cost of one call through the Python wrapper vs the kernel time (small wavefronts).
+    python tools/host_overhead.py [binding ...]      (default: ctypes torch)
+With $BSDFD_LIB_PATH pointing at another build, name ctypes only: the torch operators are linked against the tree's own library, and a
+handle is private to the library that created it."""
 import sys, time, torch
 sys.path.insert(0,'.')
 import bench
 from bsdf_diffusion_sampling_amd import weights as W
 from bsdf_diffusion_sampling_amd.sampler import FlowSampler
 dev=torch.device('cuda')
-for binding, n in [(b, n) for b in ("ctypes", "torch") for n in (4096, 65536)]:
+for binding, n in [(b, n) for b in (sys.argv[1:] or ("ctypes", "torch")) for n in (4096, 65536)]:
     s=FlowSampler(W.load(W.shipped_path("aniso_miro_7_rgb","disk")), binding=binding)
     wi=bench.make_wi("disk",n,1,dev); wo=torch.empty_like(wi); p=torch.empty(n,device=dev); p2=torch.empty(n,device=dev)
     for _ in range(200): s.plugin_sample(wi,None,T=4,seed=1,offset=0,out=(wo,p)); s.plugin_pdf(wi,wo,T=4,out=p2)

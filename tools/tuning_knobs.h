@@ -1,6 +1,6 @@
 // Grid-shape knobs for tools/tscan.py and tools/nscan.py.  NOT part of the product: a tools build force-includes this header
 //     tools/ab_build.sh tune "-include tools/tuning_knobs.h"
-// and csrc/bsdfd.hip expands BSDFD_TOOLS_KNOBS(per_cu) inside its launch routine.
+// and csrc/host.hip expands BSDFD_TOOLS_KNOBS(per_cu) inside its launch routine, run() (ab_build.sh passes the flags to it too).
 #pragma once
 #include <cstdlib>
 #define BSDFD_TOOLS_KNOBS(per_cu)                                          \
