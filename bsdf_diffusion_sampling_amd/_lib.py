@@ -18,7 +18,7 @@ SRC32_PATH = os.path.join(_HERE, "csrc", "flow32.hip")   # the 32-query-tile flo
 HOST_PATH = os.path.join(_HERE, "csrc", "host.hip")      # handle, launch routine and entry points of both kernel families
 SRC_PATHS = [SRC_PATH, SRC32_PATH, HOST_PATH, os.path.join(_HERE, "csrc", "wavefront.hip"), os.path.join(_HERE, "csrc", "pathtrace.hip"),
              os.path.join(_HERE, "csrc", "pathlights.hip"), os.path.join(_HERE, "csrc", "pathenv.hip"),
-             os.path.join(_HERE, "csrc", "encoding.hip"),
+             os.path.join(_HERE, "csrc", "pathrr.hip"), os.path.join(_HERE, "csrc", "encoding.hip"),
              os.path.join(_HERE, "csrc", "measured.hip"), os.path.join(_HERE, "csrc", "measured_table.hip"),
              os.path.join(_HERE, "csrc", "bucket.hip"),
              os.path.join(_HERE, "csrc", "bucket_wide.hip"), os.path.join(_HERE, "csrc", "live.hip"),
@@ -44,7 +44,7 @@ EXPORTS = (
     "bsdfd_plugin_pdf_multi_ex", "bsdfd_plugin_sample_pdf_multi_ex", "bsdfd_plugin_sample_pdf_ex",
     "bsdfd_flow_samples_only", "bsdfd_wf_primary", "bsdfd_wf_shade", "bsdfd_wf_path_begin", "bsdfd_wf_bounce", "bsdfd_wf_resolve",
     "bsdfd_wf_sample_emitter", "bsdfd_wf_bounce_lit",
-    "bsdfd_env_sample", "bsdfd_env_pdf", "bsdfd_wf_sample_env", "bsdfd_wf_bounce_env",
+    "bsdfd_env_sample", "bsdfd_env_pdf", "bsdfd_wf_sample_env", "bsdfd_wf_bounce_env", "bsdfd_wf_bounce_rr",
     "bsdfd_positional_encoding", "bsdfd_bucket_workspace_bytes", "bsdfd_bucket_by_material",
     "bsdfd_bucket_wide_workspace_bytes", "bsdfd_bucket_by_material_wide",
     "bsdfd_gather_lanes", "bsdfd_scatter_lanes", "bsdfd_live_workspace_bytes", "bsdfd_compact_live",
@@ -431,6 +431,7 @@ def lib():
     L.bsdfd_env_pdf.argtypes = [C.POINTER(EnvDist), i64, fp, fp, vp]
     L.bsdfd_wf_sample_env.argtypes = [C.POINTER(WfScene), fp, C.POINTER(EnvDist), i32, i32, i32, u64, u64, u64, i64] + [fp] * 8 + [vp]
     L.bsdfd_wf_bounce_env.argtypes = L.bsdfd_wf_bounce_lit.argtypes[:-1] + [fp, C.POINTER(EnvDist), vp]
+    L.bsdfd_wf_bounce_rr.argtypes = L.bsdfd_wf_bounce_env.argtypes[:-1] + [i32, vp]
     L.bsdfd_positional_encoding.argtypes = [fp, i64, i32, i32, i32, i32, fp, vp]
     L.bsdfd_measured_create_from_file.argtypes = [C.c_char_p, C.POINTER(vp)]
     L.bsdfd_measured_destroy.argtypes = [vp]

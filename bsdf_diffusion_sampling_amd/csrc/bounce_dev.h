@@ -9,7 +9,8 @@
 // does not depend on the mode, so the three kernels' continuation states are equal bit for bit by construction.  The modes
 // differ, under `if constexpr`, in where the emitter sample comes from, in how the floor's environment term is gated or
 // weighted, in the light-strategy density the escaping BSDF sample is weighted against, and in the light strategy's own term.
-// Each instantiation is straight-line code of its own.
+// Each instantiation is straight-line code of its own.  pathrr.hip instantiates the three modes once more with RR = true: the
+// same body with Russian roulette in front of continue_path.
 //
 // The arrays travel in small structs passed by value (kernel arguments: scalar loads); no struct is indexed per lane.
 #pragma once
@@ -81,10 +82,17 @@ __device__ __forceinline__ void store_local_direction(float* __restrict__ wl, V3
 
 // One bounce of lane p's path: rad += beta * (the vertex' estimate), then the path moves to what its BSDF sample hits or ends.
 // `e`, `n_e` and `has_env` are read by the modes that have them (ENV; LIT and ENV; LIT).
-template <int M>
+//
+// RR (pathrr.hip): Russian roulette, Mitsuba's `path` integrator's rule.  From the vertex with bounce + 1 >= rr_depth on (its
+// `depth >= rr_depth`, depth = the surface vertices processed so far) a path that would continue survives with probability
+// q = min(max over the channels of the throughput after this vertex, 0.95) — eta is 1 here — and its throughput is divided by q.
+// The variate is a Philox draw of the lane's own (counter word 3 = "Roul" + depth), made only where the decision is.  A path
+// that is killed ends exactly as one that escaped; `rad` is formed and stored before, and where a survivor goes does not depend on
+// the roulette: only the `thr` that continue_path multiplies into beta does.
+template <int M, bool RR = false>
 __device__ __forceinline__ void bounce_vertex(const Scene& sc, const float* __restrict__ env, const EnvDist& e, int n_e, int has_env,
                                               const Step& st, const PathState& ps, const SamplerAnswer& sa,
-                                              const EmitterSample& es) {
+                                              const EmitterSample& es, int rr_depth = 0) {
     long long p, m;
     if (!live_lane(sc, st.n, ps.mat, p, m)) return;
     const int occlusion = st.occlusion;
@@ -185,6 +193,20 @@ __device__ __forceinline__ void bounce_vertex(const Scene& sc, const float* __re
         ps.mat[p] = sc.n_sph + 1;
         return;
     }
+    if constexpr (RR) {
+        if (st.bounce + 1 >= rr_depth) {   // (wave-uniform)
+            const float q = fminf(fmaxf(fmaxf(b.x * thr[0], b.y * thr[1]), b.z * thr[2]), 0.95f);
+            unsigned u[4];
+            tagged_draw(st.seed, st.pass, st.path_offset, p, 0x526F756Cu /* "Roul" */, st.bounce, u);
+            if (!(q > 0.0f && (float)(u[0] >> 8) * (1.0f / 16777216.0f) < q)) {   // (a NaN q ends the path too)
+                ps.mat[p] = sc.n_sph + 1;
+                return;
+            }
+            const float inv_q = 1.0f / q;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) thr[c] *= inv_q;
+        }
+    }
     continue_path(sc, h, x, d, b, thr, st.seed, st.pass, st.path_offset, st.bounce, p, ps.org, ps.nrm, ps.wi, ps.wl, ps.mat, ps.beta);
 }
 
@@ -205,6 +227,40 @@ int checked_bounce(int32_t bounce, int32_t last, int32_t occlusion, uint64_t see
     if (!ps.org || !ps.nrm || !ps.wi || !ps.wl || !ps.mat || !ps.beta || !ps.rad || !sa.wo || !sa.pdf_o || !sa.pdf_l || !emitter_arrays)
         return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
     return launch(make_step(bounce, last, occlusion, seed, pass, path_offset, N));
+}
+
+// the emitter counts of a bsdfd_wf_lights: n point lights, n_e emitters with the environment
+inline int light_counts(const bsdfd_wf_lights* l, int& n, int& n_e) {
+    if (!l) return bsdfd_fail_(BSDFD_EINVAL, "null lights");
+    if (l->n_lights < 1 || l->n_lights > BSDFD_WF_MAX_LIGHTS) return bsdfd_fail_(BSDFD_EINVAL, "1..8 point lights");
+    n = l->n_lights;
+    n_e = l->n_lights + (l->has_env ? 1 : 0);
+    return BSDFD_OK;
+}
+
+// scene + environment + distribution (of the environment's size) + emitter count of a launch over N paths
+inline int env_scene(const bsdfd_wf_scene* scene, const float* env, const bsdfd_env_dist* dist, int n_e, bool has_lsel, long long n,
+                     Scene& sc, EnvDist& e) {
+    if (int rc = path_scene(scene, env, n, sc)) return rc;
+    if (int rc = env_dev::to_env_dist(dist, e)) return rc;
+    if (e.w != sc.env_w || e.h != sc.env_h) return bsdfd_fail_(BSDFD_EINVAL, "the distribution is not of the environment map's size");
+    if (n_e < 1 || n_e > BSDFD_WF_MAX_LIGHTS + 1) return bsdfd_fail_(BSDFD_EINVAL, "n_e must be 1..9: the environment and up to 8 point lights");
+    if (!has_lsel && n_e != 1) return bsdfd_fail_(BSDFD_EINVAL, "without lsel the environment is the only emitter: n_e must be 1");
+    return BSDFD_OK;
+}
+
+// ... with the emitters of bsdfd_wf_bounce_env: `lights` and `lsel` both NULL (n_e = 1) or both given (has_env set, n_e = n_lights + 1)
+inline int env_bounce_scene(const bsdfd_wf_scene* scene, const float* env, const bsdfd_env_dist* dist, const bsdfd_wf_lights* lights,
+                            const int32_t* lsel, long long n, Scene& sc, EnvDist& e, int& n_e) {
+    n_e = 1;
+    if (lights) {
+        if (lights->n_lights < 1 || lights->n_lights > BSDFD_WF_MAX_LIGHTS) return bsdfd_fail_(BSDFD_EINVAL, "1..8 point lights");
+        if (!lights->has_env) return bsdfd_fail_(BSDFD_EINVAL, "the environment must be one of the emitters (has_env)");
+        n_e = lights->n_lights + 1;
+    }
+    if ((lights == nullptr) != (lsel == nullptr) && n != 0)
+        return bsdfd_fail_(BSDFD_EINVAL, "lights and lsel are both NULL or both given");
+    return env_scene(scene, env, dist, n_e, lights != nullptr, n, sc, e);
 }
 
 }  // namespace bounce_dev

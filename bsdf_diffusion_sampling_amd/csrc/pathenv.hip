@@ -85,17 +85,6 @@ __global__ __launch_bounds__(256) void bounce_env_kernel(Scene sc, const float* 
     bounce_vertex<ENV>(sc, env, e, n_e, 1, st, ps, sa, es);
 }
 
-// scene + environment + distribution (of the environment's size) + emitter count of a launch over N paths
-int env_scene(const bsdfd_wf_scene* scene, const float* env, const bsdfd_env_dist* dist, int n_e, bool has_lsel, long long n,
-              Scene& sc, EnvDist& e) {
-    if (int rc = path_scene(scene, env, n, sc)) return rc;
-    if (int rc = env_dev::to_env_dist(dist, e)) return rc;
-    if (e.w != sc.env_w || e.h != sc.env_h) return bsdfd_fail_(BSDFD_EINVAL, "the distribution is not of the environment map's size");
-    if (n_e < 1 || n_e > BSDFD_WF_MAX_LIGHTS + 1) return bsdfd_fail_(BSDFD_EINVAL, "n_e must be 1..9: the environment and up to 8 point lights");
-    if (!has_lsel && n_e != 1) return bsdfd_fail_(BSDFD_EINVAL, "without lsel the environment is the only emitter: n_e must be 1");
-    return BSDFD_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -142,15 +131,8 @@ int bsdfd_wf_bounce_env(const bsdfd_wf_scene* scene, const float* env, int32_t b
                         const int32_t* lsel, const float* emit, const float* lpdf, const bsdfd_env_dist* dist, void* stream) {
     Scene sc;
     EnvDist e;
-    int n_e = 1;
-    if (lights) {
-        if (lights->n_lights < 1 || lights->n_lights > BSDFD_WF_MAX_LIGHTS) return bsdfd_fail_(BSDFD_EINVAL, "1..8 point lights");
-        if (!lights->has_env) return bsdfd_fail_(BSDFD_EINVAL, "the environment must be one of the emitters (has_env)");
-        n_e = lights->n_lights + 1;
-    }
-    if ((lights == nullptr) != (lsel == nullptr) && N != 0)
-        return bsdfd_fail_(BSDFD_EINVAL, "lights and lsel are both NULL or both given");
-    if (int rc = env_scene(scene, env, dist, n_e, lights != nullptr, N, sc, e)) return rc;
+    int n_e;
+    if (int rc = env_bounce_scene(scene, env, dist, lights, lsel, N, sc, e, n_e)) return rc;
     const PathState ps{org, nrm, wi, wl, reinterpret_cast<long long*>(material), beta, rad};
     const SamplerAnswer sa{wo, pdf_o, pdf_l, f_o, f_l};
     const EmitterSample es{reinterpret_cast<const int*>(lsel), lpdf, emit};

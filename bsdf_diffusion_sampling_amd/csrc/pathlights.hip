@@ -75,10 +75,7 @@ __global__ __launch_bounds__(256) void bounce_lit_kernel(Scene sc, const float* 
 
 // the kernel-argument form of a bsdfd_wf_lights
 int to_lights(const bsdfd_wf_lights* l, Lights& lt) {
-    if (!l) return bsdfd_fail_(BSDFD_EINVAL, "null lights");
-    if (l->n_lights < 1 || l->n_lights > BSDFD_WF_MAX_LIGHTS) return bsdfd_fail_(BSDFD_EINVAL, "1..8 point lights");
-    lt.n = l->n_lights;
-    lt.n_e = l->n_lights + (l->has_env ? 1 : 0);
+    if (int rc = light_counts(l, lt.n, lt.n_e)) return rc;
     for (int k = 0; k < BSDFD_WF_MAX_LIGHTS; ++k)
         for (int c = 0; c < 3; ++c) {
             lt.pos[k][c] = k < lt.n ? l->position[k][c] : 0.0f;

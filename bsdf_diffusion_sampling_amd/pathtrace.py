@@ -1,7 +1,8 @@
 """Path tracer for the array scene: occlusion, further bounces (csrc/pathtrace.hip, C ABI ``bsdfd_wf_path_begin`` /
 ``bsdfd_wf_bounce`` / ``bsdfd_wf_resolve``), point emitters (csrc/pathlights.hip, ``bsdfd_wf_sample_emitter`` /
-``bsdfd_wf_bounce_lit``) and importance sampling of the environment map (csrc/pathenv.hip, ``bsdfd_wf_sample_env`` /
-``bsdfd_wf_bounce_env``; the distribution: ``envmap.EnvDistribution``).
+``bsdfd_wf_bounce_lit``), importance sampling of the environment map (csrc/pathenv.hip, ``bsdfd_wf_sample_env`` /
+``bsdfd_wf_bounce_env``; the distribution: ``envmap.EnvDistribution``) and Russian roulette with unbounded depth
+(csrc/pathrr.hip, ``bsdfd_wf_bounce_rr``).
 
 The reference renders its 12-ball array scenes with Mitsuba's ``path`` integrator at unbounded depth
 (matpreview/disney_bsdf_array*_envmap.xml, scene_measured.xml: ``max_depth = -1``): balls shadow the floor and each
@@ -13,7 +14,7 @@ the loop that feeds a shrinking wavefront through the same pieces bounce after b
     per bounce k:  table.bucket(mat)            ended paths carry the "miss" id and sort behind the materials
                    table.sample_pdf(plan, ...)  flow evaluations for the lanes that carry a material only
                    measured_table.eval_t(...)   when there is ground truth
-                   bounce(k, last = k == max_depth - 1)
+                   bounce(k, last = k == max_depth - 1)      [rr_depth: bounce_rr, which also ends paths by roulette]
     resolve -> film tile += mean_spp of rad
 
 The geometry is at most 32 analytic spheres and one plane, intersected by brute force like the primary rays.  Without
@@ -40,8 +41,18 @@ parity-unpinned against it like the evaluator — and leaves its density in ``lp
 ``emit``; ``bounce_env`` weights both strategies against that density.  The floor keeps its cosine direction as BSDF sample and
 way on, so where a path goes does not depend on ``env_sampling``.
 
-There is no Russian roulette: a path ends when it escapes, when its BSDF sample is invalid, or at ``max_depth`` (the
-reference's unbounded depth is a finite ``max_depth`` here).  There are no area or spot emitters.  There is no CPU fallback.
+A path ends when it escapes, when its BSDF sample is invalid, at ``max_depth``, or — with ``rr_depth=R`` — by Russian
+roulette: the reference's six ``max_depth = -1`` scenes set no ``rr_depth``, so Mitsuba's default of 5 applies, and from the fifth
+vertex on (``bounce + 1 >= R``) a path that would continue survives with probability ``q = min(max(throughput), 0.95)`` and its
+throughput is divided by ``q``.  The decision is made inside the bounce kernel (``bsdfd_wf_bounce_rr`` stands in for whichever of
+the three bounce calls the emitters select; one Philox draw of the lane's own per decision, counter word 3 = "Roul" + depth), a
+killed path carries the "miss" id like one that escaped, and ``rad`` and the way a survivor goes do not depend on it.  With
+roulette ``max_depth=None`` is the reference's unbounded depth: the loop runs until the bucketing finds no live lane, or to
+``PathArrayRenderer.DEPTH_CAP`` bounces — a truncation, should it ever be hit (``stats["depth_cap_hit"]``).  This is Mitsuba's
+rule restated; like the evaluator it is parity-unpinned against Mitsuba (neither its random stream nor its images are matched).
+``integrator_from_matpreview_xml`` reads both settings from a reference scene file.
+
+There are no area or spot emitters.  There is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -109,6 +120,34 @@ def lights_from_matpreview_xml(path: str):
     return out
 
 
+def integrator_from_matpreview_xml(path: str):
+    """``(max_depth, rr_depth)`` of the ``<integrator>`` of a reference scene file, as ``PathArrayRenderer`` takes them.  Mitsuba
+    counts segments (``maxDepth = 2``: direct illumination) and this renderer counts vertices, so ``maxDepth = 2`` is
+    ``max_depth = 1``, and ``-1`` (Mitsuba's default too) is ``None``: unbounded.  ``rrDepth`` is read if present and is otherwise
+    Mitsuba's default, 5.  Both spellings of either name are read (``maxDepth`` / ``max_depth``, ``rrDepth`` / ``rr_depth``), and a
+    ``$name`` value is looked up among the file's ``<default>`` elements (scene_measured.xml)."""
+    import xml.etree.ElementTree as ET
+    root = ET.parse(path).getroot()
+    defaults = {d.get("name"): d.get("value") for d in root.iter("default")}
+    found = {}
+    for integ in root.iter("integrator"):
+        for child in integ.iter("integer"):
+            name = {"maxDepth": "max_depth", "rrDepth": "rr_depth"}.get(child.get("name"), child.get("name"))
+            if name in ("max_depth", "rr_depth") and name not in found:
+                value = child.get("value", "")
+                if value.startswith("$"):
+                    if value[1:] not in defaults:
+                        raise ValueError(f"{path}: {child.get('name')} = {value} has no <default>")
+                    value = defaults[value[1:]]
+                found[name] = int(value)
+    depth, rr = found.get("max_depth", -1), found.get("rr_depth", 5)
+    if depth == 0 or depth == 1 or depth < -1:
+        raise ValueError(f"{path}: maxDepth = {depth} leaves no surface vertex to shade")
+    if rr < 1:
+        raise ValueError(f"{path}: rrDepth must be >= 1, got {rr}")
+    return (None if depth == -1 else depth - 1), rr
+
+
 class PathArrayRenderer(ArrayRenderer):
     """``ArrayRenderer`` with ``max_depth`` vertices per path and, with ``occlusion``, shadow rays.
 
@@ -124,16 +163,33 @@ class PathArrayRenderer(ArrayRenderer):
 
     ``env_sampling``: ``"cosine"`` (the default: the renderer without the argument, bit for bit) or ``"importance"``, which
     samples the environment in proportion to its luminance (``envmap.EnvDistribution``, built once here).  ``"importance"``
-    needs an emitting environment: with lights and ``env=None`` it is refused."""
+    needs an emitting environment: with lights and ``env=None`` it is refused.
 
-    def __init__(self, table, centers, radii, camera=None, env: Optional[torch.Tensor] = None, *args, max_depth: int = 1,
+    ``rr_depth``: None (the default: the renderer without the argument, bit for bit; ``bsdfd_wf_bounce_rr`` is never called) or an
+    integer >= 1: Russian roulette from the vertex ``bounce + 1 >= rr_depth`` on (Mitsuba's default is 5).  ``max_depth=None``
+    is unbounded depth; it needs ``rr_depth`` and implies occlusion.  A pass then ends when no live lane is left, or after
+    ``DEPTH_CAP`` bounces (the bounce at the cap gets ``last=True``: a truncation, reported in ``stats["depth_cap_hit"]``).
+    ``stats["depth"]``: the bounces the last pass ran."""
+
+    DEPTH_CAP = 1024   # bounces of a pass at max_depth=None; with roulette (q <= 0.95) a path outlives it with probability < 1e-22
+
+    def __init__(self, table, centers, radii, camera=None, env: Optional[torch.Tensor] = None, *args, max_depth: Optional[int] = 1,
                  occlusion: Optional[bool] = None, lights: Optional[Sequence[PointLight]] = None, env_sampling: str = "cosine",
-                 **kwargs):
-        max_depth = int(max_depth)
-        if max_depth < 1:
-            raise ValueError("max_depth must be >= 1")
-        occlusion = max_depth > 1 if occlusion is None else bool(occlusion)
-        if max_depth > 1 and not occlusion:
+                 rr_depth: Optional[int] = None, **kwargs):
+        if rr_depth is not None:
+            rr_depth = int(rr_depth)
+            if rr_depth < 1:
+                raise ValueError("rr_depth must be >= 1 (or None: no Russian roulette)")
+        if max_depth is None:
+            if rr_depth is None:
+                raise ValueError("max_depth=None (unbounded depth) needs rr_depth: only Russian roulette makes it finite")
+        else:
+            max_depth = int(max_depth)
+            if max_depth < 1:
+                raise ValueError("max_depth must be >= 1")
+        deep = max_depth is None or max_depth > 1
+        occlusion = deep if occlusion is None else bool(occlusion)
+        if deep and not occlusion:
             raise ValueError("max_depth > 1 needs occlusion: without it every vertex would see the environment through the balls")
         if env_sampling not in ("cosine", "importance"):
             raise ValueError(f'env_sampling must be "cosine" or "importance", got {env_sampling!r}')
@@ -147,13 +203,13 @@ class PathArrayRenderer(ArrayRenderer):
         super().__init__(table, centers, radii, camera, env, *args, **kwargs)
         if self.use_ground_truth and self.measured_table is None:
             raise ValueError("PathArrayRenderer evaluates the ground truth on the lane-ordered wavefront (fused_ground_truth=True)")
-        self.max_depth, self.occlusion = max_depth, occlusion
+        self.max_depth, self.occlusion, self.rr_depth = max_depth, occlusion, rr_depth
         self.env_sampling = env_sampling
         self.env_dist = None
         if env_sampling == "importance":
             from .envmap import EnvDistribution
             self.env_dist = EnvDistribution(self.env)
-        self.stats = {"lanes_per_bounce": []}
+        self.stats = {"lanes_per_bounce": [], "depth": 0, "depth_cap_hit": False}
 
     def _buffers(self, n: int):
         b = super()._buffers(n)
@@ -202,13 +258,15 @@ class PathArrayRenderer(ArrayRenderer):
         torch.autograd.graph.increment_version([b["wl"], b["lpdf"], b["emit"]])
 
     def bounce(self, b, bounce: int, last: bool, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
-               lights: Optional[_lib.WfLights] = None, env_dist=None):
+               lights: Optional[_lib.WfLights] = None, env_dist=None, rr_depth: Optional[int] = None):
         """Shade the vertices in ``b`` (``wo``, ``pdf_o``, ``pdf_l`` [, ``f_o``, ``f_l``] from the sampler; with lights also
         ``lsel`` and ``emit`` from ``sample_emitter``; with an ``EnvDistribution`` also ``lpdf`` and ``emit`` from ``sample_env``)
-        and move the paths on."""
+        and move the paths on.  ``rr_depth`` (default: the instance's): with an integer the same emitters go through
+        ``bsdfd_wf_bounce_rr``, which plays Russian roulette on the paths that would continue once ``bounce + 1 >= rr_depth``."""
         occlusion = self.occlusion if occlusion is None else occlusion
         lights = self.lights if lights is None else lights
         env_dist = self.env_dist if env_dist is None else env_dist
+        rr_depth = self.rr_depth if rr_depth is None else rr_depth
         with torch.cuda.device(self.device):
             fn, args = _lib.lib().bsdfd_wf_bounce, [
                 C.byref(self.scene), _p(self.env), bounce, int(bool(last)), int(bool(occlusion)), seed, pass_idx, path_offset,
@@ -220,6 +278,9 @@ class PathArrayRenderer(ArrayRenderer):
             if env_dist is not None:                         # ... and bounce_env's follow bounce_lit's
                 fn = _lib.lib().bsdfd_wf_bounce_env
                 args += [_p(b["lpdf"]), C.byref(env_dist.struct(self.device))]
+            if rr_depth is not None:                         # ... and bounce_rr's are bounce_env's (NULL: not this mode's) + rr_depth
+                fn = _lib.lib().bsdfd_wf_bounce_rr
+                args += [None] * (26 - len(args)) + [int(rr_depth)]
             _lib.check(fn(*args, self._stream()))
         # written through raw pointers: tell torch (the plugin cores key their per-query context cache on wi._version)
         torch.autograd.graph.increment_version([b["wi"], b["wl"], b["nrm"], b["org"], b["mat"], b["beta"], b["rad"]])
@@ -246,7 +307,8 @@ class PathArrayRenderer(ArrayRenderer):
         skey = (seed * 0x9E3779B97F4A7C15 + pass_idx + 1) & _M64
         n_balls = len(self.table)
         lanes = []
-        for k in range(self.max_depth):
+        depth = self.DEPTH_CAP if self.max_depth is None else self.max_depth   # (unbounded: the loop ends where no lane is live)
+        for k in range(depth):
             if self.lights is not None:
                 self.sample_emitter(b, k, seed, pass_idx, offset)
             if self.env_dist is not None:
@@ -265,6 +327,8 @@ class PathArrayRenderer(ArrayRenderer):
                     self.measured_table.eval_t(b["mat"], b["wi"], b["wo"], b["wl"], tint=self.plugin.albedo, out_o=b["f_o"],
                                                out_l=b["f_l"])
             # (no material lane: only floor vertices are left, which read neither the sampler's nor the evaluator's arrays)
-            self.bounce(b, k, k == self.max_depth - 1, seed, pass_idx, offset)
+            self.bounce(b, k, k == depth - 1, seed, pass_idx, offset)
         self.stats["lanes_per_bounce"] = lanes
+        self.stats["depth"] = len(lanes)
+        self.stats["depth_cap_hit"] = self.max_depth is None and len(lanes) == depth
         self.resolve(row_begin, row_end, spp, b, film)

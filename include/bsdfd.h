@@ -45,7 +45,8 @@ extern "C" {
  *      bsdfd_wf_sample_emitter() and bsdfd_wf_bounce_lit(), which take a struct of their own, bsdfd_wf_lights: point emitters
  *      in the array scene;
  *      bsdfd_env_sample(), bsdfd_env_pdf(), bsdfd_wf_sample_env() and bsdfd_wf_bounce_env(), which take a struct of their own,
- *      bsdfd_env_dist: importance sampling of the environment map in the array scene. */
+ *      bsdfd_env_dist: importance sampling of the environment map in the array scene;
+ *      bsdfd_wf_bounce_rr(): Russian roulette inside the bounce of the array scene. */
 #define BSDFD_ABI_VERSION 8
 
 #define BSDFD_OK 0
@@ -589,6 +590,30 @@ int bsdfd_wf_bounce_env(const bsdfd_wf_scene* scene, const float* env, int32_t b
                         float* wl, int64_t* material, float* beta, float* rad, const float* wo, const float* pdf_o,
                         const float* pdf_l, const float* f_o, const float* f_l, const bsdfd_wf_lights* lights,
                         const int32_t* lsel, const float* emit, const float* lpdf, const bsdfd_env_dist* dist, void* hip_stream);
+
+/* ---- Russian roulette in the array scene (csrc/pathrr.hip) ------------------------------------------
+ * Six of the reference's array scenes are rendered by Mitsuba's `path` integrator at max_depth = -1 with its default rr_depth = 5.
+ * Mitsuba's rule (the `path` integrator's `rr_depth` parameter): once  depth >= rr_depth  — depth = the surface vertices processed so far, here bounce + 1 —
+ * a path continues with probability  q = min(max over the channels of throughput * eta^2, 0.95)  and its throughput is divided
+ * by q.  This is that rule restated (eta = 1; the throughput is the one after this vertex, beta * f / pdf); it is NOT pinned to
+ * Mitsuba's random stream or images.
+ *
+ * bsdfd_wf_bounce_rr is bsdfd_wf_bounce, bsdfd_wf_bounce_lit or bsdfd_wf_bounce_env with that rule inside the kernel:
+ *   dist == NULL, lights == NULL : bsdfd_wf_bounce     (lsel, emit, lpdf are not read)
+ *   dist == NULL, lights given   : bsdfd_wf_bounce_lit (lpdf is not read)
+ *   dist given                   : bsdfd_wf_bounce_env
+ * and every check of the chosen call applies; rr_depth >= 1.  While bounce + 1 < rr_depth, and whenever `last` is set, every
+ * array is written exactly as by that call and no variate is drawn.  From then on a path that would continue draws
+ * u = (word 0 >> 8) * 2^-24  of  philox4x32(key = seed, counter = (global path index lo, hi, pass, 0x526F756C + bounce))  and
+ * continues iff q is a positive number and u < q, with beta *= (f_o / pdf_o) / q; otherwise it ends like a path that escaped:
+ * material = n_balls + 1, nothing else written.  rad does not depend on the roulette, nor do org, nrm, wi, wl, material of a
+ * path that survives. */
+int bsdfd_wf_bounce_rr(const bsdfd_wf_scene* scene, const float* env, int32_t bounce, int32_t last, int32_t occlusion,
+                       uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, float* org, float* nrm, float* wi,
+                       float* wl, int64_t* material, float* beta, float* rad, const float* wo, const float* pdf_o,
+                       const float* pdf_l, const float* f_o, const float* f_l, const bsdfd_wf_lights* lights,
+                       const int32_t* lsel, const float* emit, const float* lpdf, const bsdfd_env_dist* dist, int32_t rr_depth,
+                       void* hip_stream);
 
 const char* bsdfd_last_error(void);
 const char* bsdfd_version(void);

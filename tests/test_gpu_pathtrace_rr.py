@@ -1,0 +1,411 @@
+"""GPU tests of Russian roulette and unbounded depth in the array-scene path tracer: ``bsdfd_wf_bounce_rr`` (csrc/pathrr.hip) row
+by row against the three existing bounce calls and against tests/pathtrace_rr_ref.py, and ``PathArrayRenderer(..., rr_depth=,
+max_depth=None)`` as whole recorded passes against ``pathtrace_rr_ref.reference_pass_rr``, at the depth cap, and in the mean.
+
+The kernel tests run on ONE wavefront for all modes: ``pathtrace_ref.synthetic_vertices`` with the throughputs of
+``pathtrace_rr_ref.rr_wavefront`` (tests/test_pathtrace_rr_cpu.py shows it is fit for purpose), the emitter arrays of LIT and ENV
+from the references of ``sample_emitter`` / ``sample_env`` on it.  ``rad`` and where a survivor goes are compared bit for bit with
+the non-RR call on the same inputs, so nothing here depends on how well those calls match their own references (their tests do)."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+import envmap_ref as ER  # noqa: E402
+import pass_replay as PR  # noqa: E402
+import pathtrace_lights_ref as LR  # noqa: E402
+import pathtrace_ref as R  # noqa: E402
+import pathtrace_rr_ref as RR  # noqa: E402
+from test_gpu_envmap import _dist  # noqa: E402
+from test_gpu_pathtrace import _array, _scene_renderer, _shade_bound, _to_device  # noqa: E402
+from test_gpu_pathtrace_lights import _device_lights  # noqa: E402
+from test_pass_replay_cpu import five_ball_lights  # noqa: E402
+from test_pathtrace_cpu import STATE  # noqa: E402
+from test_pathtrace_rr_cpu import UNBIASED, rr_vertices  # noqa: E402
+
+SEED, PASS, OFFSET = 0x1234567890ABCDEF, 3, RR.OFFSET      # (the path index crosses 2^32 at row 100)
+MODES = ("cosine", "lit", "env", "env+lights")
+OUT = ("org", "nrm", "wi", "wl", "mat", "beta", "rad")
+SCENE = R.SYNTH_SCENE
+N_B = len(SCENE["spheres"])
+
+
+@functools.lru_cache(maxsize=None)
+def _inputs(mode, with_f, tail=0):
+    """The wavefront of ``mode``: the state and the sampler's answers [+ lsel, emit, lpdf], fp32 / int, shared by the tests (nobody writes them).  ``tail``: that many
+    more rows, copied from the head."""
+    v = dict(rr_vertices(with_f))
+    env = R.synthetic_env()
+    vertex = [v[k] for k in ("org", "nrm", "wi", "material")]
+    if "lit" in mode or "lights" in mode:
+        s = LR.sample_emitter(SCENE, LR.synthetic_lights(), True, 1, True, SEED, PASS, OFFSET, *vertex, v["wl"])
+        v.update(wl=s["wl"].astype(np.float32), lsel=s["lsel"], emit=s["emit"].astype(np.float32))
+    if "env" in mode:
+        lsel = v.get("lsel")
+        s = ER.sample_env(SCENE, env, ER.build_tables(env), 4 if lsel is not None else 1, 1, True, SEED, PASS, OFFSET, *vertex, lsel, v["wl"])
+        picked = s["picked"]
+        v.update(wl=np.where(picked[:, None], s["wl"], v["wl"]).astype(np.float32), lpdf=np.where(picked, s["lpdf"], 0.0).astype(np.float32),
+                 emit=np.where(picked[:, None], s["emit"], v.get("emit", np.zeros((len(picked), 3)))).astype(np.float32))
+    if tail:
+        v = {k: np.concatenate([a, a[:tail]]) for k, a in v.items()}
+    return v
+
+
+@functools.lru_cache(maxsize=None)
+def _env_dist():
+    return _dist(R.synthetic_env())
+
+
+@functools.lru_cache(maxsize=None)
+def _reference(bounce, with_f, tail):
+    """``pathtrace_rr_ref.bounce_rr`` (rr_depth = 1, last = 0) of the cosine wavefront.  Which rows continue, and what the roulette
+    decides, is the same in every mode: the emitter stages move ``wl`` on ball rows only, which ``rad`` alone reads."""
+    v = _inputs("cosine", with_f, tail)
+    return RR.bounce_rr(SCENE, R.synthetic_env(), 1, bounce, False, True, SEED, PASS, OFFSET, *[v.get(k) for k in STATE])
+
+
+def _call(r, v, mode, bounce, last, rr_depth):
+    """One bounce call on a fresh device copy of ``v`` -> {name: numpy array} of the seven arrays it may write."""
+    b = _to_device(r, v)
+    lights = _device_lights(LR.synthetic_lights(), 1) if ("lit" in mode or "lights" in mode) else None
+    r.bounce(b, bounce, bool(last), SEED, PASS, OFFSET, occlusion=True, lights=lights,
+             env_dist=_env_dist() if "env" in mode else None, rr_depth=rr_depth)
+    torch.cuda.synchronize()
+    return {k: b[k].cpu().numpy() for k in OUT}
+
+
+def _same_bits(a, b):
+    return a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+@pytest.fixture(scope="module")
+def renderer():
+    return _scene_renderer(SCENE, R.synthetic_env())
+
+
+@pytest.mark.parametrize("with_f", [True, False])
+@pytest.mark.parametrize("bounce", [0, 2])
+@pytest.mark.parametrize("mode", MODES)
+def test_inactive_roulette_is_the_existing_entry_point_bit_for_bit(renderer, mode, bounce, with_f):
+    """rr_depth = bounce + 2: the vertex is one short of the roulette.  Every array bsdfd_wf_bounce_rr writes equals what
+    bsdfd_wf_bounce / _lit / _env writes on the same inputs."""
+    v = _inputs(mode, with_f)
+    plain, rr = _call(renderer, v, mode, bounce, 0, None), _call(renderer, v, mode, bounce, 0, bounce + 2)
+    for k in OUT:
+        assert _same_bits(plain[k], rr[k]), k
+    assert ((plain["mat"] <= N_B) & (v["material"] <= N_B)).sum() > 900          # (paths do continue)
+
+
+def _check_active(renderer, mode, bounce, last, with_f, tail=0):
+    v = _inputs(mode, with_f, tail)
+    n = len(v["material"])
+    plain, rr = _call(renderer, v, mode, bounce, last, None), _call(renderer, v, mode, bounce, last, 1)
+    assert _same_bits(plain["rad"], rr["rad"])                                       # roulette never touches rad
+    live = (v["material"] >= 0) & (v["material"] <= N_B)
+    would = live & (plain["mat"] <= N_B)
+    if last:
+        for k in OUT:
+            assert _same_bits(plain[k], rr[k]), k
+        assert not would.any()
+        return
+    for k in OUT:                                                                    # rows that end anyway, and ended paths
+        assert _same_bits(plain[k][~would], rr[k][~would]), k
+    # the decision, row by row, from the kernel's own inputs in fp64
+    thr = RR.throughput_factor(SCENE, v["wi"], v["material"], v["pdf_o"], v.get("f_o"))
+    u, q, ok = RR.roulette(v["beta"], thr, SEED, PASS, bounce, OFFSET, n)
+    survive = would & (rr["mat"] <= N_B)
+    killed = would & ~survive
+    assert (rr["mat"][killed] == N_B + 1).all()
+    wrong = would & (survive != ok)
+    print(f"{mode} bounce={bounce} f={with_f} rows={n}: {int(would.sum())} would continue, {int(survive.sum())} survive, "
+          f"{int((would & (q == 0)).sum())} with q = 0, {int(wrong.sum())} decided differently from the reference")
+    assert not wrong.any()
+    assert survive.sum() > 250 and killed.sum() > 500
+    for k, name in (("org", "org"), ("nrm", "nrm"), ("wi", "wi"), ("wl", "wl"), ("beta", "beta")):
+        assert _same_bits(rr[k][killed], v[name][killed]), k                         # a killed path keeps its input bits
+    for k in ("org", "nrm", "wi", "wl", "mat"):
+        assert _same_bits(rr[k][survive], plain[k][survive]), k                      # a survivor goes where it went
+    with np.errstate(all="ignore"):
+        want = v["beta"].astype(np.float64) * thr / q[:, None]
+    err = np.abs(rr["beta"][survive] - want[survive]).max()
+    print(f"  beta of the survivors: max error {err:.2e}, largest {want[survive].max():.3g}")
+    assert np.isfinite(rr["beta"][survive]).all() and err < 2e-5                     # test_bounce_kernel_matches_reference's bound
+    # ... and the whole call is the reference's: the same rows continue (all but the 0.1 % test_bounce_kernel_matches_reference
+    # allows the geometry), the same of them survive
+    ref = _reference(bounce, with_f, tail)
+    agree = would & ref["would"]
+    assert (would != ref["would"]).sum() <= n // 1000 and np.array_equal(survive[agree], ref["survive"][agree])
+
+
+@pytest.mark.parametrize("with_f", [True, False])
+@pytest.mark.parametrize("last", [0, 1])
+@pytest.mark.parametrize("bounce", [0, 2])
+@pytest.mark.parametrize("mode", MODES)
+def test_active_roulette_matches_the_reference(renderer, mode, bounce, last, with_f):
+    """rr_depth = 1 on 4096 vertices: rad is the non-RR call's, the survive / kill decision is the reference's on every row, a killed
+    row carries the miss id and its input bits, a survivor the non-RR call's bits and beta thr / q; last = 1 is the non-RR call."""
+    _check_active(renderer, mode, bounce, last, with_f)
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_a_row_count_that_is_no_multiple_of_the_block(renderer, mode):
+    """4096 + 37 rows (17 blocks, the last one 37 lanes full), the tail copied from the head: the tail rows are paths of their own
+    (other variates), decided like the reference decides them."""
+    _check_active(renderer, mode, 2, 0, True, tail=37)
+    v = _inputs(mode, True, 37)
+    u = RR.variates(SEED, PASS, 2, OFFSET, len(v["material"]))
+    assert not np.array_equal(u[:37], u[4096:])
+
+
+# ---- whole passes ---------------------------------------------------------------------------------------------------------------
+W, H, SPP, PASS_SEED, FILL, RR_DEPTH = 120, 90, 1, 4, 0.25, 2
+
+
+def _sky():
+    from bsdf_diffusion_sampling_amd.wavefront import make_sky
+    return make_sky(64, 128, seed=5)
+
+
+def _pass_renderer(emitters, max_depth, **more):
+    from bsdf_diffusion_sampling_amd.pathtrace import PointLight
+    kw = dict(max_depth=max_depth, rr_depth=RR_DEPTH)
+    kw.update(more)
+    if emitters == "importance+lights":
+        lights = five_ball_lights()
+        kw.update(env_sampling="importance",
+                  lights=[PointLight(tuple(p), tuple(i)) for p, i in zip(lights["position"].tolist(), lights["intensity"].tolist())])
+    return _array(kw, w=W, h=H, env=_sky(), low_camera=True)
+
+
+@functools.lru_cache(maxsize=None)
+def _recorded(emitters, max_depth):
+    r = _pass_renderer(emitters, max_depth)
+    film = torch.full((H, W, 3), FILL, dtype=torch.float32, device=r.device)
+    with PR.Recorder(r) as rec:
+        r.render_pass(film, 0, H, SPP, PASS_SEED, 0)
+    torch.cuda.synchronize()
+    k = 0
+    for s in rec.stages:
+        s["k"] = k
+        k += s["name"] == "bounce"
+    lit = emitters == "importance+lights"
+    env = _sky().numpy()
+    return dict(r=r, stages=rec.stages, stats=dict(r.stats), scene=PR.scene_of(r), env=env, lit=lit,
+                tables=ER.build_tables(env) if lit else None, lights=five_ball_lights() if lit else None, n_b=len(r.table), n=H * W * SPP)
+
+
+def _near_cell(rec, snap):
+    """tests/test_gpu_pass_replay.py::_near_cell: live rows whose environment-density lookup lies within 1e-3 cells of a cell
+    boundary, where the fp32 kernel may read the neighbouring cell's density."""
+    n_b, mat = rec["n_b"], snap["mat"]
+    live = (mat >= 0) & (mat <= n_b)
+    fs, ft, nn = LR._frames(snap["nrm"].astype(np.float64), live, np.float64)
+    local = np.where((mat == n_b)[:, None], snap["wl"], snap["wo"]).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        edge = ER.cell_of(rec["tables"]["pdf_uv"].shape, local[:, 0:1] * fs + local[:, 1:2] * ft + local[:, 2:3] * nn)[3]
+    return live & ~(edge >= 1e-3)
+
+
+@pytest.mark.parametrize("max_depth", [6, None])
+@pytest.mark.parametrize("emitters", ["cosine", "importance+lights"])
+def test_recorded_pass_matches_reference_pass_rr(emitters, max_depth):
+    """One recorded pass, 120x90, 1 spp, rr_depth = 2: the stages come in the documented order, every bounce is held to
+    ``pathtrace_rr_ref.bounce_rr`` on the device's own input with the bounds of tests/test_gpu_pass_replay.py::_check_bounce, the
+    whole pass to ``reference_pass_rr`` with the recorded answers of the sampler as
+    test_pass_matches_the_free_running_reference_pass does; the loop ends with no live lane."""
+    rec = _recorded(emitters, max_depth)
+    r, n_b, n, scene, lit = rec["r"], rec["n_b"], rec["n"], rec["scene"], rec["lit"]
+    named = lambda name: [s for s in rec["stages"] if s["name"] == name]
+    bounces, buckets = named("bounce"), named("bucket")
+    depth = len(bounces)
+    cap = r.DEPTH_CAP if max_depth is None else max_depth
+    # the order of the stages, the scalars of the bounces, the statistics
+    want = ["primary", "path_begin"]
+    for k in range(depth):
+        want += ["sample_emitter", "sample_env"] * lit + ["bucket", "sample_pdf"] * 1 + ["bounce"]
+    if depth < cap:
+        want += ["sample_emitter", "sample_env"] * lit + ["bucket"]                 # the bucketing that found no live lane
+    got = [s["name"] for s in rec["stages"]]
+    lanes = rec["stats"]["lanes_per_bounce"]
+    print(f"{emitters} max_depth={max_depth}: {depth} bounces, material lanes {lanes}")
+    if all(lanes):                                                                   # (a bounce without material lanes skips the sampler)
+        assert got == want + ["resolve"]
+    assert rec["stats"]["depth"] == len(lanes) == depth and rec["stats"]["depth_cap_hit"] is False
+    assert 2 <= depth <= cap and (max_depth is not None or depth < 64)
+    for s in bounces:
+        assert s["args"] == dict(bounce=s["k"], last=s["k"] == cap - 1, seed=PASS_SEED, pass_idx=0, path_offset=0, occlusion=True)
+    final = named("resolve")[0]
+    assert (final["before"]["mat"] > n_b).all()                                      # the loop ended with no live lane
+    if depth < cap:
+        assert sum(buckets[-1]["counts"][:n_b + 1]) == 0 and len(buckets) == depth + 1
+    # every bounce against the reference on the device's own input
+    names = ("org", "nrm", "wi", "wl", "mat", "beta", "rad", "wo", "pdf_o", "pdf_l")
+    killed_total = decisions = 0
+    for s in bounces:
+        v, out = s["before"], s["after"]
+        ref = RR.bounce_rr(scene, rec["env"], RR_DEPTH, s["k"], s["args"]["last"], True, PASS_SEED, 0, 0, *[v[k] for k in names], None, None,
+                           n_e=4 if lit else 1, has_env=True, lsel=v["lsel"] if lit else None, emit=v.get("emit"), lpdf=v.get("lpdf"),
+                           tables=rec["tables"])
+        live = (v["mat"] >= 0) & (v["mat"] <= n_b)
+        for k in OUT:                                                                # ended paths: not a byte of their state moves
+            assert out[k][~live].tobytes() == v[k][~live].tobytes(), k
+        differ = live & (PR.decision_code(scene, out["mat"], out["wi"]) != PR.decision_code(scene, ref["material"], ref["wi"]))
+        assert differ.sum() <= live.sum() // 1000, (s["k"], int(differ.sum()), int(live.sum()))
+        same = live & ~differ
+        cont = same & (ref["material"] <= n_b)
+        if s["k"] + 1 < RR_DEPTH:
+            assert not ref["killed"].any()
+        killed_total += int((same & ref["killed"]).sum())
+        decisions += int((same & ref["would"]).sum()) * (s["k"] + 1 >= RR_DEPTH and not s["args"]["last"])
+        if cont.any():
+            t = np.linalg.norm(ref["org"] - v["org"].astype(np.float64), axis=1)
+            far = cont & (ref["material"] == n_b) & (t > 50.0)
+            graze = cont & (ref["cos_in"] < 0.1)
+            ok = cont & ~graze
+            for k in ("org", "nrm", "wi", "beta"):
+                err = np.abs(out[k] - ref[k]).max(1)
+                rows = cont & ~far if k == "org" else cont
+                assert err[ok & rows].max(initial=0.0) < 2e-5 and err[rows].max(initial=0.0) < 2e-3, (s["k"], k)
+            if far.any():
+                err = np.abs(out["org"] - ref["org"]).max(1)[far]
+                assert (err <= 2e-5 + 2.0 ** -22 * t[far] / ref["cos_in"][far]).all()
+            assert np.abs(out["wl"][cont] - R.next_wl(PASS_SEED, 0, s["k"], 0, n)[cont]).max() < 2e-6
+        ended = same & ~cont                                                         # rows that end — killed ones too — keep their state
+        for k in ("org", "nrm", "wi", "wl", "beta"):
+            assert out[k][ended].tobytes() == v[k][ended].tobytes(), k
+        rows = same & ~_near_cell(rec, v) if lit else same
+        if rows.any():
+            p999, worst = _shade_bound(out["rad"][rows], ref["rad"][rows])
+            assert np.isfinite(out["rad"][live]).all() and p999 < 2e-4 and worst < 5e-3, (s["k"], p999, worst)
+    # (not vacuous: q <= 0.95, so a decision ends the path with probability >= 0.05 — half of that, and a hundred paths, at least)
+    print(f"  {decisions} roulette decisions, {killed_total} paths killed")
+    assert killed_total >= 100 and killed_total >= 0.025 * decisions
+    # end to end
+    answers = [{k: s["before"][k] for k in ("wo", "pdf_o", "pdf_l")} for s in bounces]
+    ref = RR.reference_pass_rr(scene, rec["env"], "importance" if lit else "cosine", rec["lights"], rec["tables"], 0, H, SPP, PASS_SEED, 0,
+                               max_depth, RR_DEPTH, True, answers)
+    codes = lambda snap: PR.decision_code(scene, snap["mat"], snap["wi"])
+    history = [codes(named("primary")[0]["after"])] + [codes(s["after"]) for s in bounces]
+    differ = PR.histories_differ(history, ref["history"])
+    assert differ.sum() <= n // 1000
+    if differ.sum() == 0:
+        assert ref["depth"] == depth and ref["depth_cap_hit"] is False
+    agree = ~differ
+    if lit:
+        agree &= ~np.any([_near_cell(rec, s["before"]) for s in bounces], axis=0)
+    rad = final["before"]["rad"]
+    p999, worst = _shade_bound(rad[agree], ref["rad"][agree])
+    print(f"  histories differ on {int(differ.sum())} of {n} paths, {int(agree.sum())} compared; rad p99.9 {p999:.1e} max {worst:.1e}")
+    assert np.isfinite(rad).all() and p999 < 2e-4 and worst < 5e-3
+    film = final["film_after"].astype(np.float64)
+    want_film = FILL + R.resolve(rad, SPP)
+    assert (final["film_before"] == FILL).all() and np.abs(film.reshape(-1, 3) - want_film).max() < 1e-5 * max(1.0, want_film.max())
+
+
+def test_depth_cap_truncates_like_max_depth(monkeypatch):
+    """DEPTH_CAP = 3 with max_depth=None: the bounce at the cap is the last one, stats say so, and the film is max_depth=3's."""
+    from bsdf_diffusion_sampling_amd.pathtrace import PathArrayRenderer
+    monkeypatch.setattr(PathArrayRenderer, "DEPTH_CAP", 3)
+    capped, fixed = _pass_renderer("cosine", None), _pass_renderer("cosine", 3)
+    a, b = capped.render(2, spp=2, seed=7), fixed.render(2, spp=2, seed=7)
+    torch.cuda.synchronize()
+    assert capped.stats["depth"] == 3 and capped.stats["depth_cap_hit"] is True and len(capped.stats["lanes_per_bounce"]) == 3
+    assert fixed.stats["depth"] == 3 and fixed.stats["depth_cap_hit"] is False
+    assert torch.equal(a, b) and float(a.mean()) > 0
+    monkeypatch.undo()
+    free = _pass_renderer("cosine", None)
+    free.render(1, spp=2, seed=7)
+    assert free.stats["depth"] > 3 and free.stats["depth_cap_hit"] is False
+
+
+@pytest.mark.parametrize("emitters", ["cosine", "importance+lights"])
+def test_without_rr_depth_no_bounce_rr_call_is_made(monkeypatch, emitters):
+    from bsdf_diffusion_sampling_amd import _lib
+    L = _lib.lib()
+    calls = {"rr": 0}
+    inner = L.bsdfd_wf_bounce_rr
+
+    def spy(*args):
+        calls["rr"] += 1
+        return inner(*args)
+    monkeypatch.setattr(L, "bsdfd_wf_bounce_rr", spy)
+    r = _pass_renderer(emitters, 4, rr_depth=None)
+    assert r.rr_depth is None
+    img = r.render(1, spp=1, seed=PASS_SEED)
+    assert calls["rr"] == 0 and float(img.mean()) > 0
+    rr = _pass_renderer(emitters, 4)
+    rr.render(1, spp=1, seed=PASS_SEED)
+    assert calls["rr"] == rr.stats["depth"] > 0                                    # ... and with it every bounce is one
+
+
+def test_roulette_is_unbiased_in_the_mean():
+    """rr_depth = 1 against rr_depth = None, both at max_depth = 6, on a scene where the roulette kills often (albedo <= 0.5, floor
+    0.4 / 0.2, unit environment): 64 independent passes at 4 spp each, different seeds.  Per channel the image means differ by at most
+    4 sqrt(se_a^2 + se_b^2), the standard errors from the per-pass image means of the two runs themselves.
+    tests/test_pathtrace_rr_cpu.py::test_leaving_out_the_division_moves_the_mean shows the power: without the 1/q the mean moves
+    by more than ten times this tolerance."""
+    w, h, spp, passes = UNBIASED["w"], UNBIASED["h"], UNBIASED["spp"], UNBIASED["passes"]
+    env = torch.ones((8, 16, 3))
+    means, killed = {}, 0
+    for name, rr_depth, seed in (("rr", 1, 21), ("plain", None, 22)):
+        r = _array(dict(max_depth=UNBIASED["max_depth"], rr_depth=rr_depth), w=w, h=h, env=env, low_camera=True, albedo=UNBIASED["albedo"])
+        film = torch.zeros((h, w, 3), device=r.device)
+        per_pass = []
+        for p in range(passes):
+            film.zero_()
+            r.render_pass(film, 0, h, spp, seed, p)
+            per_pass.append(film.double().mean((0, 1)).cpu().numpy())
+        means[name] = np.array(per_pass)
+        means[name + "_lanes"] = list(r.stats["lanes_per_bounce"])
+    a, b = means["rr"], means["plain"]
+    se = lambda x: x.std(0, ddof=1) / np.sqrt(len(x))
+    tolerance = 4.0 * np.sqrt(se(a) ** 2 + se(b) ** 2)
+    diff = a.mean(0) - b.mean(0)
+    print(f"image mean with roulette {a.mean(0)}, without {b.mean(0)}, difference {diff}, tolerance {tolerance}; material lanes per bounce "
+          f"{means['rr_lanes']} against {means['plain_lanes']}")
+    assert sum(means["rr_lanes"][1:]) < 0.7 * sum(means["plain_lanes"][1:])         # (the roulette does kill often)
+    assert (np.abs(diff) <= tolerance).all()
+
+
+def test_errors(renderer):
+    from bsdf_diffusion_sampling_amd import _lib
+    L, p = _lib.lib(), (lambda t: C.c_void_p(t.data_ptr()))
+    r = renderer
+    v = _inputs("env+lights", True)
+    n = len(v["material"])
+    b = _to_device(r, v)
+    before = {k: t.clone() for k, t in b.items()}
+    state = [p(b["mat" if k == "material" else k]) for k in STATE]
+    lt = _device_lights(LR.synthetic_lights(), 1)
+    dist = _dist(R.synthetic_env())
+    good = dist.struct(r.device)
+
+    def call(rr_depth, lights, lsel, emit, lpdf, d, count=n, arrays=state, env=p(r.env)):
+        return L.bsdfd_wf_bounce_rr(C.byref(r.scene), env, 0, 0, 1, 0, 0, 0, count, *arrays, lights, lsel, emit, lpdf, d, rr_depth, None)
+    for bad in (0, -3):
+        assert call(bad, None, None, None, None, None) == 1 and b"rr_depth must be >= 1" in L.bsdfd_last_error()
+    assert call(1, C.byref(lt), None, p(b["emit"]), None, None) == 1 and b"null pointer" in L.bsdfd_last_error()      # lights without lsel
+    assert call(1, None, None, p(b["emit"]), None, C.byref(good)) == 1 and b"null pointer" in L.bsdfd_last_error()    # dist without lpdf
+    assert call(1, C.byref(lt), None, p(b["emit"]), p(b["lpdf"]), C.byref(good)) == 1 and b"both NULL or both given" in L.bsdfd_last_error()
+    bad_lights = _device_lights(LR.synthetic_lights(), 1)
+    bad_lights.n_lights = 9
+    assert call(1, C.byref(bad_lights), p(b["lsel"]), p(b["emit"]), None, None) == 1 and b"point lights" in L.bsdfd_last_error()
+    assert L.bsdfd_wf_bounce_rr(C.byref(r.scene), p(r.env), -1, 0, 1, 0, 0, 0, n, *state, None, None, None, None, None, 1, None) == 1
+    assert b"bounce must be >= 0" in L.bsdfd_last_error()
+    missing = list(state)
+    missing[4] = None
+    assert call(1, None, None, None, None, None, arrays=missing) == 1 and b"null pointer" in L.bsdfd_last_error()
+    assert call(1, None, None, None, None, None, env=None) == 1
+    # N = 0: a no-op, in every mode
+    none = [None] * len(state)
+    assert call(1, None, None, None, None, None, count=0, arrays=none, env=None) == 0
+    assert call(1, C.byref(lt), None, None, None, None, count=0, arrays=none, env=None) == 0
+    assert call(1, None, None, None, None, C.byref(good), count=0, arrays=none, env=None) == 0
+    assert call(0, None, None, None, None, None, count=0, arrays=none, env=None) == 1
+    torch.cuda.synchronize()
+    for k, t in b.items():                                                           # nothing ran
+        assert t.dtype == before[k].dtype and t.cpu().numpy().tobytes() == before[k].cpu().numpy().tobytes(), k

@@ -19,6 +19,14 @@ the cosine renderer at the same depths.  Both trace the same vertices; the diffe
 with device events too) plus what bounce_env costs over bounce.  At depth 1 the per-path radiance variance of both renderers
 (within a pixel, over its spp paths, averaged over the pixels) is recorded next to the times: variance x time is the figure of
 merit.
+
+``--rr-depth R`` measures Russian roulette and unbounded depth -> profiles/pathtrace_rr.json, rounds interleaved the same way:
+  (a) PathArrayRenderer(rr_depth=9) — bsdfd_wf_bounce_rr's kernels with the roulette never active — at max_depth 4 / 8 against
+      rr_depth=None at the same depths: what the RR instantiations cost, next to the non-RR variant's own round-to-round spread
+      (max - min over the rounds) in this run;
+  (b) PathArrayRenderer(max_depth=None, rr_depth=R): ms per pass, the depth reached and the lanes per bounce, next to the fixed
+      depths 8 and 16 without roulette;
+  (c) the per-path radiance variance (as above) x time of (b) against those fixed depths.
 """
 import argparse
 import json
@@ -41,21 +49,32 @@ ap.add_argument("--rounds", type=int, default=9); ap.add_argument("--passes", ty
 ap.add_argument("--lights", type=int, default=0, help="measure N point lights against the unlit renderer instead")
 ap.add_argument("--env-sampling", choices=("cosine", "importance"), default="cosine",
                 help="importance: measure the importance-sampled environment against the cosine renderer instead")
+ap.add_argument("--rr-depth", type=int, default=None, metavar="R",
+                help="measure Russian roulette from the R-th vertex on, and unbounded depth, against fixed depths instead")
 ap.add_argument("--out", default=None, help="default: profiles/pathtrace.json, pathtrace_lights.json with --lights, "
-                                            "pathtrace_envis.json with --env-sampling importance")
+                                            "pathtrace_envis.json with --env-sampling importance, pathtrace_rr.json with --rr-depth")
 a = ap.parse_args()
 envis = a.env_sampling == "importance"
-if envis and a.lights:
-    sys.exit("--lights and --env-sampling importance are measured one at a time")
+if (envis and a.lights) or (a.rr_depth is not None and (envis or a.lights)):
+    sys.exit("--lights, --env-sampling importance and --rr-depth are measured one at a time")
 a.out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "pathtrace_envis.json" if envis else "pathtrace_lights.json" if a.lights else "pathtrace.json")
+                              "pathtrace_rr.json" if a.rr_depth is not None else "pathtrace_envis.json" if envis
+                              else "pathtrace_lights.json" if a.lights else "pathtrace.json")
 if not torch.cuda.is_available():
     sys.exit("tools/pathtrace_bench.py measures on the GPU: no device visible")
 
 cam, centers, radii = WF.array0_scene(a.width, a.height)
 table = MaterialTable([m + "_" + a.domain for m in WF.ARRAY0_MATERIALS])
 LIT_DEPTHS = (1, 2, 4)
-if a.lights:   # (LIT_DEPTHS: the depths of the two A/B modes)
+RR_INACTIVE = 9   # an rr_depth the depths 4 and 8 never reach: the RR kernels without a single decision
+if a.rr_depth is not None:
+    variants = {}
+    for d in (4, 8):
+        variants[f"plain_d{d}"] = PathArrayRenderer(table, centers, radii, camera=cam, max_depth=d)
+        variants[f"rr_inactive_d{d}"] = PathArrayRenderer(table, centers, radii, camera=cam, max_depth=d, rr_depth=RR_INACTIVE)
+    variants["plain_d16"] = PathArrayRenderer(table, centers, radii, camera=cam, max_depth=16)
+    variants["unbounded_rr"] = PathArrayRenderer(table, centers, radii, camera=cam, max_depth=None, rr_depth=a.rr_depth)
+elif a.lights:   # (LIT_DEPTHS: the depths of the two A/B modes)
     from bsdf_diffusion_sampling_amd.pathtrace import PointLight
     # the reference's emitter (position 0, 4, 5 in its z-up frame, intensity 200), further ones on a circle at the same height
     lights = [PointLight((4.0 * np.sin(2 * np.pi * k / a.lights), 5.0, -4.0 * np.cos(2 * np.pi * k / a.lights)), 200.0)
@@ -107,6 +126,47 @@ def write(res):
     print(json.dumps(res))
 
 
+def path_variance(r, passes=5):
+    """Mean over pixels and passes of the variance (ddof = 1) of the channel-averaged radiance over a pixel's spp paths."""
+    n_paths = a.width * a.height * a.spp
+    out = []
+    for k in range(passes):
+        r.render_pass(film, 0, a.height, a.spp, 0, 2000 + k)
+        torch.cuda.synchronize(dev)
+        rad = r._buffers(n_paths)["rad"].mean(1).reshape(-1, a.spp).double()
+        out.append(float(rad.var(dim=1, unbiased=True).mean()))
+    return float(np.mean(out))
+
+
+if a.rr_depth is not None:
+    res.update(rr_depth=a.rr_depth, rr_depth_inactive=RR_INACTIVE, inactive={}, unbounded={})
+    for d in (4, 8):
+        plain, rr = times[f"plain_d{d}"], times[f"rr_inactive_d{d}"]
+        res["inactive"][str(d)] = {"plain_pass_ms_median": med[f"plain_d{d}"], "rr_inactive_pass_ms_median": med[f"rr_inactive_d{d}"],
+                                   "extra_ms": med[f"rr_inactive_d{d}"] - med[f"plain_d{d}"],
+                                   "plain_round_to_round_spread_ms": float(max(plain) - min(plain)),
+                                   "rr_inactive_round_to_round_spread_ms": float(max(rr) - min(rr)),
+                                   "within_spread": bool(med[f"rr_inactive_d{d}"] - med[f"plain_d{d}"] <= max(plain) - min(plain))}
+    r = variants["unbounded_rr"]
+    depths, lanes = [], None
+    for k in range(a.passes):
+        r.render_pass(film, 0, a.height, a.spp, 0, 1000 + k)
+        depths.append(r.stats["depth"])
+        lanes = r.stats["lanes_per_bounce"]
+    torch.cuda.synchronize(dev)
+    res["unbounded"] = {"pass_ms_median": med["unbounded_rr"], "depth_reached_median": float(np.median(depths)),
+                        "depth_reached_max": int(max(depths)), "depth_cap_hit": bool(r.stats["depth_cap_hit"]),
+                        "lanes_per_bounce_last_pass": lanes,
+                        "fixed_depth_pass_ms_median": {"8": med["plain_d8"], "16": med["plain_d16"]},
+                        "fixed_depth_lanes_per_bounce_last_pass": {"8": variants["plain_d8"].stats["lanes_per_bounce"],
+                                                                   "16": variants["plain_d16"].stats["lanes_per_bounce"]}}
+    var = {name: path_variance(variants[name]) for name in ("unbounded_rr", "plain_d8", "plain_d16")}
+    res["per_path_variance"] = var
+    res["variance_x_ms"] = {name: v * med[name] for name, v in var.items()}
+    res["variance_x_ms_unbounded_over_fixed"] = {d: res["variance_x_ms"]["unbounded_rr"] / res["variance_x_ms"][f"plain_d{d}"]
+                                                 for d in ("8", "16")}
+    write(res)
+    sys.exit(0)
 if a.lights:
     res.update(point_lights=a.lights, environment="black, no emitter", occlusion=True, depth={})
     for d in LIT_DEPTHS:
@@ -140,17 +200,6 @@ if a.lights:
 if envis:
     env = variants["importance_d1"].env
     res.update(environment=f"make_sky {env.shape[0]}x{env.shape[1]}", occlusion=True, depth={})
-    n_paths = a.width * a.height * a.spp
-
-    def path_variance(r, passes=5):
-        """Mean over pixels and passes of the variance (ddof = 1) of the channel-averaged radiance over a pixel's spp paths."""
-        out = []
-        for k in range(passes):
-            r.render_pass(film, 0, a.height, a.spp, 0, 2000 + k)
-            torch.cuda.synchronize(dev)
-            rad = r._buffers(n_paths)["rad"].mean(1).reshape(-1, a.spp).double()
-            out.append(float(rad.var(dim=1, unbiased=True).mean()))
-        return float(np.mean(out))
     for d in LIT_DEPTHS:
         r = variants[f"importance_d{d}"]
         marks, per_pass = [], []
