@@ -22,10 +22,11 @@ SRC_PATHS = [SRC_PATH, SRC32_PATH, HOST_PATH, os.path.join(_HERE, "csrc", "wavef
              os.path.join(_HERE, "csrc", "measured.hip"), os.path.join(_HERE, "csrc", "measured_table.hip"),
              os.path.join(_HERE, "csrc", "bucket.hip"),
              os.path.join(_HERE, "csrc", "bucket_wide.hip"), os.path.join(_HERE, "csrc", "live.hip"),
-             os.path.join(_HERE, "csrc", "clock.hip")]  # translation units of libbsdfd.so
+             os.path.join(_HERE, "csrc", "clock.hip"), os.path.join(_HERE, "csrc", "dielectric.hip")]  # translation units of libbsdfd.so
 FLOW_TUS = (SRC_PATH, SRC32_PATH)   # ... whose device assembly the build verifies (_asmcheck)
 DEP_PATHS = SRC_PATHS + [os.path.join(_HERE, "csrc", f) for f in ("common.h", "flow_dev.h", "flow_kernels.h", "bucket_scan.h",
-                                                                     "measured_dev.h", "wavefront_dev.h", "env_dev.h", "bounce_dev.h")]
+                                                                     "measured_dev.h", "wavefront_dev.h", "env_dev.h", "bounce_dev.h",
+                                                                     "dielectric_dev.h")]
 INCLUDE_DIR = os.path.join(ROOT, "include")
 ASM_CACHE_DIR = os.path.join(ROOT, "build", "asm")   # device assembly of the last product build (bsdfd.s, flow32.s)
 
@@ -54,6 +55,7 @@ EXPORTS = (
     "bsdfd_measured_sample_weight_table",
     "bsdfd_measured_has_luminance", "bsdfd_measured_sample", "bsdfd_measured_pdf", "bsdfd_measured_sample_table",
     "bsdfd_measured_pdf_table",
+    "bsdfd_dielectric_eval", "bsdfd_dielectric_sample_weight", "bsdfd_dielectric_sample", "bsdfd_dielectric_pdf",
     "bsdfd_set_profiling", "bsdfd_profile_read", "bsdfd_profile_read_op", "bsdfd_profile_clock_mhz", "bsdfd_last_kernel_ms", "bsdfd_shader_clock_mhz",
     "bsdfd_last_error", "bsdfd_version", "bsdfd_abi_version",
 )
@@ -84,6 +86,11 @@ class EnvDist(C.Structure):
     """bsdfd_env_dist (include/bsdfd.h)."""
     _fields_ = [("marginal", C.c_void_p), ("conditional", C.c_void_p), ("pdf_uv", C.c_void_p), ("width", C.c_int32),
                 ("height", C.c_int32)]
+
+
+class Dielectric(C.Structure):
+    """bsdfd_dielectric (include/bsdfd.h)."""
+    _fields_ = [("alpha", C.c_float), ("eta", C.c_float), ("distribution", C.c_int32), ("reserved", C.c_int32)]
 
 
 class Opts(C.Structure):
@@ -449,6 +456,11 @@ def lib():
     L.bsdfd_measured_pdf.argtypes = [vp, fp, fp, fp, i64, fp, vp]
     L.bsdfd_measured_sample_table.argtypes = [vp, fp, fp, fp, fp, i64, C.POINTER(C.c_float), fp, fp, fp, vp]
     L.bsdfd_measured_pdf_table.argtypes = [vp, fp, fp, fp, fp, i64, fp, vp]
+    dp = C.POINTER(Dielectric)
+    L.bsdfd_dielectric_eval.argtypes = [dp, fp, fp, i64, C.POINTER(C.c_float), fp, vp]
+    L.bsdfd_dielectric_sample_weight.argtypes = [dp, fp, fp, fp, fp, i64, C.POINTER(C.c_float), C.c_float, fp, fp, vp]
+    L.bsdfd_dielectric_sample.argtypes = [dp, fp, fp, fp, i64, C.POINTER(C.c_float), fp, fp, fp, vp]
+    L.bsdfd_dielectric_pdf.argtypes = [dp, fp, fp, fp, i64, fp, vp]
     L.bsdfd_bucket_workspace_bytes.argtypes = [i64, i32]
     L.bsdfd_bucket_workspace_bytes.restype = i64
     L.bsdfd_bucket_by_material.argtypes = [fp, i64, i32, fp, fp, fp, i64, vp]

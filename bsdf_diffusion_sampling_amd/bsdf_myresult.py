@@ -9,6 +9,12 @@ Same spherical operators, different post-processing:
                     weight = f * albedo / pdf * sin(theta_o) (:97); pdf := 0 where weight.x >= 3.5 (:100-103).
   pdf    (:115-133) no guards, no cos masks: pdf * clamp(1/|sin theta_o|, 1, FLT_MAX).
   eval   (:106-113) ground truth from the analytic BSDF list, no cos masks.
+
+The list is rendering/utils/bsdf_dict.py.  Its entries 23..25 are rough dielectrics, which ``analytic.RoughDielectric`` evaluates
+natively: for those ``idx`` the plugin has its ground truth by default (``props["analytic"] = False`` turns that off, ``props["bsdf"]``
+overrides it) — eval() is one launch and sample()'s weight and firefly rule another.  Entries 0..22 are Mitsuba ``principled``
+BSDFs without a native counterpart: there ``self.bsdf`` stays None unless ``props["bsdf"]`` is given, sample() returns
+``(bs, None)`` and eval() raises.
 """
 from __future__ import annotations
 
@@ -32,6 +38,14 @@ class MyBSDF(NeuralBSDFCore):
         self.idx = int(self._get("idx"))
         self.m_flags = FLAG_DIFFUSE_REFLECTION | FLAG_DIFFUSE_TRANSMISSION | FLAG_FRONT_SIDE | FLAG_BACK_SIDE
         self.m_components = [self.m_flags]
+        if self.bsdf is None and self._get("analytic", True):
+            from .analytic import REFERENCE_ROUGHDIELECTRIC, reference_material
+            if self.idx in REFERENCE_ROUGHDIELECTRIC:
+                self.bsdf = reference_material(self.idx)
+
+    def _analytic_gt(self):
+        from .analytic import RoughDielectric
+        return self.bsdf if isinstance(self.bsdf, RoughDielectric) else None
 
     def _material_name(self) -> str:
         return f"bsdf_{int(self._get('idx'))}"
@@ -48,6 +62,9 @@ class MyBSDF(NeuralBSDFCore):
                           sampled_component=2)
         if self.bsdf is None:
             return bs, None
+        if self._analytic_gt() is not None:  # the lines below, fused into the evaluator's launch
+            weight, bs.pdf = self.bsdf.sample_weight(wi, wo, pdf_sa, tint=self.albedo, firefly_threshold=self.FIREFLY)
+            return bs, weight
         # f * albedo / pdf * sin(theta_o) with pdf_sa = pdf / sin(theta_o) wherever the clamp is inactive
         value = _vec(self._need_bsdf().eval(ctx, si, wo)) * self.albedo.to(wo.device) / pdf_sa[:, None]
         value = torch.where((pdf_sa > 0)[:, None], value, torch.zeros_like(value))
@@ -55,4 +72,6 @@ class MyBSDF(NeuralBSDFCore):
         return bs, torch.where((bs.pdf > 0)[:, None], value, torch.zeros_like(value))
 
     def eval(self, ctx, si, wo, active=True):
+        if self._analytic_gt() is not None:
+            return self.bsdf.eval_t(_wi_of(si), _vec(wo), tint=self.albedo)
         return _vec(self._need_bsdf().eval(ctx, si, wo)) * self.albedo.to(_wi_of(si).device)

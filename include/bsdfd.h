@@ -46,7 +46,9 @@ extern "C" {
  *      in the array scene;
  *      bsdfd_env_sample(), bsdfd_env_pdf(), bsdfd_wf_sample_env() and bsdfd_wf_bounce_env(), which take a struct of their own,
  *      bsdfd_env_dist: importance sampling of the environment map in the array scene;
- *      bsdfd_wf_bounce_rr(): Russian roulette inside the bounce of the array scene. */
+ *      bsdfd_wf_bounce_rr(): Russian roulette inside the bounce of the array scene;
+ *      bsdfd_dielectric_eval(), bsdfd_dielectric_sample_weight(), bsdfd_dielectric_sample() and bsdfd_dielectric_pdf(), which
+ *      take a struct of their own, bsdfd_dielectric: the rough-dielectric ground truth of the full-sphere plugin. */
 #define BSDFD_ABI_VERSION 8
 
 #define BSDFD_OK 0
@@ -425,6 +427,42 @@ int bsdfd_measured_sample_table(bsdfd_measured_table t, const int64_t* material_
                                 float* weight_out, void* hip_stream);
 int bsdfd_measured_pdf_table(bsdfd_measured_table t, const int64_t* material_id, const float* wi, const float* wo,
                              const unsigned char* active, int64_t N, float* pdf_out, void* hip_stream);
+
+/* ---- analytic ground truth of the full-sphere plugin: the rough dielectric (csrc/dielectric.hip) -------------------------
+ * The reference's full-sphere plugin takes eval(), the sample weight and the firefly rule from an analytic Mitsuba BSDF of its
+ * material list (rendering/bsdf_myresult.py:97-110, rendering/utils/bsdf_dict.py); entries 23..25 of that list are
+ * `roughdielectric` (Beckmann, alpha 0.2 / 0.3 / 0.5, bk7 in air).  Model: Walter et al. 2007 with Mitsuba's defaults — Beckmann
+ * D, the rational Smith G1, exact unpolarised Fresnel, visible-normal sampling, radiance transport (the transmitted lobe carries
+ * 1 / eta^2).  Restated from the publications; PARITY-UNPINNED against Mitsuba, like the measured model above.  fp32.
+ * The material is this descriptor, read on the host at the call (zero-initialise it; it may grow at the end):
+ *   alpha         Beckmann roughness (isotropic), > 0
+ *   eta           int_ior / ext_ior, > 0
+ *   distribution  0 = Beckmann; anything else is BSDFD_EINVAL
+ * Directions are in the local shading frame; BOTH sides of the surface are served (wi.z < 0: from inside).  Per row:
+ *   eval           rgb_out [N,3] = f(wi, wo) |cos theta_o| * tint (grey), 0 where wi.z == 0 or wo.z == 0, where the half vector is
+ *                  undefined (|wi + k wo| < 1e-6) and where the value is not finite.
+ *   sample_weight  the tail of the plugin's sample(): value = f |cos| * tint / pdf_sa (0 where pdf_sa <= 0); pdf_out = pdf_sa where
+ *                  value.x < firefly_threshold, else 0; weight_out = value where pdf_out > 0, else 0.  No cosine masks.
+ *   sample         u [N,3] in [0,1)^3: columns 0..1 are Mitsuba's sample2 (the visible normal), column 2 its sample1 (reflection
+ *                  iff u2 <= F).  wo_out [N,3]; pdf_out [N] = what bsdfd_dielectric_pdf gives for (wi, wo_out), bit for bit;
+ *                  weight_out [N,3] (may be NULL) = what bsdfd_dielectric_eval gives for that pair, divided by pdf_out — 0 where
+ *                  pdf_out is 0 or wo_out is on the wrong side of the surface for the chosen lobe.  Rows with wi.z == 0 get zeros.
+ *   pdf            the solid-angle density of that sampler at a given wo.
+ * Rows with active[i] == 0, when a mask is given (u8 [N] or NULL), get 0 in every output.  tint: 3 floats on the host or NULL
+ * (white).  All four calls are stream-ordered, allocate nothing and do not synchronise; N = 0 is a no-op. */
+typedef struct {
+    float alpha, eta;
+    int32_t distribution, reserved;
+} bsdfd_dielectric;
+int bsdfd_dielectric_eval(const bsdfd_dielectric* desc, const float* wi, const float* wo, int64_t N, const float* tint,
+                          float* rgb_out, void* hip_stream);
+int bsdfd_dielectric_sample_weight(const bsdfd_dielectric* desc, const float* wi, const float* wo, const float* pdf_sa,
+                                   const unsigned char* active, int64_t N, const float* tint, float firefly_threshold,
+                                   float* weight_out, float* pdf_out, void* hip_stream);
+int bsdfd_dielectric_sample(const bsdfd_dielectric* desc, const float* wi, const float* u, const unsigned char* active, int64_t N,
+                            const float* tint, float* wo_out, float* pdf_out, float* weight_out, void* hip_stream);
+int bsdfd_dielectric_pdf(const bsdfd_dielectric* desc, const float* wi, const float* wo, const unsigned char* active, int64_t N,
+                         float* pdf_out, void* hip_stream);
 
 /* ---- wavefront harness ------------------------------------
  * The reference renders through Mitsuba 3 (rendering/brdf_measured_disk.py:146-155: passes of

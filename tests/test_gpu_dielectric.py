@@ -1,0 +1,347 @@
+"""GPU: the rough-dielectric ground truth (csrc/dielectric.hip, ``analytic.RoughDielectric``) and the full-sphere plugin's use of it.
+
+Accuracy is held to a yardstick computed here: tests/dielectric_ref.py run in fp32 on the same rows, both errors taken against
+its fp64 run; the kernels may be 4x worse at the 99th percentile and at the maximum (the project's tail margin, DESIGN.md
+section 5).  An error is relative to max(|fp64 value|, 1e-6 of the column's largest): smaller values are compared absolutely.
+
+Where a product cannot be exact the check is the exact statement next to it: ``weight * pdf`` cannot reproduce ``eval``'s
+bits after a division, so the weight is held, bit for bit, to ``eval_t / pdf`` formed in IEEE fp32 on the host (and
+``weight * pdf`` to eval_t within one rounding).  A transmission PAIR can never be beyond the critical angle (its generalised
+half vector always has |wi . m| >= the critical cosine), so total internal reflection is checked where it occurs: in sample()."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+import dielectric_ref as R  # noqa: E402
+
+N = 4096
+TINT = (0.9, 0.2, 0.4)
+ALPHAS = (0.2, 0.3, 0.5)
+ETA0 = R.ETA_BK7_AIR
+
+
+def _cuda(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _np(t):
+    return t.cpu().numpy()
+
+
+def _unit(v):
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def _hand_rows():
+    """(wi, wo, exactly_zero): the hand-placed pairs; ``exactly_zero`` marks those whose eval and pdf are 0 by rule."""
+    w = R.wi_of
+    graze = w(1.55, 0.3)[0]
+    inside = w(np.pi - 1.2, 0.7)[0]                               # from inside, beyond the critical angle (sin = 0.665)
+    tilted = w(0.4, 2.0)[0]
+    rows = [
+        ((0, 0, 1), (0, 0, 1), False), ((0, 0, 1), w(0.3, 1.0)[0], False), ((0, 0, 1), (0, 0, -1), False),   # perpendicular G1
+        ((0, 0, 1), w(np.pi - 0.2, 1.0)[0], False), ((0, 0, -1), w(0.2, 1.0)[0], False),
+        (tilted, (1, 0, 0), True), (tilted, (0.6, -0.8, 0), True),                                            # co == 0
+        ((1, 0, 0), tilted, True), ((0, 1, 0), -tilted, True), ((1, 0, 0), (0, 1, 0), True),                  # ci == 0
+        (inside, w(1.0, 0.7 + np.pi)[0], False), (inside, w(0.3, 0.7)[0], False), (inside, inside * [-1, -1, 1], False),
+        (tilted, -tilted / ETA0, True), (graze, -graze / ETA0, True),                                         # degenerate half vector
+        (-tilted, tilted * ETA0, True),
+        (graze, graze * [-1, -1, 1], False), (graze, w(np.pi - 0.72, 0.3 + np.pi)[0], False), (graze, -graze, False),
+    ]
+    wi, wo, z = zip(*rows)
+    return np.array(wi, np.float32), np.array(wo, np.float32), np.array(z)
+
+
+@pytest.fixture(scope="module")
+def gpu():
+    from bsdf_diffusion_sampling_amd.analytic import RoughDielectric
+    if not torch.cuda.is_available():
+        pytest.fail("GPU test selected but no GPU visible")
+    return {a: RoughDielectric(a) for a in ALPHAS}
+
+
+@pytest.fixture(scope="module")
+def case(gpu):
+    """Per alpha, computed once and shared (read-only): the fp32 inputs, the fp64 reference, the fp32 yardstick and the kernels'
+    results on the same rows."""
+    cache = {}
+
+    def get(alpha):
+        if alpha in cache:
+            return cache[alpha]
+        g = np.random.default_rng(int(alpha * 100))
+        r64, r32 = R.RoughDielectric(alpha, dtype=np.float64), R.RoughDielectric(alpha, dtype=np.float32)
+        # sample(): both sides of the surface, grazing rows included, and the hand-placed incident directions
+        hw_i, hw_o, hz = _hand_rows()
+        wi = R.sphere_dirs(g, N)
+        wi[: N // 8] = _unit(wi[: N // 8] * [1, 1, 0.05])        # an eighth of them within ~3 degrees of the horizon
+        wi = np.concatenate([wi.astype(np.float32), hw_i])
+        u = g.random((len(wi), 3)).astype(np.float32)
+        # eval() / pdf(): half of the directions around where the model puts its mass (its own samples, blurred), half anywhere
+        wo = R.sphere_dirs(g, len(wi))
+        k = N // 2
+        wo[:k] = _unit(r64.sample(wi[:k], g.random((k, 3)))[0] + g.normal(size=(k, 3)) * 0.05 * alpha / 0.2)
+        wo = wo.astype(np.float32)
+        wo[N:] = hw_o
+        wi_d, wo_d, u_d = _cuda(wi), _cuda(wo), _cuda(u)
+        b = gpu[alpha]
+        c = dict(wi=wi, wo=wo, u=u, r64=r64, r32=r32, wi_d=wi_d, wo_d=wo_d, u_d=u_d, zero=np.concatenate([np.zeros(N, bool), hz]),
+                 eval_d=b.eval_t(wi_d, wo_d, tint=TINT), pdf_d=b.pdf_t(wi_d, wo_d), sample_d=b.sample_t(wi_d, u_d, tint=TINT),
+                 sample_ref=r64.sample(wi, u, TINT, details=True), sample_yard=r32.sample(wi, u, TINT, details=True))
+        cache[alpha] = c
+        return c
+    return get
+
+
+def _err(got, ref):
+    """Per-row error against fp64: relative to max(|ref|, 1e-6 of the column's largest)."""
+    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
+    return np.abs(got - ref) / np.maximum(np.abs(ref), 1e-6 * np.abs(ref).max(0))
+
+
+def _held_to_yardstick(label, got, yard):
+    fig = {q: dict(gpu_p99=np.percentile(got[q], 99), yard_p99=np.percentile(yard[q], 99), gpu_max=got[q].max(), yard_max=yard[q].max())
+           for q in got}
+    msg = label + ": " + "; ".join(f"{q} p99 gpu {f['gpu_p99']:.3e} yardstick {f['yard_p99']:.3e}, max gpu {f['gpu_max']:.3e} "
+                                   f"yardstick {f['yard_max']:.3e}" for q, f in fig.items())
+    print(msg)
+    for q, f in fig.items():
+        assert f["gpu_p99"] <= 4 * f["yard_p99"], msg
+        assert f["gpu_max"] <= 4 * f["yard_max"], msg
+
+
+@pytest.mark.parametrize("alpha", ALPHAS)
+def test_eval_and_pdf_match_fp64_within_the_fp32_yardstick(case, alpha):
+    c = case(alpha)
+    f, p = _np(c["eval_d"]), _np(c["pdf_d"])
+    assert np.isfinite(f).all() and np.isfinite(p).all() and (f >= 0).all() and (p >= 0).all()
+    f_ref, p_ref = c["r64"].eval(c["wi"], c["wo"], TINT), c["r64"].pdf(c["wi"], c["wo"])
+    f_yard, p_yard = c["r32"].eval(c["wi"], c["wo"], TINT), c["r32"].pdf(c["wi"], c["wo"])
+    assert (f_ref[:N, 0] > 0).mean() > 0.4 and (p_ref[:N] > 0).mean() > 0.4
+    assert ((c["wi"][:N, 2] * c["wo"][:N, 2] > 0) & (f_ref[:N, 0] > 0)).mean() > 0.1     # both lobes are scored
+    assert ((c["wi"][:N, 2] * c["wo"][:N, 2] < 0) & (f_ref[:N, 0] > 0)).mean() > 0.1
+    grey = f[:, 0].astype(np.float64) / TINT[0]
+    assert np.abs(f[:, 1] / TINT[1] - grey).max() <= 1e-6 * grey.max() and np.abs(f[:, 2] / TINT[2] - grey).max() <= 1e-6 * grey.max()
+    # the degenerate rows: exactly zero, in the kernels and in both runs of the reference
+    z = c["zero"]
+    assert z.sum() == 8 and (f[z] == 0).all() and (p[z] == 0).all() and (f_ref[z] == 0).all() and (p_ref[z] == 0).all()
+    assert (f_yard[z] == 0).all() and (p_yard[z] == 0).all()
+    _held_to_yardstick(f"alpha {alpha}", {"eval": _err(f, f_ref).max(1), "pdf": _err(p, p_ref)},
+                       {"eval": _err(f_yard, f_ref).max(1), "pdf": _err(p_yard, p_ref)})
+
+
+@pytest.mark.parametrize("alpha", ALPHAS)
+def test_sample_matches_fp64_within_the_fp32_yardstick(case, alpha):
+    c = case(alpha)
+    wo, pdf, w = (_np(t) for t in c["sample_d"])
+    wo_r, pdf_r, w_r, refl_r, F_r = c["sample_ref"]
+    wo_y, pdf_y, w_y, refl_y, F_y = c["sample_yard"]
+    assert all(np.isfinite(a).all() for a in (wo, pdf, w)) and (pdf >= 0).all() and (w >= 0).all()
+    live = c["wi"][:, 2] != 0
+    assert (~live).sum() == 3 and (wo[~live] == 0).all() and (pdf[~live] == 0).all() and (w[~live] == 0).all()
+    assert np.abs(np.linalg.norm(wo[live].astype(np.float64), axis=1) - 1).max() <= 1e-5
+    # the lobe: the reference's, except within 1e-5 of the Fresnel term (excluded and counted; expected count 0.08)
+    close = live & (np.abs(c["u"][:, 2].astype(np.float64) - F_r) < 1e-5)
+    assert close.sum() <= 4, close.sum()
+    ci = c["wi"][:, 2].astype(np.float64)
+    # which lobe a direction belongs to: nearer the reference's reflected or its refracted direction
+    m_r = c["r64"].sample_normal(c["wi"].astype(np.float64) * np.where(ci > 0, 1.0, -1.0)[:, None], c["u"][:, 0].astype(np.float64),
+                                 c["u"][:, 1].astype(np.float64))
+    cc = (c["wi"] * m_r).sum(1)
+    wo_refl = m_r * (2 * cc)[:, None] - c["wi"]
+    _, ct, eta_ti = c["r64"].fresnel(cc)
+    wo_trans = m_r * (eta_ti * cc + ct)[:, None] - c["wi"] * eta_ti[:, None]
+    refl = np.linalg.norm(wo - wo_refl, axis=1) <= np.linalg.norm(wo - wo_trans, axis=1)
+    rows = live & ~close
+    assert np.array_equal(refl[rows], refl_r[rows]), int((refl != refl_r)[rows].sum())
+    assert refl_r[rows].mean() > 0.05 and (~refl_r[rows]).mean() > 0.3
+    # total internal reflection: the rows from inside whose sampled normal is hit beyond the critical angle reflect, whatever u2
+    tir = rows & (F_r == 1.0)
+    assert tir.sum() >= 50 and refl[tir].all() and (c["u"][tir, 2] > 0.9).any()
+    yrows = rows & (refl_y == refl_r)                             # (the fp32 yardstick flips on rows of its own)
+    got = {"wo": np.abs(wo.astype(np.float64) - wo_r).max(1)[rows], "pdf": _err(pdf, pdf_r)[rows]}
+    yard = {"wo": np.abs(wo_y.astype(np.float64) - wo_r).max(1)[yrows], "pdf": _err(pdf_y, pdf_r)[yrows]}
+    _held_to_yardstick(f"alpha {alpha} sample", got, yard)
+
+
+@pytest.mark.parametrize("alpha", ALPHAS)
+def test_the_kernels_agree_bit_for_bit(case, gpu, alpha):
+    c = case(alpha)
+    b = gpu[alpha]
+    wo_d, pdf_d, w_d = c["sample_d"]
+    wo, pdf, w = _np(wo_d), _np(pdf_d), _np(w_d)
+    # pdf_t of the sampled pair IS the sampler's pdf
+    assert torch.equal(b.pdf_t(c["wi_d"], wo_d), pdf_d)
+    # the weight is eval_t of the sampled pair over that pdf — IEEE fp32 division, formed here on the host — where the direction
+    # is on its lobe's side, and exactly 0 elsewhere
+    f = _np(b.eval_t(c["wi_d"], wo_d, tint=TINT))
+    refl_r = c["sample_ref"][3]
+    ci, co = c["wi"][:, 2], wo[:, 2]
+    close = np.abs(c["u"][:, 2].astype(np.float64) - c["sample_ref"][4]) < 1e-5
+    side = np.where(refl_r, ci * co > 0, ci * co < 0)
+    keep = side & (pdf > 0)
+    rows = ~close
+    assert 0.5 < keep[rows].mean() < 1 and (w[rows & ~keep] == 0).all()
+    with np.errstate(all="ignore"):
+        expect = (f / pdf[:, None]).astype(np.float32)
+    assert np.array_equal(w[rows & keep].view(np.uint32), expect[rows & keep].view(np.uint32))
+    back = w.astype(np.float64) * pdf.astype(np.float64)[:, None]
+    assert (np.abs(back - f)[rows & keep] <= 2.0 ** -23 * f[rows & keep]).all()
+    assert (f[rows & keep, 0] > 0).mean() > 0.99
+
+
+@pytest.mark.parametrize("n", [0, 1, 67])
+def test_results_do_not_depend_on_the_grid(case, gpu, n):
+    c, b = case(0.3), gpu[0.3]
+    wi, wo, u = (c[k][:n].contiguous() for k in ("wi_d", "wo_d", "u_d"))
+    got = b.sample_t(wi, u, tint=TINT)
+    assert got[0].shape == (n, 3) and got[1].shape == (n,) and got[2].shape == (n, 3)
+    for a, full in zip(got, c["sample_d"]):
+        assert torch.equal(a, full[:n])
+    assert torch.equal(b.eval_t(wi, wo, tint=TINT), c["eval_d"][:n]) and torch.equal(b.pdf_t(wi, wo), c["pdf_d"][:n])
+
+
+def test_masks_checks_and_call_shapes(case, gpu):
+    from bsdf_diffusion_sampling_amd import _lib
+    from bsdf_diffusion_sampling_amd.plugin_base import BSDFSample3f, SurfaceInteraction
+    c, b = case(0.3), gpu[0.3]
+    n = len(c["wi"])
+    wi_d, wo_d, u_d = c["wi_d"], c["wo_d"], c["u_d"]
+    mask = (torch.rand(n, generator=torch.Generator().manual_seed(3)) < 0.6).cuda()
+    out = (torch.full((n, 3), 7.0, device="cuda"), torch.full((n,), 7.0, device="cuda"), torch.full((n, 3), 7.0, device="cuda"))
+    ret = b.sample_t(wi_d, u_d, tint=TINT, active=mask, out=out)
+    assert all(r.data_ptr() == o.data_ptr() for r, o in zip(ret, out))
+    for r, full in zip(ret, c["sample_d"]):
+        assert torch.equal(r[mask], full[mask]) and bool((r[~mask] == 0).all())
+    p = b.pdf_t(wi_d, wo_d, active=mask.to(torch.uint8))
+    assert torch.equal(p[mask], c["pdf_d"][mask]) and bool((p[~mask] == 0).all())
+    pdf_sa = c["pdf_d"] * 0.1 + 1e-3
+    wgt, pk = b.sample_weight(wi_d, wo_d, pdf_sa, tint=TINT)
+    wgt_m, pk_m = b.sample_weight(wi_d, wo_d, pdf_sa, tint=TINT, active=mask)
+    assert torch.equal(wgt_m[mask], wgt[mask]) and torch.equal(pk_m[mask], pk[mask])
+    assert bool((wgt_m[~mask] == 0).all()) and bool((pk_m[~mask] == 0).all())
+    # sample_weight against the reference's lines in fp64: the same rows are kept, the same values to fp32 rounding
+    w_r, p_r = c["r64"].sample_weight(c["wi"], c["wo"], _np(pdf_sa), TINT, 3.5)
+    v_r = c["r64"].eval(c["wi"], c["wo"], TINT) / _np(pdf_sa).astype(np.float64)[:, None]
+    clear = np.abs(v_r[:, 0] - 3.5) > 1e-2
+    assert np.array_equal((_np(pk) > 0)[clear], (p_r > 0)[clear]) and (_np(pk)[_np(pk) > 0] == _np(pdf_sa)[_np(pk) > 0]).all()
+    assert (p_r == 0).mean() > 0.01 and (p_r > 0).mean() > 0.01
+    kept = _np(pk) > 0
+    with np.errstate(all="ignore"):
+        expect = (_np(c["eval_d"]) / _np(pdf_sa)[:, None]).astype(np.float32)       # IEEE fp32 division of the kernels' own eval
+    assert np.array_equal(_np(wgt)[kept].view(np.uint32), expect[kept].view(np.uint32)) and (_np(wgt)[~kept] == 0).all()
+    # argument checks
+    with pytest.raises(ValueError, match="u must be"):
+        b.sample_t(wi_d, wo_d[:, :2].contiguous())
+    with pytest.raises(ValueError, match="active"):
+        b.sample_t(wi_d, u_d, active=mask[:5])
+    with pytest.raises(ValueError, match="rows"):
+        b.eval_t(wi_d, wo_d[:5].contiguous())
+    import ctypes as C
+    bad = _lib.Dielectric(0.3, 1.5, 1, 0)
+    assert _lib.lib().bsdfd_dielectric_pdf(C.byref(bad), wi_d.data_ptr(), wo_d.data_ptr(), None, n, p.data_ptr(), None) == 1
+    # Mitsuba's call shapes
+    si = SurfaceInteraction(wi_d)
+    bs, weight = b.sample(None, si, u_d[:, 2].contiguous(), u_d[:, :2].contiguous())
+    wo_s, pdf_s, w_s = b.sample_t(wi_d, u_d)
+    assert isinstance(bs, BSDFSample3f) and torch.equal(bs.wo, wo_s) and torch.equal(bs.pdf, pdf_s) and torch.equal(weight, w_s)
+    e, q = b.eval_pdf(None, si, wo_d)
+    assert torch.equal(e, b.eval_t(wi_d, wo_d)) and torch.equal(q, c["pdf_d"])
+    assert torch.equal(e, b.eval(None, si, wo_d)) and torch.equal(q, b.pdf(None, si, wo_d))
+
+
+# ---- the full-sphere plugin ---------------------------------------------------------------------------------------------------
+class _EvalOnly:
+    """A ground truth that exposes nothing but ``eval``: the plugin then runs its torch lines."""
+
+    def __init__(self, b):
+        self.b = b
+
+    def eval(self, ctx, si, wo):
+        return self.b.eval_t(si.wi, wo)
+
+
+def test_plugin_sample_weight_is_the_torch_lines_bit_for_bit(gpu):
+    from bsdf_diffusion_sampling_amd import weights as W
+    from bsdf_diffusion_sampling_amd.analytic import RoughDielectric
+    from bsdf_diffusion_sampling_amd.bsdf_myresult import MyBSDF
+    from bsdf_diffusion_sampling_amd.plugin_base import SurfaceInteraction
+    from oracle import bsdf_oracle as O
+    n = 4096
+    g = np.random.default_rng(5)
+    th, ph = g.uniform(0.05, 1.5, n), g.uniform(-np.pi, np.pi, n)
+    wi = np.stack([np.sin(th) * np.cos(ph), np.sin(th) * np.sin(ph), np.cos(th)], 1).astype(np.float32)
+    orc = O.Oracle(W.load(W.shipped_path("bsdf_24", "spherical")))
+    cond = O.cart_to_spher(wi.astype(np.float64))
+    mu, kappa = orc.base_von_mises_params(cond)
+    # half of the base samples as the sampler would draw them, half overdispersed: those land where the net's density is far
+    # below the model's, which is where the firefly rule bites
+    x0 = orc.base_sample(cond, g.standard_normal(n), phi=g.vonmises(mu, kappa))
+    x0[n // 2:] = orc.base_sample(cond, 2.0 * g.standard_normal(n), phi=g.uniform(-np.pi, np.pi, n))[n // 2:]
+    x0_d, si = _cuda(x0.astype(np.float32)), SurfaceInteraction(_cuda(wi))
+    fused = MyBSDF({"idx": 24, "albedo": list(TINT)})
+    assert isinstance(fused.bsdf, RoughDielectric) and fused.bsdf.alpha == 0.3
+    torch_lines = MyBSDF({"idx": 24, "albedo": list(TINT), "bsdf": _EvalOnly(fused.bsdf)})
+    assert torch_lines._analytic_gt() is None
+    bs_a, w_a = fused.sample(None, si, x0=x0_d)
+    bs_b, w_b = torch_lines.sample(None, si, x0=x0_d)
+    assert torch.equal(bs_a.wo, bs_b.wo)
+    kept = float((bs_b.pdf > 0).float().mean())
+    pdf_sa = fused.sample_t(si.wi, x0=x0_d)[1]   # the density before the rule
+    value_x = fused.bsdf.eval_t(si.wi, bs_a.wo, tint=TINT)[:, 0] / pdf_sa
+    below = float(((value_x < 3.5) & (pdf_sa > 0) & (value_x > 0)).float().mean())
+    above = float(((value_x >= 3.5) & (pdf_sa > 0)).float().mean())
+    print(f"value.x below the threshold on {below:.3f} of the rows, at or above it on {above:.3f}; pdf kept on {kept:.3f}")
+    assert below >= 0.01 and above >= 0.01
+    assert torch.equal(bs_a.pdf.view(torch.int32), bs_b.pdf.view(torch.int32))
+    assert torch.equal(w_a.view(torch.int32), w_b.view(torch.int32))
+    assert bool((bs_a.pdf[value_x >= 3.5] == 0).all()) and bool((w_a[bs_a.pdf == 0] == 0).all())
+    # eval(): one launch, the tint inside
+    assert torch.equal(fused.eval(None, si, bs_a.wo), fused.bsdf.eval_t(si.wi, bs_a.wo, tint=TINT))
+    assert torch.allclose(fused.eval(None, si, bs_a.wo), torch_lines.eval(None, si, bs_a.wo), rtol=1e-6, atol=0)
+
+
+def test_plugin_defaults():
+    from bsdf_diffusion_sampling_amd.analytic import RoughDielectric
+    from bsdf_diffusion_sampling_amd.bsdf_myresult import MyBSDF
+    from bsdf_diffusion_sampling_amd.plugin_base import SurfaceInteraction
+    wi = _cuda(R.wi_of(0.5, 0.2, 64).astype(np.float32))
+    p23 = MyBSDF({"idx": 23})
+    assert isinstance(p23.bsdf, RoughDielectric) and p23.bsdf.alpha == 0.2
+    bs, w = p23.sample(None, SurfaceInteraction(wi), seed=1)
+    assert w is not None and w.shape == (64, 3) and bool(torch.isfinite(w).all())
+    assert p23.eval(None, SurfaceInteraction(wi), bs.wo).shape == (64, 3)
+    off = MyBSDF({"idx": 23, "analytic": False})
+    assert off.bsdf is None
+    bs, w = off.sample(None, SurfaceInteraction(wi), seed=1)
+    assert w is None
+    with pytest.raises(RuntimeError, match="ground-truth"):
+        off.eval(None, SurfaceInteraction(wi), bs.wo)
+    p3 = MyBSDF({"idx": 3})
+    assert p3.bsdf is None and p3.sample(None, SurfaceInteraction(wi), seed=1)[1] is None
+
+
+@pytest.fixture(scope="module")
+def sphere20k():
+    return _cuda(R.sphere_dirs(np.random.default_rng(2), 20000).astype(np.float32))
+
+
+@pytest.mark.parametrize("idx", (23, 24, 25))
+def test_the_nets_identify_their_material(gpu, sphere20k, idx):
+    """L1 distance between the normalised density of the shipped net (the full-sphere plugin's pdf, T = 8) and the normalised
+    model on 20 000 uniform directions: smallest at the set's own alpha."""
+    from bsdf_diffusion_sampling_amd.bsdf_myresult import MyBSDF
+    plug = MyBSDF({"idx": idx, "analytic": False})
+    assert plug.T == 8
+    for theta in (0.3, 1.0):
+        wi = _cuda(R.wi_of(theta, 0.0, 20000).astype(np.float32))
+        p = plug.pdf_t(wi, sphere20k).double()
+        p = p / p.sum()
+        dist = {}
+        for alpha in ALPHAS:
+            q = gpu[alpha].eval_t(wi, sphere20k)[:, 0].double()
+            dist[alpha] = float((p - q / q.sum()).abs().sum())
+        print(f"bsdf_{idx} theta_i {theta}: L1 to alpha 0.2 / 0.3 / 0.5 = " + " / ".join(f"{dist[a]:.2f}" for a in ALPHAS))
+        assert min(dist, key=dist.get) == R.REFERENCE_ALPHA[idx], dist
