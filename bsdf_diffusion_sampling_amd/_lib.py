@@ -18,7 +18,7 @@ SRC32_PATH = os.path.join(_HERE, "csrc", "flow32.hip")   # the 32-query-tile flo
 HOST_PATH = os.path.join(_HERE, "csrc", "host.hip")      # handle, launch routine and entry points of both kernel families
 SRC_PATHS = [SRC_PATH, SRC32_PATH, HOST_PATH, os.path.join(_HERE, "csrc", "wavefront.hip"), os.path.join(_HERE, "csrc", "pathtrace.hip"),
              os.path.join(_HERE, "csrc", "pathlights.hip"), os.path.join(_HERE, "csrc", "pathenv.hip"),
-             os.path.join(_HERE, "csrc", "pathrr.hip"), os.path.join(_HERE, "csrc", "encoding.hip"),
+             os.path.join(_HERE, "csrc", "bounce.hip"), os.path.join(_HERE, "csrc", "encoding.hip"),
              os.path.join(_HERE, "csrc", "measured.hip"), os.path.join(_HERE, "csrc", "measured_table.hip"),
              os.path.join(_HERE, "csrc", "bucket.hip"),
              os.path.join(_HERE, "csrc", "bucket_wide.hip"), os.path.join(_HERE, "csrc", "live.hip"),

@@ -1,5 +1,5 @@
-// bounce_dev.h — the one bounce of the array-scene path tracer, and what its kernels' launchers and the two emitter samplers
-// share.  pathtrace.hip, pathlights.hip and pathenv.hip each instantiate bounce_vertex<Mode> in a thin __global__ stub:
+// bounce_dev.h — the one bounce of the array-scene path tracer, and what its launcher (bounce.hip) and the two emitter samplers
+// (pathlights.hip, pathenv.hip) share.  bounce.hip instantiates bounce_vertex<Mode, RR> in six thin __global__ stubs:
 //
 //   COSINE : only the environment emits; the light strategy is the cosine-weighted direction primary / bounce left in wl
 //   LIT    : one emitter sample per vertex, uniform among n_e = point lights [+ the environment] (sample_emitter: lsel, emit)
@@ -9,8 +9,8 @@
 // does not depend on the mode, so the three kernels' continuation states are equal bit for bit by construction.  The modes
 // differ, under `if constexpr`, in where the emitter sample comes from, in how the floor's environment term is gated or
 // weighted, in the light-strategy density the escaping BSDF sample is weighted against, and in the light strategy's own term.
-// Each instantiation is straight-line code of its own.  pathrr.hip instantiates the three modes once more with RR = true: the
-// same body with Russian roulette in front of continue_path.
+// Each instantiation is straight-line code of its own.  RR = true is the same body with Russian roulette in front of
+// continue_path.
 //
 // The arrays travel in small structs passed by value (kernel arguments: scalar loads); no struct is indexed per lane.
 #pragma once
@@ -83,7 +83,7 @@ __device__ __forceinline__ void store_local_direction(float* __restrict__ wl, V3
 // One bounce of lane p's path: rad += beta * (the vertex' estimate), then the path moves to what its BSDF sample hits or ends.
 // `e`, `n_e` and `has_env` are read by the modes that have them (ENV; LIT and ENV; LIT).
 //
-// RR (pathrr.hip): Russian roulette, Mitsuba's `path` integrator's rule.  From the vertex with bounce + 1 >= rr_depth on (its
+// RR: Russian roulette, Mitsuba's `path` integrator's rule.  From the vertex with bounce + 1 >= rr_depth on (its
 // `depth >= rr_depth`, depth = the surface vertices processed so far) a path that would continue survives with probability
 // q = min(max over the channels of the throughput after this vertex, 0.95) — eta is 1 here — and its throughput is divided by q.
 // The variate is a Philox draw of the lane's own (counter word 3 = "Roul" + depth), made only where the decision is.  A path
@@ -216,19 +216,6 @@ inline Step make_step(int32_t bounce, int32_t last, int32_t occlusion, uint64_t 
                 (unsigned long long)path_offset, (long long)N};
 }
 
-// The arguments bsdfd_wf_bounce, _lit and _env share, in the structs the kernels take, checked after the launcher's own scene
-// and emitter arguments; then `launch`, unless there is nothing to do.  `emitter_arrays`: the mode's own arrays are all given.
-template <class Launch>
-int checked_bounce(int32_t bounce, int32_t last, int32_t occlusion, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N,
-                   const PathState& ps, const SamplerAnswer& sa, bool emitter_arrays, Launch launch) {
-    if (bounce < 0) return bsdfd_fail_(BSDFD_EINVAL, "bounce must be >= 0");
-    if ((sa.f_o == nullptr) != (sa.f_l == nullptr)) return bsdfd_fail_(BSDFD_EINVAL, "f_o and f_l are both NULL or both given");
-    if (N == 0) return BSDFD_OK;
-    if (!ps.org || !ps.nrm || !ps.wi || !ps.wl || !ps.mat || !ps.beta || !ps.rad || !sa.wo || !sa.pdf_o || !sa.pdf_l || !emitter_arrays)
-        return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
-    return launch(make_step(bounce, last, occlusion, seed, pass, path_offset, N));
-}
-
 // the emitter counts of a bsdfd_wf_lights: n point lights, n_e emitters with the environment
 inline int light_counts(const bsdfd_wf_lights* l, int& n, int& n_e) {
     if (!l) return bsdfd_fail_(BSDFD_EINVAL, "null lights");
@@ -247,20 +234,6 @@ inline int env_scene(const bsdfd_wf_scene* scene, const float* env, const bsdfd_
     if (n_e < 1 || n_e > BSDFD_WF_MAX_LIGHTS + 1) return bsdfd_fail_(BSDFD_EINVAL, "n_e must be 1..9: the environment and up to 8 point lights");
     if (!has_lsel && n_e != 1) return bsdfd_fail_(BSDFD_EINVAL, "without lsel the environment is the only emitter: n_e must be 1");
     return BSDFD_OK;
-}
-
-// ... with the emitters of bsdfd_wf_bounce_env: `lights` and `lsel` both NULL (n_e = 1) or both given (has_env set, n_e = n_lights + 1)
-inline int env_bounce_scene(const bsdfd_wf_scene* scene, const float* env, const bsdfd_env_dist* dist, const bsdfd_wf_lights* lights,
-                            const int32_t* lsel, long long n, Scene& sc, EnvDist& e, int& n_e) {
-    n_e = 1;
-    if (lights) {
-        if (lights->n_lights < 1 || lights->n_lights > BSDFD_WF_MAX_LIGHTS) return bsdfd_fail_(BSDFD_EINVAL, "1..8 point lights");
-        if (!lights->has_env) return bsdfd_fail_(BSDFD_EINVAL, "the environment must be one of the emitters (has_env)");
-        n_e = lights->n_lights + 1;
-    }
-    if ((lights == nullptr) != (lsel == nullptr) && n != 0)
-        return bsdfd_fail_(BSDFD_EINVAL, "lights and lsel are both NULL or both given");
-    return env_scene(scene, env, dist, n_e, lights != nullptr, n, sc, e);
 }
 
 }  // namespace bounce_dev

@@ -11,10 +11,8 @@
 //                direction — what the sampler's pdf() and the evaluator are then asked about —, lpdf = p_l, emit = E V / p_l, 0
 //                below the horizon or (occlusion) behind a surface.  On the floor: wl stays (the cosine direction is the floor's
 //                BSDF sample and the way on), emit = the whole term mis(p_l, cos/pi) (refl/pi) cos E V / p_l.
-//   bounce_env : bounce_dev.h's bounce_vertex<ENV> — bounce_lit_kernel's body with that light term (mis(lpdf, pdf_l) emit f cos,
-//                no lookup along wl); the escaping BSDF samples (the floor's cosine direction included) are weighted against
-//                pdf_env / n_e.  Where the path goes is bounce_kernel's: the same lines of the one body.
 //
+// The bounce that reads lpdf and emit is bounce.hip's ENV kernel.
 // One path per lane; the scene travels by value; a lane whose path has ended returns after reading its id.
 #include <hip/hip_runtime.h>
 
@@ -70,7 +68,7 @@ __global__ __launch_bounds__(256) void sample_env_kernel(Scene sc, const float* 
         s = 1.0f / p_l;
     }
     if (m == sc.n_sph) {
-        // diffuse floor: f cos = (reflectance / pi) cos, weighted against the cosine strategy bounce_env runs along wl
+        // diffuse floor: f cos = (reflectance / pi) cos, weighted against the cosine strategy the bounce runs along wl
         const float inv_pi = 0.31830988618379067154f;
         s *= mis_power(p_l, cosl * inv_pi) * wi[3 * p] * inv_pi * cosl;
     } else {
@@ -78,11 +76,6 @@ __global__ __launch_bounds__(256) void sample_env_kernel(Scene sc, const float* 
     }
     lpdf[p] = p_l;
     st3(emit + 3 * p, v3(s * E[0], s * E[1], s * E[2]));
-}
-
-__global__ __launch_bounds__(256) void bounce_env_kernel(Scene sc, const float* __restrict__ env, EnvDist e, int n_e, Step st,
-                                                         PathState ps, SamplerAnswer sa, EmitterSample es) {
-    bounce_vertex<ENV>(sc, env, e, n_e, 1, st, ps, sa, es);
 }
 
 }  // namespace
@@ -122,23 +115,6 @@ int bsdfd_wf_sample_env(const bsdfd_wf_scene* scene, const float* env, const bsd
     const Step st = make_step(bounce, 0, occlusion, seed, pass, path_offset, N);
     return launch_lanes(N, sample_env_kernel, stream, sc, env, e, (int)n_e, st, org, nrm, wi, reinterpret_cast<const long long*>(material),
                         reinterpret_cast<const int*>(lsel), wl, lpdf, emit);
-}
-
-int bsdfd_wf_bounce_env(const bsdfd_wf_scene* scene, const float* env, int32_t bounce, int32_t last, int32_t occlusion,
-                        uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, float* org, float* nrm, float* wi,
-                        float* wl, int64_t* material, float* beta, float* rad, const float* wo, const float* pdf_o,
-                        const float* pdf_l, const float* f_o, const float* f_l, const bsdfd_wf_lights* lights,
-                        const int32_t* lsel, const float* emit, const float* lpdf, const bsdfd_env_dist* dist, void* stream) {
-    Scene sc;
-    EnvDist e;
-    int n_e;
-    if (int rc = env_bounce_scene(scene, env, dist, lights, lsel, N, sc, e, n_e)) return rc;
-    const PathState ps{org, nrm, wi, wl, reinterpret_cast<long long*>(material), beta, rad};
-    const SamplerAnswer sa{wo, pdf_o, pdf_l, f_o, f_l};
-    const EmitterSample es{reinterpret_cast<const int*>(lsel), lpdf, emit};
-    return checked_bounce(bounce, last, occlusion, seed, pass, path_offset, N, ps, sa, emit && lpdf, [&](const Step& st) {
-        return launch_lanes(N, bounce_env_kernel, stream, sc, env, e, n_e, st, ps, sa, es);
-    });
 }
 
 }  // extern "C"

@@ -10,10 +10,8 @@
 //                    wl = the local direction to the light — what the sampler's pdf() and the evaluator are then asked about —
 //                    and emit = n_e I_k / d^2, 0 below the horizon or (occlusion) behind another surface.  Point k on the floor:
 //                    wl stays (the path continues along it), emit = the whole term n_e (refl / pi) cos I_k / d^2.
-//   bounce_lit     : bounce_dev.h's bounce_vertex<LIT> — bounce_kernel's body with the light strategy chosen by lsel.  A point
-//                    light is a delta: no MIS weight, and the BSDF strategy can never hit it.  The environment's terms are
-//                    gated by has_env, and its two MIS densities carry the selection probability 1 / n_e.
 //
+// The bounce that reads lsel and emit is bounce.hip's LIT kernel.
 // The lights travel by value in the kernel arguments like the scene; the picked light is selected by a wave-uniform loop
 // with a per-lane select, because indexing the argument array per lane would move it to scratch.  One path per lane; a
 // lane whose path has ended returns after reading its id.
@@ -46,7 +44,7 @@ __global__ __launch_bounds__(256) void sample_emitter_kernel(Scene sc, Lights lt
     unsigned u[4];
     tagged_draw(st.seed, st.pass, st.path_offset, p, 0x4C697465u /* "Lite" */, st.bounce, u);
     const int pick = (int)(((unsigned long long)u[0] * (unsigned long long)lt.n_e) >> 32);
-    if (pick == lt.n) {   // the environment: bounce_lit looks it up along the cosine sample that is already in wl
+    if (pick == lt.n) {   // the environment: the bounce looks it up along the cosine sample that is already in wl
         lsel[p] = -1;
         st3(emit + 3 * p, v3(0.f, 0.f, 0.f));
         return;
@@ -66,11 +64,6 @@ __global__ __launch_bounds__(256) void sample_emitter_kernel(Scene sc, Lights lt
     else store_local_direction(wl + 3 * p, nn, dir, cosl);
     lsel[p] = pick;
     st3(emit + 3 * p, s * I);
-}
-
-__global__ __launch_bounds__(256) void bounce_lit_kernel(Scene sc, const float* __restrict__ env, int n_e, int has_env, Step st,
-                                                         PathState ps, SamplerAnswer sa, EmitterSample es) {
-    bounce_vertex<LIT>(sc, env, EnvDist{}, n_e, has_env, st, ps, sa, es);
 }
 
 // the kernel-argument form of a bsdfd_wf_lights
@@ -103,23 +96,6 @@ int bsdfd_wf_sample_emitter(const bsdfd_wf_scene* scene, const bsdfd_wf_lights* 
     const Step st = make_step(bounce, 0, occlusion, seed, pass, path_offset, N);
     return launch_lanes(N, sample_emitter_kernel, stream, sc, lt, st, org, nrm, wi, reinterpret_cast<const long long*>(material), wl,
                         reinterpret_cast<int*>(lsel), emit);
-}
-
-int bsdfd_wf_bounce_lit(const bsdfd_wf_scene* scene, const float* env, int32_t bounce, int32_t last, int32_t occlusion,
-                        uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, float* org, float* nrm, float* wi,
-                        float* wl, int64_t* material, float* beta, float* rad, const float* wo, const float* pdf_o,
-                        const float* pdf_l, const float* f_o, const float* f_l, const bsdfd_wf_lights* lights,
-                        const int32_t* lsel, const float* emit, void* stream) {
-    Scene sc;
-    Lights lt;
-    if (int rc = path_scene(scene, env, N, sc)) return rc;
-    if (int rc = to_lights(lights, lt)) return rc;
-    const PathState ps{org, nrm, wi, wl, reinterpret_cast<long long*>(material), beta, rad};
-    const SamplerAnswer sa{wo, pdf_o, pdf_l, f_o, f_l};
-    const EmitterSample es{reinterpret_cast<const int*>(lsel), nullptr, emit};
-    return checked_bounce(bounce, last, occlusion, seed, pass, path_offset, N, ps, sa, lsel && emit, [&](const Step& st) {
-        return launch_lanes(N, bounce_lit_kernel, stream, sc, env, lt.n_e, lt.n_e - lt.n, st, ps, sa, es);
-    });
 }
 
 }  // extern "C"

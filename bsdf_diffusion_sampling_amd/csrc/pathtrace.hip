@@ -8,32 +8,26 @@
 //
 //   path_begin : dir, nrm, material of bsdfd_wf_primary -> org (world position of the first vertex), beta = 1,
 //                rad = env(dir) for a miss, 0 otherwise
-//   bounce     : + wo, pdf(wo), pdf(wl) [, f(wo), f(wl)] of the sampler for the vertices that carry a material
-//                -> rad += beta * (MIS estimate of the environment seen from the vertex); the path moves to the vertex its
-//                BSDF sample hits (org, nrm, wi, material, beta, a fresh light sample wl) or ends (material = n_balls + 1,
-//                the "miss" id: the next bucketing sorts it behind the materials and it costs no flow evaluation)
+//   (bounce)   : bounce.hip — per depth, with the sampler's answers for the vertices that carry a material; an ended path gets
+//                material = n_balls + 1, the "miss" id: the next bucketing sorts it behind the materials and it costs no flow
+//                evaluation
 //   resolve    : film += mean over spp of rad
 //
-// The bounce itself is bounce_dev.h's bounce_vertex<Mode>, which bounce_kernel instantiates as COSINE: only the environment
-// emits, and both strategies are cosine-weighted against each other (point emitters: pathlights.hip, LIT; the environment's own
-// distribution: pathenv.hip, ENV — their kernels stand in for bounce_kernel and move the paths the same way).  So a
-// BSDF sample that hits geometry adds nothing and a light sample that hits geometry is shadowed.  A ray skips the surface it
-// starts on (known from the material id; a sphere is convex, a plane flat): there is no epsilon offset.  One path per lane; a
-// lane whose path has ended returns after reading its id.  Streaming kernels: ~125 B read and ~90 B written per live path, a
-// few hundred flops.
+// A ray skips the surface it starts on (known from the material id; a sphere is convex, a plane flat): there is no epsilon
+// offset.  One path per lane.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 #include <string>
 
-#include "bounce_dev.h"
 #include "bsdfd.h"
 #include "common.h"
+#include "wavefront_dev.h"
 
 namespace {
 
-using namespace bounce_dev;
+using namespace wf_dev;
 
 __global__ __launch_bounds__(256) void path_begin_kernel(Scene sc, const float* __restrict__ env, long long n,
                                                          const float* __restrict__ dir, const float* __restrict__ nrm,
@@ -61,10 +55,6 @@ __global__ __launch_bounds__(256) void path_begin_kernel(Scene sc, const float* 
     st3(rad + 3 * p, v3(L[0], L[1], L[2]));
 }
 
-__global__ __launch_bounds__(256) void bounce_kernel(Scene sc, const float* __restrict__ env, Step st, PathState ps, SamplerAnswer sa) {
-    bounce_vertex<COSINE>(sc, env, EnvDist{}, 1, 1, st, ps, sa, EmitterSample{});
-}
-
 __global__ __launch_bounds__(256) void resolve_kernel(long long npix, int spp, const float* __restrict__ rad,
                                                       float* __restrict__ film) {
     const long long pix = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -84,18 +74,6 @@ int bsdfd_wf_path_begin(const bsdfd_wf_scene* scene, const float* env, int64_t N
     if (!dir || !nrm || !material || !org || !beta || !rad) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
     return launch_lanes(N, path_begin_kernel, stream, sc, env, (long long)N, dir, nrm, reinterpret_cast<const long long*>(material),
                         org, beta, rad);
-}
-
-int bsdfd_wf_bounce(const bsdfd_wf_scene* scene, const float* env, int32_t bounce, int32_t last, int32_t occlusion,
-                    uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, float* org, float* nrm, float* wi,
-                    float* wl, int64_t* material, float* beta, float* rad, const float* wo, const float* pdf_o,
-                    const float* pdf_l, const float* f_o, const float* f_l, void* stream) {
-    Scene sc;
-    if (int rc = path_scene(scene, env, N, sc)) return rc;
-    const PathState ps{org, nrm, wi, wl, reinterpret_cast<long long*>(material), beta, rad};
-    const SamplerAnswer sa{wo, pdf_o, pdf_l, f_o, f_l};
-    return checked_bounce(bounce, last, occlusion, seed, pass, path_offset, N, ps, sa, true,
-                          [&](const Step& st) { return launch_lanes(N, bounce_kernel, stream, sc, env, st, ps, sa); });
 }
 
 int bsdfd_wf_resolve(const bsdfd_wf_scene* scene, int32_t row_begin, int32_t row_end, int32_t spp, const float* rad,

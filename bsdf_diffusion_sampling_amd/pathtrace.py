@@ -1,8 +1,8 @@
 """Path tracer for the array scene: occlusion, further bounces (csrc/pathtrace.hip, C ABI ``bsdfd_wf_path_begin`` /
-``bsdfd_wf_bounce`` / ``bsdfd_wf_resolve``), point emitters (csrc/pathlights.hip, ``bsdfd_wf_sample_emitter`` /
-``bsdfd_wf_bounce_lit``), importance sampling of the environment map (csrc/pathenv.hip, ``bsdfd_wf_sample_env`` /
-``bsdfd_wf_bounce_env``; the distribution: ``envmap.EnvDistribution``) and Russian roulette with unbounded depth
-(csrc/pathrr.hip, ``bsdfd_wf_bounce_rr``).
+``bsdfd_wf_resolve``), point emitters (csrc/pathlights.hip, ``bsdfd_wf_sample_emitter``), importance sampling of the
+environment map (csrc/pathenv.hip, ``bsdfd_wf_sample_env``; the distribution: ``envmap.EnvDistribution``), and the bounce
+for each of them, with Russian roulette for unbounded depth (csrc/bounce.hip, ``bsdfd_wf_bounce`` / ``_lit`` / ``_env`` /
+``_rr``).
 
 The reference renders its 12-ball array scenes with Mitsuba's ``path`` integrator at unbounded depth
 (matpreview/disney_bsdf_array*_envmap.xml, scene_measured.xml: ``max_depth = -1``): balls shadow the floor and each
@@ -268,19 +268,23 @@ class PathArrayRenderer(ArrayRenderer):
         env_dist = self.env_dist if env_dist is None else env_dist
         rr_depth = self.rr_depth if rr_depth is None else rr_depth
         with torch.cuda.device(self.device):
-            fn, args = _lib.lib().bsdfd_wf_bounce, [
+            args = [
                 C.byref(self.scene), _p(self.env), bounce, int(bool(last)), int(bool(occlusion)), seed, pass_idx, path_offset,
                 b["mat"].shape[0], _p(b["org"]), _p(b["nrm"]), _p(b["wi"]), _p(b["wl"]), _p(b["mat"]), _p(b["beta"]), _p(b["rad"]),
                 _p(b["wo"]), _p(b["pdf_o"]), _p(b["pdf_l"]), _p(b.get("f_o")), _p(b.get("f_l"))]
-            if lights is not None or env_dist is not None:   # bounce_lit's arguments follow bounce's ...
-                fn = _lib.lib().bsdfd_wf_bounce_lit
-                args += [None if lights is None else C.byref(lights), None if lights is None else _p(b["lsel"]), _p(b["emit"])]
-            if env_dist is not None:                         # ... and bounce_env's follow bounce_lit's
-                fn = _lib.lib().bsdfd_wf_bounce_env
-                args += [_p(b["lpdf"]), C.byref(env_dist.struct(self.device))]
-            if rr_depth is not None:                         # ... and bounce_rr's are bounce_env's (NULL: not this mode's) + rr_depth
-                fn = _lib.lib().bsdfd_wf_bounce_rr
-                args += [None] * (26 - len(args)) + [int(rr_depth)]
+            # the emitter tail (lights, lsel, emit, lpdf, dist), None where the mode has none: bounce takes none of it, bounce_lit
+            # the first three, bounce_env all five, bounce_rr all five + rr_depth
+            lit, env = lights is not None, env_dist is not None
+            tail = [C.byref(lights) if lit else None, _p(b["lsel"]) if lit else None, _p(b["emit"]) if lit or env else None,
+                    _p(b["lpdf"]) if env else None, C.byref(env_dist.struct(self.device)) if env else None]
+            if rr_depth is not None:
+                fn, args = _lib.lib().bsdfd_wf_bounce_rr, args + tail + [int(rr_depth)]
+            elif env:
+                fn, args = _lib.lib().bsdfd_wf_bounce_env, args + tail
+            elif lit:
+                fn, args = _lib.lib().bsdfd_wf_bounce_lit, args + tail[:3]
+            else:
+                fn = _lib.lib().bsdfd_wf_bounce
             _lib.check(fn(*args, self._stream()))
         # written through raw pointers: tell torch (the plugin cores key their per-query context cache on wi._version)
         torch.autograd.graph.increment_version([b["wi"], b["wl"], b["nrm"], b["org"], b["mat"], b["beta"], b["rad"]])

@@ -629,7 +629,7 @@ int bsdfd_wf_bounce_env(const bsdfd_wf_scene* scene, const float* env, int32_t b
                         const float* pdf_l, const float* f_o, const float* f_l, const bsdfd_wf_lights* lights,
                         const int32_t* lsel, const float* emit, const float* lpdf, const bsdfd_env_dist* dist, void* hip_stream);
 
-/* ---- Russian roulette in the array scene (csrc/pathrr.hip) ------------------------------------------
+/* ---- Russian roulette in the array scene (csrc/bounce.hip) ------------------------------------------
  * Six of the reference's array scenes are rendered by Mitsuba's `path` integrator at max_depth = -1 with its default rr_depth = 5.
  * Mitsuba's rule (the `path` integrator's `rr_depth` parameter): once  depth >= rr_depth  — depth = the surface vertices processed so far, here bounce + 1 —
  * a path continues with probability  q = min(max over the channels of throughput * eta^2, 0.95)  and its throughput is divided

@@ -1,7 +1,8 @@
 """Reference for the environment map's importance sampler (bsdf_diffusion_sampling_amd/envmap.py, csrc/env_dev.h,
 csrc/pathenv.hip): a numpy restatement of the table build, of ``bsdfd_env_sample`` / ``bsdfd_env_pdf`` and of
-``bsdfd_wf_sample_env`` / ``bsdfd_wf_bounce_env``, fp64 by default, fp32 on request, on top of tests/pathtrace_ref.py (``trace``,
-``bounce`` for where a path goes, the synthetic scene) and tests/pathtrace_lights_ref.py (frames, the synthetic lit wavefront).
+``bsdfd_wf_sample_env``, fp64 by default, fp32 on request, on top of tests/pathtrace_ref.py (``trace``, the synthetic scene) and
+tests/pathtrace_lights_ref.py (frames, the synthetic lit wavefront).  ``bsdfd_wf_bounce_env`` is tests/bounce_ref.py's ``bounce``
+in the mode "env".
 
 Test infrastructure only.  The tables are the fp32 data kernel and reference share; a variate is ``(word >> 8) * 2^-24``, an exact
 fp32 number, so the cell either of them picks is an exact decision in both precisions.
@@ -12,7 +13,7 @@ import numpy as np
 
 import pathtrace_lights_ref as LR
 import pathtrace_ref as R
-from oracle.wavefront_oracle import env_lookup, mis_power, philox4x32
+from oracle.wavefront_oracle import env_lookup, mis_power
 
 F = np.float32
 INV_PI = 0.31830988618379067154
@@ -126,10 +127,8 @@ def direction_bound(shape, s: dict):
 # ---- the path kernels ----------------------------------------------------------------------------------------------------------
 def env_variates(seed: int, pass_idx: int, bounce: int, path_offset: int, n: int):
     """[n,2] fp32: (word 0 >> 8, word 1 >> 8) * 2^-24 of philox(key = seed, counter = (path lo, hi, pass, "Envm" + bounce))."""
-    gp = np.uint64(path_offset) + np.arange(n, dtype=np.uint64)
-    u = philox4x32(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, gp & np.uint64(0xFFFFFFFF), gp >> np.uint64(32),
-                   pass_idx & 0xFFFFFFFF, (0x456E766D + bounce) & 0xFFFFFFFF)
-    return np.stack([(u[k] >> np.uint32(8)).astype(F) * F(1.0 / 16777216.0) for k in (0, 1)], 1)
+    u = R.tagged_draw(0x456E766D, seed, pass_idx, bounce, path_offset, n)
+    return np.stack([R.unit(u[0]), R.unit(u[1])], 1)
 
 
 def sample_env(scene: dict, env, tables: dict, n_e: int, bounce: int, occlusion: bool, seed: int, pass_idx: int, path_offset: int,
@@ -160,52 +159,6 @@ def sample_env(scene: dict, env, tables: dict, n_e: int, bounce: int, occlusion:
                     lpdf=np.where(picked, p_l, np.nan).astype(dtype),
                     emit=np.where(picked[:, None], np.where(lit[:, None], scale[:, None] * E, dtype(0)), np.nan).astype(dtype),
                     lit=lit, picked=picked, cell=(s["j"], s["i"]))
-
-
-def bounce_env(scene: dict, env, tables: dict, n_e: int, bounce: int, last: bool, occlusion: bool, seed: int, pass_idx: int,
-               path_offset: int, org, nrm, wi, wl, material, beta, rad, wo, pdf_o, pdf_l, f_o=None, f_l=None, lsel=None, emit=None,
-               lpdf=None, dtype=np.float64):
-    """One call of bsdfd_wf_bounce_env -> the dict of ``pathtrace_ref.bounce``.  Where the path goes does not depend on how the
-    light was sampled, so that part IS ``pathtrace_ref.bounce``; ``rad`` is restated here."""
-    out = R.bounce(scene, env, bounce, last, occlusion, seed, pass_idx, path_offset, org, nrm, wi, wl, material, beta, rad, wo,
-                   pdf_o, pdf_l, f_o, f_l, dtype=dtype)
-    with np.errstate(all="ignore"):
-        n_b, n = len(scene["spheres"]), len(material)
-        org, nrm, wi, wl, beta, rad, wo = (np.asarray(a).astype(dtype) for a in (org, nrm, wi, wl, beta, rad, wo))
-        emit = np.nan_to_num(np.asarray(emit)).astype(dtype)        # (rows nobody wrote are rows nobody reads)
-        lpdf = np.nan_to_num(np.asarray(lpdf)).astype(dtype)
-        live = (material >= 0) & (material <= n_b)
-        floor = live & (material == n_b)
-        ball = live & ~floor
-        point = np.zeros(n, dtype=bool) if lsel is None else live & (lsel >= 0)
-        fs, ft, nn = LR._frames(nrm, live, dtype)
-        to_world = lambda v: v[:, 0:1] * fs + v[:, 1:2] * ft + v[:, 2:3] * nn
-        own = np.where(live, material, -2)
-        look = lambda dw: env_lookup(np.asarray(env, dtype=np.float64), dw.astype(F)).astype(dtype)
-        inv_pi, sel_p = dtype(INV_PI), dtype(1) / dtype(n_e)
-        albedo = np.asarray(scene["albedo"], dtype=F).astype(dtype)[None, :]
-        lw, dw = to_world(wl), to_world(wo)
-        no_hit = np.zeros(n, dtype=bool)
-        hit_l = R.trace(scene, org, lw, own, dtype)[1] >= 0 if occlusion else no_hit
-        hit_o = R.trace(scene, org, dw, own, dtype)[1] >= 0 if occlusion else no_hit
-        pb = np.where(np.isfinite(pdf_o) & (pdf_o > 0), pdf_o, 0).astype(dtype)
-        pbl = np.where(np.isfinite(pdf_l) & (pdf_l > 0), pdf_l, 0).astype(dtype)
-        gt_o = np.zeros(n, dtype=bool) if f_o is None else ~np.isnan(f_o[:, 0])
-        gt_l = np.zeros(n, dtype=bool) if f_l is None else ~np.isnan(f_l[:, 0])
-        thr_o = np.where(gt_o[:, None], (np.zeros((n, 3)) if f_o is None else np.nan_to_num(f_o)).astype(dtype) / pb[:, None], albedo)
-        f_l_v = albedo * pbl[:, None] if f_l is None else np.where(gt_l[:, None], np.nan_to_num(f_l).astype(dtype), albedo * pbl[:, None])
-        follow = ball & (pb > 0) & ((wo[:, 2] > 0) if occlusion else ~no_hit)
-        # a BSDF sample that escapes, weighted against the environment strategy's density pdf_env / n_e
-        w_o = mis_power(pb, pdf(tables, dw, dtype) * sel_p).astype(dtype)
-        L = np.where((follow & ~hit_o)[:, None], w_o[:, None] * look(dw) * thr_o, dtype(0))
-        # the emitter sample: a point is a delta, the environment's draw is weighted against the sampler's density
-        w_l = np.where(point, dtype(1), mis_power(lpdf, pbl).astype(dtype))
-        L = L + np.where((ball & ((pbl > 0) | gt_l))[:, None], w_l[:, None] * emit * f_l_v, dtype(0))
-        w_f = mis_power(wl[:, 2] * inv_pi, pdf(tables, lw, dtype) * sel_p).astype(dtype)
-        L_floor = np.where(hit_l[:, None], dtype(0), w_f[:, None] * wi[:, 0:1] * look(lw)) + emit
-        L = np.where(floor[:, None], L_floor, L)
-        out["rad"] = np.where(live[:, None], rad + beta * L, rad)
-    return out
 
 
 # ---- the synthetic wavefront of tests/test_gpu_envmap.py ---------------------------------------------------------------------

@@ -9,7 +9,7 @@ strings the kernels together — ``render_pass`` — is held here:
                     It calls no product code of its own.
 ``reference_pass``  the pass as the module docstring of pathtrace.py describes it, as a plain loop over the references of the
                     stages (oracle/wavefront_oracle.py ``primary``, tests/pathtrace_ref.py, tests/pathtrace_lights_ref.py,
-                    tests/envmap_ref.py), fp64 by default, fp32 on request.  The sampler and the evaluator are inputs
+                    tests/envmap_ref.py, tests/bounce_ref.py), fp64 by default, fp32 on request.  The sampler and the evaluator are inputs
                     (``answers``), exactly as in the kernel tests.
 """
 from __future__ import annotations
@@ -18,13 +18,14 @@ import math
 
 import numpy as np
 
+import bounce_ref as B
 import envmap_ref as ER
 import pathtrace_lights_ref as LR
 import pathtrace_ref as R
 from oracle import wavefront_oracle as WO
 
 F = np.float32
-M64 = (1 << 64) - 1
+M64 = R.M64
 STATE = ("org", "nrm", "wi", "wl", "material", "beta", "rad")
 ANSWER = ("wo", "pdf_o", "pdf_l", "f_o", "f_l")
 
@@ -193,8 +194,13 @@ def mock_answers(seed: int):
     return answer
 
 
+def bounce_mode(mode: str, lights) -> str:
+    """The mode of ``bounce_ref.bounce`` a renderer in ``mode`` ("cosine" / "importance") with or without ``lights`` calls."""
+    return "env" if mode == "importance" else "cosine" if lights is None else "lit"
+
+
 def reference_pass(scene: dict, env, mode: str, lights, tables, row_begin: int, row_end: int, spp: int, seed: int, pass_idx: int,
-                   max_depth: int, occlusion: bool, answers, dtype=np.float64):
+                   max_depth, occlusion: bool, answers, dtype=np.float64, rr_depth=None, depth_cap: int = 1024, scale=True):
     """One pass of ``PathArrayRenderer`` over rows [row_begin, row_end), written from the module docstring of pathtrace.py:
 
         primary -> path_begin
@@ -203,10 +209,14 @@ def reference_pass(scene: dict, env, mode: str, lights, tables, row_begin: int, 
 
     ``mode``: "cosine" or "importance" (then ``tables`` = ``envmap_ref.build_tables(env)``); ``lights``: None or the dict of
     ``pathtrace_lights_ref.make_lights``; ``env`` None (with lights only): black, and no emitter.  ``answers``: a sequence of
-    dicts ``wo, pdf_o, pdf_l[, f_o, f_l]`` per bounce (rows in path order), or ``f(k, state)`` that returns one.
+    dicts ``wo, pdf_o, pdf_l[, f_o, f_l]`` per bounce (rows in path order), or ``f(k, state)`` that returns one; a sequence that
+    runs out ends the loop (the device's pass was shorter: its rows then differ in their histories).  ``rr_depth``: Russian
+    roulette in every bounce (``scale`` as in ``bounce_ref.bounce``), and only then may ``max_depth`` be None, the unbounded loop:
+    it runs until no lane is live, ``depth_cap`` bounces at the most (the bounce at the cap is ``last``).
     -> dict(stages: [(name, bounce, state dict)] after every stage, history: [``decision_code`` after primary and after every
-    bounce], rad [N,3], film [rows, width, 3]: the tile the pass adds)."""
+    bounce], rad [N,3], film [rows, width, 3]: the tile the pass adds, depth: bounces run, depth_cap_hit)."""
     assert mode in ("cosine", "importance")
+    assert max_depth is not None or rr_depth is not None
     has_env = env is not None
     assert has_env or lights is not None
     env = np.zeros((2, 4, 3), F) if env is None else np.asarray(env, dtype=F)
@@ -222,9 +232,11 @@ def reference_pass(scene: dict, env, mode: str, lights, tables, row_begin: int, 
     st = {k: (v if k == "material" else np.asarray(v).astype(dtype)) for k, v in dict(st, org=org, beta=beta, rad=rad).items()}
     stages.append(("path_begin", None, dict(st)))
     history = [decision_code(scene, mat, wi)]
-    for k in range(max_depth):
+    depth = depth_cap if max_depth is None else max_depth
+    ran = 0
+    for k in range(depth):
         live = (st["material"] >= 0) & (st["material"] <= n_b)
-        if not live.any():
+        if not live.any() or (not callable(answers) and k >= len(answers)):
             break
         vertex = [st[name] for name in ("org", "nrm", "wi", "material")]
         if lights is not None:
@@ -239,20 +251,17 @@ def reference_pass(scene: dict, env, mode: str, lights, tables, row_begin: int, 
                       emit=np.where(picked[:, None], s["emit"], st.get("emit", np.zeros((n, 3)))).astype(dtype))
             stages.append(("sample_env", k, dict(st)))
         a = answers(k, st) if callable(answers) else answers[k]
-        last = k == max_depth - 1
-        args = (k, last, occlusion, seed, pass_idx, offset, *[st[name] for name in STATE], a["wo"], a["pdf_o"], a["pdf_l"],
-                a.get("f_o"), a.get("f_l"))
-        if mode == "importance":
-            out = ER.bounce_env(scene, env, tables, n_e, *args, lsel=st.get("lsel"), emit=st["emit"], lpdf=st["lpdf"], dtype=dtype)
-        elif lights is not None:
-            out = LR.bounce_lit(scene, env, n_e, has_env, *args, lsel=st["lsel"], emit=st["emit"], dtype=dtype)
-        else:
-            out = R.bounce(scene, env, *args, dtype=dtype)
+        out = B.bounce(scene, env, bounce_mode(mode, lights), k, k == depth - 1, occlusion, seed, pass_idx, offset,
+                       *[st[name] for name in STATE], a["wo"], a["pdf_o"], a["pdf_l"], a.get("f_o"), a.get("f_l"), n_e=n_e,
+                       has_env=has_env, lsel=st.get("lsel"), emit=st.get("emit"), lpdf=st.get("lpdf"), tables=tables,
+                       rr_depth=rr_depth, scale=scale, dtype=dtype)
         st.update({name: (out[name] if name == "material" else out[name].astype(dtype)) for name in STATE})
-        stages.append(("bounce", k, dict(st)))
+        rr = {} if rr_depth is None else {name: out[name] for name in ("cos_in", "killed", "survive", "q")}
+        stages.append(("bounce", k, dict(st, **rr)))
         history.append(decision_code(scene, st["material"], st["wi"]))
+        ran = k + 1
     film = R.resolve(st["rad"], spp).reshape(row_end - row_begin, width, 3)
-    return dict(stages=stages, history=history, rad=st["rad"], film=film)
+    return dict(stages=stages, history=history, rad=st["rad"], film=film, depth=ran, depth_cap_hit=max_depth is None and ran == depth)
 
 
 def decision_code(scene: dict, material, wi):

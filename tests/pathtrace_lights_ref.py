@@ -1,6 +1,6 @@
 """Reference for the point-emitter kernels (bsdf_diffusion_sampling_amd/csrc/pathlights.hip): a numpy restatement of
-``bsdfd_wf_sample_emitter`` / ``bsdfd_wf_bounce_lit``, fp64 by default, fp32 on request, on top of tests/pathtrace_ref.py
-(``trace``, the bases, ``bounce`` for where a path goes, the synthetic scene and wavefront).
+``bsdfd_wf_sample_emitter``, fp64 by default, fp32 on request, on top of tests/pathtrace_ref.py (``trace``, the bases, the
+synthetic scene and wavefront).  ``bsdfd_wf_bounce_lit`` is tests/bounce_ref.py's ``bounce`` in the mode "lit".
 
 Test infrastructure only.  Lights are a dict ``position`` [n,3], ``intensity`` [n,3] (world, y up, stored in fp32 like the scene).
 """
@@ -9,7 +9,7 @@ from __future__ import annotations
 import numpy as np
 
 import pathtrace_ref as R
-from oracle.wavefront_oracle import env_lookup, mis_power, onb, philox4x32
+from oracle.wavefront_oracle import onb
 
 F = np.float32
 INV_PI = 0.31830988618379067154
@@ -22,9 +22,7 @@ def make_lights(position, intensity):
 
 def pick_emitter(seed: int, pass_idx: int, bounce: int, path_offset: int, n: int, n_e: int):
     """(u0 * n_e) >> 32 of the paths path_offset .. path_offset + n - 1 at depth ``bounce`` — integers throughout."""
-    gp = np.uint64(path_offset) + np.arange(n, dtype=np.uint64)
-    u = philox4x32(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, gp & np.uint64(0xFFFFFFFF), gp >> np.uint64(32),
-                   pass_idx & 0xFFFFFFFF, (0x4C697465 + bounce) & 0xFFFFFFFF)
+    u = R.tagged_draw(0x4C697465, seed, pass_idx, bounce, path_offset, n)   # "Lite"
     return ((u[0].astype(np.uint64) * np.uint64(n_e)) >> np.uint64(32)).astype(np.int64)
 
 
@@ -66,54 +64,6 @@ def sample_emitter(scene: dict, lights: dict, has_env: bool, bounce: int, occlus
         return dict(wl=np.where((point & ~floor)[:, None], local, wl).astype(dtype),
                     lsel=np.where(live, np.where(point, pick, -1), -2).astype(np.int32),
                     emit=np.where(point[:, None], s[:, None] * I, dtype(0)).astype(dtype), lit=lit)
-
-
-def bounce_lit(scene: dict, env, n_e: int, has_env: bool, bounce: int, last: bool, occlusion: bool, seed: int, pass_idx: int,
-               path_offset: int, org, nrm, wi, wl, material, beta, rad, wo, pdf_o, pdf_l, f_o=None, f_l=None, lsel=None, emit=None,
-               dtype=np.float64):
-    """One call of bsdfd_wf_bounce_lit -> the dict of ``pathtrace_ref.bounce``.  Where the path goes does not depend on the
-    emitters, so that part IS ``pathtrace_ref.bounce``; ``rad`` is restated here."""
-    out = R.bounce(scene, env, bounce, last, occlusion, seed, pass_idx, path_offset, org, nrm, wi, wl, material, beta, rad, wo,
-                   pdf_o, pdf_l, f_o, f_l, dtype=dtype)
-    with np.errstate(all="ignore"):
-        n_b, n = len(scene["spheres"]), len(material)
-        org, nrm, wi, wl, beta, rad, wo, emit = (np.asarray(a).astype(dtype) for a in (org, nrm, wi, wl, beta, rad, wo, emit))
-        live = (material >= 0) & (material <= n_b)
-        floor = live & (material == n_b)
-        ball = live & ~floor
-        point = live & (lsel >= 0)
-        fs, ft, nn = _frames(nrm, live, dtype)
-        to_world = lambda v: v[:, 0:1] * fs + v[:, 1:2] * ft + v[:, 2:3] * nn
-        own = np.where(live, material, -2)
-        look = lambda dw: env_lookup(env.astype(np.float64), dw.astype(F)).astype(dtype)
-        inv_pi, sel_p = dtype(INV_PI), dtype(1) / dtype(n_e)
-        albedo = np.asarray(scene["albedo"], dtype=F).astype(dtype)[None, :]
-        lw, dw = to_world(wl), to_world(wo)
-        no_hit = np.zeros(n, dtype=bool)
-        hit_l = R.trace(scene, org, lw, own, dtype)[1] >= 0 if occlusion else no_hit
-        hit_o = R.trace(scene, org, dw, own, dtype)[1] >= 0 if occlusion else no_hit
-        pb = np.where(np.isfinite(pdf_o) & (pdf_o > 0), pdf_o, 0).astype(dtype)
-        pbl = np.where(np.isfinite(pdf_l) & (pdf_l > 0), pdf_l, 0).astype(dtype)
-        gt_o = np.zeros(n, dtype=bool) if f_o is None else ~np.isnan(f_o[:, 0])
-        gt_l = np.zeros(n, dtype=bool) if f_l is None else ~np.isnan(f_l[:, 0])
-        thr_o = np.where(gt_o[:, None], (np.zeros((n, 3)) if f_o is None else np.nan_to_num(f_o)).astype(dtype) / pb[:, None], albedo)
-        f_l_v = albedo * pbl[:, None] if f_l is None else np.where(gt_l[:, None], np.nan_to_num(f_l).astype(dtype), albedo * pbl[:, None])
-        follow = ball & (pb > 0) & ((wo[:, 2] > 0) if occlusion else ~no_hit)
-        L = np.zeros((n, 3), dtype=dtype)
-        if has_env:   # a BSDF sample that escapes, weighted against the environment strategy's density (cos / pi) / n_e
-            w_o = mis_power(pb, np.maximum(wo[:, 2], 0) * inv_pi * sel_p).astype(dtype)
-            L = np.where((follow & ~hit_o)[:, None], w_o[:, None] * look(dw) * thr_o, L)
-        ok_l = ball & ((pbl > 0) | gt_l)
-        L = L + np.where((ok_l & point)[:, None], emit * f_l_v, dtype(0))            # a delta light: no MIS weight
-        pl = wl[:, 2] * inv_pi * sel_p
-        ok_env = ok_l & ~point & (pl > 0) & ~hit_l
-        w_l = np.where(ok_env, mis_power(pl, pbl).astype(dtype) / pl, dtype(0))
-        L = L + np.where(ok_env[:, None], w_l[:, None] * look(lw) * f_l_v, dtype(0))
-        L_floor = np.where(hit_l[:, None], dtype(0), wi[:, 0:1] * look(lw)) if has_env else np.zeros((n, 3), dtype=dtype)
-        L_floor = L_floor + np.where(point[:, None], emit, dtype(0))
-        L = np.where(floor[:, None], L_floor, L)
-        out["rad"] = np.where(live[:, None], rad + beta * L, rad)
-    return out
 
 
 # ---- the synthetic lights and wavefront of tests/test_gpu_pathtrace_lights.py ------------------------------------------------

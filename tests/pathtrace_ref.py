@@ -1,6 +1,7 @@
 """Reference for the path kernels (bsdf_diffusion_sampling_amd/csrc/pathtrace.hip): a numpy restatement of
-``bsdfd_wf_path_begin`` / ``bsdfd_wf_bounce`` / ``bsdfd_wf_resolve``, fp64 by default, fp32 on request (``dtype=np.float32``:
-the same statements in the kernels' own precision, to show which decisions the arithmetic alone can flip).
+``bsdfd_wf_path_begin`` / ``bsdfd_wf_resolve`` and of what the bounce (tests/bounce_ref.py) is built from — ``trace``, the tagged
+Philox draw, the next light sample —, fp64 by default, fp32 on request (``dtype=np.float32``: the same statements in the kernels'
+own precision, to show which decisions the arithmetic alone can flip).
 
 Test infrastructure only.  The pieces it shares with the one-bounce harness — Philox, the orthonormal basis, the
 environment lookup, the power heuristic — are the oracle's (oracle/wavefront_oracle.py); the scene is the oracle's dict:
@@ -10,9 +11,10 @@ from __future__ import annotations
 
 import numpy as np
 
-from oracle.wavefront_oracle import env_lookup, mis_power, onb, philox4x32
+from oracle.wavefront_oracle import env_lookup, philox4x32
 
 F = np.float32
+M64 = (1 << 64) - 1
 T_NONE = 3.0e38
 
 
@@ -71,107 +73,25 @@ def path_begin(scene: dict, env, dir_, nrm, material, dtype=np.float64):
     return org.astype(dtype), np.ones((len(d), 3), dtype=dtype), rad.astype(dtype)
 
 
+def tagged_draw(tag: int, seed: int, pass_idx: int, bounce: int, path_offset: int, n: int):
+    """``bounce_dev::tagged_draw`` of the paths path_offset .. path_offset + n - 1 (the sum wraps at 2^64): the four words [4][n] of
+    philox(key = seed, counter = (path lo, hi, pass, tag + bounce))."""
+    gp = np.uint64(path_offset & M64) + np.arange(n, dtype=np.uint64)
+    return philox4x32(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, gp & np.uint64(0xFFFFFFFF), gp >> np.uint64(32),
+                      pass_idx & 0xFFFFFFFF, (tag + bounce) & 0xFFFFFFFF)
+
+
+def unit(word):
+    """(word >> 8) * 2^-24: an exact fp32 number in [0, 1)."""
+    return (word >> np.uint32(8)).astype(F) * F(1.0 / 16777216.0)
+
+
 def next_wl(seed: int, pass_idx: int, bounce: int, path_offset: int, n: int):
     """The light sample of the vertex bounce + 1 of paths path_offset .. path_offset + n - 1 (fp32, primary's mapping)."""
-    gp = np.uint64(path_offset) + np.arange(n, dtype=np.uint64)
-    u = philox4x32(seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF, gp & np.uint64(0xFFFFFFFF), gp >> np.uint64(32),
-                   pass_idx & 0xFFFFFFFF, (0x57617665 + bounce + 1) & 0xFFFFFFFF)
-    u2 = ((u[2] >> np.uint32(8)).astype(F) + F(1.0)) * F(1.0 / 16777216.0)
-    u3 = (u[3] >> np.uint32(8)).astype(F) * F(1.0 / 16777216.0)
+    u = tagged_draw(0x57617665, seed, pass_idx, bounce + 1, path_offset, n)
+    u2, u3 = ((u[2] >> np.uint32(8)).astype(F) + F(1.0)) * F(1.0 / 16777216.0), unit(u[3])
     r, ang = np.sqrt(u2), F(6.28318530717958647692) * u3
     return np.stack([r * np.cos(ang), r * np.sin(ang), np.sqrt(np.maximum(F(1.0) - u2, F(0.0)))], 1).astype(F)
-
-
-def bounce(*args, **kwargs):
-    """``_bounce`` with numpy's floating-point warnings off: rows that are masked out divide by zero on the way."""
-    with np.errstate(all="ignore"):
-        return _bounce(*args, **kwargs)
-
-
-def _bounce(scene: dict, env, bounce: int, last: bool, occlusion: bool, seed: int, pass_idx: int, path_offset: int,
-           org, nrm, wi, wl, material, beta, rad, wo, pdf_o, pdf_l, f_o=None, f_l=None, dtype=np.float64):
-    """One call of bsdfd_wf_bounce -> dict(org, nrm, wi, wl, material, beta, rad, cos_in): the arrays after the call (rows the
-    kernel does not write keep their input values); ``cos_in`` [N] = -d . n at the new vertex (nan where none), for the
-    grazing-hit bound."""
-    assert (f_o is None) == (f_l is None)
-    n_b = len(scene["spheres"])
-    n = len(material)
-    cast = lambda a: np.asarray(a).astype(dtype)
-    org, nrm, wi, wl, beta, rad, wo = (cast(a) for a in (org, nrm, wi, wl, beta, rad, wo))
-    live = (material >= 0) & (material <= n_b)
-    floor = live & (material == n_b)
-    ball = live & ~floor
-    safe_n = np.where(live[:, None], nrm, np.array([0.0, 0.0, 1.0], dtype=dtype))
-    fs, ft = onb(safe_n.astype(F))
-    fs, ft = fs.astype(dtype), ft.astype(dtype)
-    to_world = lambda v: v[:, 0:1] * fs + v[:, 1:2] * ft + v[:, 2:3] * safe_n
-    own = np.where(live, material, -2)
-    env64 = env.astype(np.float64)
-    look = lambda dw: env_lookup(env64, dw.astype(F)).astype(dtype)
-    inv_pi = dtype(0.31830988618379067154)
-    albedo = np.asarray(scene["albedo"], dtype=F).astype(dtype)[None, :]
-
-    nothing = (np.full(n, dtype(T_NONE)), np.full(n, -1), np.zeros((n, 3), dtype=dtype), np.ones(n, dtype=dtype))
-    lw = to_world(wl)
-    t_f, id_f, c_f, r_f = trace(scene, org, lw, own, dtype) if occlusion else nothing
-    hit_l = id_f >= 0
-    e_l = look(lw)
-    # ---- ball vertices: the two strategies of shade_kernel ----
-    pb = np.where(np.isfinite(pdf_o) & (pdf_o > 0), pdf_o, 0).astype(dtype)
-    gt_o = np.zeros(n, dtype=bool) if f_o is None else ~np.isnan(f_o[:, 0])
-    gt_l = np.zeros(n, dtype=bool) if f_l is None else ~np.isnan(f_l[:, 0])
-    follow = ball & (pb > 0) & ((wo[:, 2] > 0) if occlusion else np.ones(n, dtype=bool))
-    dw = to_world(wo)
-    t_o, id_o, c_o, r_o = trace(scene, org, dw, own, dtype) if occlusion else nothing
-    with np.errstate(divide="ignore", invalid="ignore"):
-        thr_o = np.where(gt_o[:, None], (np.zeros((n, 3)) if f_o is None else np.nan_to_num(f_o)).astype(dtype) / pb[:, None], albedo)
-    w_o = mis_power(pb, np.maximum(wo[:, 2], 0) * inv_pi).astype(dtype)
-    L = np.where((follow & (id_o < 0))[:, None], w_o[:, None] * look(dw) * thr_o, dtype(0))
-    pl = wl[:, 2] * inv_pi
-    pbl = np.where(np.isfinite(pdf_l) & (pdf_l > 0), pdf_l, 0).astype(dtype)
-    ok_l = ball & (pl > 0) & ((pbl > 0) | gt_l) & ~hit_l
-    with np.errstate(divide="ignore", invalid="ignore"):
-        w_l = np.where(ok_l, mis_power(pl, pbl).astype(dtype) / pl, dtype(0))
-    f_l_v = albedo * pbl[:, None] if f_l is None else np.where(gt_l[:, None], np.nan_to_num(f_l).astype(dtype), albedo * pbl[:, None])
-    L = L + np.where(ok_l[:, None], w_l[:, None] * e_l * f_l_v, dtype(0))
-    # ---- floor vertices: the one cosine-sampled direction ----
-    refl = wi[:, 0:1]
-    L = np.where(floor[:, None], np.where(hit_l[:, None], dtype(0), refl * e_l), L)
-    rad_new = np.where(live[:, None], rad + beta * L, rad)
-    # ---- where the path goes ----
-    go = (follow & (id_o >= 0)) | (floor & hit_l)
-    d = np.where(floor[:, None], lw, dw)
-    t = np.where(floor, t_f, t_o)
-    hid = np.where(floor, id_f, id_o)
-    c, r = np.where(floor[:, None], c_f, c_o), np.where(floor, r_f, r_o)
-    thr = np.where(floor[:, None], refl, thr_o)
-    cont = go & (not last)
-    mat_new = np.where(live, np.where(cont, hid, n_b + 1), material).astype(np.int64)
-    on_ball = cont & (hid < n_b)
-    tt = np.where(cont, t, dtype(0))
-    with np.errstate(divide="ignore", invalid="ignore"):
-        nv = ((org - c) + tt[:, None] * d) / r[:, None]
-        nv = nv / np.sqrt(_dot(nv, nv))[:, None]
-    nv = np.where(on_ball[:, None], nv, np.array([0.0, 1.0, 0.0], dtype=dtype))
-    gs, gt = _onb(nv)   # (the oracle's onb rounds its input to fp32: the new basis is formed in `dtype`)
-    w_ball = np.stack([-_dot(d, gs), -_dot(d, gt), -_dot(d, nv)], 1)
-    x_ball = c + r[:, None] * nv
-    x_floor = org + tt[:, None] * d
-    plane = scene.get("plane") or dict(scale=1.0, c0=0.0, c1=0.0)
-    cx = np.floor(x_floor[:, 0] * dtype(F(plane["scale"]))).astype(np.int64)
-    cz = np.floor(x_floor[:, 2] * dtype(F(plane["scale"]))).astype(np.int64)
-    refl_new = np.where(((cx + cz) & 1) == 1, dtype(F(plane["c1"])), dtype(F(plane["c0"])))
-    out = dict(
-        org=np.where(cont[:, None], np.where(on_ball[:, None], x_ball, x_floor), org),
-        nrm=np.where(cont[:, None], nv, nrm),
-        wi=np.where(cont[:, None], np.where(on_ball[:, None], w_ball, refl_new[:, None]), wi),
-        wl=np.where(cont[:, None], next_wl(seed, pass_idx, bounce, path_offset, n).astype(dtype), wl),
-        material=mat_new,
-        beta=np.where(cont[:, None], beta * thr, beta),
-        rad=rad_new,
-        cos_in=np.where(cont, -_dot(d, nv), np.nan),
-    )
-    return out
 
 
 def _onb(n):

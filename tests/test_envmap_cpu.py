@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import bounce_ref as B
 import envmap_ref as ER
 import pathtrace_lights_ref as LR
 import pathtrace_ref as R
@@ -222,11 +223,11 @@ def test_reference_decides_the_same_in_fp32_and_fp64(with_lights):
     assert picked.sum() >= (400 if with_lights else 3000) and (picked == live).all() == (not with_lights)
     assert (ball & (s64["wl"][:, 2] <= 0)).sum() >= 100 and (open_["lit"] & ~s64["lit"]).sum() >= 50
     assert (floor & s64["lit"]).sum() >= 50 and np.isnan(s64["emit"][~picked]).all()
-    # and bounce_env moves the paths as pathtrace_ref.bounce does, whatever the light sample was
+    # and the "env" bounce moves the paths as the "cosine" bounce does, whatever the light sample was
     st = dict(v, wl=s64["wl"].astype(np.float32))
-    b = ER.bounce_env(R.SYNTH_SCENE, env, t, n_e, bounce, False, True, seed, pass_idx, offset, *[st[k] for k in STATE], lsel=lsel,
-                      emit=s64["emit"].astype(np.float32), lpdf=s64["lpdf"].astype(np.float32))
-    plain = R.bounce(R.SYNTH_SCENE, env, bounce, False, True, seed, pass_idx, offset, *[st[k] for k in STATE])
+    b = B.bounce(R.SYNTH_SCENE, env, "env", bounce, False, True, seed, pass_idx, offset, *[st[k] for k in STATE], n_e=n_e, lsel=lsel,
+                 emit=s64["emit"].astype(np.float32), lpdf=s64["lpdf"].astype(np.float32), tables=t)
+    plain = B.bounce(R.SYNTH_SCENE, env, "cosine", bounce, False, True, seed, pass_idx, offset, *[st[k] for k in STATE])
     assert all(np.array_equal(b[k], plain[k], equal_nan=True) for k in ("org", "nrm", "wi", "wl", "material", "beta"))
     assert np.isfinite(b["rad"][live]).all()
 

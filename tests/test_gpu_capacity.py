@@ -12,6 +12,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
+import bounce_ref as B  # noqa: E402
 import envmap_ref as ER  # noqa: E402
 import pass_replay as PR  # noqa: E402
 import pathtrace_lights_ref as LR  # noqa: E402
@@ -91,7 +92,7 @@ def test_bounce_with_32_balls(table):
     """bsdfd_wf_bounce, occlusion 1, last 0, on 4096 synthetic vertices that carry all 34 ids."""
     v, env = R.synthetic_vertices(scene=SCENE), R.synthetic_env()
     assert set(np.unique(v["material"]).tolist()) == set(range(N_B + 2))
-    want = R.bounce(SCENE, env, BOUNCE, False, True, SEED, PASS, OFFSET, *[v[k] for k in STATE])
+    want = B.bounce(SCENE, env, "cosine", BOUNCE, False, True, SEED, PASS, OFFSET, *[v[k] for k in STATE])
     r = _renderer(table, env)
     b = _to_device(r, v)
     r.bounce(b, BOUNCE, False, SEED, PASS, OFFSET, occlusion=True)
@@ -146,7 +147,8 @@ def test_sample_emitter_and_bounce_lit_with_8_lights(table, lit):
     # the bounce, on the reference's emitter samples rounded to fp32
     u = dict(v, wl=want["wl"].astype(np.float32))
     lsel_in, emit_in = want["lsel"], want["emit"].astype(np.float32)
-    ref = LR.bounce_lit(SCENE, env, 9, True, BOUNCE, False, True, SEED, PASS, OFFSET, *[u[k] for k in STATE], lsel=lsel_in, emit=emit_in)
+    ref = B.bounce(SCENE, env, "lit", BOUNCE, False, True, SEED, PASS, OFFSET, *[u[k] for k in STATE], n_e=9, has_env=True, lsel=lsel_in,
+                   emit=emit_in)
     b = _to_device(r, u)
     b["lsel"], b["emit"] = torch.from_numpy(lsel_in).to(r.device), torch.from_numpy(emit_in).to(r.device)
     r.bounce(b, BOUNCE, False, SEED, PASS, OFFSET, occlusion=True, lights=lights)
@@ -199,8 +201,8 @@ def test_sample_env_and_bounce_env_with_8_lights(table):
     u = dict(v, wl=np.where(picked[:, None], want["wl"], wl_in).astype(np.float32))
     emit_b = np.where(picked[:, None], want["emit"], np.where(emit_in == EMIT_SENTINEL, 0.0, emit_in)).astype(np.float32)
     lpdf_b = np.where(picked, want["lpdf"], 0.0).astype(np.float32)
-    ref = ER.bounce_env(SCENE, env, t, 9, BOUNCE, False, True, SEED, PASS, OFFSET, *[u[k] for k in STATE], lsel=lsel, emit=emit_b,
-                        lpdf=lpdf_b)
+    ref = B.bounce(SCENE, env, "env", BOUNCE, False, True, SEED, PASS, OFFSET, *[u[k] for k in STATE], n_e=9, lsel=lsel, emit=emit_b,
+                   lpdf=lpdf_b, tables=t)
     b = _to_device(r, dict(u, emit=emit_b, lpdf=lpdf_b, lsel=lsel))
     r.bounce(b, BOUNCE, False, SEED, PASS, OFFSET, occlusion=True, lights=lights, env_dist=dist)
     torch.cuda.synchronize()

@@ -11,6 +11,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
+import bounce_ref as B  # noqa: E402
 import envmap_ref as ER  # noqa: E402
 import pathtrace_lights_ref as LR  # noqa: E402
 import pathtrace_ref as R  # noqa: E402
@@ -227,8 +228,8 @@ def test_bounce_env_kernel_matches_reference(synth, with_lights, occlusion, last
     scene = R.SYNTH_SCENE
     n_b, n = len(scene["spheres"]), len(v["material"])
     n_e = 4 if with_lights else 1
-    want = ER.bounce_env(scene, env, t, n_e, BOUNCE, bool(last), bool(occlusion), SEED, PASS, OFFSET, *[v.get(k) for k in STATE],
-                         lsel=lsel, emit=emit, lpdf=lpdf)
+    want = B.bounce(scene, env, "env", BOUNCE, bool(last), bool(occlusion), SEED, PASS, OFFSET, *[v.get(k) for k in STATE], n_e=n_e,
+                    lsel=lsel, emit=emit, lpdf=lpdf, tables=t)
     r = _scene_renderer(scene, env)
     b, plain = _to_device(r, v), _to_device(r, v)
     b["emit"], b["lpdf"] = torch.from_numpy(emit).to(r.device), torch.from_numpy(lpdf).to(r.device)

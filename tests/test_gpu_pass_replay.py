@@ -22,6 +22,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
+import bounce_ref as B  # noqa: E402
 import envmap_ref as ER  # noqa: E402
 import pass_replay as PR  # noqa: E402
 import pathtrace_lights_ref as LR  # noqa: E402
@@ -184,12 +185,8 @@ def _reference_bounce(rec, s, case):
     args = (s["k"], s["k"] == depth - 1, True, SEED, pass_idx, rec["offset"], *[b[k] for k in STATE],
             b["f_o"] if gt else None, b["f_l"] if gt else None)
     n_e = (3 if lit else 0) + int(with_env)
-    if mode == "importance":
-        return ER.bounce_env(rec["scene"], env, rec["tables"], n_e, *args, lsel=b["lsel"] if lit else None, emit=b["emit"],
-                             lpdf=b["lpdf"])
-    if lit:
-        return LR.bounce_lit(rec["scene"], env, n_e, with_env, *args, lsel=b["lsel"], emit=b["emit"])
-    return R.bounce(rec["scene"], env, *args)
+    return B.bounce(rec["scene"], env, PR.bounce_mode(mode, rec["lights"]), *args, n_e=n_e, has_env=with_env,
+                    lsel=b["lsel"] if lit else None, emit=b.get("emit"), lpdf=b.get("lpdf"), tables=rec["tables"])
 
 
 def _check_bounce(rec, s, case):

@@ -9,6 +9,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
+import bounce_ref as B  # noqa: E402
 import pathtrace_ref as R  # noqa: E402
 from test_pathtrace_cpu import STATE, _floor_vertices, form_factor_complement  # noqa: E402
 
@@ -94,7 +95,7 @@ def test_bounce_kernel_matches_reference(synth, occlusion, last, bounce, with_f)
     scene = R.SYNTH_SCENE
     n_b, n = len(scene["spheres"]), len(v["material"])
     seed, pass_idx, offset = 0x1234567890ABCDEF, 3, (1 << 32) - 2000     # (the path index crosses 2^32 inside the wavefront)
-    want = R.bounce(scene, env, bounce, bool(last), bool(occlusion), seed, pass_idx, offset, *[v.get(k) for k in STATE])
+    want = B.bounce(scene, env, "cosine", bounce, bool(last), bool(occlusion), seed, pass_idx, offset, *[v.get(k) for k in STATE])
     r = _scene_renderer(scene, env)
     b = _to_device(r, v)
     r.bounce(b, bounce, bool(last), seed, pass_idx, offset, occlusion=bool(occlusion))

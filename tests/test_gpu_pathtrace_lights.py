@@ -10,6 +10,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
+import bounce_ref as B  # noqa: E402
 import pathtrace_lights_ref as LR  # noqa: E402
 import pathtrace_ref as R  # noqa: E402
 from test_gpu_pathtrace import ROOT, _array, _scene_renderer, _shade_bound, _to_device  # noqa: E402
@@ -108,8 +109,8 @@ def test_bounce_lit_kernel_matches_reference(synth, has_env, last, with_f):
     v, lsel, emit = _lit_inputs(synth, has_env, with_f)
     scene = R.SYNTH_SCENE
     n_b, n = len(scene["spheres"]), len(v["material"])
-    want = LR.bounce_lit(scene, env, 3 + has_env, bool(has_env), BOUNCE, bool(last), True, SEED, PASS, OFFSET,
-                         *[v.get(k) for k in STATE], lsel=lsel, emit=emit)
+    want = B.bounce(scene, env, "lit", BOUNCE, bool(last), True, SEED, PASS, OFFSET, *[v.get(k) for k in STATE], n_e=3 + has_env,
+                    has_env=bool(has_env), lsel=lsel, emit=emit)
     r = _scene_renderer(scene, env)
     b, unlit = _to_device(r, v), _to_device(r, v)
     b["lsel"], b["emit"] = torch.from_numpy(lsel).to(r.device), torch.from_numpy(emit).to(r.device)

@@ -1,6 +1,6 @@
-"""GPU tests of Russian roulette and unbounded depth in the array-scene path tracer: ``bsdfd_wf_bounce_rr`` (csrc/pathrr.hip) row
-by row against the three existing bounce calls and against tests/pathtrace_rr_ref.py, and ``PathArrayRenderer(..., rr_depth=,
-max_depth=None)`` as whole recorded passes against ``pathtrace_rr_ref.reference_pass_rr``, at the depth cap, and in the mean.
+"""GPU tests of Russian roulette and unbounded depth in the array-scene path tracer: ``bsdfd_wf_bounce_rr`` (csrc/bounce.hip) row
+by row against the three existing bounce calls and against tests/bounce_ref.py, and ``PathArrayRenderer(..., rr_depth=,
+max_depth=None)`` as whole recorded passes against ``pass_replay.reference_pass``, at the depth cap, and in the mean.
 
 The kernel tests run on ONE wavefront for all modes: ``pathtrace_ref.synthetic_vertices`` with the throughputs of
 ``pathtrace_rr_ref.rr_wavefront`` (tests/test_pathtrace_rr_cpu.py shows it is fit for purpose), the emitter arrays of LIT and ENV
@@ -15,6 +15,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
+import bounce_ref as B  # noqa: E402
 import envmap_ref as ER  # noqa: E402
 import pass_replay as PR  # noqa: E402
 import pathtrace_lights_ref as LR  # noqa: E402
@@ -62,10 +63,10 @@ def _env_dist():
 
 @functools.lru_cache(maxsize=None)
 def _reference(bounce, with_f, tail):
-    """``pathtrace_rr_ref.bounce_rr`` (rr_depth = 1, last = 0) of the cosine wavefront.  Which rows continue, and what the roulette
+    """``bounce_ref.bounce`` (rr_depth = 1, last = 0) of the cosine wavefront.  Which rows continue, and what the roulette
     decides, is the same in every mode: the emitter stages move ``wl`` on ball rows only, which ``rad`` alone reads."""
     v = _inputs("cosine", with_f, tail)
-    return RR.bounce_rr(SCENE, R.synthetic_env(), 1, bounce, False, True, SEED, PASS, OFFSET, *[v.get(k) for k in STATE])
+    return B.bounce(SCENE, R.synthetic_env(), "cosine", bounce, False, True, SEED, PASS, OFFSET, *[v.get(k) for k in STATE], rr_depth=1)
 
 
 def _call(r, v, mode, bounce, last, rr_depth):
@@ -115,8 +116,9 @@ def _check_active(renderer, mode, bounce, last, with_f, tail=0):
     for k in OUT:                                                                    # rows that end anyway, and ended paths
         assert _same_bits(plain[k][~would], rr[k][~would]), k
     # the decision, row by row, from the kernel's own inputs in fp64
-    thr = RR.throughput_factor(SCENE, v["wi"], v["material"], v["pdf_o"], v.get("f_o"))
-    u, q, ok = RR.roulette(v["beta"], thr, SEED, PASS, bounce, OFFSET, n)
+    ref = _reference(bounce, with_f, tail)
+    thr = ref["thr"]                                                                 # (the same in every mode)
+    u, q, ok = B.roulette(v["beta"], thr, SEED, PASS, bounce, OFFSET, n)
     survive = would & (rr["mat"] <= N_B)
     killed = would & ~survive
     assert (rr["mat"][killed] == N_B + 1).all()
@@ -136,7 +138,6 @@ def _check_active(renderer, mode, bounce, last, with_f, tail=0):
     assert np.isfinite(rr["beta"][survive]).all() and err < 2e-5                     # test_bounce_kernel_matches_reference's bound
     # ... and the whole call is the reference's: the same rows continue (all but the 0.1 % test_bounce_kernel_matches_reference
     # allows the geometry), the same of them survive
-    ref = _reference(bounce, with_f, tail)
     agree = would & ref["would"]
     assert (would != ref["would"]).sum() <= n // 1000 and np.array_equal(survive[agree], ref["survive"][agree])
 
@@ -157,7 +158,7 @@ def test_a_row_count_that_is_no_multiple_of_the_block(renderer, mode):
     (other variates), decided like the reference decides them."""
     _check_active(renderer, mode, 2, 0, True, tail=37)
     v = _inputs(mode, True, 37)
-    u = RR.variates(SEED, PASS, 2, OFFSET, len(v["material"]))
+    u = B.variates(SEED, PASS, 2, OFFSET, len(v["material"]))
     assert not np.array_equal(u[:37], u[4096:])
 
 
@@ -214,8 +215,8 @@ def _near_cell(rec, snap):
 @pytest.mark.parametrize("emitters", ["cosine", "importance+lights"])
 def test_recorded_pass_matches_reference_pass_rr(emitters, max_depth):
     """One recorded pass, 120x90, 1 spp, rr_depth = 2: the stages come in the documented order, every bounce is held to
-    ``pathtrace_rr_ref.bounce_rr`` on the device's own input with the bounds of tests/test_gpu_pass_replay.py::_check_bounce, the
-    whole pass to ``reference_pass_rr`` with the recorded answers of the sampler as
+    ``bounce_ref.bounce`` on the device's own input with the bounds of tests/test_gpu_pass_replay.py::_check_bounce, the
+    whole pass to ``pass_replay.reference_pass`` with the recorded answers of the sampler as
     test_pass_matches_the_free_running_reference_pass does; the loop ends with no live lane."""
     rec = _recorded(emitters, max_depth)
     r, n_b, n, scene, lit = rec["r"], rec["n_b"], rec["n"], rec["scene"], rec["lit"]
@@ -247,9 +248,9 @@ def test_recorded_pass_matches_reference_pass_rr(emitters, max_depth):
     killed_total = decisions = 0
     for s in bounces:
         v, out = s["before"], s["after"]
-        ref = RR.bounce_rr(scene, rec["env"], RR_DEPTH, s["k"], s["args"]["last"], True, PASS_SEED, 0, 0, *[v[k] for k in names], None, None,
-                           n_e=4 if lit else 1, has_env=True, lsel=v["lsel"] if lit else None, emit=v.get("emit"), lpdf=v.get("lpdf"),
-                           tables=rec["tables"])
+        ref = B.bounce(scene, rec["env"], "env" if lit else "cosine", s["k"], s["args"]["last"], True, PASS_SEED, 0, 0,
+                       *[v[k] for k in names], n_e=4 if lit else 1, lsel=v["lsel"] if lit else None, emit=v.get("emit"), lpdf=v.get("lpdf"),
+                       tables=rec["tables"], rr_depth=RR_DEPTH)
         live = (v["mat"] >= 0) & (v["mat"] <= n_b)
         for k in OUT:                                                                # ended paths: not a byte of their state moves
             assert out[k][~live].tobytes() == v[k][~live].tobytes(), k
@@ -286,8 +287,8 @@ def test_recorded_pass_matches_reference_pass_rr(emitters, max_depth):
     assert killed_total >= 100 and killed_total >= 0.025 * decisions
     # end to end
     answers = [{k: s["before"][k] for k in ("wo", "pdf_o", "pdf_l")} for s in bounces]
-    ref = RR.reference_pass_rr(scene, rec["env"], "importance" if lit else "cosine", rec["lights"], rec["tables"], 0, H, SPP, PASS_SEED, 0,
-                               max_depth, RR_DEPTH, True, answers)
+    ref = PR.reference_pass(scene, rec["env"], "importance" if lit else "cosine", rec["lights"], rec["tables"], 0, H, SPP, PASS_SEED, 0,
+                            max_depth, True, answers, rr_depth=RR_DEPTH)
     codes = lambda snap: PR.decision_code(scene, snap["mat"], snap["wi"])
     history = [codes(named("primary")[0]["after"])] + [codes(s["after"]) for s in bounces]
     differ = PR.histories_differ(history, ref["history"])

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import bounce_ref as B
 import pathtrace_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,7 +28,7 @@ def test_library_exports_the_path_kernels_without_a_new_abi():
     assert C.sizeof(_lib.WfScene) == 4 * (13 + 2 + 7 + 3 + 124 + 1 + 4) == 616
     src = os.path.join(ROOT, "bsdf_diffusion_sampling_amd", "csrc", "pathtrace.hip")
     assert src in _lib.SRC_PATHS and src in _lib.DEP_PATHS and os.path.exists(src)
-    body = os.path.join(os.path.dirname(src), "bounce_dev.h")   # the bounce the three path translation units instantiate
+    body = os.path.join(os.path.dirname(src), "bounce_dev.h")   # the bounce body csrc/bounce.hip instantiates
     assert body in _lib.DEP_PATHS and body not in _lib.SRC_PATHS and os.path.exists(body)
 
 
@@ -64,7 +65,7 @@ def form_factor_complement(d, r=0.33):
 def test_reference_matches_the_tangent_sphere_form_factor(d, dtype):
     n = 400_000
     scene, st = _floor_vertices(d, n, seed=int(d * 100))
-    out = R.bounce(scene, np.ones((4, 8, 3), np.float32), 0, True, True, 1, 0, 0, *[st[k] for k in STATE[:10]], dtype=dtype)
+    out = B.bounce(scene, np.ones((4, 8, 3), np.float32), "cosine", 0, True, True, 1, 0, 0, *[st[k] for k in STATE[:10]], dtype=dtype)
     assert (out["material"] == 2).all()                          # last = 1: every path has ended
     vals = out["rad"].astype(np.float64)
     assert ((vals == 0) | (np.abs(vals - 1) < 1e-6)).all()        # shadowed, or the unit environment (bilinear weights sum to 1 +- ulp)
@@ -81,7 +82,7 @@ def test_reference_decides_the_same_in_fp32_and_fp64(occlusion):
     differ on at most 0.1 % of the rows: the cap the kernel is held to is one the arithmetic alone respects."""
     v = R.synthetic_vertices()
     env = R.synthetic_env()
-    a, b = (R.bounce(R.SYNTH_SCENE, env, 0, False, occlusion, 0x1234567890, 3, 1000, *[v[k] for k in STATE], dtype=dt)
+    a, b = (B.bounce(R.SYNTH_SCENE, env, "cosine", 0, False, occlusion, 0x1234567890, 3, 1000, *[v[k] for k in STATE], dtype=dt)
             for dt in (np.float64, np.float32))
     differ = int((a["material"] != b["material"]).sum())
     print(f"occlusion = {occlusion}: {differ} of {len(v['material'])} rows decide differently in fp32")
@@ -108,7 +109,7 @@ def test_reference_decides_the_same_in_fp32_and_fp64_at_the_kernels_capacity():
     n = len(v["material"])
     assert set(np.unique(v["material"]).tolist()) == set(range(n_b + 2))
     for occlusion in (False, True):
-        a, b = (R.bounce(scene, env, 0, False, occlusion, 0x1234567890, 3, 1000, *[v[k] for k in STATE], dtype=dt)
+        a, b = (B.bounce(scene, env, "cosine", 0, False, occlusion, 0x1234567890, 3, 1000, *[v[k] for k in STATE], dtype=dt)
                 for dt in (np.float64, np.float32))
         differ = int((a["material"] != b["material"]).sum())
         print(f"32 balls, occlusion = {occlusion}: {differ} of {n} rows decide differently in fp32")
@@ -130,7 +131,7 @@ def test_reference_decides_the_same_in_fp32_and_fp64_at_the_kernels_capacity():
 
 def test_reference_leaves_ended_paths_alone_and_replays_philox():
     v = R.synthetic_vertices()
-    out = R.bounce(R.SYNTH_SCENE, R.synthetic_env(), 2, False, True, 9, 1, 77, *[v[k] for k in STATE])
+    out = B.bounce(R.SYNTH_SCENE, R.synthetic_env(), "cosine", 2, False, True, 9, 1, 77, *[v[k] for k in STATE])
     dead = v["material"] > len(R.SYNTH_SCENE["spheres"])
     assert dead.sum() > 100
     for k in ("org", "nrm", "wi", "wl", "beta", "rad"):

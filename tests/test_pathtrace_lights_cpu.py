@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import bounce_ref as B
 import pathtrace_lights_ref as LR
 import pathtrace_ref as R
 from test_pathtrace_cpu import STATE
@@ -70,7 +71,7 @@ SHADOW_RADIUS = H_LIGHT * np.tan(np.arcsin(R_BALL / (H_LIGHT - R_BALL)))
 
 def _lit_floor(d, occlusion, dtype):
     """Unit-reflectance floor vertices at the horizontal distances ``d`` from the light's foot, at random azimuths, through
-    sample_emitter and bounce_lit (a bright environment that is no emitter: has_env = 0) -> rad[:, c], want."""
+    sample_emitter and the "lit" bounce (a bright environment that is no emitter: has_env = 0) -> rad[:, c], want."""
     n = len(d)
     g = np.random.default_rng(3)
     az = g.uniform(0, 2 * np.pi, n)
@@ -82,8 +83,9 @@ def _lit_floor(d, occlusion, dtype):
     lights = LR.make_lights([(0.0, H_LIGHT, 0.0)], [I_LIGHT])
     s = LR.sample_emitter(ONE_BALL, lights, False, 0, occlusion, 5, 0, 0, *[st[k] for k in VERTEX], dtype=dtype)
     assert (s["lsel"] == 0).all() and np.array_equal(s["wl"], st["wl"].astype(dtype))     # floor rows keep their direction
-    out = LR.bounce_lit(ONE_BALL, np.full((4, 8, 3), 9.0, np.float32), 1, False, 0, True, occlusion, 5, 0, 0,
-                        *[s["wl"] if k == "wl" else st[k] for k in STATE[:10]], lsel=s["lsel"], emit=s["emit"], dtype=dtype)
+    out = B.bounce(ONE_BALL, np.full((4, 8, 3), 9.0, np.float32), "lit", 0, True, occlusion, 5, 0, 0,
+                   *[s["wl"] if k == "wl" else st[k] for k in STATE[:10]], n_e=1, has_env=False, lsel=s["lsel"], emit=s["emit"],
+                   dtype=dtype)
     assert (out["material"] == 2).all()
     d64 = np.linalg.norm(st["org"].astype(np.float64)[:, [0, 2]], axis=1)       # (the fp32 positions the reference saw)
     return out["rad"].astype(np.float64), I_LIGHT * H_LIGHT / (np.pi * (d64 ** 2 + H_LIGHT ** 2) ** 1.5), d64
@@ -139,7 +141,7 @@ def test_reference_one_sample_estimator_sums_the_lights():
 def test_reference_environment_with_a_dark_light_is_the_unlit_estimator():
     """has_env = 1 and one light of intensity 0 (n_e = 2), 400 000 synthetic ball vertices with a sampler whose densities are
     consistent (cosine-weighted wo, pdf = cos / pi): the mean per-row difference between the lit estimate and
-    pathtrace_ref.bounce's is zero within 5 of its own standard errors — the 1 / n_e in both MIS densities and the factor
+    the "cosine" bounce's is zero within 5 of its own standard errors — the 1 / n_e in both MIS densities and the factor
     n_e of picking the environment half of the time cancel."""
     v = R.synthetic_vertices(400_000, seed=3)
     n_b = len(R.SYNTH_SCENE["spheres"])
@@ -153,11 +155,11 @@ def test_reference_environment_with_a_dark_light_is_the_unlit_estimator():
     env = R.synthetic_env()
     dark = LR.make_lights([(0.0, 2.5, 0.5)], [0.0])
     args = lambda st: [st[k] for k in STATE[:10]]
-    unlit = R.bounce(R.SYNTH_SCENE, env, 0, True, True, 21, 0, 0, *args(v))["rad"]
+    unlit = B.bounce(R.SYNTH_SCENE, env, "cosine", 0, True, True, 21, 0, 0, *args(v))["rad"]
     s = LR.sample_emitter(R.SYNTH_SCENE, dark, True, 0, True, 21, 0, 0, *[v[k] for k in VERTEX])
     assert (s["emit"] == 0).all() and 0.49 < (s["lsel"] == 0).mean() < 0.51
-    lit = LR.bounce_lit(R.SYNTH_SCENE, env, 2, True, 0, True, True, 21, 0, 0, *args(dict(v, wl=s["wl"])), lsel=s["lsel"],
-                        emit=s["emit"])["rad"]
+    lit = B.bounce(R.SYNTH_SCENE, env, "lit", 0, True, True, 21, 0, 0, *args(dict(v, wl=s["wl"])), n_e=2, has_env=True, lsel=s["lsel"],
+                   emit=s["emit"])["rad"]
     diff = lit - unlit
     mean, sem = diff.mean(0), diff.std(0, ddof=1) / np.sqrt(n)
     print(f"unlit mean {unlit.mean(0)}, lit - unlit {mean}, {mean / sem} sigma")
@@ -175,8 +177,8 @@ def test_reference_decides_the_same_in_fp32_and_fp64(has_env):
     for dt in (np.float64, np.float32):
         s = LR.sample_emitter(R.SYNTH_SCENE, lights, has_env, 1, True, 0x1234567890, 3, 1000, *[v[k] for k in VERTEX], dtype=dt)
         st = dict(v, wl=s["wl"].astype(np.float32))
-        b = LR.bounce_lit(R.SYNTH_SCENE, env, 3 + has_env, has_env, 1, False, True, 0x1234567890, 3, 1000, *[st[k] for k in STATE],
-                          lsel=s["lsel"], emit=s["emit"].astype(np.float32), dtype=dt)
+        b = B.bounce(R.SYNTH_SCENE, env, "lit", 1, False, True, 0x1234567890, 3, 1000, *[st[k] for k in STATE], n_e=3 + has_env,
+                     has_env=has_env, lsel=s["lsel"], emit=s["emit"].astype(np.float32), dtype=dt)
         runs.append((s, b))
     (s64, b64), (s32, b32) = runs
     assert np.array_equal(s64["lsel"], s32["lsel"])

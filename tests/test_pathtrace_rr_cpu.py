@@ -1,12 +1,13 @@
 """CPU side of Russian roulette and unbounded depth in the array-scene path tracer (bsdf_diffusion_sampling_amd/pathtrace.py,
-csrc/pathrr.hip): the export, the reader of the reference's integrator settings, the argument checks, and the reference rule of
-tests/pathtrace_rr_ref.py held to itself — unbiased on the variate grid, the same decisions in fp32 and fp64 on every row of a
+csrc/bounce.hip): the export, the reader of the reference's integrator settings, the argument checks, and the reference rule of
+tests/bounce_ref.py held to itself — unbiased on the variate grid, the same decisions in fp32 and fp64 on every row of a
 test wavefront that exercises every outcome, and a mean that moves when the 1/q is left out."""
 import os
 
 import numpy as np
 import pytest
 
+import bounce_ref as B
 import pass_replay as PR
 import pathtrace_ref as R
 import pathtrace_rr_ref as RR
@@ -50,7 +51,7 @@ def test_library_exports_bounce_rr_without_a_new_abi():
     env_args, rr_args = L.bsdfd_wf_bounce_env.argtypes, L.bsdfd_wf_bounce_rr.argtypes
     assert list(rr_args) == list(env_args[:-1]) + [_lib.C.c_int32, env_args[-1]] and len(rr_args) == 28
     csrc = os.path.join(ROOT, "bsdf_diffusion_sampling_amd", "csrc")
-    assert os.path.join(csrc, "pathrr.hip") in _lib.SRC_PATHS and os.path.exists(os.path.join(csrc, "pathrr.hip"))
+    assert os.path.join(csrc, "bounce.hip") in _lib.SRC_PATHS and os.path.exists(os.path.join(csrc, "bounce.hip"))
     decl = hdr[hdr.index(f"int {name}("):]
     decl = " ".join(decl[:decl.index(";")].split())
     assert decl.endswith("const float* lpdf, const bsdfd_env_dist* dist, int32_t rr_depth, void* hip_stream)")
@@ -122,7 +123,7 @@ def test_rule_is_unbiased_on_the_variate_grid(q):
 def test_variates_replay_philox_and_wrap_the_low_counter_word():
     from oracle.wavefront_oracle import philox4x32
     n = 256
-    u = RR.variates(SEED, PASS, 2, RR.OFFSET, n)
+    u = B.variates(SEED, PASS, 2, RR.OFFSET, n)
     assert u.dtype == np.float32 and (u >= 0).all() and (u < 1).all() and len(np.unique(u)) > n - 4
     for row in (0, 99, 100, 255):           # row 100 is global path 2^32: low word 0, high word 1
         gp = RR.OFFSET + row
@@ -130,7 +131,7 @@ def test_variates_replay_philox_and_wrap_the_low_counter_word():
                        0x526F756C + 2)
         assert u[row] == np.float32(int(w[0][0]) >> 8) * np.float32(2.0 ** -24)
     assert (RR.OFFSET + 100) >> 32 == 1 and (RR.OFFSET + 99) >> 32 == 0
-    assert not np.array_equal(u, RR.variates(SEED, PASS, 3, RR.OFFSET, n))
+    assert not np.array_equal(u, B.variates(SEED, PASS, 3, RR.OFFSET, n))
 
 
 @pytest.mark.parametrize("bounce", [0, 2])
@@ -140,11 +141,11 @@ def test_wavefront_is_fit_for_purpose_and_decides_the_same_in_fp32_and_fp64(boun
     env = R.synthetic_env()
     for with_f in (True, False):
         v = rr_vertices(with_f)
-        args = (R.SYNTH_SCENE, env, 1, bounce, False, True, SEED, PASS, RR.OFFSET, *[v.get(k) for k in STATE])
-        a, b = RR.bounce_rr(*args), RR.bounce_rr(*args, dtype=np.float32)
+        args = (R.SYNTH_SCENE, env, "cosine", bounce, False, True, SEED, PASS, RR.OFFSET, *[v.get(k) for k in STATE])
+        a, b = B.bounce(*args, rr_depth=1), B.bounce(*args, rr_depth=1, dtype=np.float32)
         would, q = a["would"], a["q"]
         share = lambda rows: (would & rows).sum() / would.sum()
-        clamped, free, killed = share(q == RR.Q_MAX), share(a["survive"] & (q < RR.Q_MAX)), share(a["killed"])
+        clamped, free, killed = share(q == B.Q_MAX), share(a["survive"] & (q < B.Q_MAX)), share(a["killed"])
         zero = int((would & (q == 0)).sum())
         print(f"bounce {bounce} f={with_f}: {int(would.sum())} rows would continue: clamped {clamped:.3f}, survive unclamped {free:.3f}, "
               f"killed {killed:.3f}, q = 0 on {zero}")
@@ -156,7 +157,7 @@ def test_wavefront_is_fit_for_purpose_and_decides_the_same_in_fp32_and_fp64(boun
         if with_f:
             assert zero >= 8 and a["killed"][would & (q == 0)].all()
         # killed rows keep their inputs, survivors carry beta thr / q, rad is the plain bounce's
-        plain = R.bounce(*args[:2], *args[3:])
+        plain = B.bounce(*args)
         for k in RR.KEPT:
             assert np.array_equal(a[k][a["killed"]], v[k][a["killed"]].astype(np.float64)), k
         assert (a["material"][a["killed"]] == len(R.SYNTH_SCENE["spheres"]) + 1).all()
@@ -173,12 +174,12 @@ def test_roulette_is_inactive_before_rr_depth_and_at_last():
     v = rr_vertices()
     tail = [v.get(k) for k in STATE]
     for rr_depth, bounce, last in ((4, 2, False), (1, 0, True), (3, 2, True)):
-        a = RR.bounce_rr(R.SYNTH_SCENE, env, rr_depth, bounce, last, True, SEED, PASS, RR.OFFSET, *tail)
-        plain = R.bounce(R.SYNTH_SCENE, env, bounce, last, True, SEED, PASS, RR.OFFSET, *tail)
+        a = B.bounce(R.SYNTH_SCENE, env, "cosine", bounce, last, True, SEED, PASS, RR.OFFSET, *tail, rr_depth=rr_depth)
+        plain = B.bounce(R.SYNTH_SCENE, env, "cosine", bounce, last, True, SEED, PASS, RR.OFFSET, *tail)
         assert not a["killed"].any()
         for k in ("org", "nrm", "wi", "wl", "material", "beta", "rad"):
             assert np.array_equal(a[k], plain[k], equal_nan=True), k
-    a = RR.bounce_rr(R.SYNTH_SCENE, env, 3, 2, False, True, SEED, PASS, RR.OFFSET, *tail)       # bounce + 1 == rr_depth: active
+    a = B.bounce(R.SYNTH_SCENE, env, "cosine", 2, False, True, SEED, PASS, RR.OFFSET, *tail, rr_depth=3)       # bounce + 1 == rr_depth: active
     assert a["killed"].sum() > 100
 
 
@@ -195,8 +196,8 @@ def test_leaving_out_the_division_moves_the_mean():
     env = np.ones((8, 16, 3), np.float32)
 
     def image_mean(p, spp, scale):
-        out = RR.reference_pass_rr(scene, env, "cosine", None, None, 0, scene["height"], spp, 4, p, UNBIASED["max_depth"], 1, True,
-                                   PR.mock_answers(11 + p), scale=scale)
+        out = PR.reference_pass(scene, env, "cosine", None, None, 0, scene["height"], spp, 4, p, UNBIASED["max_depth"], True,
+                                PR.mock_answers(11 + p), rr_depth=1, scale=scale)
         return out["film"].reshape(-1, 3).mean(0)
     shift = np.mean([image_mean(p, 1, True) - image_mean(p, 1, False) for p in range(8)], axis=0)
     sd = np.std([image_mean(p, UNBIASED["spp"], True) for p in range(8)], axis=0, ddof=1)

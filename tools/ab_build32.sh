@@ -7,7 +7,7 @@ ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 OUT="$ROOT/build_ab"; mkdir -p "$OUT"
 CS="$ROOT/bsdf_diffusion_sampling_amd/csrc"
 COMMON="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value -Wno-pass-failed -I $ROOT/include"
-SIDE="bsdfd host wavefront pathtrace pathlights pathenv pathrr encoding measured measured_table bucket bucket_wide live clock"   # tools/ab_build.sh's list
+SIDE="$(cd "$ROOT" && python -c "import os; from bsdf_diffusion_sampling_amd import _lib; print(' '.join(s for s in (os.path.basename(p)[:-4] for p in _lib.SRC_PATHS) if s not in 'flow32'.split()))")"   # the library's other translation units
 for tu in $SIDE; do
   if [ ! -f "$OUT/$tu.o" ] || [ "$CS/$tu.hip" -nt "$OUT/$tu.o" ] || [ "$CS/flow_dev.h" -nt "$OUT/$tu.o" ] || [ "$CS/flow_kernels.h" -nt "$OUT/$tu.o" ] || [ "$ROOT/include/bsdfd.h" -nt "$OUT/$tu.o" ]; then
     hipcc $COMMON -c "$CS/$tu.hip" -o "$OUT/$tu.o" &
