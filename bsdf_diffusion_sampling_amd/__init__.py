@@ -9,8 +9,11 @@ Modules (everything below the tensors runs in libbsdfd.so, include/bsdfd.h; no C
   model, weights      reference-named weight containers, the neutral .bsdfw weight format
   materials           MaterialTable: material-tagged wavefronts (bucketing + segmented launches)
   live                live_rows: an ``active`` mask -> the row list the flow kernels run on (csrc/live.hip)
+  ground_truth        the host layer of the native ground-truth evaluators: launch, argument checks, the tensor calls and
+                      ``mi.BSDF`` call shapes of a single-material evaluator, written once
   measured            MeasuredBSDF: the ground-truth evaluator behind eval() (RGL tensor files);
                       MeasuredTable: eval() of a mixed-material wavefront in one launch
+  analytic            RoughDielectric: the full-sphere plugin's ground truth for bsdf_23..25
   measured_synth      synthetic RGL tensor files for tests and tools (numpy only)
   encoding            positional_encoding_1 as a stand-alone pass
   wavefront           WavefrontRenderer / ArrayRenderer: the render loop around the plugin calls

@@ -21,7 +21,7 @@ import torch
 
 from . import _lib
 from . import weights as W
-from .plugin_base import (FLAG_DELTA_REFLECTION, FLAG_FRONT_SIDE, BSDFSample3f, NeuralBSDFCore, _wi_of, rgb2lum)
+from .plugin_base import FLAG_DELTA_REFLECTION, FLAG_FRONT_SIDE, BSDFSample3f, NeuralBSDFCore, rgb2lum
 
 
 class MyBSDF(NeuralBSDFCore):
@@ -36,25 +36,14 @@ class MyBSDF(NeuralBSDFCore):
         self.m_flags = FLAG_DELTA_REFLECTION | FLAG_FRONT_SIDE  # :55-57
         self.m_components = [self.m_flags]
 
-    def sample(self, ctx, si, sample1=None, sample2=None, active=True, *, x0=None, seed=None):
-        wi = _wi_of(si)
-        wo, pdf_sa = self.sample_t(wi, x0=x0, seed=seed, active=self._mask(active, wi))
-        bs = BSDFSample3f(wo=wo, pdf=pdf_sa, eta=1.0, sampled_type=self.m_flags, sampled_component=0)
-        if self.bsdf is None:  # no ground-truth evaluator: the sampler-only use (bench / harness)
-            return bs, None
-        if self._native_gt() is not None:  # weight, firefly rule and masks fused into the evaluator's launch
-            weight, bs.pdf = self.bsdf.sample_weight(wi, wo, pdf_sa, tint=self.albedo, firefly_threshold=self.FIREFLY,
-                                                     active=None if active is True else torch.as_tensor(active, device=wi.device))
-            return bs, weight
-        act = (wi[:, 2] > 0) if active is True else (torch.as_tensor(active, device=wi.device) & (wi[:, 2] > 0))
-        value = self.eval_unmasked(ctx, si, wo) / pdf_sa[:, None]
-        bs.pdf = self.apply_firefly_clamp(pdf_sa, rgb2lum(value), self.FIREFLY)
-        keep = act & (bs.pdf > 0) & (wo[:, 2] > 0)
-        return bs, torch.where(keep[:, None], value, torch.zeros_like(value))
+    def _bsdf_sample(self, wo, pdf_sa):
+        return BSDFSample3f(wo=wo, pdf=pdf_sa, eta=1.0, sampled_type=self.m_flags, sampled_component=0)
 
-    def eval_unmasked(self, ctx, si, wo):
-        from .plugin_base import _vec
-        return _vec(self._need_bsdf().eval(ctx, si, wo)) * self.albedo.to(wo.device)
+    def _weight_lines(self, value, wi, bs, act):
+        act = (wi[:, 2] > 0) if act is None else (act & (wi[:, 2] > 0))
+        bs.pdf = self.apply_firefly_clamp(bs.pdf, rgb2lum(value), self.FIREFLY)
+        keep = act & (bs.pdf > 0) & (bs.wo[:, 2] > 0)
+        return torch.where(keep[:, None], value, torch.zeros_like(value))
 
 
 if __name__ == "__main__":  # rendering/brdf_measured_disk.py:__main__ — render with this plugin

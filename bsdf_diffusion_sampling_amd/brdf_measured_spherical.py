@@ -19,8 +19,7 @@ import torch
 
 from . import _lib
 from . import weights as W
-from .plugin_base import (FLAG_DELTA_REFLECTION, FLAG_FRONT_SIDE, BSDFSample3f, NeuralBSDFCore, _vec, _wi_of,
-                          rgb2lum)
+from .plugin_base import FLAG_DELTA_REFLECTION, FLAG_FRONT_SIDE, BSDFSample3f, NeuralBSDFCore, rgb2lum
 
 
 def cart_to_spher(xyz: torch.Tensor) -> torch.Tensor:
@@ -41,22 +40,15 @@ class MyBSDF(NeuralBSDFCore):
         self.m_flags = FLAG_DELTA_REFLECTION | FLAG_FRONT_SIDE  # :63-65
         self.m_components = [self.m_flags]
 
-    def sample(self, ctx, si, sample1=None, sample2=None, active=True, *, x0=None, seed=None):
-        wi = _wi_of(si)
-        wo, pdf_sa = self.sample_t(wi, x0=x0, seed=seed, active=self._mask(active, wi))
-        bs = BSDFSample3f(wo=wo, pdf=pdf_sa, eta=1.0, sampled_type=self.m_flags, sampled_component=0)
-        if self.bsdf is None:
-            return bs, None
-        if self._native_gt() is not None:  # weight, firefly rule and masks fused into the evaluator's launch
-            weight, bs.pdf = self.bsdf.sample_weight(wi, wo, pdf_sa, tint=self.albedo, firefly_threshold=self.FIREFLY,
-                                                     active=None if active is True else torch.as_tensor(active, device=wi.device))
-            return bs, weight
-        act = (wi[:, 2] > 0) if active is True else (torch.as_tensor(active, device=wi.device) & (wi[:, 2] > 0))
-        value = _vec(self._need_bsdf().eval(ctx, si, wo)) * self.albedo.to(wo.device) / pdf_sa[:, None]
-        value = torch.where((act & (pdf_sa > 0))[:, None], value, torch.zeros_like(value))  # :105
-        bs.pdf = self.apply_firefly_clamp(pdf_sa, rgb2lum(value), self.FIREFLY)
-        keep = act & (bs.pdf > 0) & (wo[:, 2] > 0)
-        return bs, torch.where(keep[:, None], value, torch.zeros_like(value))
+    def _bsdf_sample(self, wo, pdf_sa):
+        return BSDFSample3f(wo=wo, pdf=pdf_sa, eta=1.0, sampled_type=self.m_flags, sampled_component=0)
+
+    def _weight_lines(self, value, wi, bs, act):
+        act = (wi[:, 2] > 0) if act is None else (act & (wi[:, 2] > 0))
+        value = torch.where((act & (bs.pdf > 0))[:, None], value, torch.zeros_like(value))  # :105
+        bs.pdf = self.apply_firefly_clamp(bs.pdf, rgb2lum(value), self.FIREFLY)
+        keep = act & (bs.pdf > 0) & (bs.wo[:, 2] > 0)
+        return torch.where(keep[:, None], value, torch.zeros_like(value))
 
 
 if __name__ == "__main__":  # rendering/brdf_measured_spherical.py:__main__ — render with this plugin

@@ -23,7 +23,7 @@ import torch
 from . import _lib
 from . import weights as W
 from .plugin_base import (FLAG_BACK_SIDE, FLAG_DIFFUSE_REFLECTION, FLAG_DIFFUSE_TRANSMISSION, FLAG_FRONT_SIDE,
-                          BSDFSample3f, NeuralBSDFCore, _vec, _wi_of)
+                          BSDFSample3f, NeuralBSDFCore)
 
 
 class MyBSDF(NeuralBSDFCore):
@@ -32,6 +32,8 @@ class MyBSDF(NeuralBSDFCore):
     VARIANT = _lib.PLUGIN_FULLSPHERE
     T = 8
     FIREFLY = 3.5
+    FUSED_GT = "analytic.RoughDielectric"
+    WEIGHT_TAKES_ACTIVE = False  # as in the reference: ``active`` reaches the flow only
 
     def __init__(self, props):
         super().__init__(props)
@@ -43,35 +45,23 @@ class MyBSDF(NeuralBSDFCore):
             if self.idx in REFERENCE_ROUGHDIELECTRIC:
                 self.bsdf = reference_material(self.idx)
 
-    def _analytic_gt(self):
-        from .analytic import RoughDielectric
-        return self.bsdf if isinstance(self.bsdf, RoughDielectric) else None
-
     def _material_name(self) -> str:
         return f"bsdf_{int(self._get('idx'))}"
 
     def _ckpt_tag(self) -> str:
         return str(int(self._get("idx")))
 
-    def sample(self, ctx, si, sample1=None, sample2=None, active=True, *, x0=None, seed=None):
-        wi = _wi_of(si)
-        wo, pdf_sa = self.sample_t(wi, x0=x0, seed=seed, active=self._mask(active, wi))
+    def _bsdf_sample(self, wo, pdf_sa):
         up = wo[:, 2] > 0
-        bs = BSDFSample3f(wo=wo, pdf=pdf_sa, eta=torch.where(up, 1.0, 1.788),
-                          sampled_type=torch.where(up, FLAG_DIFFUSE_REFLECTION, FLAG_DIFFUSE_TRANSMISSION),
-                          sampled_component=2)
-        if self.bsdf is None:
-            return bs, None
-        if self._analytic_gt() is not None:  # the lines below, fused into the evaluator's launch
-            weight, bs.pdf = self.bsdf.sample_weight(wi, wo, pdf_sa, tint=self.albedo, firefly_threshold=self.FIREFLY)
-            return bs, weight
-        # f * albedo / pdf * sin(theta_o) with pdf_sa = pdf / sin(theta_o) wherever the clamp is inactive
-        value = _vec(self._need_bsdf().eval(ctx, si, wo)) * self.albedo.to(wo.device) / pdf_sa[:, None]
-        value = torch.where((pdf_sa > 0)[:, None], value, torch.zeros_like(value))
-        bs.pdf = self.apply_firefly_clamp(pdf_sa, value[:, 0], self.FIREFLY)
-        return bs, torch.where((bs.pdf > 0)[:, None], value, torch.zeros_like(value))
+        return BSDFSample3f(wo=wo, pdf=pdf_sa, eta=torch.where(up, 1.0, 1.788),
+                            sampled_type=torch.where(up, FLAG_DIFFUSE_REFLECTION, FLAG_DIFFUSE_TRANSMISSION),
+                            sampled_component=2)
 
-    def eval(self, ctx, si, wo, active=True):
-        if self._analytic_gt() is not None:
-            return self.bsdf.eval_t(_wi_of(si), _vec(wo), tint=self.albedo)
-        return _vec(self._need_bsdf().eval(ctx, si, wo)) * self.albedo.to(_wi_of(si).device)
+    def _weight_lines(self, value, wi, bs, act):
+        # value = f * albedo / pdf * sin(theta_o) with pdf_sa = pdf / sin(theta_o) wherever the clamp is inactive
+        value = torch.where((bs.pdf > 0)[:, None], value, torch.zeros_like(value))
+        bs.pdf = self.apply_firefly_clamp(bs.pdf, value[:, 0], self.FIREFLY)
+        return torch.where((bs.pdf > 0)[:, None], value, torch.zeros_like(value))
+
+    def _eval_lines(self, ctx, si, wo, wi, wo_t):
+        return self.eval_unmasked(ctx, si, wo)  # no cos masks

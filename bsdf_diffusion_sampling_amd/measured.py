@@ -22,6 +22,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
+from .ground_truth import GroundTruth, RowKernels, check, launch, tint3
 
 
 def find_measured_file(material: str, directory: Optional[str] = None) -> Optional[str]:
@@ -35,16 +36,18 @@ def find_measured_file(material: str, directory: Optional[str] = None) -> Option
     return None
 
 
-def _launch(name: str, device, *args):
-    """One launch of the library's ``name`` on ``device``'s current stream, with that device current: tensors go as their data
-    pointers, None as NULL, everything else as it is; the stream is the last argument."""
-    with torch.cuda.device(device):
-        stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        _lib.check(getattr(_lib.lib(), name)(*[C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in args],
-                                             stream))
+class MeasuredBSDF(GroundTruth):
+    """One RGL material.  ``eval_t`` is zero on the lower hemispheres.  ``sample_weight`` is the tail of the measured plugins'
+    sample() (brdf_measured_disk.py:89-101): the firefly rule reads lum(value), and weight = 0 also on lanes that leave through
+    the lower hemisphere.  ``sample_t`` is the file's own importance sampler (Dupuy & Jakob: luminance warp, VNDF warp, reflection
+    about the half vector) at ``u`` in [0,1)^2: lanes with wi.z <= 0 get zeros, pdf = weight = 0 where wo leaves through the lower
+    hemisphere (wo is still written); ``pdf_t`` is 0 on the lower hemispheres."""
 
+    NAME = "MeasuredBSDF"
+    ENTRY = dict(eval="bsdfd_measured_eval", sample_weight="bsdfd_measured_sample_weight", sample="bsdfd_measured_sample",
+                 pdf="bsdfd_measured_pdf")
+    COERCE_ACTIVE = True        # the plugins and the Mitsuba adapter hand sample_weight masks of any dtype, wherever they live
 
-class MeasuredBSDF:
     def __init__(self, path: str):
         self.path = path
         self._h = C.c_void_p()
@@ -65,123 +68,10 @@ class MeasuredBSDF:
         except Exception:
             pass
 
-    @staticmethod
-    def _check(**tensors):
-        ref = None
-        for name, (t, cols) in tensors.items():
-            shape_ok = (t.dim() == 2 and t.shape[1] == cols) if cols else t.dim() == 1
-            if not (t.is_cuda and t.dtype == torch.float32 and shape_ok and t.is_contiguous()):
-                raise ValueError(f"MeasuredBSDF: {name} must be a contiguous fp32 CUDA tensor "
-                                 f"[N{',' + str(cols) if cols else ''}]")
-            if ref is not None and t.shape[0] != ref:
-                raise ValueError(f"MeasuredBSDF: {name} has {t.shape[0]} rows, expected {ref}")
-            ref = t.shape[0]
+    def _lead(self):
+        return self._h
 
-    @staticmethod
-    def _tint(tint):
-        if tint is None:
-            return None
-        vals = [float(v) for v in (tint.tolist() if hasattr(tint, "tolist") else tint)]
-        return (C.c_float * 3)(*vals)
-
-    def eval_t(self, wi: torch.Tensor, wo: torch.Tensor, out: Optional[torch.Tensor] = None, tint=None) -> torch.Tensor:
-        """f(wi, wo) cos(theta_o) [* tint] -> [N,3]; zero on the lower hemispheres."""
-        self._check(wi=(wi, 3), wo=(wo, 3))
-        if out is None:
-            out = torch.empty_like(wi)
-        _launch("bsdfd_measured_eval", wi.device, self._h, wi, wo, wi.shape[0], self._tint(tint), out)
-        return out
-
-    def sample_weight(self, wi: torch.Tensor, wo: torch.Tensor, pdf_sa: torch.Tensor, tint=None,
-                      firefly_threshold: float = 30.0, active: Optional[torch.Tensor] = None):
-        """The tail of the plugins' sample() in one launch (brdf_measured_disk.py:89-101): -> (weight [N,3],
-        pdf [N]) with value = f * tint / pdf_sa, the firefly rule pdf := 0 where lum(value) >= threshold,
-        and weight = 0 on lanes that are inactive, have pdf 0 or leave through the lower hemisphere."""
-        self._check(wi=(wi, 3), wo=(wo, 3), pdf_sa=(pdf_sa, 0))
-        act = None
-        if active is not None:
-            act = active.to(device=wi.device, dtype=torch.uint8).contiguous()
-            if act.shape != (wi.shape[0],):
-                raise ValueError("MeasuredBSDF.sample_weight: active must be [N]")
-        weight, pdf = torch.empty_like(wi), torch.empty_like(pdf_sa)
-        _launch("bsdfd_measured_sample_weight", wi.device, self._h, wi, wo, pdf_sa, act, wi.shape[0], self._tint(tint),
-                float(firefly_threshold), weight, pdf)
-        return weight, pdf
-
-    @staticmethod
-    def _active(active, n: int, device, who: str):
-        """``active`` as a contiguous uint8 [N] on ``device`` (None = every lane)."""
-        if active is None:
-            return None
-        if not (isinstance(active, torch.Tensor) and active.shape == (n,) and active.device == device
-                and active.dtype in (torch.bool, torch.uint8)):
-            raise ValueError(f"{who}: active must be a bool or uint8 tensor [N] on the device of wi")
-        return active.to(torch.uint8).contiguous()
-
-    @staticmethod
-    def _sample_out(wi, out, who: str):
-        """(wo, pdf, weight) to write into: the caller's ``out`` triple, checked, or fresh tensors."""
-        if out is None:
-            return torch.empty_like(wi), torch.empty(wi.shape[0], dtype=torch.float32, device=wi.device), torch.empty_like(wi)
-        if len(out) != 3:
-            raise ValueError(f"{who}: out is a (wo [N,3], pdf [N], weight [N,3]) triple")
-        return tuple(out)
-
-    def sample_t(self, wi: torch.Tensor, u: torch.Tensor, tint=None, active: Optional[torch.Tensor] = None, out=None):
-        """The file's own importance sampler (Dupuy & Jakob: luminance warp, VNDF warp, reflection about the half vector) at the
-        variates ``u`` [N,2] in [0,1)^2 -> (wo [N,3], pdf [N], weight [N,3]), weight = f cos [* tint] / pdf.  Lanes with
-        wi.z <= 0 or ``active`` false get zeros; pdf = weight = 0 where wo leaves through the lower hemisphere (wo is still
-        written).  ``out`` = (wo, pdf, weight) buffers to write into."""
-        wo, pdf, weight = self._sample_out(wi, out, "MeasuredBSDF.sample_t")
-        self._check(wi=(wi, 3), u=(u, 2), wo=(wo, 3), pdf=(pdf, 0), weight=(weight, 3))
-        act = self._active(active, wi.shape[0], wi.device, "MeasuredBSDF.sample_t")
-        _launch("bsdfd_measured_sample", wi.device, self._h, wi, u, act, wi.shape[0], self._tint(tint), wo, pdf, weight)
-        return wo, pdf, weight
-
-    def pdf_t(self, wi: torch.Tensor, wo: torch.Tensor, active: Optional[torch.Tensor] = None,
-              out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Solid-angle density with which ``sample_t(wi, .)`` returns ``wo`` -> [N]; 0 on the lower hemispheres and on lanes
-        with ``active`` false."""
-        if out is None:
-            out = torch.empty(wi.shape[0], dtype=torch.float32, device=wi.device)
-        self._check(wi=(wi, 3), wo=(wo, 3), out=(out, 0))
-        act = self._active(active, wi.shape[0], wi.device, "MeasuredBSDF.pdf_t")
-        _launch("bsdfd_measured_pdf", wi.device, self._h, wi, wo, act, wi.shape[0], out)
-        return out
-
-    # the call shapes of ``mi.BSDF`` as the reference's plugins use them (brdf_measured_disk.py:59,96,107,112)
-    def eval(self, ctx, si, wo, active=True):
-        from .plugin_base import _vec, _wi_of
-        return self.eval_t(_wi_of(si), _vec(wo))
-
-    @staticmethod
-    def _mask_of(active, wi):
-        """Mitsuba's ``active`` argument (True, a bool, or a mask) as the ``active`` of the tensor calls."""
-        if active is True or active is None:
-            return None
-        if isinstance(active, bool):
-            return torch.zeros(wi.shape[0], dtype=torch.uint8, device=wi.device)
-        if not isinstance(active, torch.Tensor):
-            active = active.torch()
-        return active.to(device=wi.device, dtype=torch.uint8).contiguous()
-
-    def sample(self, ctx, si, sample1, sample2, active=True):
-        """``mi.BSDF.sample``: -> (BSDFSample3f(wo, pdf), weight [N,3]).  ``sample1`` is ignored (one lobe)."""
-        from .plugin_base import BSDFSample3f, _vec, _wi_of
-        wi = _wi_of(si)
-        wo, pdf, weight = self.sample_t(wi, _vec(sample2), active=self._mask_of(active, wi))
-        return BSDFSample3f(wo=wo, pdf=pdf), weight
-
-    def pdf(self, ctx, si, wo, active=True):
-        from .plugin_base import _vec, _wi_of
-        wi = _wi_of(si)
-        return self.pdf_t(wi, _vec(wo), active=self._mask_of(active, wi))
-
-    def eval_pdf(self, ctx, si, wo, active=True):
-        return self.eval(ctx, si, wo, active), self.pdf(ctx, si, wo, active)
-
-
-class MeasuredTable:
+class MeasuredTable(RowKernels):
     """``eval()`` for a mixed-material wavefront: ``entries[m]`` (a ``MeasuredBSDF``, or None = no ground truth) serves the lanes
     whose ``material_id`` is m.  One launch for the whole wavefront in LANE order (``bsdfd_measured_eval_table``), where
     ``MeasuredBSDF.eval_t`` takes one launch per material on gathered slices; lanes with ground truth get that evaluator's
@@ -190,6 +80,9 @@ class MeasuredTable:
     (the launches then neither allocate nor synchronise); only a table without any ground truth, which the library refuses,
     is left to fail at its first launch."""
 
+    NAME = "MeasuredTable"
+    ENTRY = dict(sample_weight="bsdfd_measured_sample_weight_table", sample="bsdfd_measured_sample_table",
+                 pdf="bsdfd_measured_pdf_table")
     MAX_MATERIALS = 65536
 
     def __init__(self, entries: Sequence[Optional[MeasuredBSDF]]):
@@ -220,20 +113,7 @@ class MeasuredTable:
             _lib.check(_lib.lib().bsdfd_measured_table_create(handles, len(self.entries), C.byref(self._t)))
         return self._t
 
-    @staticmethod
-    def _check(material_id: torch.Tensor, **tensors):
-        """``MeasuredBSDF._check`` plus the ids: dtype and shape, then the row counts, then device and layout."""
-        if material_id.dtype != torch.int64 or material_id.dim() != 1:
-            raise ValueError("MeasuredTable: material_id must be an int64 tensor [N]")
-        n = material_id.shape[0]
-        for name, (t, cols) in tensors.items():
-            if t.dtype != torch.float32 or not ((t.dim() == 2 and t.shape[1] == cols) if cols else t.dim() == 1):
-                raise ValueError(f"MeasuredTable: {name} must be an fp32 tensor [N{',' + str(cols) if cols else ''}]")
-            if t.shape[0] != n:
-                raise ValueError(f"MeasuredTable: {name} has {t.shape[0]} rows, material_id has {n}")
-        for name, t in [("material_id", material_id)] + [(k, t) for k, (t, _) in tensors.items()]:
-            if not (t.is_cuda and t.is_contiguous() and t.device == material_id.device):
-                raise ValueError(f"MeasuredTable: {name} must be a contiguous CUDA tensor, all on one device")
+    _lead = _table
 
     def eval_t(self, material_id: torch.Tensor, wi: torch.Tensor, wo: torch.Tensor, wl: Optional[torch.Tensor] = None,
                tint=None, out_o: Optional[torch.Tensor] = None, out_l: Optional[torch.Tensor] = None):
@@ -241,49 +121,28 @@ class MeasuredTable:
         (f_o, f_l), both evaluations in the same launch.  NaN rows = no ground truth for that lane."""
         if out_l is not None and wl is None:
             raise ValueError("MeasuredTable.eval_t: out_l without wl")
-        given = dict(wi=(wi, 3), wo=(wo, 3))
-        given.update({k: (t, 3) for k, t in (("wl", wl), ("out_o", out_o), ("out_l", out_l)) if t is not None})
-        self._check(material_id, **given)
+        given = (("wi", wi), ("wo", wo), ("wl", wl), ("out_o", out_o), ("out_l", out_l))
+        check("MeasuredTable.eval_t", [(k, t, 3) for k, t in given if t is not None], material_id)
         if out_o is None:
             out_o = torch.empty_like(wi)
         if wl is not None and out_l is None:
             out_l = torch.empty_like(wi)
-        _launch("bsdfd_measured_eval_table", wi.device, self._table(), material_id, wi, wo, wl, wi.shape[0],
-                MeasuredBSDF._tint(tint), out_o, out_l)
+        launch("bsdfd_measured_eval_table", wi.device, self._table(), material_id, wi, wo, wl, wi.shape[0], tint3(tint), out_o, out_l)
         return out_o if wl is None else (out_o, out_l)
 
-    def sample_weight(self, material_id: torch.Tensor, wi: torch.Tensor, wo: torch.Tensor, pdf_sa: torch.Tensor, tint=None,
-                      active: Optional[torch.Tensor] = None, firefly_threshold: float = 30.0):
+    def sample_weight(self, material_id: torch.Tensor, wi: torch.Tensor, wo: torch.Tensor, pdf_sa: torch.Tensor, *, tint=None,
+                      firefly_threshold: Optional[float] = None, active: Optional[torch.Tensor] = None):
         """``MeasuredBSDF.sample_weight`` of each lane's material in one launch -> (weight [N,3], pdf [N]); lanes without
-        ground truth get weight NaN and pdf = pdf_sa."""
-        self._check(material_id, wi=(wi, 3), wo=(wo, 3), pdf_sa=(pdf_sa, 0))
-        act = None
-        if active is not None:
-            if active.shape != (wi.shape[0],) or active.device != wi.device or active.dtype not in (torch.bool, torch.uint8):
-                raise ValueError("MeasuredTable.sample_weight: active must be a bool or uint8 tensor [N] on the device of wi")
-            act = active.to(torch.uint8).contiguous()
-        weight, pdf = torch.empty_like(wi), torch.empty_like(pdf_sa)
-        _launch("bsdfd_measured_sample_weight_table", wi.device, self._table(), material_id, wi, wo, pdf_sa, act, wi.shape[0],
-                MeasuredBSDF._tint(tint), float(firefly_threshold), weight, pdf)
-        return weight, pdf
+        ground truth get weight NaN and pdf = pdf_sa.  A mask on another device is refused, not copied across."""
+        return self._sample_weight(material_id, wi, wo, pdf_sa, tint, firefly_threshold, active)
 
     def sample_t(self, material_id: torch.Tensor, wi: torch.Tensor, u: torch.Tensor, tint=None,
                  active: Optional[torch.Tensor] = None, out=None):
         """``MeasuredBSDF.sample_t`` of each lane's material in one launch -> (wo [N,3], pdf [N], weight [N,3]); lanes without
         ground truth get NaN in all three."""
-        wo, pdf, weight = MeasuredBSDF._sample_out(wi, out, "MeasuredTable.sample_t")
-        self._check(material_id, wi=(wi, 3), u=(u, 2), wo=(wo, 3), pdf=(pdf, 0), weight=(weight, 3))
-        act = MeasuredBSDF._active(active, wi.shape[0], wi.device, "MeasuredTable.sample_t")
-        _launch("bsdfd_measured_sample_table", wi.device, self._table(), material_id, wi, u, act, wi.shape[0],
-                MeasuredBSDF._tint(tint), wo, pdf, weight)
-        return wo, pdf, weight
+        return self._sample_t(material_id, wi, u, tint, active, out)
 
     def pdf_t(self, material_id: torch.Tensor, wi: torch.Tensor, wo: torch.Tensor, active: Optional[torch.Tensor] = None,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``MeasuredBSDF.pdf_t`` of each lane's material in one launch -> [N]; NaN = no ground truth for that lane."""
-        if out is None:
-            out = torch.empty(material_id.shape[0], dtype=torch.float32, device=material_id.device)
-        self._check(material_id, wi=(wi, 3), wo=(wo, 3), out=(out, 0))
-        act = MeasuredBSDF._active(active, wi.shape[0], wi.device, "MeasuredTable.pdf_t")
-        _launch("bsdfd_measured_pdf_table", wi.device, self._table(), material_id, wi, wo, act, wi.shape[0], out)
-        return out
+        return self._pdf_t(material_id, wi, wo, active, out)

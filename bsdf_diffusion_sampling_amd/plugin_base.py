@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import dataclasses
 import os
+import sys
 from typing import Any, Optional
 
 import torch
@@ -69,6 +70,8 @@ class NeuralBSDFCore:
     DOMAIN_NAME = "disk"
     VARIANT = _lib.PLUGIN_MEASURED
     T = 4
+    FUSED_GT = "measured.MeasuredBSDF"  # <module>.<class> of the native evaluator this plugin fuses with (``_fused_gt``)
+    WEIGHT_TAKES_ACTIVE = True          # sample()'s ``active`` reaches the weight pass, not the flow alone
 
     def __init__(self, props):
         self.props = props
@@ -240,9 +243,14 @@ class NeuralBSDFCore:
         return self.sampler.plugin_sample_pdf(wi, wl, x0, T=self.T, variant=self.VARIANT, seed=seed, offset=offset, active=active)
 
     def _mask(self, active, wi: torch.Tensor) -> Optional[torch.Tensor]:
-        """The ``active`` argument of a protocol method as the [N] device mask the tensor core takes, or None: ``active is
-        True`` (Mitsuba's default) or ``props["compact_active"] = False``."""
-        if active is True or active is None or not self.compact_active:
+        """``active`` as the tensor core takes it: ``_device_mask``, or None with ``props["compact_active"] = False``."""
+        return self._device_mask(active, wi) if self.compact_active else None
+
+    @staticmethod
+    def _device_mask(active, wi: torch.Tensor) -> Optional[torch.Tensor]:
+        """The ``active`` argument of a protocol method as a bool / uint8 [N] mask on the device of ``wi``, or None: ``active is
+        True`` (Mitsuba's default).  What the flow (``_mask``) and the weight pass of sample() both take."""
+        if active is True or active is None:
             return None
         if not isinstance(active, torch.Tensor):
             active = active.torch() if hasattr(active, "torch") else torch.as_tensor(active)
@@ -264,17 +272,47 @@ class NeuralBSDFCore:
                                "reference, rendering/brdf_measured_disk.py:36-42); pass props['bsdf']")
         return self.bsdf
 
-    def _native_gt(self):
-        from .measured import MeasuredBSDF
-        return self.bsdf if isinstance(self.bsdf, MeasuredBSDF) else None
+    def _fused_gt(self):
+        """``self.bsdf`` where it is the native evaluator whose launches do this plugin's eval() and the tail of its sample()
+        (``FUSED_GT``: the families' tails differ in masks and firefly channel, so each fuses with its own), else None.  Nothing
+        is imported for the question: a class whose module was never loaded has no instances."""
+        module, name = self.FUSED_GT.split(".")
+        module = sys.modules.get(f"{__package__}.{module}")
+        return self.bsdf if module is not None and isinstance(self.bsdf, getattr(module, name)) else None
+
+    def eval_unmasked(self, ctx, si, wo):
+        """The ground-truth evaluator's eval() * albedo, as the torch lines take it."""
+        value = _vec(self._need_bsdf().eval(ctx, si, wo))
+        return value * self.albedo.to(value.device)
 
     def eval(self, ctx, si, wo, active=True):
         wi, wo_t = _wi_of(si), _vec(wo)
-        if self._native_gt() is not None:  # one launch: f cos * albedo, zero on the lower hemispheres
-            return self.bsdf.eval_t(wi, wo_t, tint=self.albedo)
-        value = _vec(self._need_bsdf().eval(ctx, si, wo)) * self.albedo.to(wi.device)
+        gt = self._fused_gt()
+        if gt is not None:  # one launch: f cos * albedo, with the evaluator's masks
+            return gt.eval_t(wi, wo_t, tint=self.albedo)
+        return self._eval_lines(ctx, si, wo, wi, wo_t)
+
+    def _eval_lines(self, ctx, si, wo, wi, wo_t):
+        value = self.eval_unmasked(ctx, si, wo)
         ok = (wi[:, 2] > 0) & (wo_t[:, 2] > 0)
         return torch.where(ok[:, None], value, torch.zeros_like(value))
+
+    def sample(self, ctx, si, sample1=None, sample2=None, active=True, *, x0=None, seed=None):
+        """-> (bs, weight).  A plugin says what ``bs`` it reports (``_bsdf_sample``), what its torch lines make of
+        value = f * albedo / pdf_sa where no native evaluator fuses them (``_weight_lines``: -> weight, ``bs.pdf`` replaced by the
+        firefly rule's), and whether its weight pass sees ``active`` at all (``WEIGHT_TAKES_ACTIVE``)."""
+        wi = _wi_of(si)
+        act = self._device_mask(active, wi)
+        wo, pdf_sa = self.sample_t(wi, x0=x0, seed=seed, active=act if self.compact_active else None)
+        bs = self._bsdf_sample(wo, pdf_sa)
+        if self.bsdf is None:  # no ground-truth evaluator: the sampler-only use (bench / harness)
+            return bs, None
+        act = act if self.WEIGHT_TAKES_ACTIVE else None
+        gt = self._fused_gt()
+        if gt is None:
+            return bs, self._weight_lines(self.eval_unmasked(ctx, si, wo) / pdf_sa[:, None], wi, bs, act)
+        weight, bs.pdf = gt.sample_weight(wi, wo, pdf_sa, tint=self.albedo, firefly_threshold=self.FIREFLY, active=act)
+        return bs, weight  # weight, firefly rule and masks fused into the evaluator's launch
 
     def pdf(self, ctx, si, wo, active=True):
         wi = _wi_of(si)

@@ -264,7 +264,7 @@ def test_plugin_methods_honour_active(kind):
     dev = _dev()
     n = 5000
     plug, legacy = _plugin(kind), _plugin(kind, compact_active=False)
-    assert plug.compact_active and not legacy.compact_active and plug._native_gt() is not None
+    assert plug.compact_active and not legacy.compact_active and plug._fused_gt() is not None
     si, wo_q = SurfaceInteraction(_dirs(n, 1)), _dirs(n, 2)
     mask = (torch.rand(n, generator=torch.Generator().manual_seed(3)) < 0.4).to(dev)
     dead = ~mask

@@ -147,9 +147,9 @@ def test_python_calls_check_their_tensors():
     from bsdf_diffusion_sampling_amd.measured import MeasuredBSDF, MeasuredTable
     v = torch.zeros(8, 3)
     bare = MeasuredBSDF.__new__(MeasuredBSDF)      # no file, no handle: the tensor checks come before the native call
-    with pytest.raises(ValueError, match="contiguous fp32 CUDA"):
+    with pytest.raises(ValueError, match="must be a contiguous CUDA tensor"):
         bare.sample_t(v, torch.zeros(8, 2))
-    with pytest.raises(ValueError, match="contiguous fp32 CUDA"):
+    with pytest.raises(ValueError, match="must be a contiguous CUDA tensor"):
         bare.pdf_t(v, v)
     tab = MeasuredTable([None, None])
     ids = torch.zeros(8, dtype=torch.int64)
