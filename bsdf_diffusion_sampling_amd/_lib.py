@@ -22,11 +22,12 @@ SRC_PATHS = [SRC_PATH, SRC32_PATH, HOST_PATH, os.path.join(_HERE, "csrc", "wavef
              os.path.join(_HERE, "csrc", "measured.hip"), os.path.join(_HERE, "csrc", "measured_table.hip"),
              os.path.join(_HERE, "csrc", "bucket.hip"),
              os.path.join(_HERE, "csrc", "bucket_wide.hip"), os.path.join(_HERE, "csrc", "live.hip"),
-             os.path.join(_HERE, "csrc", "clock.hip"), os.path.join(_HERE, "csrc", "dielectric.hip")]  # translation units of libbsdfd.so
+             os.path.join(_HERE, "csrc", "clock.hip"), os.path.join(_HERE, "csrc", "dielectric.hip"),
+             os.path.join(_HERE, "csrc", "principled.hip")]  # translation units of libbsdfd.so
 FLOW_TUS = (SRC_PATH, SRC32_PATH)   # ... whose device assembly the build verifies (_asmcheck)
 DEP_PATHS = SRC_PATHS + [os.path.join(_HERE, "csrc", f) for f in ("common.h", "flow_dev.h", "flow_kernels.h", "bucket_scan.h",
                                                                      "measured_dev.h", "wavefront_dev.h", "env_dev.h", "bounce_dev.h",
-                                                                     "dielectric_dev.h")]
+                                                                     "dielectric_dev.h", "principled_dev.h")]
 INCLUDE_DIR = os.path.join(ROOT, "include")
 ASM_CACHE_DIR = os.path.join(ROOT, "build", "asm")   # device assembly of the last product build (bsdfd.s, flow32.s)
 
@@ -56,6 +57,7 @@ EXPORTS = (
     "bsdfd_measured_has_luminance", "bsdfd_measured_sample", "bsdfd_measured_pdf", "bsdfd_measured_sample_table",
     "bsdfd_measured_pdf_table",
     "bsdfd_dielectric_eval", "bsdfd_dielectric_sample_weight", "bsdfd_dielectric_sample", "bsdfd_dielectric_pdf",
+    "bsdfd_principled_eval", "bsdfd_principled_sample_weight", "bsdfd_principled_sample", "bsdfd_principled_pdf",
     "bsdfd_set_profiling", "bsdfd_profile_read", "bsdfd_profile_read_op", "bsdfd_profile_clock_mhz", "bsdfd_last_kernel_ms", "bsdfd_shader_clock_mhz",
     "bsdfd_last_error", "bsdfd_version", "bsdfd_abi_version",
 )
@@ -91,6 +93,13 @@ class EnvDist(C.Structure):
 class Dielectric(C.Structure):
     """bsdfd_dielectric (include/bsdfd.h)."""
     _fields_ = [("alpha", C.c_float), ("eta", C.c_float), ("distribution", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Principled(C.Structure):
+    """bsdfd_principled (include/bsdfd.h)."""
+    _fields_ = [("base_color", C.c_float * 3)] + \
+               [(n, C.c_float) for n in ("roughness", "anisotropic", "metallic", "spec_trans", "eta", "spec_tint", "sheen", "sheen_tint",
+                                         "flatness", "clearcoat", "clearcoat_gloss")] + [("reserved", C.c_int32 * 2)]
 
 
 class Opts(C.Structure):
@@ -461,6 +470,8 @@ def lib():
     L.bsdfd_dielectric_sample_weight.argtypes = [dp, fp, fp, fp, fp, i64, C.POINTER(C.c_float), C.c_float, fp, fp, vp]
     L.bsdfd_dielectric_sample.argtypes = [dp, fp, fp, fp, i64, C.POINTER(C.c_float), fp, fp, fp, vp]
     L.bsdfd_dielectric_pdf.argtypes = [dp, fp, fp, fp, i64, fp, vp]
+    for call in ("eval", "sample_weight", "sample", "pdf"):   # the dielectric's argument lists behind a descriptor of their own
+        getattr(L, "bsdfd_principled_" + call).argtypes = [C.POINTER(Principled)] + getattr(L, "bsdfd_dielectric_" + call).argtypes[1:]
     L.bsdfd_bucket_workspace_bytes.argtypes = [i64, i32]
     L.bsdfd_bucket_workspace_bytes.restype = i64
     L.bsdfd_bucket_by_material.argtypes = [fp, i64, i32, fp, fp, fp, i64, vp]

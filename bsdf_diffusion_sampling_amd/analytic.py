@@ -1,17 +1,22 @@
-"""Analytic ground truth of the full-sphere plugin: the rough dielectric on the GPU.
+"""Analytic ground truth of the full-sphere plugin: the rough dielectric and the principled BSDF on the GPU.
 
 The reference's full-sphere plugin takes its ``eval()``, sample weight and firefly rule from an analytic Mitsuba BSDF out of a
-list (rendering/utils/bsdf_dict.py; rendering/bsdf_myresult.py:97-110).  Entries 23..25 of that list are ``roughdielectric``
-(Beckmann, alpha 0.2 / 0.3 / 0.5, bk7 in air); Mitsuba has no AMD GPU variant, so ``RoughDielectric`` is the same published
-model (Walter et al. 2007; Mitsuba's defaults: visible-normal sampling, radiance transport) over ``libbsdfd.so``
-(csrc/dielectric.hip, csrc/dielectric_dev.h): ``eval`` = f |cos theta_o| on both sides of the surface, its own importance
-sampler (``sample`` / ``pdf``) and the fused tail of the plugin's ``sample()`` (``sample_weight``).  Restated from the
-publication, PARITY-UNPINNED against Mitsuba, like ``measured.MeasuredBSDF``.  Entries 0..22 are ``principled`` BSDFs and have no
-native counterpart.  No CPU fallback.
+list (rendering/utils/bsdf_dict.py; rendering/bsdf_myresult.py:97-110).  Mitsuba has no AMD GPU variant, so both kinds of entry are
+restated from their publications over ``libbsdfd.so``, PARITY-UNPINNED against Mitsuba, like ``measured.MeasuredBSDF``:
+
+* entries 23..25 are ``roughdielectric`` (Beckmann, alpha 0.2 / 0.3 / 0.5, bk7 in air): ``RoughDielectric`` (Walter et al. 2007;
+  Mitsuba's defaults: visible-normal sampling, radiance transport; csrc/dielectric.hip, csrc/dielectric_dev.h);
+* entries 0..22 are ``principled``: ``Principled`` (Burley 2012 / 2015 with Mitsuba's choices: diffuse + retro-reflection + fake
+  subsurface + sheen, a GTR1 clearcoat, specular transmission and reflection over anisotropic GGX, Fresnel mixed with Schlick
+  terms; visible normals as in Heitz 2018; csrc/principled.hip, csrc/principled_dev.h).
+
+Each is ``eval`` = f |cos theta_o| on both sides of the surface, its own importance sampler (``sample`` / ``pdf``) and the fused
+tail of the plugin's ``sample()`` (``sample_weight``).  ``reference_bsdf(idx)`` builds any entry of the list.  No CPU fallback.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import torch
 
@@ -35,7 +40,23 @@ def _ior(v) -> float:
     return float(v)
 
 
-class RoughDielectric(GroundTruth):
+class FullSphereGroundTruth(GroundTruth):
+    """What the full-sphere plugin fuses with (``bsdf_myresult.MyBSDF.FUSED_GT``): an analytic model of both sides of the surface whose
+    ``sample_weight`` is the tail of that plugin's sample() (rendering/bsdf_myresult.py:97-104) — value = 0 where pdf_sa <= 0, the
+    firefly rule reads value.x at 3.5, no cosine masks — and whose sampler takes ``u`` [N,3]: Mitsuba's sample2, then its sample1."""
+
+    U_COLS = 3
+    FIREFLY = 3.5
+
+    def _lead(self):
+        return C.byref(self._desc)
+
+    def _variates(self, sample1, sample2):
+        from .plugin_base import _vec
+        return torch.cat([_vec(sample2).reshape(-1, 2), _vec(sample1).reshape(-1, 1)], 1).contiguous()
+
+
+class RoughDielectric(FullSphereGroundTruth):
     """``eval_t`` = f |cos theta_o|, grey: reflection and (radiance-mode) transmission, either side.  ``sample_weight`` is the tail
     of the full-sphere plugin's sample() (rendering/bsdf_myresult.py:97-104): value = 0 where pdf_sa <= 0, the firefly rule reads
     value.x, no cosine masks.  ``sample_t`` takes ``u`` [N,3] in [0,1)^3 (columns 0..1: Mitsuba's sample2, the visible normal;
@@ -45,8 +66,6 @@ class RoughDielectric(GroundTruth):
     NAME = "RoughDielectric"
     ENTRY = dict(eval="bsdfd_dielectric_eval", sample_weight="bsdfd_dielectric_sample_weight", sample="bsdfd_dielectric_sample",
                  pdf="bsdfd_dielectric_pdf")
-    U_COLS = 3
-    FIREFLY = 3.5
 
     def __init__(self, alpha: float, int_ior="bk7", ext_ior="air", distribution: str = "beckmann"):
         if distribution not in DISTRIBUTIONS:
@@ -62,13 +81,6 @@ class RoughDielectric(GroundTruth):
     def __repr__(self):
         return f"RoughDielectric(alpha={self.alpha}, int_ior={self.int_ior}, ext_ior={self.ext_ior}, distribution={self.distribution!r})"
 
-    def _lead(self):
-        return C.byref(self._desc)
-
-    def _variates(self, sample1, sample2):
-        from .plugin_base import _vec
-        return torch.cat([_vec(sample2).reshape(-1, 2), _vec(sample1).reshape(-1, 1)], 1).contiguous()
-
     def _bsdf_sample(self, wi, wo, pdf):
         from .plugin_base import FLAG_DIFFUSE_REFLECTION, FLAG_DIFFUSE_TRANSMISSION, BSDFSample3f
         refl = wi[:, 2] * wo[:, 2] > 0
@@ -78,13 +90,111 @@ class RoughDielectric(GroundTruth):
                             sampled_component=torch.where(refl, 0, 1))
 
 
-def reference_material(idx: int) -> RoughDielectric:
-    """Entry ``idx`` of the reference's analytic material list (rendering/utils/bsdf_dict.py) as a native evaluator: 23 / 24 / 25
-    are its three rough dielectrics; 0..22 are ``principled`` BSDFs, which are not built."""
+def eta_of_specular(specular: float) -> float:
+    """Mitsuba's ``specular`` parameter as a relative index of refraction (1 -> 1.78885, the 1.788 of the reference's plugin)."""
+    return 2.0 / (1.0 - math.sqrt(0.08 * float(specular))) - 1.0
+
+
+class Principled(FullSphereGroundTruth):
+    """``eval_t`` = f |cos theta_o| per channel: diffuse (+ retro-reflection, fake subsurface, sheen) and clearcoat above the
+    surface, specular reflection and (radiance-mode) transmission on either side.  The parameters are Mitsuba's, each in [0, 1];
+    the interface is given as ``specular`` OR ``eta`` (>= 1; neither: Mitsuba's specular = 0.5, eta 1.5).  ``sample_t`` takes ``u``
+    [N,3] in [0,1)^3 (columns 0..1: Mitsuba's sample2; column 2: sample1, which picks the lobe on the cumulative order diffuse,
+    clearcoat, transmission, reflection); a failed sample is zeros in wo, pdf and weight.  ``sample`` fills eta, sampled_type and
+    sampled_component (Mitsuba's 0..3, in that order)."""
+
+    NAME = "Principled"
+    ENTRY = dict(eval="bsdfd_principled_eval", sample_weight="bsdfd_principled_sample_weight", sample="bsdfd_principled_sample",
+                 pdf="bsdfd_principled_pdf")
+    UNIT = ("roughness", "anisotropic", "metallic", "spec_trans", "spec_tint", "sheen", "sheen_tint", "flatness", "clearcoat",
+            "clearcoat_gloss")
+
+    def __init__(self, base_color=(1.0, 1.0, 1.0), roughness=0.5, anisotropic=0.0, metallic=0.0, spec_trans=0.0, specular=None,
+                 eta=None, spec_tint=0.0, sheen=0.0, sheen_tint=0.0, flatness=0.0, clearcoat=0.0, clearcoat_gloss=0.0):
+        if specular is not None and eta is not None:
+            raise ValueError("Principled: give specular or eta, not both")
+        given = dict(roughness=roughness, anisotropic=anisotropic, metallic=metallic, spec_trans=spec_trans, spec_tint=spec_tint,
+                     sheen=sheen, sheen_tint=sheen_tint, flatness=flatness, clearcoat=clearcoat, clearcoat_gloss=clearcoat_gloss)
+        self.base_color = tuple(float(c) for c in base_color)
+        for k in self.UNIT:
+            setattr(self, k, float(given[k]))
+        if len(self.base_color) != 3 or not all(0.0 <= v <= 1.0 for v in self.base_color + tuple(getattr(self, k) for k in self.UNIT)):
+            raise ValueError("Principled: base_color (3 channels) and every parameter but eta must lie in [0, 1]")
+        if specular is not None and not 0.0 <= float(specular) <= 1.0:
+            raise ValueError("Principled: specular must lie in [0, 1]")
+        self.eta = float(eta) if eta is not None else eta_of_specular(0.5 if specular is None else specular)
+        if not (self.eta >= 1.0 and math.isfinite(self.eta)):
+            raise ValueError("Principled: eta must be finite and >= 1")
+        if self.eta == 1.0 and self.spec_trans > 0.0:
+            raise ValueError("Principled: eta == 1 (no interface) needs spec_trans == 0")
+        # derived, as csrc/principled.hip forms them (there in fp32): the GGX roughness pair, the lobe weights and the two
+        # constant thresholds of the lobe choice
+        aspect = math.sqrt(1.0 - 0.9 * self.anisotropic)
+        self.ax, self.ay = max(1e-3, self.roughness ** 2 / aspect), max(1e-3, self.roughness ** 2 * aspect)
+        self.brdf, self.bsdf = (1.0 - self.metallic) * (1.0 - self.spec_trans), (1.0 - self.metallic) * self.spec_trans
+        total = 1.0 + 0.25 * self.clearcoat + self.brdf
+        self.cum_d, self.cum_c = self.brdf / total, (self.brdf + 0.25 * self.clearcoat) / total
+        self._desc = _lib.Principled((C.c_float * 3)(*self.base_color), self.roughness, self.anisotropic, self.metallic,
+                                     self.spec_trans, self.eta, self.spec_tint, self.sheen, self.sheen_tint, self.flatness,
+                                     self.clearcoat, self.clearcoat_gloss)
+
+    def __repr__(self):
+        return (f"Principled(base_color={self.base_color}, eta={self.eta}, "
+                + ", ".join(f"{k}={getattr(self, k)}" for k in self.UNIT) + ")")
+
+    def _bsdf_sample(self, wi, wo, pdf):
+        from .plugin_base import FLAG_DIFFUSE_REFLECTION, FLAG_DIFFUSE_TRANSMISSION, BSDFSample3f
+        refl = wi[:, 2] * wo[:, 2] > 0
+        eta = torch.where(refl, 1.0, torch.where(wi[:, 2] > 0, self.eta, 1.0 / self.eta))
+        # (Mitsuba's flags are Glossy* / Diffuse*; the reference's plugin reports the Diffuse pair, which is what plugin_base defines)
+        return BSDFSample3f(wo=wo, pdf=pdf, eta=eta, sampled_type=torch.where(refl, FLAG_DIFFUSE_REFLECTION, FLAG_DIFFUSE_TRANSMISSION),
+                            sampled_component=torch.where(refl, 3, 2))
+
+    def sample(self, ctx, si, sample1, sample2, active=True):
+        """``mi.BSDF.sample``: -> (BSDFSample3f, weight [N,3]); ``sampled_component`` 0..3 = diffuse, clearcoat, transmission,
+        reflection: sample1 against the two constant thresholds (0 from inside), then the side of wo."""
+        from .plugin_base import _vec, _wi_of
+        bs, weight = super().sample(ctx, si, sample1, sample2, active)
+        front, u2 = _wi_of(si)[:, 2] > 0, _vec(sample1).reshape(-1)
+        bs.sampled_component = torch.where(u2 < torch.where(front, self.cum_d, 0.0), 0,
+                                           torch.where(u2 < torch.where(front, self.cum_c, 0.0), 1, bs.sampled_component))
+        return bs, weight
+
+
+# rendering/utils/bsdf_dict.py: the 23 principled entries as (metallic, specular, roughness, anisotropic); everything else is common
+# to them (sheen_tint: 0.3 at idx 7).  The file defines dict4_principled twice: the second definition wins, which is row 3.
+REFERENCE_PRINCIPLED = {
+    0: (.1, 1, .2, .5), 1: (.3, .7, .5, .5), 2: (1, .8, .1, .5), 3: (.2, .3, .3, .7), 4: (.1, .8, .3, .7), 5: (.1, 1, .1, .7),
+    6: (.9, .7, .3, .7), 7: (.5, .8, .3, .7), 8: (.1, .8, .3, .7), 9: (.3, .2, .1, .7), 10: (0, 1, .1, .7), 11: (.8, .2, .1, .7),
+    12: (.6, .2, .3, .7), 13: (.3, .2, .7, .7), 14: (.9, .2, .5, .7), 15: (.9, .2, .3, .7), 16: (.9, .2, .6, .7), 17: (.9, .2, .9, .7),
+    18: (.1, .8, .1, .7), 19: (.1, .5, .4, .7), 20: (.1, .8, .3, .7), 21: (.1, .5, .7, .7), 22: (.1, .3, .8, .7),
+}
+REFERENCE_PRINCIPLED_COMMON = dict(base_color=(1.0, 1.0, 1.0), spec_tint=0.5, sheen=0.5, sheen_tint=0.5, clearcoat=0.5,
+                                   clearcoat_gloss=0.5, spec_trans=0.9, flatness=1.0)
+
+
+def reference_bsdf(idx: int):
+    """Entry ``idx`` of the reference's analytic material list (rendering/utils/bsdf_dict.py) as a native evaluator: a
+    ``Principled`` for 0..22, a ``RoughDielectric`` for 23..25."""
     idx = int(idx)
     if idx in REFERENCE_ROUGHDIELECTRIC:
         return RoughDielectric(REFERENCE_ROUGHDIELECTRIC[idx], int_ior="bk7", ext_ior="air")
+    if idx in REFERENCE_PRINCIPLED:
+        metallic, specular, roughness, anisotropic = REFERENCE_PRINCIPLED[idx]
+        params = dict(REFERENCE_PRINCIPLED_COMMON, metallic=metallic, specular=specular, roughness=roughness, anisotropic=anisotropic)
+        if idx == 7:
+            params["sheen_tint"] = 0.3
+        return Principled(**params)
+    raise IndexError(f"the reference's material list has entries 0..{N_REFERENCE_MATERIALS - 1}, not {idx}")
+
+
+def reference_material(idx: int) -> RoughDielectric:
+    """The rough dielectrics of the reference's list, 23 / 24 / 25, as native evaluators — what the full-sphere plugin builds by
+    default.  0..22 are ``principled`` BSDFs, which this call keeps refusing: ``reference_bsdf`` builds every entry."""
+    idx = int(idx)
+    if idx in REFERENCE_ROUGHDIELECTRIC:
+        return reference_bsdf(idx)
     if 0 <= idx < N_REFERENCE_MATERIALS:
-        raise NotImplementedError(f"material {idx} of the reference's list is a Mitsuba `principled` BSDF: only the "
-                                  "roughdielectric entries 23..25 have a native evaluator")
+        raise NotImplementedError(f"material {idx} of the reference's list is a Mitsuba `principled` BSDF, which this call does not "
+                                  "build: reference_bsdf(idx) does (analytic.Principled)")
     raise IndexError(f"the reference's material list has entries 0..{N_REFERENCE_MATERIALS - 1}, not {idx}")

@@ -13,8 +13,9 @@ Same spherical operators, different post-processing:
 The list is rendering/utils/bsdf_dict.py.  Its entries 23..25 are rough dielectrics, which ``analytic.RoughDielectric`` evaluates
 natively: for those ``idx`` the plugin has its ground truth by default (``props["analytic"] = False`` turns that off, ``props["bsdf"]``
 overrides it) — eval() is one launch and sample()'s weight and firefly rule another.  Entries 0..22 are Mitsuba ``principled``
-BSDFs without a native counterpart: there ``self.bsdf`` stays None unless ``props["bsdf"]`` is given, sample() returns
-``(bs, None)`` and eval() raises.
+BSDFs, which ``analytic.Principled`` evaluates natively; that one is opt-in: ``props["analytic"] = "all"`` gives every ``idx`` its
+native evaluator (``analytic.reference_bsdf``).  By default ``self.bsdf`` stays None there unless ``props["bsdf"]`` is given,
+sample() returns ``(bs, None)`` and eval() raises.
 """
 from __future__ import annotations
 
@@ -32,7 +33,7 @@ class MyBSDF(NeuralBSDFCore):
     VARIANT = _lib.PLUGIN_FULLSPHERE
     T = 8
     FIREFLY = 3.5
-    FUSED_GT = "analytic.RoughDielectric"
+    FUSED_GT = "analytic.FullSphereGroundTruth"
     WEIGHT_TAKES_ACTIVE = False  # as in the reference: ``active`` reaches the flow only
 
     def __init__(self, props):
@@ -40,10 +41,13 @@ class MyBSDF(NeuralBSDFCore):
         self.idx = int(self._get("idx"))
         self.m_flags = FLAG_DIFFUSE_REFLECTION | FLAG_DIFFUSE_TRANSMISSION | FLAG_FRONT_SIDE | FLAG_BACK_SIDE
         self.m_components = [self.m_flags]
-        if self.bsdf is None and self._get("analytic", True):
-            from .analytic import REFERENCE_ROUGHDIELECTRIC, reference_material
-            if self.idx in REFERENCE_ROUGHDIELECTRIC:
-                self.bsdf = reference_material(self.idx)
+        analytic = self._get("analytic", True)
+        if isinstance(analytic, str) and analytic != "all":
+            raise ValueError(f"props['analytic'] is True, False or 'all', not {analytic!r}")
+        if self.bsdf is None and analytic:
+            from .analytic import REFERENCE_ROUGHDIELECTRIC, reference_bsdf
+            if analytic == "all" or self.idx in REFERENCE_ROUGHDIELECTRIC:
+                self.bsdf = reference_bsdf(self.idx)
 
     def _material_name(self) -> str:
         return f"bsdf_{int(self._get('idx'))}"

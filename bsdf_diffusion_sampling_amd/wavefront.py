@@ -96,11 +96,11 @@ class WavefrontRenderer:
         self.skip_misses = bool(skip_misses)
         # shade with the ground-truth f (the plugin's native `measured` evaluator) when it is available,
         # else with the proxy f cos = albedo * pdf_net
-        # (not the full-sphere plugin's rough dielectric: these rays never travel inside the ball, so its transmitted lobe has no
-        # path to light — such a plugin is shaded with the proxy, as before it had an evaluator)
-        from .analytic import RoughDielectric
+        # (not the full-sphere plugin's rough dielectric or principled BSDF: these rays never travel inside the ball, so a
+        # transmitted lobe has no path to light — such a plugin is shaded with the proxy, as before it had an evaluator)
+        from .analytic import FullSphereGroundTruth
         gt = getattr(plugin, "bsdf", None)
-        has_gt = hasattr(gt, "eval_t") and not isinstance(gt, RoughDielectric)
+        has_gt = hasattr(gt, "eval_t") and not isinstance(gt, FullSphereGroundTruth)
         self.use_ground_truth = has_gt if use_ground_truth is None else bool(use_ground_truth)
         if self.use_ground_truth and not has_gt:
             raise ValueError("use_ground_truth needs a plugin with a native MeasuredBSDF (props['measured_dir'])")

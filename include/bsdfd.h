@@ -48,7 +48,9 @@ extern "C" {
  *      bsdfd_env_dist: importance sampling of the environment map in the array scene;
  *      bsdfd_wf_bounce_rr(): Russian roulette inside the bounce of the array scene;
  *      bsdfd_dielectric_eval(), bsdfd_dielectric_sample_weight(), bsdfd_dielectric_sample() and bsdfd_dielectric_pdf(), which
- *      take a struct of their own, bsdfd_dielectric: the rough-dielectric ground truth of the full-sphere plugin. */
+ *      take a struct of their own, bsdfd_dielectric: the rough-dielectric ground truth of the full-sphere plugin;
+ *      bsdfd_principled_eval(), bsdfd_principled_sample_weight(), bsdfd_principled_sample() and bsdfd_principled_pdf(), which
+ *      take a struct of their own, bsdfd_principled: the principled ground truth of the full-sphere plugin. */
 #define BSDFD_ABI_VERSION 8
 
 #define BSDFD_OK 0
@@ -462,6 +464,44 @@ int bsdfd_dielectric_sample_weight(const bsdfd_dielectric* desc, const float* wi
 int bsdfd_dielectric_sample(const bsdfd_dielectric* desc, const float* wi, const float* u, const unsigned char* active, int64_t N,
                             const float* tint, float* wo_out, float* pdf_out, float* weight_out, void* hip_stream);
 int bsdfd_dielectric_pdf(const bsdfd_dielectric* desc, const float* wi, const float* wo, const unsigned char* active, int64_t N,
+                         float* pdf_out, void* hip_stream);
+
+/* ---- analytic ground truth of the full-sphere plugin: the principled BSDF (csrc/principled.hip) ---------------------------
+ * Entries 0..22 of the reference's material list (rendering/utils/bsdf_dict.py) are Mitsuba `principled` BSDFs.  Model: Burley
+ * 2012 / 2015 with Mitsuba's choices — four sampled lobes (diffuse with retro-reflection, fake subsurface and sheen; a GTR1
+ * clearcoat; specular transmission; specular reflection) over an anisotropic GGX distribution with the separable Smith G, exact
+ * unpolarised Fresnel mixed with Schlick terms, radiance transport; visible normals drawn as in Heitz 2018.  Restated from the
+ * publications; PARITY-UNPINNED against Mitsuba, like the two models above.  fp32.
+ * The material is this descriptor, read on the host at the call (zero-initialise it; it may grow at the end).  Every parameter
+ * but eta lies in [0, 1]; eta = int_ior / ext_ior >= 1, and eta == 1 (no interface) only with spec_trans == 0; anything else is
+ * BSDFD_EINVAL.  (Mitsuba's `specular` is eta = 2 / (1 - sqrt(0.08 specular)) - 1.)
+ * Directions are in the local shading frame, x the tangent the anisotropy refers to; BOTH sides of the surface are served
+ * (wi.z < 0: from inside, where only the two specular lobes exist, and nothing at all without transmission).  Per row:
+ *   eval           rgb_out [N,3] = f(wi, wo) |cos theta_o| * tint, 0 where wi.z == 0 or wo.z == 0, where the half vector is
+ *                  undefined (|wi + k wo| < 1e-6) and, per channel, where the value is not finite.
+ *   sample_weight  the tail of the plugin's sample(), as bsdfd_dielectric_sample_weight: value = f |cos| * tint / pdf_sa (0 where
+ *                  pdf_sa <= 0); pdf_out = pdf_sa where value.x < firefly_threshold, else 0; weight_out = value where pdf_out > 0.
+ *   sample         u [N,3] in [0,1)^3: columns 0..1 are Mitsuba's sample2, column 2 its sample1, which picks the lobe on the
+ *                  cumulative order diffuse, clearcoat, transmission, reflection (Mitsuba's components 0..3).  wo_out [N,3];
+ *                  pdf_out [N] = what bsdfd_principled_pdf gives for (wi, wo_out), bit for bit; weight_out [N,3] (may be NULL) =
+ *                  what bsdfd_principled_eval gives for that pair, divided by pdf_out.  A failed sample (a direction on the
+ *                  wrong side for its lobe, wi.z == 0, from inside without transmission, pdf 0) is zeros in all three.
+ *   pdf            the solid-angle density of that sampler at a given wo: the mixture of the four lobes.
+ * Rows with active[i] == 0, when a mask is given (u8 [N] or NULL), get 0 in every output.  tint: 3 floats on the host or NULL
+ * (white).  All four calls are stream-ordered, allocate nothing and do not synchronise; N = 0 is a no-op. */
+typedef struct {
+    float base_color[3];
+    float roughness, anisotropic, metallic, spec_trans, eta, spec_tint, sheen, sheen_tint, flatness, clearcoat, clearcoat_gloss;
+    int32_t reserved[2];
+} bsdfd_principled;
+int bsdfd_principled_eval(const bsdfd_principled* desc, const float* wi, const float* wo, int64_t N, const float* tint,
+                          float* rgb_out, void* hip_stream);
+int bsdfd_principled_sample_weight(const bsdfd_principled* desc, const float* wi, const float* wo, const float* pdf_sa,
+                                   const unsigned char* active, int64_t N, const float* tint, float firefly_threshold,
+                                   float* weight_out, float* pdf_out, void* hip_stream);
+int bsdfd_principled_sample(const bsdfd_principled* desc, const float* wi, const float* u, const unsigned char* active, int64_t N,
+                            const float* tint, float* wo_out, float* pdf_out, float* weight_out, void* hip_stream);
+int bsdfd_principled_pdf(const bsdfd_principled* desc, const float* wi, const float* wo, const unsigned char* active, int64_t N,
                          float* pdf_out, void* hip_stream);
 
 /* ---- wavefront harness ------------------------------------
