@@ -13,7 +13,8 @@ Modules (everything below the tensors runs in libbsdfd.so, include/bsdfd.h; no C
                       ``mi.BSDF`` call shapes of a single-material evaluator, written once
   measured            MeasuredBSDF: the ground-truth evaluator behind eval() (RGL tensor files);
                       MeasuredTable: eval() of a mixed-material wavefront in one launch
-  analytic            the full-sphere plugin's ground truth: RoughDielectric (bsdf_23..25), Principled (bsdf_0..22)
+  analytic            the full-sphere plugin's ground truth: RoughDielectric (bsdf_23..25), Principled (bsdf_0..22);
+                      AnalyticTable: both for a mixed-material wavefront in one launch, with an albedo per material
   measured_synth      synthetic RGL tensor files for tests and tools (numpy only)
   encoding            positional_encoding_1 as a stand-alone pass
   wavefront           WavefrontRenderer / ArrayRenderer: the render loop around the plugin calls

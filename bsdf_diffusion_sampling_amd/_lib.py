@@ -23,11 +23,12 @@ SRC_PATHS = [SRC_PATH, SRC32_PATH, HOST_PATH, os.path.join(_HERE, "csrc", "wavef
              os.path.join(_HERE, "csrc", "bucket.hip"),
              os.path.join(_HERE, "csrc", "bucket_wide.hip"), os.path.join(_HERE, "csrc", "live.hip"),
              os.path.join(_HERE, "csrc", "clock.hip"), os.path.join(_HERE, "csrc", "dielectric.hip"),
-             os.path.join(_HERE, "csrc", "principled.hip")]  # translation units of libbsdfd.so
+             os.path.join(_HERE, "csrc", "principled.hip"),
+             os.path.join(_HERE, "csrc", "analytic_table.hip")]  # translation units of libbsdfd.so
 FLOW_TUS = (SRC_PATH, SRC32_PATH)   # ... whose device assembly the build verifies (_asmcheck)
 DEP_PATHS = SRC_PATHS + [os.path.join(_HERE, "csrc", f) for f in ("common.h", "flow_dev.h", "flow_kernels.h", "bucket_scan.h",
                                                                      "measured_dev.h", "wavefront_dev.h", "env_dev.h", "bounce_dev.h",
-                                                                     "dielectric_dev.h", "principled_dev.h")]
+                                                                     "dielectric_dev.h", "principled_dev.h", "analytic_host.h")]
 INCLUDE_DIR = os.path.join(ROOT, "include")
 ASM_CACHE_DIR = os.path.join(ROOT, "build", "asm")   # device assembly of the last product build (bsdfd.s, flow32.s)
 
@@ -58,6 +59,8 @@ EXPORTS = (
     "bsdfd_measured_pdf_table",
     "bsdfd_dielectric_eval", "bsdfd_dielectric_sample_weight", "bsdfd_dielectric_sample", "bsdfd_dielectric_pdf",
     "bsdfd_principled_eval", "bsdfd_principled_sample_weight", "bsdfd_principled_sample", "bsdfd_principled_pdf",
+    "bsdfd_analytic_table_create", "bsdfd_analytic_table_destroy", "bsdfd_analytic_eval_table",
+    "bsdfd_analytic_sample_weight_table", "bsdfd_analytic_sample_table", "bsdfd_analytic_pdf_table",
     "bsdfd_set_profiling", "bsdfd_profile_read", "bsdfd_profile_read_op", "bsdfd_profile_clock_mhz", "bsdfd_last_kernel_ms", "bsdfd_shader_clock_mhz",
     "bsdfd_last_error", "bsdfd_version", "bsdfd_abi_version",
 )
@@ -100,6 +103,19 @@ class Principled(C.Structure):
     _fields_ = [("base_color", C.c_float * 3)] + \
                [(n, C.c_float) for n in ("roughness", "anisotropic", "metallic", "spec_trans", "eta", "spec_tint", "sheen", "sheen_tint",
                                          "flatness", "clearcoat", "clearcoat_gloss")] + [("reserved", C.c_int32 * 2)]
+
+
+ANALYTIC_NONE, ANALYTIC_PRINCIPLED, ANALYTIC_DIELECTRIC = 0, 1, 2   # BSDFD_ANALYTIC_*
+
+
+class AnalyticDesc(C.Union):
+    """bsdfd_analytic_entry.desc (include/bsdfd.h)."""
+    _fields_ = [("principled", Principled), ("dielectric", Dielectric)]
+
+
+class AnalyticEntry(C.Structure):
+    """bsdfd_analytic_entry (include/bsdfd.h)."""
+    _fields_ = [("kind", C.c_int32), ("albedo", C.c_float * 3), ("desc", AnalyticDesc)]
 
 
 class Opts(C.Structure):
@@ -472,6 +488,11 @@ def lib():
     L.bsdfd_dielectric_pdf.argtypes = [dp, fp, fp, fp, i64, fp, vp]
     for call in ("eval", "sample_weight", "sample", "pdf"):   # the dielectric's argument lists behind a descriptor of their own
         getattr(L, "bsdfd_principled_" + call).argtypes = [C.POINTER(Principled)] + getattr(L, "bsdfd_dielectric_" + call).argtypes[1:]
+    L.bsdfd_analytic_table_create.argtypes = [C.POINTER(AnalyticEntry), i32, C.POINTER(vp)]
+    L.bsdfd_analytic_table_destroy.argtypes = [vp]
+    L.bsdfd_analytic_table_destroy.restype = None
+    for call in ("eval", "sample_weight", "sample", "pdf"):   # the measured table's argument lists behind a table of their own
+        getattr(L, f"bsdfd_analytic_{call}_table").argtypes = getattr(L, f"bsdfd_measured_{call}_table").argtypes
     L.bsdfd_bucket_workspace_bytes.argtypes = [i64, i32]
     L.bsdfd_bucket_workspace_bytes.restype = i64
     L.bsdfd_bucket_by_material.argtypes = [fp, i64, i32, fp, fp, fp, i64, vp]

@@ -12,16 +12,28 @@ restated from their publications over ``libbsdfd.so``, PARITY-UNPINNED against M
 
 Each is ``eval`` = f |cos theta_o| on both sides of the surface, its own importance sampler (``sample`` / ``pdf``) and the fused
 tail of the plugin's ``sample()`` (``sample_weight``).  ``reference_bsdf(idx)`` builds any entry of the list.  No CPU fallback.
+
+``AnalyticTable`` serves a MIXED-material wavefront — one material id per lane, as a renderer's primary rays write them — in one
+launch per call (csrc/analytic_table.hip), where the classes above take one launch per material on gathered slices: every lane
+gets the bits of its own material's single-material call, and lanes without ground truth NaN.  Each entry carries an ``albedo``
+of its own, the per-ball colour of the reference's array scenes (rendering/bsdf_myresult.py:97,112), multiplied into the call's
+tint.  It is what ``wavefront.ArrayRenderer`` and ``pathtrace.PathArrayRenderer`` shade with when their ``ground_truth`` is
+analytic; ``ground_truth_for(names)`` builds that dict for the materials named ``bsdf_<idx>``.  Two limits of those renderers hold
+here too: under occlusion a BSDF sample below the surface is dropped (no transmission through the balls), and without occlusion
+such a direction looks the environment up weighted with the transmission lobe's ``f |cos|``.  Measured against the per-material
+loop it replaces: profiles/analytic_table.json (tools/analytic_table_bench.py).
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
+import re
+from typing import Optional, Sequence
 
 import torch
 
 from . import _lib
-from .ground_truth import GroundTruth
+from .ground_truth import GroundTruth, RowKernels, check, launch, tint3
 
 # Mitsuba's named indices of refraction, as far as the reference's list uses them
 IOR = {"bk7": 1.5046, "air": 1.000277, "vacuum": 1.0}
@@ -198,3 +210,97 @@ def reference_material(idx: int) -> RoughDielectric:
         raise NotImplementedError(f"material {idx} of the reference's list is a Mitsuba `principled` BSDF, which this call does not "
                                   "build: reference_bsdf(idx) does (analytic.Principled)")
     raise IndexError(f"the reference's material list has entries 0..{N_REFERENCE_MATERIALS - 1}, not {idx}")
+
+
+class AnalyticTable(RowKernels):
+    """The analytic models for a mixed-material wavefront: ``entries[m]`` (a ``Principled``, a ``RoughDielectric``, or None = no
+    ground truth) serves the lanes whose ``material_id`` is m, in ONE launch on the wavefront in LANE order, call for call what
+    ``measured.MeasuredTable`` is for the measured materials.  Lanes with ground truth get that entry's single-material result bit
+    for bit, every other lane (None entry, id negative or >= len(entries): a renderer's floor hits and misses) NaN.
+    ``albedo``: None, or one RGB triple per entry, finite and >= 0: lane by lane the tint is ``float32(tint) * float32(albedo[m])``.
+    The native table is created here, on the current device; it copies what it needs from the entries."""
+
+    NAME = "AnalyticTable"
+    ENTRY = dict(eval="bsdfd_analytic_eval_table", sample_weight="bsdfd_analytic_sample_weight_table",
+                 sample="bsdfd_analytic_sample_table", pdf="bsdfd_analytic_pdf_table")
+    U_COLS = 3
+    FIREFLY = 3.5
+    MAX_MATERIALS = 65536
+
+    def __init__(self, entries: Sequence[Optional[FullSphereGroundTruth]], albedo=None):
+        self.entries = list(entries)
+        if not 1 <= len(self.entries) <= self.MAX_MATERIALS:
+            raise ValueError(f"AnalyticTable: 1..{self.MAX_MATERIALS} entries")
+        if any(e is not None and not isinstance(e, (Principled, RoughDielectric)) for e in self.entries):
+            raise ValueError("AnalyticTable: entries are Principled or RoughDielectric objects, or None")
+        self.albedo = [(1.0, 1.0, 1.0)] * len(self.entries) if albedo is None else \
+            [tuple(float(v) for v in (a.tolist() if hasattr(a, "tolist") else a)) for a in albedo]
+        if len(self.albedo) != len(self.entries) or any(len(a) != 3 for a in self.albedo):
+            raise ValueError("AnalyticTable: albedo is None or one RGB triple per entry")
+        self._t = C.c_void_p()
+        recs = (_lib.AnalyticEntry * len(self.entries))()
+        for r, e, a in zip(recs, self.entries, self.albedo):
+            r.albedo = (C.c_float * 3)(*a)
+            if isinstance(e, Principled):
+                r.kind, r.desc.principled = _lib.ANALYTIC_PRINCIPLED, e._desc
+            elif isinstance(e, RoughDielectric):
+                r.kind, r.desc.dielectric = _lib.ANALYTIC_DIELECTRIC, e._desc
+        _lib.check(_lib.lib().bsdfd_analytic_table_create(recs, len(self.entries), C.byref(self._t)))
+
+    def __len__(self):
+        return len(self.entries)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_t", None) is not None and self._t.value:
+                _lib.lib().bsdfd_analytic_table_destroy(self._t)
+                self._t = C.c_void_p()
+        except Exception:
+            pass
+
+    def _lead(self):
+        return self._t
+
+    def eval_t(self, material_id: torch.Tensor, wi: torch.Tensor, wo: torch.Tensor, wl: Optional[torch.Tensor] = None,
+               tint=None, out_o: Optional[torch.Tensor] = None, out_l: Optional[torch.Tensor] = None):
+        """f(wi, wo) |cos theta_o| * tint * albedo of each lane's material -> f_o [N,3]; with ``wl`` also f(wi, wl) |cos theta_l|
+        -> (f_o, f_l), both evaluations in the same launch.  NaN rows = no ground truth for that lane."""
+        if out_l is not None and wl is None:
+            raise ValueError("AnalyticTable.eval_t: out_l without wl")
+        given = (("wi", wi), ("wo", wo), ("wl", wl), ("out_o", out_o), ("out_l", out_l))
+        check("AnalyticTable.eval_t", [(k, t, 3) for k, t in given if t is not None], material_id)
+        if out_o is None:
+            out_o = torch.empty_like(wi)
+        if wl is not None and out_l is None:
+            out_l = torch.empty_like(wi)
+        launch(self.ENTRY["eval"], wi.device, self._t, material_id, wi, wo, wl, wi.shape[0], tint3(tint), out_o, out_l)
+        return out_o if wl is None else (out_o, out_l)
+
+    def sample_weight(self, material_id: torch.Tensor, wi: torch.Tensor, wo: torch.Tensor, pdf_sa: torch.Tensor, *, tint=None,
+                      firefly_threshold: Optional[float] = None, active: Optional[torch.Tensor] = None):
+        """``sample_weight`` of each lane's material in one launch -> (weight [N,3], pdf [N]); lanes without ground truth get
+        weight NaN and pdf = pdf_sa."""
+        return self._sample_weight(material_id, wi, wo, pdf_sa, tint, firefly_threshold, active)
+
+    def sample_t(self, material_id: torch.Tensor, wi: torch.Tensor, u: torch.Tensor, tint=None,
+                 active: Optional[torch.Tensor] = None, out=None):
+        """``sample_t`` of each lane's material (``u`` [N,3]) in one launch -> (wo [N,3], pdf [N], weight [N,3]); lanes without
+        ground truth get NaN in all three."""
+        return self._sample_t(material_id, wi, u, tint, active, out)
+
+    def pdf_t(self, material_id: torch.Tensor, wi: torch.Tensor, wo: torch.Tensor, active: Optional[torch.Tensor] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``pdf_t`` of each lane's material in one launch -> [N]; NaN = no ground truth for that lane."""
+        return self._pdf_t(material_id, wi, wo, active, out)
+
+
+def ground_truth_for(names) -> dict:
+    """{i: reference_bsdf(idx)} for every ``names[i]`` of the form ``bsdf_<idx>`` or ``bsdf_<idx>_spherical`` (what
+    ``wavefront.scene_from_matpreview_xml`` calls the ``mybsdf idx = N`` balls): the ``ground_truth`` of the array renderers.
+    Other names (the measured materials) are left out; an idx the reference's list does not have raises ``IndexError``."""
+    out = {}
+    for i, name in enumerate(names):
+        m = re.fullmatch(r"bsdf_(\d+)(_spherical)?", str(name))
+        if m:
+            out[i] = reference_bsdf(int(m.group(1)))
+    return out

@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "analytic_host.h"
 #include "bsdfd.h"
 #include "common.h"
 #include "dielectric_dev.h"
@@ -91,13 +92,10 @@ template <class... P, class... A>
 int dielectric_launch(const bsdfd_dielectric* desc, int64_t n, bool pointers_given, void (*kernel)(P...), void* stream,
                       A... args) {
     if (!desc) return bsdfd_fail_(BSDFD_EINVAL, "null descriptor");
-    if (desc->distribution != 0) return bsdfd_fail_(BSDFD_EINVAL, "bsdfd_dielectric.distribution: only 0 (Beckmann) is built");
-    if (!(desc->alpha > 0.0f && std::isfinite(desc->alpha) && desc->eta > 0.0f && std::isfinite(desc->eta)))
-        return bsdfd_fail_(BSDFD_EINVAL, "bsdfd_dielectric: alpha and eta must be positive and finite");
+    if (const char* bad = descriptor_error(*desc)) return bsdfd_fail_(BSDFD_EINVAL, bad);
     if (n < 0) return bsdfd_fail_(BSDFD_EINVAL, "N must be >= 0");
     if (((long long)n + 255) / 256 > 0x7fffffffLL) return bsdfd_fail_(BSDFD_EINVAL, "N too large for one launch");
-    return launch_rows(n, pointers_given ? nullptr : "null pointer", kernel, stream,
-                       DielectricDev{desc->alpha, desc->eta, 1.0f / desc->eta}, args...);
+    return launch_rows(n, pointers_given ? nullptr : "null pointer", kernel, stream, derive(*desc), args...);
 }
 
 }  // namespace

@@ -4,12 +4,13 @@
 // (rendering/bsdf_myresult.py:97-110); entries 0..22 of its material list (rendering/utils/bsdf_dict.py) are principled BSDFs.
 // Four kernels, one row per lane, over the device functions of principled_dev.h: eval, the tail of the plugin's sample()
 // (weight + firefly rule), the model's own importance sampler, and its pdf.  No tables, no handle: the material is a 64-byte
-// descriptor read on the host at the call; what depends on it alone is derived there, once, and passed by value.
+// descriptor read on the host at the call; what depends on it alone is derived there, once (analytic_host.h), and passed by value.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 
+#include "analytic_host.h"
 #include "bsdfd.h"
 #include "common.h"
 #include "measured_dev.h"
@@ -88,54 +89,12 @@ __global__ __launch_bounds__(256) void principled_pdf_kernel(PrincipledDev d, co
     pdf_out[q] = !active || active[q] != 0 ? principled_pdf(d, load3(wi, q), load3(wo, q)) : 0.0f;
 }
 
-// what depends on the material alone, in fp32 (tests/principled_ref.py forms the same values in its dtype)
-PrincipledDev derive(const bsdfd_principled& p) {
-    PrincipledDev d{};
-    const float lum = 0.212671f * p.base_color[0] + 0.715160f * p.base_color[1] + 0.072169f * p.base_color[2];
-    for (int k = 0; k < 3; ++k) {
-        d.base[k] = p.base_color[k];
-        d.sqrt_base[k] = std::sqrt(p.base_color[k]);
-        d.c_tint[k] = lum > 0.0f ? p.base_color[k] / lum : 1.0f;
-    }
-    d.roughness = p.roughness; d.metallic = p.metallic; d.spec_tint = p.spec_tint; d.sheen = p.sheen;
-    d.sheen_tint = p.sheen_tint; d.flatness = p.flatness; d.clearcoat = p.clearcoat;
-    d.eta = p.eta;
-    d.inv_eta = 1.0f / p.eta;
-    const float aspect = std::sqrt(1.0f - 0.9f * p.anisotropic);
-    const float r2 = p.roughness * p.roughness;
-    d.ax = std::fmax(1e-3f, r2 / aspect);
-    d.ay = std::fmax(1e-3f, r2 * aspect);
-    d.inv_ax = 1.0f / d.ax;
-    d.inv_ay = 1.0f / d.ay;
-    d.d_norm = 1.0f / (kPi * d.ax * d.ay);
-    const float a_cc = (1.0f - p.clearcoat_gloss) * 0.1f + p.clearcoat_gloss * 0.001f;
-    d.a2_cc = a_cc * a_cc;
-    d.ln_a2_cc = std::log(d.a2_cc);
-    d.brdf = (1.0f - p.metallic) * (1.0f - p.spec_trans);
-    d.bsdf = (1.0f - p.metallic) * p.spec_trans;
-    const float r0 = (p.eta - 1.0f) / (p.eta + 1.0f);
-    d.r0_eta = r0 * r0;
-    d.p_c = 0.25f * p.clearcoat;
-    d.inv_sum = 1.0f / (1.0f + d.p_c + d.brdf);
-    d.cum_d = d.brdf * d.inv_sum;
-    d.cum_c = (d.brdf + d.p_c) * d.inv_sum;
-    return d;
-}
-
 // the host path of the four launchers: the descriptor's checks, then `kernel` over N rows
 template <class... P, class... A>
 int principled_launch(const bsdfd_principled* desc, int64_t n, bool pointers_given, void (*kernel)(P...), void* stream,
                       A... args) {
     if (!desc) return bsdfd_fail_(BSDFD_EINVAL, "null descriptor");
-    const float unit[] = {desc->base_color[0], desc->base_color[1], desc->base_color[2], desc->roughness, desc->anisotropic,
-                          desc->metallic, desc->spec_trans, desc->spec_tint, desc->sheen, desc->sheen_tint, desc->flatness,
-                          desc->clearcoat, desc->clearcoat_gloss};
-    for (float v : unit)
-        if (!(v >= 0.0f && v <= 1.0f))   // (false for NaN)
-            return bsdfd_fail_(BSDFD_EINVAL, "bsdfd_principled: every parameter but eta must be finite and in [0, 1]");
-    if (!(desc->eta >= 1.0f && std::isfinite(desc->eta))) return bsdfd_fail_(BSDFD_EINVAL, "bsdfd_principled.eta must be finite and >= 1");
-    if (desc->eta == 1.0f && desc->spec_trans != 0.0f)
-        return bsdfd_fail_(BSDFD_EINVAL, "bsdfd_principled: eta == 1 (no interface) needs spec_trans == 0");
+    if (const char* bad = descriptor_error(*desc)) return bsdfd_fail_(BSDFD_EINVAL, bad);
     if (n < 0) return bsdfd_fail_(BSDFD_EINVAL, "N must be >= 0");
     if (((long long)n + 255) / 256 > 0x7fffffffLL) return bsdfd_fail_(BSDFD_EINVAL, "N too large for one launch");
     return launch_rows(n, pointers_given ? nullptr : "null pointer", kernel, stream, derive(*desc), args...);

@@ -11,7 +11,7 @@
 // pdf() and eval() of the same pair are the same bits.  One row per lane, no memory but the row's own, no LDS, no scratch, no
 // lane-dependent branch: every lobe's term is computed and selected under its mask, and sample() forms its four candidate
 // directions, selects one and evaluates pdf / eval of that pair once.  What depends on the material alone is derived on the host
-// (principled.hip: derive()) and arrives by value.  tests/principled_ref.py restates this file statement for statement.
+// (analytic_host.h: derive()) and arrives by value.  tests/principled_ref.py restates this file statement for statement.
 #pragma once
 #include <hip/hip_runtime.h>
 

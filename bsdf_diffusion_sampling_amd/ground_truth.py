@@ -1,5 +1,5 @@
-"""The host layer the native ground-truth evaluators share: ``measured.MeasuredBSDF``, ``measured.MeasuredTable`` and
-``analytic.RoughDielectric``.
+"""The host layer the native ground-truth evaluators share: ``measured.MeasuredBSDF``, ``measured.MeasuredTable``,
+``analytic.RoughDielectric``, ``analytic.Principled`` and ``analytic.AnalyticTable``.
 
 In ``libbsdfd.so`` each is four kernels over rows (eval, the tail of the plugins' sample(), sample, pdf) behind entry points of one
 shape.  That shape is written once here; a class says which entry points are its own, what their leading argument is, how many

@@ -13,7 +13,7 @@ the loop that feeds a shrinking wavefront through the same pieces bounce after b
     primary -> path_begin (org, beta = 1, rad = env for a miss)
     per bounce k:  table.bucket(mat)            ended paths carry the "miss" id and sort behind the materials
                    table.sample_pdf(plan, ...)  flow evaluations for the lanes that carry a material only
-                   measured_table.eval_t(...)   when there is ground truth
+                   ground_truth_table.eval_t(...)   when there is ground truth: a MeasuredTable or an AnalyticTable
                    bounce(k, last = k == max_depth - 1)      [rr_depth: bounce_rr, which also ends paths by roulette]
     resolve -> film tile += mean_spp of rad
 
@@ -51,6 +51,16 @@ roulette ``max_depth=None`` is the reference's unbounded depth: the loop runs un
 ``PathArrayRenderer.DEPTH_CAP`` bounces — a truncation, should it ever be hit (``stats["depth_cap_hit"]``).  This is Mitsuba's
 rule restated; like the evaluator it is parity-unpinned against Mitsuba (neither its random stream nor its images are matched).
 ``integrator_from_matpreview_xml`` reads both settings from a reference scene file.
+
+The ground truth is ``ArrayRenderer``'s: {ball: ``MeasuredBSDF``}, or {ball: ``analytic.Principled`` / ``RoughDielectric``}
+(``analytic.ground_truth_for(names)`` for the ``mybsdf idx = N`` balls of matpreview/disney_bsdf_array2_spherical_*.xml), evaluated
+on the lane-ordered wavefront by ``measured.MeasuredTable`` or ``analytic.AnalyticTable``; with analytic ground truth on every ball
+``ball_albedo`` gives each ball the colour its scene file gives it (``wavefront.albedos_from_matpreview_xml``).  Two limits: under
+occlusion ``bounce`` keeps dropping a BSDF sample with ``wo.z <= 0`` ("blocked by the ball itself") — nothing is transmitted
+through the balls; the reference's plugin answers for ``cos_theta_i > 0`` only (rendering/bsdf_myresult.py:63), so a vertex inside
+would have no sampler — and without occlusion (``max_depth=1``) the estimator keeps looking the environment up along such a
+direction, which the analytic ``f |cos|`` of the transmission lobe now weights.  What the table costs a pass:
+profiles/analytic_table.json (tools/analytic_table_bench.py).
 
 There are no area or spot emitters.  There is no CPU fallback.
 """

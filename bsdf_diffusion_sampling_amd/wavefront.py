@@ -287,6 +287,23 @@ def parse_matpreview_xml(path: str):
     return out
 
 
+def albedos_from_matpreview_xml(path: str):
+    """The ``albedo`` vector of every <shape> that carries a <bsdf type="mybsdf">, in the order of ``parse_matpreview_xml``; a
+    shape without one gives (1, 1, 1), the plugin's default.  ``ball_albedo`` of the array renderers."""
+    import xml.etree.ElementTree as ET
+    out = []
+    for shape in ET.parse(path).getroot().iter("shape"):
+        bsdf = next((b for b in shape.findall("bsdf") if b.get("type") == "mybsdf"), None)
+        if bsdf is None:
+            continue
+        vec = next((c for c in bsdf if c.tag in ("vector", "rgb") and c.get("name") == "albedo"), None)
+        rgb = (1.0, 1.0, 1.0) if vec is None else tuple(float(v) for v in vec.get("value").replace(",", " ").split())
+        if len(rgb) != 3:
+            raise ValueError(f"{path}: albedo {vec.get('value')!r} is not an RGB triple")
+        out.append(rgb)
+    return out
+
+
 def scene_from_matpreview_xml(path: str, width: int = 683, height: int = 512):
     """(material names, camera, centres, radii) for ``ArrayRenderer`` from a reference scene file; ball layout and
     camera direction as ``array0_scene`` (spheres of radius 0.33 on one floor, same ground-plane positions)."""
@@ -312,16 +329,34 @@ class ArrayRenderer(WavefrontRenderer):
     balls that have an RGL tensor file; the others shade with the proxy ``f cos = albedo * pdf``.  Their ``eval()`` is ONE launch
     on the lane-ordered wavefront (``measured.MeasuredTable``); ``fused_ground_truth=False`` keeps the earlier form — gathered
     copies, two ``MeasuredBSDF.eval_t`` launches per material, a scatter — for A/B runs: the same film bit for bit.
+    The values may instead be analytic (``analytic.Principled`` / ``RoughDielectric``: ``analytic.ground_truth_for(names)`` for the
+    ``bsdf_<idx>`` balls) — all of one family, a mixture is refused; the lane-ordered evaluator is then an
+    ``analytic.AnalyticTable``.  Either table is ``self.ground_truth_table`` (and ``self.measured_table``, its first name).
+    ``ball_albedo``: one RGB triple per ball, the per-ball ``albedo`` of the reference's array scenes
+    (``albedos_from_matpreview_xml``), which the analytic table multiplies into the scene-wide ``albedo`` lane by lane; it needs
+    analytic ground truth on every ball (the proxy only knows the scene-wide ``albedo``) and ``fused_ground_truth=True``.
     The Philox counter of a path is its global index in the film — primary's, and the sampler's too (``rng="lane"`` with the
     tile's first path as ``offset``) — so a tile is the rows of the whole film bit for bit, like the single-ball renderer's."""
 
     def __init__(self, table, centers, radii, camera: Optional[Camera] = None, env: Optional[torch.Tensor] = None,
                  floor: bool = True, checker=(0.4, 0.2, 2.0), albedo=(1.0, 1.0, 1.0), ground_truth=None,
-                 device: Optional[torch.device] = None, fused_ground_truth: bool = True):
+                 device: Optional[torch.device] = None, fused_ground_truth: bool = True, ball_albedo=None):
         if len(centers) != len(table) or len(radii) != len(table):
             raise ValueError("one ball per material of the table")
         if not 1 <= len(table) <= 32:
             raise ValueError("1..32 balls")
+        from .analytic import FullSphereGroundTruth
+        ground_truth = dict(ground_truth or {})
+        analytic = any(isinstance(g, FullSphereGroundTruth) for g in ground_truth.values())
+        if analytic and not all(isinstance(g, FullSphereGroundTruth) for g in ground_truth.values()):
+            raise ValueError("ground_truth: MeasuredBSDF objects or analytic ones (Principled, RoughDielectric), not a mixture")
+        if ball_albedo is not None:
+            if not analytic or any(m not in ground_truth for m in range(len(table))):
+                raise ValueError("ball_albedo needs analytic ground truth on every ball: the proxy only knows the scene-wide albedo")
+            if not fused_ground_truth:
+                raise ValueError("ball_albedo needs fused_ground_truth=True: it is a factor of the AnalyticTable")
+            if len(ball_albedo) != len(table):
+                raise ValueError("ball_albedo: one RGB triple per ball")
 
         class _Tint:  # what WavefrontRenderer reads from a plugin
             pass
@@ -331,13 +366,20 @@ class ArrayRenderer(WavefrontRenderer):
         super().__init__(tint, camera, env, sphere_center=centers[0], sphere_radius=radii[0], device=device,
                          use_ground_truth=False)
         self.table = table
-        self.ground_truth = dict(ground_truth or {})
+        self.ground_truth = ground_truth
         self.use_ground_truth = bool(self.ground_truth)   # f arrays are then filled for every path
         self.fused_ground_truth = bool(fused_ground_truth)
-        self.measured_table = None
+        self.ground_truth_table = None                    # the lane-ordered evaluator: a MeasuredTable or an AnalyticTable
         if self.use_ground_truth and self.fused_ground_truth:
-            from .measured import MeasuredTable
-            self.measured_table = MeasuredTable([self.ground_truth.get(m) for m in range(len(table))])
+            entries = [self.ground_truth.get(m) for m in range(len(table))]
+            if analytic:
+                from .analytic import AnalyticTable
+                with torch.cuda.device(self.device):
+                    self.ground_truth_table = AnalyticTable(entries, albedo=ball_albedo)
+            else:
+                from .measured import MeasuredTable
+                self.ground_truth_table = MeasuredTable(entries)
+        self.measured_table = self.ground_truth_table     # (the name from when the measured family was the only one)
         self.needs_material_ids = True
         sc = self.scene
         sc.n_extra_spheres = len(centers) - 1

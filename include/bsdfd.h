@@ -50,7 +50,10 @@ extern "C" {
  *      bsdfd_dielectric_eval(), bsdfd_dielectric_sample_weight(), bsdfd_dielectric_sample() and bsdfd_dielectric_pdf(), which
  *      take a struct of their own, bsdfd_dielectric: the rough-dielectric ground truth of the full-sphere plugin;
  *      bsdfd_principled_eval(), bsdfd_principled_sample_weight(), bsdfd_principled_sample() and bsdfd_principled_pdf(), which
- *      take a struct of their own, bsdfd_principled: the principled ground truth of the full-sphere plugin. */
+ *      take a struct of their own, bsdfd_principled: the principled ground truth of the full-sphere plugin;
+ *      bsdfd_analytic_table_create(), bsdfd_analytic_table_destroy(), bsdfd_analytic_eval_table(),
+ *      bsdfd_analytic_sample_weight_table(), bsdfd_analytic_sample_table() and bsdfd_analytic_pdf_table(), which take a struct
+ *      of their own, bsdfd_analytic_entry: both analytic models for a mixed-material wavefront in one launch. */
 #define BSDFD_ABI_VERSION 8
 
 #define BSDFD_OK 0
@@ -503,6 +506,51 @@ int bsdfd_principled_sample(const bsdfd_principled* desc, const float* wi, const
                             const float* tint, float* wo_out, float* pdf_out, float* weight_out, void* hip_stream);
 int bsdfd_principled_pdf(const bsdfd_principled* desc, const float* wi, const float* wo, const unsigned char* active, int64_t N,
                          float* pdf_out, void* hip_stream);
+
+/* ---- the two analytic models for a MIXED-material wavefront (csrc/analytic_table.hip) ---------------------------------------
+ * One launch serves every material, where the calls above take one launch per material on gathered slices: the analytic
+ * counterpart of bsdfd_measured_table.  The rows stay in lane order with their material ids, as bsdfd_wf_primary writes them.
+ * entries[m] serves material id m (zero-initialise it; it may grow at the end):
+ *   kind    BSDFD_ANALYTIC_NONE ("no ground truth for this material"), _PRINCIPLED or _DIELECTRIC: which member of desc is read
+ *   albedo  the material's own RGB factor, finite and >= 0 (the `albedo` every `mybsdf` ball of the reference's array scenes
+ *           carries: rendering/bsdf_myresult.py:97,112): a row's effective tint is tint[c] * albedo[m][c], one fp32 product,
+ *           used exactly where the single-material calls use tint.  (1, 1, 1) leaves the call's tint as it is.
+ * 1 <= n_materials <= 65536, at least one entry with ground truth; a descriptor the single-material call would refuse, a kind
+ * that is none of the three and a bad albedo are BSDFD_EINVAL, the message naming the entry.  What depends on a material alone is
+ * derived here, once, by the code the single-material calls run per call, and copied to the current device; the entries are not
+ * needed afterwards. */
+#define BSDFD_ANALYTIC_NONE 0
+#define BSDFD_ANALYTIC_PRINCIPLED 1
+#define BSDFD_ANALYTIC_DIELECTRIC 2
+typedef struct {
+    int32_t kind;
+    float albedo[3];
+    union {
+        bsdfd_principled principled;
+        bsdfd_dielectric dielectric;
+    } desc;
+} bsdfd_analytic_entry;
+typedef struct bsdfd_analytic_table_ctx* bsdfd_analytic_table;
+int  bsdfd_analytic_table_create(const bsdfd_analytic_entry* entries, int32_t n_materials, bsdfd_analytic_table* out);
+void bsdfd_analytic_table_destroy(bsdfd_analytic_table t);
+/* The four calls of a whole wavefront in LANE order, one launch each; argument lists as the bsdfd_measured_*_table calls (u is
+ * [N,3], as for the single-material analytic samplers).  Row i with 0 <= material_id[i] < n_materials (the full 64-bit value)
+ * and an entry with ground truth gets what the single-material call of that entry writes for the row with the effective tint,
+ * bit for bit (zeros where active[i] == 0 included); eval_table writes f_o from wo and, when wl and f_l are given (both or
+ * neither), f_l from wl in the same launch.  Every other row (floor, miss, NONE slot, id out of range or negative) gets a quiet
+ * NaN in every output, whatever its mask says — the "use the proxy" value bsdfd_wf_shade reads — except that sample_weight_table
+ * passes pdf_out = pdf_sa through.  Stream-ordered, no allocation, no synchronisation; N = 0 is a no-op. */
+int  bsdfd_analytic_eval_table(bsdfd_analytic_table t, const int64_t* material_id, const float* wi, const float* wo,
+                               const float* wl, int64_t N, const float* tint, float* f_o, float* f_l, void* hip_stream);
+int  bsdfd_analytic_sample_weight_table(bsdfd_analytic_table t, const int64_t* material_id, const float* wi,
+                                        const float* wo, const float* pdf_sa, const unsigned char* active, int64_t N,
+                                        const float* tint, float firefly_threshold, float* weight_out, float* pdf_out,
+                                        void* hip_stream);
+int  bsdfd_analytic_sample_table(bsdfd_analytic_table t, const int64_t* material_id, const float* wi, const float* u,
+                                 const unsigned char* active, int64_t N, const float* tint, float* wo_out, float* pdf_out,
+                                 float* weight_out, void* hip_stream);
+int  bsdfd_analytic_pdf_table(bsdfd_analytic_table t, const int64_t* material_id, const float* wi, const float* wo,
+                              const unsigned char* active, int64_t N, float* pdf_out, void* hip_stream);
 
 /* ---- wavefront harness ------------------------------------
  * The reference renders through Mitsuba 3 (rendering/brdf_measured_disk.py:146-155: passes of

@@ -1,4 +1,6 @@
-"""Render the 12-ball array scene (the shape of matpreview/disney_bsdf_array0_envmap.xml) with a MaterialTable."""
+"""Render the 12-ball array scene (the shape of matpreview/disney_bsdf_array0_envmap.xml) with a MaterialTable; with --scene, the
+materials, layout and camera of a reference scene file, and with --analytic its bsdf_N balls under their analytic ground truth and
+their own albedo."""
 import sys, os, time, json, argparse
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -29,7 +31,15 @@ ap.add_argument("--no-env", action="store_true", help="with lights: a black envi
 ap.add_argument("--env-sampling", choices=("cosine", "importance"), default="cosine",
                 help="the light strategy towards the environment: a cosine-weighted draw (default), or in proportion to the map's "
                      "luminance, as the reference's envmap emitter draws (PathArrayRenderer)")
+ap.add_argument("--scene", default=None, metavar="scene.xml",
+                help="materials, ball layout and camera from a reference scene file (wavefront.scene_from_matpreview_xml) in place "
+                     "of the array0 scene; `mybsdf idx = N` balls use the shipped spherical nets bsdf_N")
+ap.add_argument("--analytic", action="store_true",
+                help="with --scene: shade the bsdf_N balls with their analytic ground truth (analytic.ground_truth_for) and give "
+                     "every ball the albedo vector the file gives it (wavefront.albedos_from_matpreview_xml)")
 a = ap.parse_args()
+if a.analytic and not a.scene:
+    ap.error("--analytic needs --scene")
 unbounded = a.max_depth == -1
 if a.integrator_from:
     from bsdf_diffusion_sampling_amd.pathtrace import integrator_from_matpreview_xml
@@ -50,35 +60,46 @@ if a.lights_from or a.point_light:
         lights.append(PointLight(tuple(float(v) for v in pos.split(",")), rgb[0] if len(rgb) == 1 else tuple(rgb)))
 if a.no_env and not lights:
     ap.error("--no-env needs --point-light or --lights-from")
-cam, centers, radii = WF.array0_scene(a.width, a.height)
-stems = [m + "_" + a.domain for m in WF.ARRAY0_MATERIALS]
+if a.scene:
+    materials, cam, centers, radii = WF.scene_from_matpreview_xml(a.scene, a.width, a.height)
+    stems = [m + "_spherical" if m.startswith("bsdf_") else m + "_" + a.domain for m in materials]
+else:
+    materials = WF.ARRAY0_MATERIALS
+    cam, centers, radii = WF.array0_scene(a.width, a.height)
+    stems = [m + "_" + a.domain for m in materials]
 tab = MaterialTable(stems)
-gts = {}
-if a.measured_dir:
+gts, extra = {}, {}
+if a.analytic:
+    from bsdf_diffusion_sampling_amd.analytic import ground_truth_for
+    gts = ground_truth_for(materials)
+    if len(gts) == len(materials):      # (a per-ball albedo needs ground truth on every ball)
+        extra["ball_albedo"] = WF.albedos_from_matpreview_xml(a.scene)
+elif a.measured_dir:
     from bsdf_diffusion_sampling_amd.measured import MeasuredBSDF, find_measured_file
-    for i, m in enumerate(WF.ARRAY0_MATERIALS):
+    for i, m in enumerate(materials):
         p = find_measured_file(m, a.measured_dir)
         if p: gts[i] = MeasuredBSDF(p)
 if a.env_sampling == "importance" and a.no_env:
     ap.error("--env-sampling importance needs an emitting environment: drop --no-env")
 if a.max_depth is None and not unbounded and a.rr_depth is None and a.occlusion is None and not lights and a.env_sampling == "cosine":
-    r = WF.ArrayRenderer(tab, centers, radii, camera=cam, ground_truth=gts)
+    r = WF.ArrayRenderer(tab, centers, radii, camera=cam, ground_truth=gts, **extra)
 else:
     from bsdf_diffusion_sampling_amd.pathtrace import PathArrayRenderer
-    r = PathArrayRenderer(tab, centers, radii, camera=cam, ground_truth=gts,
+    r = PathArrayRenderer(tab, centers, radii, camera=cam, ground_truth=gts, **extra,
                           max_depth=None if unbounded else 1 if a.max_depth is None else a.max_depth, rr_depth=a.rr_depth,
                           occlusion=None if a.occlusion is None else bool(a.occlusion), lights=lights, env_sampling=a.env_sampling,
                           env=None if a.no_env or not lights else WF.make_sky())
 r.render(2, a.spp, seed=9); torch.cuda.synchronize()
 t0 = time.perf_counter(); img = r.render(a.passes, a.spp, seed=0); torch.cuda.synchronize(); dt = time.perf_counter() - t0
-b = r.primary(0, a.height, 1, 0, 0); mat = b["mat"].cpu().numpy()
+b = r.primary(0, a.height, 1, 0, 0); mat = b["mat"].cpu().numpy(); nb = len(tab)
 paths = a.width * a.height * a.spp * a.passes
-print(json.dumps({"workload": f"array0_{a.width}x{a.height}_{a.passes}x{a.spp}spp_{a.domain}", "materials": len(tab),
+print(json.dumps({"workload": f"{os.path.splitext(os.path.basename(a.scene))[0] if a.scene else 'array0'}_{a.width}x{a.height}_{a.passes}x{a.spp}spp_{a.domain}", "materials": len(tab),
                   "max_depth": getattr(r, "max_depth", 1), "occlusion": getattr(r, "occlusion", False), "point_lights": len(lights),
                   "env_sampling": a.env_sampling, "rr_depth": getattr(r, "rr_depth", None),
                   "depth": getattr(r, "stats", {}).get("depth"), "depth_cap_hit": getattr(r, "stats", {}).get("depth_cap_hit"),
                   "lanes_per_bounce": getattr(r, "stats", {}).get("lanes_per_bounce"),
                   "ground_truth_materials": len(gts), "seconds": dt, "passes_per_s": a.passes / dt, "Mpaths_per_s": paths / dt / 1e6,
-                  "ball_fraction": float((mat < 12).mean()), "floor_fraction": float((mat == 12).mean()), "miss_fraction": float((mat == 13).mean())}))
+                  "ball_albedo": "ball_albedo" in extra,
+                  "ball_fraction": float((mat < nb).mean()), "floor_fraction": float((mat == nb).mean()), "miss_fraction": float((mat == nb + 1).mean())}))
 img = img.cpu().numpy(); os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
 np.save(a.out + ".npy", img); write_png(a.out + ".png", tonemap(img))
