@@ -61,6 +61,8 @@ EXPORTS = (
     "bsdfd_principled_eval", "bsdfd_principled_sample_weight", "bsdfd_principled_sample", "bsdfd_principled_pdf",
     "bsdfd_analytic_table_create", "bsdfd_analytic_table_destroy", "bsdfd_analytic_eval_table",
     "bsdfd_analytic_sample_weight_table", "bsdfd_analytic_sample_table", "bsdfd_analytic_pdf_table",
+    "bsdfd_bucket_rows", "bsdfd_wf_bounce_rows", "bsdfd_wf_sample_emitter_rows", "bsdfd_wf_sample_env_rows",
+    "bsdfd_measured_eval_table_rows", "bsdfd_analytic_eval_table_rows",
     "bsdfd_set_profiling", "bsdfd_profile_read", "bsdfd_profile_read_op", "bsdfd_profile_clock_mhz", "bsdfd_last_kernel_ms", "bsdfd_shader_clock_mhz",
     "bsdfd_last_error", "bsdfd_version", "bsdfd_abi_version",
 )
@@ -496,6 +498,12 @@ def lib():
     L.bsdfd_bucket_workspace_bytes.argtypes = [i64, i32]
     L.bsdfd_bucket_workspace_bytes.restype = i64
     L.bsdfd_bucket_by_material.argtypes = [fp, i64, i32, fp, fp, fp, i64, vp]
+    # the list forms: their siblings' arguments with (rows, n_rows) in front of the stream; the sort takes the list behind the ids
+    for name in ("bsdfd_wf_bounce", "bsdfd_wf_sample_emitter", "bsdfd_wf_sample_env", "bsdfd_measured_eval_table",
+                 "bsdfd_analytic_eval_table"):
+        sibling = getattr(L, "bsdfd_wf_bounce_rr" if name == "bsdfd_wf_bounce" else name).argtypes
+        getattr(L, name + "_rows").argtypes = sibling[:-1] + [fp, i64, vp]
+    L.bsdfd_bucket_rows.argtypes = L.bsdfd_bucket_by_material.argtypes[:1] + [fp] + L.bsdfd_bucket_by_material.argtypes[1:]
     L.bsdfd_bucket_wide_workspace_bytes.argtypes = [i64, i32]
     L.bsdfd_bucket_wide_workspace_bytes.restype = i64
     L.bsdfd_bucket_by_material_wide.argtypes = [fp, i64, i32, fp, fp, fp, i64, vp]

@@ -33,7 +33,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
-from .ground_truth import GroundTruth, RowKernels, check, launch, tint3
+from .ground_truth import GroundTruth, RowKernels
 
 # Mitsuba's named indices of refraction, as far as the reference's list uses them
 IOR = {"bk7": 1.5046, "air": 1.000277, "vacuum": 1.0}
@@ -262,19 +262,12 @@ class AnalyticTable(RowKernels):
         return self._t
 
     def eval_t(self, material_id: torch.Tensor, wi: torch.Tensor, wo: torch.Tensor, wl: Optional[torch.Tensor] = None,
-               tint=None, out_o: Optional[torch.Tensor] = None, out_l: Optional[torch.Tensor] = None):
+               tint=None, out_o: Optional[torch.Tensor] = None, out_l: Optional[torch.Tensor] = None,
+               rows: Optional[torch.Tensor] = None):
         """f(wi, wo) |cos theta_o| * tint * albedo of each lane's material -> f_o [N,3]; with ``wl`` also f(wi, wl) |cos theta_l|
-        -> (f_o, f_l), both evaluations in the same launch.  NaN rows = no ground truth for that lane."""
-        if out_l is not None and wl is None:
-            raise ValueError("AnalyticTable.eval_t: out_l without wl")
-        given = (("wi", wi), ("wo", wo), ("wl", wl), ("out_o", out_o), ("out_l", out_l))
-        check("AnalyticTable.eval_t", [(k, t, 3) for k, t in given if t is not None], material_id)
-        if out_o is None:
-            out_o = torch.empty_like(wi)
-        if wl is not None and out_l is None:
-            out_l = torch.empty_like(wi)
-        launch(self.ENTRY["eval"], wi.device, self._t, material_id, wi, wo, wl, wi.shape[0], tint3(tint), out_o, out_l)
-        return out_o if wl is None else (out_o, out_l)
+        -> (f_o, f_l), both evaluations in the same launch.  NaN rows = no ground truth for that lane.  ``rows`` (int64 [n_rows]):
+        only the listed rows are evaluated and written (``bsdfd_analytic_eval_table_rows``); every other row keeps what it held."""
+        return self._eval_table(material_id, wi, wo, wl, tint, out_o, out_l, rows)
 
     def sample_weight(self, material_id: torch.Tensor, wi: torch.Tensor, wo: torch.Tensor, pdf_sa: torch.Tensor, *, tint=None,
                       firefly_threshold: Optional[float] = None, active: Optional[torch.Tensor] = None):

@@ -99,15 +99,11 @@ __device__ __forceinline__ void with_material(const AnalyticRec* __restrict__ ta
     }
 }
 
-// The four kernels: the rows of principled.hip / dielectric.hip over either model; a row without ground truth gets NaN in
-// every output (the weight kernel passes its pdf through), whatever its mask says.
-__global__ __launch_bounds__(256) void analytic_eval_table_kernel(const AnalyticRec* __restrict__ table, int n_materials,
-                                                                  const long long* __restrict__ material_id,
-                                                                  const float* __restrict__ wi, const float* __restrict__ wo,
-                                                                  const float* __restrict__ wl, long long n, Tint tint,
-                                                                  float* __restrict__ f_o, float* __restrict__ f_l) {
-    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= n) return;
+// eval() of row q: f_o = f(wi, wo) |cos| * tint * albedo and, with wl, f_l likewise
+__device__ __forceinline__ void eval_table_row(const AnalyticRec* __restrict__ table, int n_materials,
+                                               const long long* __restrict__ material_id, const float* __restrict__ wi,
+                                               const float* __restrict__ wo, const float* __restrict__ wl, long long q, Tint tint,
+                                               float* __restrict__ f_o, float* __restrict__ f_l) {
     const float nan = quiet_nan();
     with_material(table, n_materials, material_id[q], tint,
                   [&](const auto& model, Tint t) {
@@ -120,6 +116,33 @@ __global__ __launch_bounds__(256) void analytic_eval_table_kernel(const Analytic
                       }
                   },
                   [&] { store3(f_o, q, nan, nan, nan); if (f_l) store3(f_l, q, nan, nan, nan); });
+}
+
+// The four kernels: the rows of principled.hip / dielectric.hip over either model; a row without ground truth gets NaN in
+// every output (the weight kernel passes its pdf through), whatever its mask says.
+__global__ __launch_bounds__(256) void analytic_eval_table_kernel(const AnalyticRec* __restrict__ table, int n_materials,
+                                                                  const long long* __restrict__ material_id,
+                                                                  const float* __restrict__ wi, const float* __restrict__ wo,
+                                                                  const float* __restrict__ wl, long long n, Tint tint,
+                                                                  float* __restrict__ f_o, float* __restrict__ f_l) {
+    const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= n) return;
+    eval_table_row(table, n_materials, material_id, wi, wo, wl, q, tint, f_o, f_l);
+}
+
+// ... over a row list: thread t serves row rows[t] of the N-row arrays and writes f_o / f_l there only.  Consecutive entries of one
+// bucket of a sorted list share their id, so the wave-uniform path serves them as it serves image-coherent lanes.
+__global__ __launch_bounds__(256) void analytic_eval_table_rows_kernel(const AnalyticRec* __restrict__ table, int n_materials,
+                                                                       const long long* __restrict__ material_id,
+                                                                       const float* __restrict__ wi, const float* __restrict__ wo,
+                                                                       const float* __restrict__ wl, long long n, Tint tint,
+                                                                       float* __restrict__ f_o, float* __restrict__ f_l,
+                                                                       const long long* __restrict__ rows, long long n_rows) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_rows) return;
+    const long long q = rows[t];
+    if ((unsigned long long)q >= (unsigned long long)n) return;   // (a contract violation: skipped, not followed)
+    eval_table_row(table, n_materials, material_id, wi, wo, wl, q, tint, f_o, f_l);
 }
 
 // the tail of the full-sphere plugin's sample() (rendering/bsdf_myresult.py:97-104): value = f * tint / pdf_sa where
@@ -280,6 +303,18 @@ int bsdfd_analytic_eval_table(bsdfd_analytic_table t, const int64_t* material_id
                       : !material_id || !wi || !wo || !f_o ? "null pointer" : nullptr;
     return table_launch(t, n, material_id, bad, analytic_eval_table_kernel, stream, wi, wo, wl, (long long)n, TintArg{tint},
                         f_o, f_l);
+}
+
+int bsdfd_analytic_eval_table_rows(bsdfd_analytic_table t, const int64_t* material_id, const float* wi, const float* wo,
+                                   const float* wl, int64_t n, const float* tint, float* f_o, float* f_l, const int64_t* rows,
+                                   int64_t n_rows, void* stream) {
+    if (int rc = table_launch_checks(t, n)) return rc;
+    if (n_rows < 0 || n_rows > n) return bsdfd_fail_(BSDFD_EINVAL, "n_rows must be in [0, N]");
+    const char* bad = (wl == nullptr) != (f_l == nullptr) ? "wl and f_l are both NULL or both given"
+                      : !material_id || !wi || !wo || !f_o || !rows ? "null pointer" : nullptr;
+    return launch_rows(n_rows, bad, analytic_eval_table_rows_kernel, stream, static_cast<const AnalyticRec*>(t->dev),
+                       (int)t->n_materials, reinterpret_cast<const long long*>(material_id), wi, wo, wl, (long long)n, TintArg{tint},
+                       f_o, f_l, reinterpret_cast<const long long*>(rows), (long long)n_rows);
 }
 
 int bsdfd_analytic_sample_weight_table(bsdfd_analytic_table t, const int64_t* material_id, const float* wi,

@@ -44,10 +44,26 @@ struct Step {
     long long n;
 };
 
-// this thread's lane and its material id; false beyond the wavefront and for a path that has ended
-__device__ __forceinline__ bool live_lane(const Scene& sc, long long n, const long long* __restrict__ mat, long long& p, long long& m) {
+// A live-lane list: the kernels' list forms run over rows[0 .. n) instead of over every lane of the wavefront.  The entries are
+// distinct lanes in [0, N); a lane that is not listed keeps every byte of every array.
+struct Rows {
+    const long long* rows;
+    long long n;
+};
+
+// this thread's lane and its material id; false beyond the wavefront and for a path that has ended.  LIST: the lane is the
+// thread's entry of `rows`, false beyond the list.  (The full-width instantiations never read `rows`: it folds away.)
+template <bool LIST = false>
+__device__ __forceinline__ bool live_lane(const Scene& sc, long long n, const long long* __restrict__ mat, long long& p, long long& m,
+                                          const Rows& rows = Rows{}) {
     p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return false;
+    if constexpr (LIST) {
+        if (p >= rows.n) return false;
+        p = rows.rows[p];
+        if ((unsigned long long)p >= (unsigned long long)n) return false;   // (a contract violation: skipped, not followed)
+    } else {
+        if (p >= n) return false;
+    }
     m = mat[p];
     return m >= 0 && m <= sc.n_sph;
 }
@@ -89,12 +105,14 @@ __device__ __forceinline__ void store_local_direction(float* __restrict__ wl, V3
 // The variate is a Philox draw of the lane's own (counter word 3 = "Roul" + depth), made only where the decision is.  A path
 // that is killed ends exactly as one that escaped; `rad` is formed and stored before, and where a survivor goes does not depend on
 // the roulette: only the `thr` that continue_path multiplies into beta does.
-template <int M, bool RR = false>
+//
+// LIST: the lanes are those of `rows` (the list forms of the six kernels); nothing else differs.
+template <int M, bool RR = false, bool LIST = false>
 __device__ __forceinline__ void bounce_vertex(const Scene& sc, const float* __restrict__ env, const EnvDist& e, int n_e, int has_env,
                                               const Step& st, const PathState& ps, const SamplerAnswer& sa,
-                                              const EmitterSample& es, int rr_depth = 0) {
+                                              const EmitterSample& es, int rr_depth = 0, const Rows& rows = Rows{}) {
     long long p, m;
-    if (!live_lane(sc, st.n, ps.mat, p, m)) return;
+    if (!live_lane<LIST>(sc, st.n, ps.mat, p, m, rows)) return;
     const int occlusion = st.occlusion;
     const float inv_pi = 0.31830988618379067154f;
     // probability with which the one emitter sample went to the environment
@@ -214,6 +232,14 @@ __device__ __forceinline__ void bounce_vertex(const Scene& sc, const float* __re
 inline Step make_step(int32_t bounce, int32_t last, int32_t occlusion, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N) {
     return Step{(int)bounce, last ? 1 : 0, occlusion ? 1 : 0, (unsigned long long)seed, (unsigned long long)pass,
                 (unsigned long long)path_offset, (long long)N};
+}
+
+// the list of a list form over arrays of N rows: at most N entries, a pointer where there are any
+inline int to_rows(const int64_t* rows, int64_t n_rows, int64_t N, Rows& out) {
+    if (n_rows < 0 || n_rows > N) return bsdfd_fail_(BSDFD_EINVAL, "n_rows must be in [0, N]");
+    if (n_rows > 0 && !rows) return bsdfd_fail_(BSDFD_EINVAL, "null rows pointer");
+    out = Rows{reinterpret_cast<const long long*>(rows), (long long)n_rows};
+    return BSDFD_OK;
 }
 
 // the emitter counts of a bsdfd_wf_lights: n point lights, n_e emitters with the environment

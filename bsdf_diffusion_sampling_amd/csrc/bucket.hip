@@ -12,6 +12,10 @@
 //             (material, block) run of perm with coalesced stores.  `perm` gathers rows into bucket order (torch.argsort
 //             semantics: bucketed[k] = rows[perm[k]]).
 // 16 Mi ids: 128 MB read twice + 128 MB written.
+//
+// bsdfd_bucket_rows is the same sort over a row list (the LIST instantiations): row r of the list has the id ids[rows[r]] and perm
+// receives rows[r], so perm holds lane numbers, stable in list order.  Ids outside [0, n_materials) are left out, as everywhere
+// here: a path tracer that keeps its "ended" id out of range gets its next live-lane list as the front of perm.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -34,14 +38,20 @@ constexpr int BK_BASE_STRIDE = BK_THREADS + 2;
 
 // Stage the block's ids into LDS with coalesced loads (u8; 255 = out of range), then count:
 // cnt[m][t] = number of rows with id m among thread t's 16 consecutive rows (each thread owns its column).
-__device__ __forceinline__ void stage_and_count(const long long* __restrict__ ids, long long n, long long row0, int M,
-                                                unsigned char* lid, unsigned char* cnt) {
+// LIST: the rows are the n entries of `rows` (lane numbers), a row's id is ids[rows[r]].
+template <bool LIST>
+__device__ __forceinline__ void stage_and_count(const long long* __restrict__ ids, const long long* __restrict__ rows, long long n,
+                                                long long row0, int M, unsigned char* lid, unsigned char* cnt) {
     for (int i = threadIdx.x; i < M * BK_CNT_STRIDE / 4; i += BK_THREADS) reinterpret_cast<unsigned*>(cnt)[i] = 0u;
 #pragma unroll
     for (int k = 0; k < BK_ROWS; ++k) {
         const int j = k * BK_THREADS + threadIdx.x;
         const long long r = row0 + j;
-        long long m = r < n ? ids[r] : -1;
+        long long m = -1;
+        if (r < n) {
+            if constexpr (LIST) m = ids[rows[r]];
+            else m = ids[r];
+        }
         lid[j] = (m >= 0 && m < M) ? (unsigned char)m : (unsigned char)255;
     }
     __syncthreads();
@@ -53,12 +63,13 @@ __device__ __forceinline__ void stage_and_count(const long long* __restrict__ id
     __syncthreads();
 }
 
-__global__ __launch_bounds__(BK_THREADS) void bucket_count_kernel(const long long* __restrict__ ids, long long n, int M,
-                                                                  long long nblocks, int* __restrict__ blockhist) {
+template <bool LIST>
+__global__ __launch_bounds__(BK_THREADS) void bucket_count_kernel(const long long* __restrict__ ids, const long long* __restrict__ rows,
+                                                                  long long n, int M, long long nblocks, int* __restrict__ blockhist) {
     extern __shared__ unsigned char smem[];
     unsigned char* lid = smem;
     unsigned char* cnt = smem + BK_CHUNK;
-    stage_and_count(ids, n, (long long)blockIdx.x * BK_CHUNK, M, lid, cnt);
+    stage_and_count<LIST>(ids, rows, n, (long long)blockIdx.x * BK_CHUNK, M, lid, cnt);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int m = wave; m < M; m += BK_THREADS / 64) {  // four u8 counters per word, each <= 16
         const unsigned v = *reinterpret_cast<const unsigned*>(cnt + m * BK_CNT_STRIDE + lane * 4);
@@ -69,8 +80,10 @@ __global__ __launch_bounds__(BK_THREADS) void bucket_count_kernel(const long lon
     }
 }
 
-__global__ __launch_bounds__(BK_THREADS) void bucket_scatter_kernel(const long long* __restrict__ ids, long long n, int M,
-                                                                    long long nblocks, const long long* __restrict__ offs,
+template <bool LIST>
+__global__ __launch_bounds__(BK_THREADS) void bucket_scatter_kernel(const long long* __restrict__ ids, const long long* __restrict__ rows,
+                                                                    long long n, int M, long long nblocks,
+                                                                    const long long* __restrict__ offs,
                                                                     const long long* __restrict__ counts,
                                                                     long long* __restrict__ perm) {
     extern __shared__ unsigned char smem[];
@@ -82,7 +95,7 @@ __global__ __launch_bounds__(BK_THREADS) void bucket_scatter_kernel(const long l
     long long* gbase = reinterpret_cast<long long*>(sbin + BK_CHUNK);             // [M] first slot of (material, block)
     int* lstart = reinterpret_cast<int*>(gbase + BK_MAX_MATERIALS);               // [M+1] local start of a material
     const long long row0 = (long long)blockIdx.x * BK_CHUNK;
-    stage_and_count(ids, n, row0, M, lid, cnt);
+    stage_and_count<LIST>(ids, rows, n, row0, M, lid, cnt);
     // exclusive scan of every material's column counts over the 256 threads: one wave per material at a
     // time, a lane takes 4 adjacent columns (one LDS word) and the lanes' sums are scanned with shuffles
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -134,7 +147,8 @@ __global__ __launch_bounds__(BK_THREADS) void bucket_scatter_kernel(const long l
     const int total = lstart[M];
     for (int j = threadIdx.x; j < total; j += BK_THREADS) {
         const int m = sbin[j];
-        perm[gbase[m] + (j - lstart[m])] = row0 + srow[j];
+        if constexpr (LIST) perm[gbase[m] + (j - lstart[m])] = rows[row0 + srow[j]];   // (the list's entry: a lane number)
+        else perm[gbase[m] + (j - lstart[m])] = row0 + srow[j];
     }
 }
 
@@ -164,6 +178,52 @@ __global__ __launch_bounds__(256) void scatter_results_kernel(const long long* _
     if (pdf_b) pdf[d] = pdf_b[i];
     if (pdf2_b) pdf2[d] = pdf2_b[i];
 }
+
+namespace {
+
+// the sort over all n rows of material_id, or (LIST) over the n lanes listed in `rows`
+template <bool LIST>
+int bucket_launch(const int64_t* material_id, const int64_t* rows, int64_t n, int32_t n_materials, int64_t* perm, int64_t* counts,
+                  void* workspace, int64_t workspace_bytes, void* stream) {
+    if (n < 0) return bsdfd_fail_(BSDFD_EINVAL, "N must be >= 0");
+    if (n_materials < 1 || n_materials > BK_MAX_MATERIALS)
+        return bsdfd_fail_(BSDFD_EINVAL, "n_materials must be in [1, 64]");
+    if (!counts) return bsdfd_fail_(BSDFD_EINVAL, "null counts pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * n_materials, st));
+        return BSDFD_OK;
+    }
+    if (!material_id || !perm || !workspace) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
+    if (workspace_bytes < bsdfd_bucket_workspace_bytes(n, n_materials))
+        return bsdfd_fail_(BSDFD_EINVAL, "workspace smaller than bsdfd_bucket_workspace_bytes()");
+    const long long nblocks = (n + BK_CHUNK - 1) / BK_CHUNK;
+    if (nblocks > 0x7fffffffLL) return bsdfd_fail_(BSDFD_EINVAL, "N too large");
+    const long long entries = (long long)n_materials * nblocks;
+    // workspace: [offs: entries x i64][blockhist: entries x i32]
+    long long* offs = static_cast<long long*>(workspace);
+    int* blockhist = reinterpret_cast<int*>(offs + entries);
+    const long long* ids = reinterpret_cast<const long long*>(material_id);
+    const long long* list = reinterpret_cast<const long long*>(rows);
+    const size_t lds_count = (size_t)BK_CHUNK + (size_t)n_materials * BK_CNT_STRIDE;
+    const size_t lds_scatter = (size_t)BK_CHUNK + (size_t)n_materials * (BK_CNT_STRIDE + 2 * BK_BASE_STRIDE) + (size_t)BK_CHUNK * 3 +
+                               BK_MAX_MATERIALS * sizeof(long long) + (BK_MAX_MATERIALS + 1) * sizeof(int) + 16;
+    // up to ~67 KB of dynamic LDS at 64 materials: above the default cap, needs the attribute (once per process)
+    static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(bucket_scatter_kernel<LIST>),
+                                                          hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+    HIP_TRY(attr_rc);
+    hipLaunchKernelGGL(bucket_count_kernel<LIST>, dim3((unsigned)nblocks), dim3(BK_THREADS), lds_count, st, ids, list, (long long)n,
+                       (int)n_materials, nblocks, blockhist);
+    hipLaunchKernelGGL(bucket_scan_kernel, dim3((unsigned)n_materials), dim3(1024), 0, st, blockhist, nblocks, offs,
+                       reinterpret_cast<long long*>(counts));
+    hipLaunchKernelGGL(bucket_scatter_kernel<LIST>, dim3((unsigned)nblocks), dim3(BK_THREADS), lds_scatter, st, ids, list,
+                       (long long)n, (int)n_materials, nblocks, offs, reinterpret_cast<const long long*>(counts),
+                       reinterpret_cast<long long*>(perm));
+    HIP_TRY(hipGetLastError());
+    return BSDFD_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -199,41 +259,13 @@ int64_t bsdfd_bucket_workspace_bytes(int64_t n, int32_t n_materials) {
 
 int bsdfd_bucket_by_material(const int64_t* material_id, int64_t n, int32_t n_materials, int64_t* perm, int64_t* counts,
                              void* workspace, int64_t workspace_bytes, void* stream) {
-    if (n < 0) return bsdfd_fail_(BSDFD_EINVAL, "N must be >= 0");
-    if (n_materials < 1 || n_materials > BK_MAX_MATERIALS)
-        return bsdfd_fail_(BSDFD_EINVAL, "n_materials must be in [1, 64]");
-    if (!counts) return bsdfd_fail_(BSDFD_EINVAL, "null counts pointer");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (n == 0) {
-        HIP_TRY(hipMemsetAsync(counts, 0, sizeof(int64_t) * n_materials, st));
-        return BSDFD_OK;
-    }
-    if (!material_id || !perm || !workspace) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
-    if (workspace_bytes < bsdfd_bucket_workspace_bytes(n, n_materials))
-        return bsdfd_fail_(BSDFD_EINVAL, "workspace smaller than bsdfd_bucket_workspace_bytes()");
-    const long long nblocks = (n + BK_CHUNK - 1) / BK_CHUNK;
-    if (nblocks > 0x7fffffffLL) return bsdfd_fail_(BSDFD_EINVAL, "N too large");
-    const long long entries = (long long)n_materials * nblocks;
-    // workspace: [offs: entries x i64][blockhist: entries x i32]
-    long long* offs = static_cast<long long*>(workspace);
-    int* blockhist = reinterpret_cast<int*>(offs + entries);
-    const long long* ids = reinterpret_cast<const long long*>(material_id);
-    const size_t lds_count = (size_t)BK_CHUNK + (size_t)n_materials * BK_CNT_STRIDE;
-    const size_t lds_scatter = (size_t)BK_CHUNK + (size_t)n_materials * (BK_CNT_STRIDE + 2 * BK_BASE_STRIDE) + (size_t)BK_CHUNK * 3 +
-                               BK_MAX_MATERIALS * sizeof(long long) + (BK_MAX_MATERIALS + 1) * sizeof(int) + 16;
-    // up to ~67 KB of dynamic LDS at 64 materials: above the default cap, needs the attribute (once per process)
-    static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(bucket_scatter_kernel),
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    HIP_TRY(attr_rc);
-    hipLaunchKernelGGL(bucket_count_kernel, dim3((unsigned)nblocks), dim3(BK_THREADS), lds_count, st, ids, (long long)n,
-                       (int)n_materials, nblocks, blockhist);
-    hipLaunchKernelGGL(bucket_scan_kernel, dim3((unsigned)n_materials), dim3(1024), 0, st, blockhist, nblocks, offs,
-                       reinterpret_cast<long long*>(counts));
-    hipLaunchKernelGGL(bucket_scatter_kernel, dim3((unsigned)nblocks), dim3(BK_THREADS), lds_scatter, st, ids,
-                       (long long)n, (int)n_materials, nblocks, offs, reinterpret_cast<const long long*>(counts),
-                       reinterpret_cast<long long*>(perm));
-    HIP_TRY(hipGetLastError());
-    return BSDFD_OK;
+    return bucket_launch<false>(material_id, nullptr, n, n_materials, perm, counts, workspace, workspace_bytes, stream);
+}
+
+int bsdfd_bucket_rows(const int64_t* material_id, const int64_t* rows, int64_t n_rows, int32_t n_materials, int64_t* perm,
+                      int64_t* counts, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (n_rows > 0 && !rows) return bsdfd_fail_(BSDFD_EINVAL, "null rows pointer");
+    return bucket_launch<true>(material_id, rows, n_rows, n_materials, perm, counts, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -85,6 +85,17 @@ __device__ __forceinline__ void with_material(const MeasuredDevG* __restrict__ t
     }
 }
 
+// eval() of row q by the material its id names
+__device__ __forceinline__ void eval_table_row(const MeasuredDevG* __restrict__ table, int n_materials,
+                                               const long long* __restrict__ material_id, const float* __restrict__ wi,
+                                               const float* __restrict__ wo, const float* __restrict__ wl, long long q, Tint tint,
+                                               float* __restrict__ f_o, float* __restrict__ f_l) {
+    const float nan = quiet_nan();
+    with_material(table, n_materials, material_id[q],
+                  [&](const MeasuredDev& m) { eval_row(m, wi, wo, wl, q, tint, f_o, f_l); },
+                  [&] { store3(f_o, q, nan, nan, nan); if (f_l) store3(f_l, q, nan, nan, nan); });
+}
+
 // The four kernels: the rows of measured_dev.h, which the single-material kernels (measured.hip) run too; a row without
 // ground truth gets NaN in every output (the weight kernel passes its pdf through).
 __global__ __launch_bounds__(256) void measured_eval_table_kernel(const MeasuredDevG* __restrict__ table, int n_materials,
@@ -95,10 +106,23 @@ __global__ __launch_bounds__(256) void measured_eval_table_kernel(const Measured
                                                                   float* __restrict__ f_o, float* __restrict__ f_l) {
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n) return;
-    const float nan = quiet_nan();
-    with_material(table, n_materials, material_id[q],
-                  [&](const MeasuredDev& m) { eval_row(m, wi, wo, wl, q, tint, f_o, f_l); },
-                  [&] { store3(f_o, q, nan, nan, nan); if (f_l) store3(f_l, q, nan, nan, nan); });
+    eval_table_row(table, n_materials, material_id, wi, wo, wl, q, tint, f_o, f_l);
+}
+
+// ... over a row list: thread t serves row rows[t] of the N-row arrays and writes f_o / f_l there only.  Consecutive entries of one
+// bucket of a sorted list share their id, so the wave-uniform path serves them as it serves image-coherent lanes.
+__global__ __launch_bounds__(256) void measured_eval_table_rows_kernel(const MeasuredDevG* __restrict__ table, int n_materials,
+                                                                       const long long* __restrict__ material_id,
+                                                                       const float* __restrict__ wi,
+                                                                       const float* __restrict__ wo,
+                                                                       const float* __restrict__ wl, long long n, Tint tint,
+                                                                       float* __restrict__ f_o, float* __restrict__ f_l,
+                                                                       const long long* __restrict__ rows, long long n_rows) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_rows) return;
+    const long long q = rows[t];
+    if ((unsigned long long)q >= (unsigned long long)n) return;   // (a contract violation: skipped, not followed)
+    eval_table_row(table, n_materials, material_id, wi, wo, wl, q, tint, f_o, f_l);
 }
 
 __global__ __launch_bounds__(256) void measured_weight_table_kernel(const MeasuredDevG* __restrict__ table, int n_materials,
@@ -216,6 +240,18 @@ int bsdfd_measured_eval_table(bsdfd_measured_table t, const int64_t* material_id
                       : !material_id || !wi || !wo || !f_o ? "null pointer" : nullptr;
     return table_launch(t, n, material_id, bad, measured_eval_table_kernel, stream, wi, wo, wl, (long long)n, TintArg{tint},
                         f_o, f_l);
+}
+
+int bsdfd_measured_eval_table_rows(bsdfd_measured_table t, const int64_t* material_id, const float* wi, const float* wo,
+                                   const float* wl, int64_t n, const float* tint, float* f_o, float* f_l, const int64_t* rows,
+                                   int64_t n_rows, void* stream) {
+    if (int rc = table_launch_checks(t, n)) return rc;
+    if (n_rows < 0 || n_rows > n) return bsdfd_fail_(BSDFD_EINVAL, "n_rows must be in [0, N]");
+    const char* bad = (wl == nullptr) != (f_l == nullptr) ? "wl and f_l are both NULL or both given"
+                      : !material_id || !wi || !wo || !f_o || !rows ? "null pointer" : nullptr;
+    return launch_rows(n_rows, bad, measured_eval_table_rows_kernel, stream, reinterpret_cast<const MeasuredDevG*>(t->dev),
+                       (int)t->n_materials, reinterpret_cast<const long long*>(material_id), wi, wo, wl, (long long)n, TintArg{tint},
+                       f_o, f_l, reinterpret_cast<const long long*>(rows), (long long)n_rows);
 }
 
 int bsdfd_measured_sample_weight_table(bsdfd_measured_table t, const int64_t* material_id, const float* wi,

@@ -12,7 +12,8 @@
 //                below the horizon or (occlusion) behind a surface.  On the floor: wl stays (the cosine direction is the floor's
 //                BSDF sample and the way on), emit = the whole term mis(p_l, cos/pi) (refl/pi) cos E V / p_l.
 //
-// The bounce that reads lpdf and emit is bounce.hip's ENV kernel.
+// The bounce that reads lpdf and emit is bounce.hip's ENV kernel.  bsdfd_wf_sample_env_rows is the same kernel over the lanes of a
+// live-lane list (bounce_dev.h's Rows).
 // One path per lane; the scene travels by value; a lane whose path has ended returns after reading its id.
 #include <hip/hip_runtime.h>
 
@@ -44,13 +45,15 @@ __global__ __launch_bounds__(256) void env_pdf_kernel(EnvDist e, long long n, co
     pdf[q] = env_dev::env_pdf(e, ld3(dir + 3 * q));
 }
 
+// `list`: nothing (every lane of the wavefront), or one Rows (the list form: the lanes of a live-lane list)
+template <class... List>
 __global__ __launch_bounds__(256) void sample_env_kernel(Scene sc, const float* __restrict__ env, EnvDist e, int n_e, Step st,
                                                          const float* __restrict__ org, const float* __restrict__ nrm,
                                                          const float* __restrict__ wi, const long long* __restrict__ mat,
                                                          const int* __restrict__ lsel, float* __restrict__ wl,
-                                                         float* __restrict__ lpdf, float* __restrict__ emit) {
+                                                         float* __restrict__ lpdf, float* __restrict__ emit, List... list) {
     long long p, m;
-    if (!live_lane(sc, st.n, mat, p, m)) return;
+    if (!live_lane<sizeof...(List) != 0>(sc, st.n, mat, p, m, list...)) return;
     if (lsel && lsel[p] != -1) return;   // a point light was picked: sample_emitter's wl and emit stand
     unsigned u[4];
     tagged_draw(st.seed, st.pass, st.path_offset, p, 0x456E766Du /* "Envm" */, st.bounce, u);
@@ -76,6 +79,27 @@ __global__ __launch_bounds__(256) void sample_env_kernel(Scene sc, const float* 
     }
     lpdf[p] = p_l;
     st3(emit + 3 * p, v3(s * E[0], s * E[1], s * E[2]));
+}
+
+// the checks of both sample_env entry points and the launch: over all N lanes, or (`list`) over the lanes of a list
+int launch_sample_env(const bsdfd_wf_scene* scene, const float* env, const bsdfd_env_dist* dist, int32_t n_e, int32_t bounce,
+                      int32_t occlusion, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, const float* org,
+                      const float* nrm, const float* wi, const int64_t* material, const int32_t* lsel, float* wl, float* lpdf,
+                      float* emit, void* stream, const Rows* list) {
+    Scene sc;
+    EnvDist e;
+    if (int rc = env_scene(scene, env, dist, n_e, lsel != nullptr, N, sc, e)) return rc;
+    if (bounce < 0) return bsdfd_fail_(BSDFD_EINVAL, "bounce must be >= 0");
+    if (N == 0) return BSDFD_OK;
+    if (!org || !nrm || !wi || !material || !wl || !lpdf || !emit) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
+    const Step st = make_step(bounce, 0, occlusion, seed, pass, path_offset, N);
+    if (list) {
+        if (list->n == 0) return BSDFD_OK;
+        return launch_lanes(list->n, sample_env_kernel<Rows>, stream, sc, env, e, (int)n_e, st, org, nrm, wi,
+                            reinterpret_cast<const long long*>(material), reinterpret_cast<const int*>(lsel), wl, lpdf, emit, *list);
+    }
+    return launch_lanes(N, sample_env_kernel<>, stream, sc, env, e, (int)n_e, st, org, nrm, wi, reinterpret_cast<const long long*>(material),
+                        reinterpret_cast<const int*>(lsel), wl, lpdf, emit);
 }
 
 }  // namespace
@@ -106,15 +130,18 @@ int bsdfd_wf_sample_env(const bsdfd_wf_scene* scene, const float* env, const bsd
                         int32_t occlusion, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, const float* org,
                         const float* nrm, const float* wi, const int64_t* material, const int32_t* lsel, float* wl, float* lpdf,
                         float* emit, void* stream) {
-    Scene sc;
-    EnvDist e;
-    if (int rc = env_scene(scene, env, dist, n_e, lsel != nullptr, N, sc, e)) return rc;
-    if (bounce < 0) return bsdfd_fail_(BSDFD_EINVAL, "bounce must be >= 0");
-    if (N == 0) return BSDFD_OK;
-    if (!org || !nrm || !wi || !material || !wl || !lpdf || !emit) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
-    const Step st = make_step(bounce, 0, occlusion, seed, pass, path_offset, N);
-    return launch_lanes(N, sample_env_kernel, stream, sc, env, e, (int)n_e, st, org, nrm, wi, reinterpret_cast<const long long*>(material),
-                        reinterpret_cast<const int*>(lsel), wl, lpdf, emit);
+    return launch_sample_env(scene, env, dist, n_e, bounce, occlusion, seed, pass, path_offset, N, org, nrm, wi, material, lsel, wl, lpdf,
+                             emit, stream, nullptr);
+}
+
+int bsdfd_wf_sample_env_rows(const bsdfd_wf_scene* scene, const float* env, const bsdfd_env_dist* dist, int32_t n_e, int32_t bounce,
+                             int32_t occlusion, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, const float* org,
+                             const float* nrm, const float* wi, const int64_t* material, const int32_t* lsel, float* wl, float* lpdf,
+                             float* emit, const int64_t* rows, int64_t n_rows, void* stream) {
+    Rows list;
+    if (int rc = to_rows(rows, n_rows, N, list)) return rc;
+    return launch_sample_env(scene, env, dist, n_e, bounce, occlusion, seed, pass, path_offset, N, org, nrm, wi, material, lsel, wl, lpdf,
+                             emit, stream, &list);
 }
 
 }  // extern "C"

@@ -11,7 +11,8 @@
 //                    and emit = n_e I_k / d^2, 0 below the horizon or (occlusion) behind another surface.  Point k on the floor:
 //                    wl stays (the path continues along it), emit = the whole term n_e (refl / pi) cos I_k / d^2.
 //
-// The bounce that reads lsel and emit is bounce.hip's LIT kernel.
+// The bounce that reads lsel and emit is bounce.hip's LIT kernel.  bsdfd_wf_sample_emitter_rows is the same kernel over the lanes of
+// a live-lane list (bounce_dev.h's Rows), for the deep bounces of a wavefront that has mostly ended.
 // The lights travel by value in the kernel arguments like the scene; the picked light is selected by a wave-uniform loop
 // with a per-lane select, because indexing the argument array per lane would move it to scratch.  One path per lane; a
 // lane whose path has ended returns after reading its id.
@@ -35,12 +36,14 @@ struct Lights {
     float inten[BSDFD_WF_MAX_LIGHTS][3];
 };
 
+// `list`: nothing (every lane of the wavefront), or one Rows (the list form: the lanes of a live-lane list)
+template <class... List>
 __global__ __launch_bounds__(256) void sample_emitter_kernel(Scene sc, Lights lt, Step st, const float* __restrict__ org,
                                                              const float* __restrict__ nrm, const float* __restrict__ wi,
                                                              const long long* __restrict__ mat, float* __restrict__ wl,
-                                                             int* __restrict__ lsel, float* __restrict__ emit) {
+                                                             int* __restrict__ lsel, float* __restrict__ emit, List... list) {
     long long p, m;
-    if (!live_lane(sc, st.n, mat, p, m)) return;
+    if (!live_lane<sizeof...(List) != 0>(sc, st.n, mat, p, m, list...)) return;
     unsigned u[4];
     tagged_draw(st.seed, st.pass, st.path_offset, p, 0x4C697465u /* "Lite" */, st.bounce, u);
     const int pick = (int)(((unsigned long long)u[0] * (unsigned long long)lt.n_e) >> 32);
@@ -77,13 +80,10 @@ int to_lights(const bsdfd_wf_lights* l, Lights& lt) {
     return BSDFD_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int bsdfd_wf_sample_emitter(const bsdfd_wf_scene* scene, const bsdfd_wf_lights* lights, int32_t bounce, int32_t occlusion,
-                            uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, const float* org, const float* nrm,
-                            const float* wi, const int64_t* material, float* wl, int32_t* lsel, float* emit, void* stream) {
+// the checks of both entry points and the launch: over all N lanes, or (`list`) over the lanes of a list
+int launch_sample_emitter(const bsdfd_wf_scene* scene, const bsdfd_wf_lights* lights, int32_t bounce, int32_t occlusion, uint64_t seed,
+                          uint64_t pass, uint64_t path_offset, int64_t N, const float* org, const float* nrm, const float* wi,
+                          const int64_t* material, float* wl, int32_t* lsel, float* emit, void* stream, const Rows* list) {
     Scene sc;
     Lights lt;
     if (int rc = to_scene(scene, 0, 0, 1, sc)) return rc;
@@ -94,8 +94,34 @@ int bsdfd_wf_sample_emitter(const bsdfd_wf_scene* scene, const bsdfd_wf_lights* 
     if (N == 0) return BSDFD_OK;
     if (!org || !nrm || !wi || !material || !wl || !lsel || !emit) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
     const Step st = make_step(bounce, 0, occlusion, seed, pass, path_offset, N);
-    return launch_lanes(N, sample_emitter_kernel, stream, sc, lt, st, org, nrm, wi, reinterpret_cast<const long long*>(material), wl,
+    if (list) {
+        if (list->n == 0) return BSDFD_OK;
+        return launch_lanes(list->n, sample_emitter_kernel<Rows>, stream, sc, lt, st, org, nrm, wi,
+                            reinterpret_cast<const long long*>(material), wl, reinterpret_cast<int*>(lsel), emit, *list);
+    }
+    return launch_lanes(N, sample_emitter_kernel<>, stream, sc, lt, st, org, nrm, wi, reinterpret_cast<const long long*>(material), wl,
                         reinterpret_cast<int*>(lsel), emit);
+}
+
+}  // namespace
+
+extern "C" {
+
+int bsdfd_wf_sample_emitter(const bsdfd_wf_scene* scene, const bsdfd_wf_lights* lights, int32_t bounce, int32_t occlusion,
+                            uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, const float* org, const float* nrm,
+                            const float* wi, const int64_t* material, float* wl, int32_t* lsel, float* emit, void* stream) {
+    return launch_sample_emitter(scene, lights, bounce, occlusion, seed, pass, path_offset, N, org, nrm, wi, material, wl, lsel, emit,
+                                 stream, nullptr);
+}
+
+int bsdfd_wf_sample_emitter_rows(const bsdfd_wf_scene* scene, const bsdfd_wf_lights* lights, int32_t bounce, int32_t occlusion,
+                                 uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, const float* org, const float* nrm,
+                                 const float* wi, const int64_t* material, float* wl, int32_t* lsel, float* emit,
+                                 const int64_t* rows, int64_t n_rows, void* stream) {
+    Rows list;
+    if (int rc = to_rows(rows, n_rows, N, list)) return rc;
+    return launch_sample_emitter(scene, lights, bounce, occlusion, seed, pass, path_offset, N, org, nrm, wi, material, wl, lsel, emit,
+                                 stream, &list);
 }
 
 }  // extern "C"

@@ -112,6 +112,29 @@ class RowKernels:
         launch(self.ENTRY["sample"], wi.device, *self._front(material_id), wi, u, act, wi.shape[0], tint3(tint), wo, pdf, weight)
         return wo, pdf, weight
 
+    def _eval_table(self, material_id, wi, wo, wl, tint, out_o, out_l, rows=None):
+        """``eval_t`` of the two tables: f_o [N,3] or, with ``wl``, (f_o, f_l).  ``rows`` (int64 [n_rows], contiguous, on the
+        device, at most N entries, distinct and in [0, N)): the ``_rows`` entry point — only the listed rows are evaluated and
+        written, every other row of ``out_o`` / ``out_l`` keeps what it held."""
+        who = self.NAME + ".eval_t"
+        if out_l is not None and wl is None:
+            raise ValueError(f"{who}: out_l without wl")
+        given = (("wi", wi), ("wo", wo), ("wl", wl), ("out_o", out_o), ("out_l", out_l))
+        check(who, [(k, t, 3) for k, t in given if t is not None], material_id)
+        if rows is not None and not (isinstance(rows, torch.Tensor) and rows.dtype == torch.int64 and rows.dim() == 1
+                                     and rows.is_contiguous() and rows.device == wi.device and rows.shape[0] <= wi.shape[0]):
+            raise ValueError(f"{who}: rows must be a contiguous int64 tensor [n_rows <= N] on the device of wi")
+        if out_o is None:
+            out_o = torch.empty_like(wi)
+        if wl is not None and out_l is None:
+            out_l = torch.empty_like(wi)
+        args = (self._lead(), material_id, wi, wo, wl, wi.shape[0], tint3(tint), out_o, out_l)
+        if rows is None:
+            launch(self.ENTRY["eval"], wi.device, *args)
+        else:
+            launch(self.ENTRY["eval"] + "_rows", wi.device, *args, rows, rows.shape[0])
+        return out_o if wl is None else (out_o, out_l)
+
     def _pdf_t(self, material_id, wi, wo, active, out):
         if out is None:
             out = torch.empty(wi.shape[0], dtype=torch.float32, device=wi.device)

@@ -239,20 +239,45 @@ class MaterialTable:
         sort behind the materials, are not evaluated, and their outputs are zero."""
         return self._buckets(material_id, extra_bins)
 
+    def bucket_rows(self, material_id: torch.Tensor, rows: torch.Tensor, extra_bins: int = 0):
+        """``bucket`` over a list of lanes: (perm, counts) of the lanes ``rows`` (int64 [n_rows], distinct, in [0, N)) by
+        ``material_id[rows]``, ``perm`` holding LANE numbers, bucket by bucket, stable in list order, cut to the kept lanes: a lane
+        whose id is outside [0, len(self) + extra_bins) is left out (a path tracer's ended paths), so ``perm`` is the next list.
+        As a plan it serves ``sample_pdf(..., direct=True, out=)``.  Native only (``bsdfd_bucket_rows``): at most 64 ids."""
+        n_ids = len(self) + extra_bins
+        if n_ids > 64:
+            raise ValueError(f"bucket_rows sorts at most 64 ids natively, got {n_ids}")
+        for name, t in (("material_id", material_id), ("rows", rows)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == torch.int64 and t.dim() == 1 and t.is_cuda and t.is_contiguous()):
+                raise ValueError(f"bucket_rows: {name} must be a contiguous int64 CUDA tensor [N]")
+        if rows.device != material_id.device or rows.shape[0] > material_id.shape[0]:
+            raise ValueError("bucket_rows: rows must be on the device of material_id and no longer than it")
+        L, dev, n = _lib.lib(), material_id.device, rows.shape[0]
+        perm = torch.empty(n, dtype=torch.int64, device=dev)
+        counts = torch.empty(n_ids, dtype=torch.int64, device=dev)
+        ws = torch.empty(max(int(L.bsdfd_bucket_workspace_bytes(n, n_ids)), 1), dtype=torch.uint8, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr())
+        with torch.cuda.device(dev):
+            _lib.check(L.bsdfd_bucket_rows(p(material_id), p(rows), n, n_ids, p(perm), p(counts), p(ws), ws.numel(),
+                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        counts = counts.cpu().tolist()
+        return perm[: sum(counts)], counts
+
     def _serve(self, which, material_id, ins, seed=0, offset=0, T=None, segmented=True, form="gathered", rng="lane",
-               ctx=None, ctx_fill=None):
+               ctx=None, ctx_fill=None, out=None):
         """The skeleton of sample() / pdf() / sample_pdf(): ``ins`` (``wi`` first, in the order ``FlowSampler.plugin_<which>`` takes
         them) -> (results, (bucket-ordered inputs, bucket-ordered results, rows, seg_end)).  ``form``: how the launches see the
         arrays — "gathered": bucket-ordered copies, the results scattered back to lane order; "bucketed": the arrays are in
         bucket order already and the results stay in it; "direct": the lane-ordered arrays themselves, read and written through
-        the bucket permutation."""
+        the bucket permutation.  ``out`` (direct only): the lane-ordered result arrays to write into, with no fill — the plan may
+        then cover fewer rows than ``wi`` has (``bucket_rows``), and rows it does not list keep what they held."""
         if ctx is not None and not segmented:
             raise ValueError("ctx= is a feature of the segmented path (segmented=False issues one plain call per bucket)")
         if rng not in ("lane", "bucketed"):
             raise ValueError("rng must be 'lane' or 'bucketed'")
         wi = ins[0]
         n, dev = wi.shape[0], wi.device
-        rows, counts, seg_end = self._plan(material_id, None if form == "bucketed" else n)
+        rows, counts, seg_end = self._plan(material_id, None if form == "bucketed" or out is not None else n)
         if form == "bucketed" and n != rows.shape[0]:
             raise ValueError(f"bucketed wi has {n} rows, the plan has {rows.shape[0]} material lanes")
         rows = rows.contiguous()
@@ -262,7 +287,7 @@ class MaterialTable:
         def new(mk, k):
             return tuple(mk((k, 3) if cols == 3 else (k,), dtype=torch.float32, device=dev)
                          for cols in {"sample": (3, 1), "pdf": (1,), "sample_pdf": (3, 1, 1)}[which])
-        outs_s = new(torch.zeros if direct and not full else torch.empty, ins_s[0].shape[0])
+        outs_s = tuple(out) if out is not None else new(torch.zeros if direct and not full else torch.empty, ins_s[0].shape[0])
         # the Philox counter of a row: offset + its ORIGINAL lane (what the direct form draws by construction), or + its bucketed row
         rng_rows = rows if rng == "lane" and which != "pdf" and not direct else None
         with torch.cuda.device(dev):
@@ -319,16 +344,29 @@ class MaterialTable:
 
     def sample_pdf(self, material_id, wi: torch.Tensor, wl: torch.Tensor, seed: int = 0, offset: int = 0,
                    T: Optional[int] = None, x0: Optional[torch.Tensor] = None, return_bucketed: bool = False,
-                   rng: str = "lane", direct: bool = False):
+                   rng: str = "lane", direct: bool = False, out=None):
         """sample(wi) and pdf(wi, wl) for the same material-tagged intersections, one launch per kernel
-        signature -> (wo [N,3], pdf(wo) [N], pdf(wl) [N]) in the callers' order."""
+        signature -> (wo [N,3], pdf(wo) [N], pdf(wl) [N]) in the callers' order.
+        ``out`` = (wo, pdf_o, pdf_l), with ``direct=True``: the results are written into these lane-ordered arrays, which are
+        returned, and nothing N rows long is allocated or filled.  The plan may then cover fewer rows than ``wi`` has (a plan of
+        ``bucket_rows``): only its material rows are written, every other row keeps what it held.  Without ``out`` a plan that
+        does not cover the batch is refused."""
         wi = self._chk_in(wi, 3, "wi")
         wl = self._chk_in(wl, 3, "wl", wi.shape[0])
         x0 = self._chk_in(x0, 2, "x0", wi.shape[0])
         if direct and (return_bucketed or rng != "lane"):
             raise ValueError("direct=True returns lane-ordered arrays only and draws with rng='lane'")
+        if out is not None:
+            if not direct:
+                raise ValueError("out= is written through the bucket permutation: it needs direct=True")
+            if len(out) != 3:
+                raise ValueError("out is a (wo [N,3], pdf_o [N], pdf_l [N]) triple")
+            if out[0] is None:
+                raise ValueError("out[0] (wo) is missing")
+            out = (self._chk_in(out[0], 3, "out[0]", wi.shape[0]),) + tuple(self.samplers[0]._chk1(t, wi.shape[0], f"out[{k + 1}]")
+                                                                          for k, t in enumerate(out[1:]))
         outs, (ins_s, outs_s, rows, seg_end) = self._serve("sample_pdf", material_id, (wi, wl, x0), seed, offset, T,
-                                                           form="direct" if direct else "gathered", rng=rng)
+                                                           form="direct" if direct else "gathered", rng=rng, out=out)
         if return_bucketed:  # the bucket-ordered arrays too (material m = rows seg_end[m-1] .. seg_end[m]) and `rows`
             return outs + (dict(wi=ins_s[0], wl=ins_s[1], wo=outs_s[0], pdf_o=outs_s[1], pdf_l=outs_s[2], rows=rows,
                                 seg_end=seg_end),)

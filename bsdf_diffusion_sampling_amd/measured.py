@@ -22,7 +22,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
-from .ground_truth import GroundTruth, RowKernels, check, launch, tint3
+from .ground_truth import GroundTruth, RowKernels
 
 
 def find_measured_file(material: str, directory: Optional[str] = None) -> Optional[str]:
@@ -81,8 +81,8 @@ class MeasuredTable(RowKernels):
     is left to fail at its first launch."""
 
     NAME = "MeasuredTable"
-    ENTRY = dict(sample_weight="bsdfd_measured_sample_weight_table", sample="bsdfd_measured_sample_table",
-                 pdf="bsdfd_measured_pdf_table")
+    ENTRY = dict(eval="bsdfd_measured_eval_table", sample_weight="bsdfd_measured_sample_weight_table",
+                 sample="bsdfd_measured_sample_table", pdf="bsdfd_measured_pdf_table")
     MAX_MATERIALS = 65536
 
     def __init__(self, entries: Sequence[Optional[MeasuredBSDF]]):
@@ -116,19 +116,12 @@ class MeasuredTable(RowKernels):
     _lead = _table
 
     def eval_t(self, material_id: torch.Tensor, wi: torch.Tensor, wo: torch.Tensor, wl: Optional[torch.Tensor] = None,
-               tint=None, out_o: Optional[torch.Tensor] = None, out_l: Optional[torch.Tensor] = None):
+               tint=None, out_o: Optional[torch.Tensor] = None, out_l: Optional[torch.Tensor] = None,
+               rows: Optional[torch.Tensor] = None):
         """f(wi, wo) cos(theta_o) [* tint] of each lane's material -> f_o [N,3]; with ``wl`` also f(wi, wl) cos(theta_l) ->
-        (f_o, f_l), both evaluations in the same launch.  NaN rows = no ground truth for that lane."""
-        if out_l is not None and wl is None:
-            raise ValueError("MeasuredTable.eval_t: out_l without wl")
-        given = (("wi", wi), ("wo", wo), ("wl", wl), ("out_o", out_o), ("out_l", out_l))
-        check("MeasuredTable.eval_t", [(k, t, 3) for k, t in given if t is not None], material_id)
-        if out_o is None:
-            out_o = torch.empty_like(wi)
-        if wl is not None and out_l is None:
-            out_l = torch.empty_like(wi)
-        launch("bsdfd_measured_eval_table", wi.device, self._table(), material_id, wi, wo, wl, wi.shape[0], tint3(tint), out_o, out_l)
-        return out_o if wl is None else (out_o, out_l)
+        (f_o, f_l), both evaluations in the same launch.  NaN rows = no ground truth for that lane.  ``rows`` (int64 [n_rows]):
+        only the listed rows are evaluated and written (``bsdfd_measured_eval_table_rows``); every other row keeps what it held."""
+        return self._eval_table(material_id, wi, wo, wl, tint, out_o, out_l, rows)
 
     def sample_weight(self, material_id: torch.Tensor, wi: torch.Tensor, wo: torch.Tensor, pdf_sa: torch.Tensor, *, tint=None,
                       firefly_threshold: Optional[float] = None, active: Optional[torch.Tensor] = None):

@@ -52,6 +52,19 @@ roulette ``max_depth=None`` is the reference's unbounded depth: the loop runs un
 rule restated; like the evaluator it is parity-unpinned against Mitsuba (neither its random stream nor its images are matched).
 ``integrator_from_matpreview_xml`` reads both settings from a reference scene file.
 
+``compact=True`` runs the bounces behind the first on a live-lane list instead of over all N lanes.  The bucketing sorts ended
+paths behind everything else, so the front of its permutation is the list ``L`` of the lanes that were alive; the next depth becomes
+
+    [sample_emitter(k, rows=L)] -> [sample_env(k, rows=L)] -> table.bucket_rows(mat, L)   -> L': "miss" ids dropped
+        -> sample_pdf(plan, direct=True, out=(wo, pdf_o, pdf_l)) -> eval_t(..., rows=material prefix of L') -> bounce(k, rows=L')
+
+and ``L'`` is the following depth's ``L`` (``bsdfd_wf_sample_emitter_rows``, ``bsdfd_wf_sample_env_rows``, ``bsdfd_bucket_rows``,
+``bsdfd_measured_eval_table_rows`` / ``bsdfd_analytic_eval_table_rows``, ``bsdfd_wf_bounce_rows``).  The state stays in lane order and
+a lane's Philox counters are keyed by the lane, never by the thread that serves it, so the film and the path state are those of
+``compact=False`` bit for bit; the sampler's answers go into the arrays of bounce 0 with no fill, since ``bounce`` reads them on the
+material lanes of its list only.  The host still reads the bucket counts back once per depth.  What it saves:
+profiles/pathtrace_compact.json (tools/pathtrace_bench.py --compact).
+
 The ground truth is ``ArrayRenderer``'s: {ball: ``MeasuredBSDF``}, or {ball: ``analytic.Principled`` / ``RoughDielectric``}
 (``analytic.ground_truth_for(names)`` for the ``mybsdf idx = N`` balls of matpreview/disney_bsdf_array2_spherical_*.xml), evaluated
 on the lane-ordered wavefront by ``measured.MeasuredTable`` or ``analytic.AnalyticTable``; with analytic ground truth on every ball
@@ -179,13 +192,18 @@ class PathArrayRenderer(ArrayRenderer):
     integer >= 1: Russian roulette from the vertex ``bounce + 1 >= rr_depth`` on (Mitsuba's default is 5).  ``max_depth=None``
     is unbounded depth; it needs ``rr_depth`` and implies occlusion.  A pass then ends when no live lane is left, or after
     ``DEPTH_CAP`` bounces (the bounce at the cap gets ``last=True``: a truncation, reported in ``stats["depth_cap_hit"]``).
-    ``stats["depth"]``: the bounces the last pass ran."""
+    ``stats["depth"]``: the bounces the last pass ran.
+
+    ``compact``: False (the default: the renderer without the argument, call for call) or True: from bounce 1 on every per-depth
+    kernel runs over the live-lane list the previous bounce's bucketing produced, not over all N lanes.  Same film, same path
+    state, bit for bit.  ``stats["list_per_bounce"]``: the lanes the bucketing of each bounce read (N at bounce 0; with
+    ``compact=False`` N at every bounce)."""
 
     DEPTH_CAP = 1024   # bounces of a pass at max_depth=None; with roulette (q <= 0.95) a path outlives it with probability < 1e-22
 
     def __init__(self, table, centers, radii, camera=None, env: Optional[torch.Tensor] = None, *args, max_depth: Optional[int] = 1,
                  occlusion: Optional[bool] = None, lights: Optional[Sequence[PointLight]] = None, env_sampling: str = "cosine",
-                 rr_depth: Optional[int] = None, **kwargs):
+                 rr_depth: Optional[int] = None, compact: bool = False, **kwargs):
         if rr_depth is not None:
             rr_depth = int(rr_depth)
             if rr_depth < 1:
@@ -219,7 +237,8 @@ class PathArrayRenderer(ArrayRenderer):
         if env_sampling == "importance":
             from .envmap import EnvDistribution
             self.env_dist = EnvDistribution(self.env)
-        self.stats = {"lanes_per_bounce": [], "depth": 0, "depth_cap_hit": False}
+        self.compact = bool(compact)
+        self.stats = {"lanes_per_bounce": [], "list_per_bounce": [], "depth": 0, "depth_cap_hit": False}
 
     def _buffers(self, n: int):
         b = super()._buffers(n)
@@ -235,6 +254,13 @@ class PathArrayRenderer(ArrayRenderer):
         return b
 
     # -- the path kernels ----------------------------------------------------------------------------
+    def _list(self, rows, b):
+        """(pointer, length) of a live-lane list for the ``_rows`` entry points; ``ValueError`` for what they should not see."""
+        if not (isinstance(rows, torch.Tensor) and rows.dtype == torch.int64 and rows.dim() == 1 and rows.is_contiguous()
+                and rows.device == b["mat"].device and rows.shape[0] <= b["mat"].shape[0]):
+            raise ValueError("rows must be a contiguous int64 tensor [n_rows <= N] on the renderer's device")
+        return _p(rows), rows.shape[0]
+
     def path_begin(self, b):
         """org, beta, rad of the first vertices from what ``primary`` wrote into ``b``."""
         with torch.cuda.device(self.device):
@@ -243,36 +269,46 @@ class PathArrayRenderer(ArrayRenderer):
                                                       self._stream()))
 
     def sample_emitter(self, b, bounce: int, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
-                       lights: Optional[_lib.WfLights] = None):
-        """The emitter sample of the vertices in ``b``: ``lsel``, ``emit``, and ``wl`` towards a picked point light."""
+                       lights: Optional[_lib.WfLights] = None, rows: Optional[torch.Tensor] = None):
+        """The emitter sample of the vertices in ``b``: ``lsel``, ``emit``, and ``wl`` towards a picked point light.  ``rows``
+        (int64 [n_rows], distinct lanes): of the listed vertices only (``bsdfd_wf_sample_emitter_rows``)."""
         occlusion = self.occlusion if occlusion is None else occlusion
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().bsdfd_wf_sample_emitter(
-                C.byref(self.scene), C.byref(self.lights if lights is None else lights), bounce, int(bool(occlusion)), seed,
-                pass_idx, path_offset, b["mat"].shape[0], _p(b["org"]), _p(b["nrm"]), _p(b["wi"]), _p(b["mat"]), _p(b["wl"]),
-                _p(b["lsel"]), _p(b["emit"]), self._stream()))
+            args = [C.byref(self.scene), C.byref(self.lights if lights is None else lights), bounce, int(bool(occlusion)), seed,
+                    pass_idx, path_offset, b["mat"].shape[0], _p(b["org"]), _p(b["nrm"]), _p(b["wi"]), _p(b["mat"]), _p(b["wl"]),
+                    _p(b["lsel"]), _p(b["emit"])]
+            if rows is None:
+                _lib.check(_lib.lib().bsdfd_wf_sample_emitter(*args, self._stream()))
+            else:
+                _lib.check(_lib.lib().bsdfd_wf_sample_emitter_rows(*args, *self._list(rows, b), self._stream()))
         torch.autograd.graph.increment_version([b["wl"], b["lsel"], b["emit"]])
 
     def sample_env(self, b, bounce: int, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
-                   lights: Optional[_lib.WfLights] = None, env_dist=None):
+                   lights: Optional[_lib.WfLights] = None, env_dist=None, rows: Optional[torch.Tensor] = None):
         """The environment's emitter sample of the vertices in ``b`` that picked it (``lsel == -1``; all live ones without
-        lights): ``lpdf``, ``emit``, and ``wl`` on the balls, drawn from the ``EnvDistribution``."""
+        lights): ``lpdf``, ``emit``, and ``wl`` on the balls, drawn from the ``EnvDistribution``.  ``rows`` (int64 [n_rows],
+        distinct lanes): of the listed vertices only (``bsdfd_wf_sample_env_rows``)."""
         occlusion = self.occlusion if occlusion is None else occlusion
         lights = self.lights if lights is None else lights
         env_dist = self.env_dist if env_dist is None else env_dist
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().bsdfd_wf_sample_env(
-                C.byref(self.scene), _p(self.env), C.byref(env_dist.struct(self.device)), 1 if lights is None else lights.n_lights + 1,
-                bounce, int(bool(occlusion)), seed, pass_idx, path_offset, b["mat"].shape[0], _p(b["org"]), _p(b["nrm"]), _p(b["wi"]),
-                _p(b["mat"]), None if lights is None else _p(b["lsel"]), _p(b["wl"]), _p(b["lpdf"]), _p(b["emit"]), self._stream()))
+            args = [C.byref(self.scene), _p(self.env), C.byref(env_dist.struct(self.device)), 1 if lights is None else lights.n_lights + 1,
+                    bounce, int(bool(occlusion)), seed, pass_idx, path_offset, b["mat"].shape[0], _p(b["org"]), _p(b["nrm"]), _p(b["wi"]),
+                    _p(b["mat"]), None if lights is None else _p(b["lsel"]), _p(b["wl"]), _p(b["lpdf"]), _p(b["emit"])]
+            if rows is None:
+                _lib.check(_lib.lib().bsdfd_wf_sample_env(*args, self._stream()))
+            else:
+                _lib.check(_lib.lib().bsdfd_wf_sample_env_rows(*args, *self._list(rows, b), self._stream()))
         torch.autograd.graph.increment_version([b["wl"], b["lpdf"], b["emit"]])
 
     def bounce(self, b, bounce: int, last: bool, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
-               lights: Optional[_lib.WfLights] = None, env_dist=None, rr_depth: Optional[int] = None):
+               lights: Optional[_lib.WfLights] = None, env_dist=None, rr_depth: Optional[int] = None,
+               rows: Optional[torch.Tensor] = None):
         """Shade the vertices in ``b`` (``wo``, ``pdf_o``, ``pdf_l`` [, ``f_o``, ``f_l``] from the sampler; with lights also
         ``lsel`` and ``emit`` from ``sample_emitter``; with an ``EnvDistribution`` also ``lpdf`` and ``emit`` from ``sample_env``)
         and move the paths on.  ``rr_depth`` (default: the instance's): with an integer the same emitters go through
-        ``bsdfd_wf_bounce_rr``, which plays Russian roulette on the paths that would continue once ``bounce + 1 >= rr_depth``."""
+        ``bsdfd_wf_bounce_rr``, which plays Russian roulette on the paths that would continue once ``bounce + 1 >= rr_depth``.
+        ``rows`` (int64 [n_rows], distinct lanes): the listed vertices only, through ``bsdfd_wf_bounce_rows`` in every mode."""
         occlusion = self.occlusion if occlusion is None else occlusion
         lights = self.lights if lights is None else lights
         env_dist = self.env_dist if env_dist is None else env_dist
@@ -287,7 +323,9 @@ class PathArrayRenderer(ArrayRenderer):
             lit, env = lights is not None, env_dist is not None
             tail = [C.byref(lights) if lit else None, _p(b["lsel"]) if lit else None, _p(b["emit"]) if lit or env else None,
                     _p(b["lpdf"]) if env else None, C.byref(env_dist.struct(self.device)) if env else None]
-            if rr_depth is not None:
+            if rows is not None:
+                fn, args = _lib.lib().bsdfd_wf_bounce_rows, args + tail + [int(rr_depth or 0), *self._list(rows, b)]
+            elif rr_depth is not None:
                 fn, args = _lib.lib().bsdfd_wf_bounce_rr, args + tail + [int(rr_depth)]
             elif env:
                 fn, args = _lib.lib().bsdfd_wf_bounce_env, args + tail
@@ -320,29 +358,49 @@ class PathArrayRenderer(ArrayRenderer):
         offset = row_begin * self.camera.width * spp
         skey = (seed * 0x9E3779B97F4A7C15 + pass_idx + 1) & _M64
         n_balls = len(self.table)
-        lanes = []
+        lanes, lists = [], []
         depth = self.DEPTH_CAP if self.max_depth is None else self.max_depth   # (unbounded: the loop ends where no lane is live)
+        rows = None   # compact, from bounce 1 on: the lanes alive entering the bounce before, the front of its bucketing's permutation
         for k in range(depth):
+            on = {} if rows is None else {"rows": rows}
             if self.lights is not None:
-                self.sample_emitter(b, k, seed, pass_idx, offset)
+                self.sample_emitter(b, k, seed, pass_idx, offset, **on)
             if self.env_dist is not None:
-                self.sample_env(b, k, seed, pass_idx, offset)
-            plan = self.table.bucket(b["mat"], extra_bins=2)      # floor vertices and ended paths behind the materials
+                self.sample_env(b, k, seed, pass_idx, offset, **on)
+            if rows is None:
+                plan = self.table.bucket(b["mat"], extra_bins=2)  # floor vertices and ended paths behind the materials
+            else:
+                plan = self.table.bucket_rows(b["mat"], rows, extra_bins=1)   # ... and here ended paths are left out
             counts = plan[1]                                      # (already on the host)
             n_mat = sum(counts[:n_balls])
-            if n_mat + counts[n_balls] == 0:
+            n_live = n_mat + counts[n_balls]
+            if n_live == 0:
                 break
             lanes.append(n_mat)
+            lists.append(n if rows is None else rows.shape[0])
             if n_mat:
                 key = skey if k == 0 else skey ^ ((k * 0xD1B54A32D192ED03) & _M64)
-                b["wo"], b["pdf_o"], b["pdf_l"] = self.table.sample_pdf(plan, b["wi"], b["wl"], seed=key, offset=offset,
-                                                                        direct=n <= WavefrontPipeline.DIRECT_MAX_LANES)
-                if self.use_ground_truth:
-                    self.measured_table.eval_t(b["mat"], b["wi"], b["wo"], b["wl"], tint=self.plugin.albedo, out_o=b["f_o"],
-                                               out_l=b["f_l"])
+                if rows is None:
+                    b["wo"], b["pdf_o"], b["pdf_l"] = self.table.sample_pdf(plan, b["wi"], b["wl"], seed=key, offset=offset,
+                                                                            direct=n <= WavefrontPipeline.DIRECT_MAX_LANES)
+                    if self.use_ground_truth:
+                        self.measured_table.eval_t(b["mat"], b["wi"], b["wo"], b["wl"], tint=self.plugin.albedo, out_o=b["f_o"],
+                                                   out_l=b["f_l"])
+                else:   # into the arrays of bounce 0, no fill: bounce reads them on the material lanes of this list only
+                    self.table.sample_pdf(plan, b["wi"], b["wl"], seed=key, offset=offset, direct=True,
+                                          out=(b["wo"], b["pdf_o"], b["pdf_l"]))
+                    if self.use_ground_truth:
+                        self.measured_table.eval_t(b["mat"], b["wi"], b["wo"], b["wl"], tint=self.plugin.albedo, out_o=b["f_o"],
+                                                   out_l=b["f_l"], rows=plan[0][:n_mat])
             # (no material lane: only floor vertices are left, which read neither the sampler's nor the evaluator's arrays)
-            self.bounce(b, k, k == depth - 1, seed, pass_idx, offset)
+            if rows is None:
+                self.bounce(b, k, k == depth - 1, seed, pass_idx, offset)
+            else:
+                self.bounce(b, k, k == depth - 1, seed, pass_idx, offset, rows=plan[0])
+            if self.compact:
+                rows = plan[0][:n_live]
         self.stats["lanes_per_bounce"] = lanes
+        self.stats["list_per_bounce"] = lists
         self.stats["depth"] = len(lanes)
         self.stats["depth_cap_hit"] = self.max_depth is None and len(lanes) == depth
         self.resolve(row_begin, row_end, spp, b, film)

@@ -53,7 +53,10 @@ extern "C" {
  *      take a struct of their own, bsdfd_principled: the principled ground truth of the full-sphere plugin;
  *      bsdfd_analytic_table_create(), bsdfd_analytic_table_destroy(), bsdfd_analytic_eval_table(),
  *      bsdfd_analytic_sample_weight_table(), bsdfd_analytic_sample_table() and bsdfd_analytic_pdf_table(), which take a struct
- *      of their own, bsdfd_analytic_entry: both analytic models for a mixed-material wavefront in one launch. */
+ *      of their own, bsdfd_analytic_entry: both analytic models for a mixed-material wavefront in one launch;
+ *      bsdfd_bucket_rows(), bsdfd_wf_bounce_rows(), bsdfd_wf_sample_emitter_rows(), bsdfd_wf_sample_env_rows(),
+ *      bsdfd_measured_eval_table_rows() and bsdfd_analytic_eval_table_rows(): the per-depth calls of the array scene over a
+ *      live-lane list. */
 #define BSDFD_ABI_VERSION 8
 
 #define BSDFD_OK 0
@@ -740,6 +743,49 @@ int bsdfd_wf_bounce_rr(const bsdfd_wf_scene* scene, const float* env, int32_t bo
                        const float* pdf_l, const float* f_o, const float* f_l, const bsdfd_wf_lights* lights,
                        const int32_t* lsel, const float* emit, const float* lpdf, const bsdfd_env_dist* dist, int32_t rr_depth,
                        void* hip_stream);
+
+/* ---- The per-depth calls of the array scene over a live-lane list (csrc/bucket.hip, bounce.hip, pathlights.hip, pathenv.hip,
+ * measured_table.hip, analytic_table.hip) ----------------------------------------------------------------------------
+ * A deep path tracer serves a few hundred lanes of a wavefront of a million; the calls above are launched over all N.  These are
+ * their list forms: `rows` (int64 [n_rows], device) names the lanes to serve, the arrays keep their N rows and their lane order,
+ * and thread t works on lane rows[t] exactly as the full-width call works on that lane — a lane's Philox counters are keyed by
+ * path_offset + lane, never by the thread — so every listed lane gets the full-width call's result bit for bit.  For each of them:
+ *   - the entries of `rows` are distinct and in [0, N);  0 <= n_rows <= N;
+ *   - a row that is not listed keeps every byte of every array;
+ *   - n_rows == 0 is a no-op (rows may then be NULL); otherwise every check of the full-width sibling applies.
+ *
+ * bsdfd_bucket_rows is bsdfd_bucket_by_material (n_materials <= 64) over the rows of a list: a row's id is
+ * material_id[rows[r]] and perm receives rows[r], so perm holds LANE numbers, bucket by bucket, stable in list order.  Rows whose id
+ * is outside [0, n_materials) are left out; the kept rows fill perm[0 .. sum(counts)), the rest of perm is unspecified.  The
+ * workspace is bsdfd_bucket_workspace_bytes(n_rows, n_materials).  Allocates nothing, does not synchronise; n_rows == 0 only
+ * zeroes counts.  (The front of the permutation a path tracer gets by leaving its "ended" id out of range is its next list.)
+ *
+ * bsdfd_wf_bounce_rows takes bsdfd_wf_bounce_rr's arguments and selects the call as it does; rr_depth == 0 means no roulette
+ * (bsdfd_wf_bounce, _lit or _env), rr_depth >= 1 is bsdfd_wf_bounce_rr.  bsdfd_wf_sample_emitter_rows and bsdfd_wf_sample_env_rows
+ * are bsdfd_wf_sample_emitter and bsdfd_wf_sample_env.  bsdfd_measured_eval_table_rows and bsdfd_analytic_eval_table_rows are the
+ * two tables' eval(): f_o / f_l are written at the listed rows only, NaN where a listed row has no ground truth. */
+int bsdfd_bucket_rows(const int64_t* material_id, const int64_t* rows, int64_t n_rows, int32_t n_materials, int64_t* perm,
+                      int64_t* counts, void* workspace, int64_t workspace_bytes, void* hip_stream);
+int bsdfd_wf_bounce_rows(const bsdfd_wf_scene* scene, const float* env, int32_t bounce, int32_t last, int32_t occlusion,
+                         uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, float* org, float* nrm, float* wi,
+                         float* wl, int64_t* material, float* beta, float* rad, const float* wo, const float* pdf_o,
+                         const float* pdf_l, const float* f_o, const float* f_l, const bsdfd_wf_lights* lights,
+                         const int32_t* lsel, const float* emit, const float* lpdf, const bsdfd_env_dist* dist, int32_t rr_depth,
+                         const int64_t* rows, int64_t n_rows, void* hip_stream);
+int bsdfd_wf_sample_emitter_rows(const bsdfd_wf_scene* scene, const bsdfd_wf_lights* lights, int32_t bounce, int32_t occlusion,
+                                 uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, const float* org, const float* nrm,
+                                 const float* wi, const int64_t* material, float* wl, int32_t* lsel, float* emit,
+                                 const int64_t* rows, int64_t n_rows, void* hip_stream);
+int bsdfd_wf_sample_env_rows(const bsdfd_wf_scene* scene, const float* env, const bsdfd_env_dist* dist, int32_t n_e, int32_t bounce,
+                             int32_t occlusion, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, const float* org,
+                             const float* nrm, const float* wi, const int64_t* material, const int32_t* lsel, float* wl, float* lpdf,
+                             float* emit, const int64_t* rows, int64_t n_rows, void* hip_stream);
+int bsdfd_measured_eval_table_rows(bsdfd_measured_table t, const int64_t* material_id, const float* wi, const float* wo,
+                                   const float* wl, int64_t N, const float* tint, float* f_o, float* f_l, const int64_t* rows,
+                                   int64_t n_rows, void* hip_stream);
+int bsdfd_analytic_eval_table_rows(bsdfd_analytic_table t, const int64_t* material_id, const float* wi, const float* wo,
+                                   const float* wl, int64_t N, const float* tint, float* f_o, float* f_l, const int64_t* rows,
+                                   int64_t n_rows, void* hip_stream);
 
 const char* bsdfd_last_error(void);
 const char* bsdfd_version(void);

@@ -27,6 +27,13 @@ merit.
   (b) PathArrayRenderer(max_depth=None, rr_depth=R): ms per pass, the depth reached and the lanes per bounce, next to the fixed
       depths 8 and 16 without roulette;
   (c) the per-path radiance variance (as above) x time of (b) against those fixed depths.
+
+``--compact`` measures the live-lane list -> profiles/pathtrace_compact.json: PathArrayRenderer(compact=True) against compact=False
+in the same process, alternating per round, at depths 1 / 2 / 4 / 8 and at max_depth=None, rr_depth=5; with ``--lights N`` or
+``--env-sampling importance`` the same under those emitters (the file keeps one section per emitter setting).  Both films are
+compared bit for bit first.  Recorded: ms per pass of both, the compact=False variant's own round-to-round spread (a difference
+inside it is "no difference this record resolves"), ms per bounce from device events, the list and the lanes per bounce, and the
+per-path variance x time of the unbounded case.
 """
 import argparse
 import json
@@ -51,14 +58,17 @@ ap.add_argument("--env-sampling", choices=("cosine", "importance"), default="cos
                 help="importance: measure the importance-sampled environment against the cosine renderer instead")
 ap.add_argument("--rr-depth", type=int, default=None, metavar="R",
                 help="measure Russian roulette from the R-th vertex on, and unbounded depth, against fixed depths instead")
+ap.add_argument("--compact", action="store_true",
+                help="measure compact=True (bounces >= 1 on a live-lane list) against compact=False instead; combines with "
+                     "--lights and --env-sampling")
 ap.add_argument("--out", default=None, help="default: profiles/pathtrace.json, pathtrace_lights.json with --lights, "
                                             "pathtrace_envis.json with --env-sampling importance, pathtrace_rr.json with --rr-depth")
 a = ap.parse_args()
 envis = a.env_sampling == "importance"
-if (envis and a.lights) or (a.rr_depth is not None and (envis or a.lights)):
+if (envis and a.lights) or (a.rr_depth is not None and (envis or a.lights or a.compact)):
     sys.exit("--lights, --env-sampling importance and --rr-depth are measured one at a time")
 a.out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "pathtrace_rr.json" if a.rr_depth is not None else "pathtrace_envis.json" if envis
+                              "pathtrace_compact.json" if a.compact else "pathtrace_rr.json" if a.rr_depth is not None else "pathtrace_envis.json" if envis
                               else "pathtrace_lights.json" if a.lights else "pathtrace.json")
 if not torch.cuda.is_available():
     sys.exit("tools/pathtrace_bench.py measures on the GPU: no device visible")
@@ -66,8 +76,22 @@ if not torch.cuda.is_available():
 cam, centers, radii = WF.array0_scene(a.width, a.height)
 table = MaterialTable([m + "_" + a.domain for m in WF.ARRAY0_MATERIALS])
 LIT_DEPTHS = (1, 2, 4)
+COMPACT_CASES = {"d1": dict(max_depth=1, occlusion=True), "d2": dict(max_depth=2), "d4": dict(max_depth=4), "d8": dict(max_depth=8),
+                 "unbounded_rr5": dict(max_depth=None, rr_depth=5)}
 RR_INACTIVE = 9   # an rr_depth the depths 4 and 8 never reach: the RR kernels without a single decision
-if a.rr_depth is not None:
+if a.compact:
+    emitters, section = {}, "cosine"
+    if a.lights:
+        from bsdf_diffusion_sampling_amd.pathtrace import PointLight
+        emitters, section = dict(lights=[PointLight((4.0 * np.sin(2 * np.pi * k / a.lights), 5.0, -4.0 * np.cos(2 * np.pi * k / a.lights)),
+                                                    200.0) for k in range(a.lights)]), f"lights{a.lights}"
+    elif envis:
+        emitters, section = dict(env_sampling="importance"), "importance"
+    variants = {}
+    for case, kw in COMPACT_CASES.items():
+        for name, compact in (("full", False), ("compact", True)):
+            variants[f"{case}_{name}"] = PathArrayRenderer(table, centers, radii, camera=cam, compact=compact, **kw, **emitters)
+elif a.rr_depth is not None:
     variants = {}
     for d in (4, 8):
         variants[f"plain_d{d}"] = PathArrayRenderer(table, centers, radii, camera=cam, max_depth=d)
@@ -104,6 +128,17 @@ def run(r, passes, first_pass=0):
     torch.cuda.synchronize(dev)
 
 
+if a.compact:   # the equalities first: one pass of each pair on the same film fill
+    for case in COMPACT_CASES:
+        films = []
+        for name in ("full", "compact"):
+            film.fill_(0.25)
+            variants[f"{case}_{name}"].render_pass(film, 0, a.height, a.spp, 0, 0)
+            torch.cuda.synchronize(dev)
+            films.append(film.clone())
+        if not torch.equal(films[0].view(torch.int32), films[1].view(torch.int32)):
+            sys.exit(f"{case}: the films of compact=False and compact=True differ")
+    film.zero_()
 for r in variants.values():   # every shape, every code object
     run(r, 3)
 times = {k: [] for k in variants}
@@ -138,6 +173,60 @@ def path_variance(r, passes=5):
     return float(np.mean(out))
 
 
+def per_bounce_ms(r):
+    """ms of every bounce (median over --passes passes): a device event at every bucketing (= the start of a bounce; the last one
+    is the bucketing that found no live lane, when there is one) and at the resolve."""
+    marks, per_pass = [], []
+    bucket, bucket_rows, resolve = r.table.bucket, r.table.bucket_rows, r.resolve
+
+    def marked(inner):
+        def f(*args, **kw):
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            marks.append(e)
+            return inner(*args, **kw)
+        return f
+    r.table.bucket, r.table.bucket_rows, r.resolve = marked(bucket), marked(bucket_rows), marked(resolve)
+    try:
+        for k in range(a.passes):
+            del marks[:]
+            r.render_pass(film, 0, a.height, a.spp, 0, 1000)     # (one pass index: the same depth every time)
+            torch.cuda.synchronize(dev)
+            per_pass.append([marks[i].elapsed_time(marks[i + 1]) for i in range(len(marks) - 1)])
+    finally:
+        del r.table.bucket, r.table.bucket_rows, r.resolve
+    return [float(np.median([p[i] for p in per_pass])) for i in range(min(len(p) for p in per_pass))]
+
+
+if a.compact:
+    sec = {"films_bit_identical": True, "case": {}}
+    for case in COMPACT_CASES:
+        full, comp = times[f"{case}_full"], times[f"{case}_compact"]
+        spread, diff = float(max(full) - min(full)), med[f"{case}_compact"] - med[f"{case}_full"]
+        rf, rc = variants[f"{case}_full"], variants[f"{case}_compact"]
+        ms_full, ms_comp = per_bounce_ms(rf), per_bounce_ms(rc)
+        sec["case"][case] = {"full_pass_ms_median": med[f"{case}_full"], "compact_pass_ms_median": med[f"{case}_compact"],
+                             "compact_minus_full_ms": diff, "compact_over_full": med[f"{case}_compact"] / med[f"{case}_full"],
+                             "full_round_to_round_spread_ms": spread,
+                             "compact_round_to_round_spread_ms": float(max(comp) - min(comp)),
+                             "verdict": "no difference this record resolves" if abs(diff) <= spread
+                                        else "compact faster" if diff < 0 else "compact slower",
+                             "full_bounce_ms_median": ms_full, "compact_bounce_ms_median": ms_comp,
+                             "lanes_per_bounce": rc.stats["lanes_per_bounce"], "list_per_bounce": rc.stats["list_per_bounce"],
+                             "same_lanes_as_full": rc.stats["lanes_per_bounce"] == rf.stats["lanes_per_bounce"]}
+    var = path_variance(variants["unbounded_rr5_full"])
+    sec["unbounded_rr5_per_path_variance"] = var
+    sec["unbounded_rr5_variance_x_ms"] = {name: var * med[f"unbounded_rr5_{name}"] for name in ("full", "compact")}
+    try:
+        merged = json.load(open(a.out))
+    except (OSError, ValueError):
+        merged = {}
+    for k in ("pass_ms_median", "pass_ms_min"):
+        res.pop(k)
+    merged.update(res)
+    merged[section] = sec
+    write(merged)
+    sys.exit(0)
 if a.rr_depth is not None:
     res.update(rr_depth=a.rr_depth, rr_depth_inactive=RR_INACTIVE, inactive={}, unbounded={})
     for d in (4, 8):
