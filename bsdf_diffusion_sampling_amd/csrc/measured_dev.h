@@ -78,24 +78,52 @@ __device__ __forceinline__ float eval_plain(const Table& t, float x, float y) {
     return bilerp(d[0], d[1], d[t.w], d[t.w + 1], p.fx, p.fy);
 }
 
+// The fold of an anisotropic file.  Only phi_i in a half-plane (reduction 2: point symmetry) or a quadrant (reduction 4: two
+// mirror planes) is stored; Mitsuba folds with mulsign_neg(v, s) = -|..|, i.e. into y <= 0 (and x <= 0), where its files keep
+// phi_i.  Here the stored side is read off the file's own phi_i range (fold_x, fold_y), which is the same thing for such files
+// and right for any other.  (wix, wiy) is folded in place; the caller applies the returned flips to wo (measured_sample: to
+// the wo it returns).  A component on the wrong side is negated together with its partner of wo (reduction 2: both
+// components, and only wiy says when).  A ZERO component of either sign is on a symmetry plane, i.e. already on the stored
+// side: it flips nothing, and it takes the stored side's sign, so that atan2f answers inside [phi_i[0], phi_i[n_phi - 1]] —
+// with the other sign, (-x, +0) in a file stored over [-pi, -pi/2] has the azimuth +pi, which `interval` clamps to the slice
+// at -pi/2, the far end of the range.  Off the planes copysignf returns the bits the negation did.  (Reduction 2 stores both
+// sides of x: a zero x is read as +0 — adding +0 changes nothing else —, so that no result depends on a zero's sign.)
+struct Fold {
+    bool x, y;
+};
+__device__ __forceinline__ Fold fold_wi(const MeasuredDev& m, float& wix, float& wiy) {
+    Fold f{false, false};
+    if (m.reduction >= 2) {
+        f.y = wiy * m.fold_y < 0.0f;
+        f.x = m.reduction == 4 ? (wix * m.fold_x < 0.0f) : f.y;
+        wiy = copysignf(wiy, m.fold_y);
+        wix = m.reduction == 4 ? copysignf(wix, m.fold_x) : (f.x ? -wix : wix) + 0.0f;
+    }
+    return f;
+}
+
+// The half vector of a folded pair at the pole of its chart.  A zero of wi carries the stored side's sign after the fold, so
+// at the exact mirror direction wi.x + wo.x can come out as -0, and the azimuth of (+-0, +-0) is 0 or +-pi by the zeros' signs
+// alone — half a table apart, at the one point where it means nothing.  Adding +0 reads a -0 of ANY origin (the fold's, or a
+// product that underflowed off the planes) as +0 and changes no non-zero value; the azimuth differs for it only where both
+// components are zero: the pole's azimuth is 0.  (my = -0 next to mx < 0 moves from -pi to +pi, which the wrap of um_y takes to
+// the same 0.)  Files without a fold are not touched.
+__device__ __forceinline__ void unsign_zeros(const MeasuredDev& m, float& mx, float& my) {
+    if (m.reduction >= 2) { mx += 0.0f; my += 0.0f; }
+}
+
 // f(wi, wo) cos(theta_o) for one pair; false (and rgb = 0) on the lower hemispheres
 __device__ __forceinline__ bool measured_f(const MeasuredDev& m, float wix, float wiy, float wiz, float wox, float woy,
                                            float woz, float rgb[3]) {
     rgb[0] = rgb[1] = rgb[2] = 0.0f;
     if (!(wiz > 0.0f && woz > 0.0f)) return false;
-    if (m.reduction >= 2) {
-        // Symmetries of an anisotropic acquisition: only phi_i in a half-plane (reduction 2: point symmetry)
-        // or a quadrant (reduction 4: two mirror planes) is stored.  Mitsuba folds with mulsign_neg(v, s) =
-        // -|..|, i.e. into y <= 0 (and x <= 0), which is where its files keep phi_i; here the target is read
-        // off the file's own phi_i range, which is the same thing for such files and right for any other.
-        const bool fy = wiy * m.fold_y < 0.0f;
-        const bool fx = m.reduction == 4 ? (wix * m.fold_x < 0.0f) : fy;
-        if (fx) { wix = -wix; wox = -wox; }
-        if (fy) { wiy = -wiy; woy = -woy; }
-    }
+    const Fold fold = fold_wi(m, wix, wiy);
+    if (fold.x) wox = -wox;
+    if (fold.y) woy = -woy;
     float mx = wix + wox, my = wiy + woy, mz = wiz + woz;
     const float inv = 1.0f / fmaxf(sqrtf(mx * mx + my * my + mz * mz), 1e-30f);
     mx *= inv; my *= inv; mz *= inv;
+    unsign_zeros(m, mx, my);
     const float theta_i = elevation(wix, wiy, wiz), phi_i = atan2f(wiy, wix);
     const float theta_m = elevation(mx, my, mz), phi_m = atan2f(my, mx);
     const float inv_2pi = 0.15915494309189533577f, pi = 3.14159265358979323846f;
@@ -318,13 +346,7 @@ __device__ __forceinline__ bool measured_sample(const MeasuredDev& m, float wix,
     weight[0] = weight[1] = weight[2] = 0.0f;
     pdf = 0.0f;
     if (!(wiz > 0.0f)) return false;
-    bool flip_x = false, flip_y = false;
-    if (m.reduction >= 2) {  // measured_f's fold; wo is unfolded at the end
-        flip_y = wiy * m.fold_y < 0.0f;
-        flip_x = m.reduction == 4 ? (wix * m.fold_x < 0.0f) : flip_y;
-        if (flip_x) wix = -wix;
-        if (flip_y) wiy = -wiy;
-    }
+    const Fold fold = fold_wi(m, wix, wiy);  // wo is unfolded at the end
     const float theta_i = elevation(wix, wiy, wiz), phi_i = atan2f(wiy, wix);
     const float inv_2pi = 0.15915494309189533577f, pi = 3.14159265358979323846f;
     const float ui_x = sqrtf(theta_i * (2.0f / pi)), ui_y = (phi_i + pi) * inv_2pi;
@@ -349,8 +371,8 @@ __device__ __forceinline__ bool measured_sample(const MeasuredDev& m, float wix,
     const float d = mx * wix + my * wiy + mz * wiz;
     float wox = 2.0f * d * mx - wix, woy = 2.0f * d * my - wiy;
     const float woz = 2.0f * d * mz - wiz;
-    if (flip_x) wox = -wox;
-    if (flip_y) woy = -woy;
+    if (fold.x) wox = -wox;
+    if (fold.y) woy = -woy;
     wo[0] = wox; wo[1] = woy; wo[2] = woz;
 
     const float p = vndf_pdf * lum_pdf / sample_jacobian(um_x, st, d);
@@ -379,15 +401,13 @@ __device__ __forceinline__ bool measured_sample(const MeasuredDev& m, float wix,
 __device__ __forceinline__ float measured_pdf(const MeasuredDev& m, float wix, float wiy, float wiz, float wox, float woy,
                                               float woz) {
     if (!(wiz > 0.0f && woz > 0.0f)) return 0.0f;
-    if (m.reduction >= 2) {
-        const bool fy = wiy * m.fold_y < 0.0f;
-        const bool fx = m.reduction == 4 ? (wix * m.fold_x < 0.0f) : fy;
-        if (fx) { wix = -wix; wox = -wox; }
-        if (fy) { wiy = -wiy; woy = -woy; }
-    }
+    const Fold fold = fold_wi(m, wix, wiy);
+    if (fold.x) wox = -wox;
+    if (fold.y) woy = -woy;
     float mx = wix + wox, my = wiy + woy, mz = wiz + woz;
     const float inv = 1.0f / fmaxf(sqrtf(mx * mx + my * my + mz * mz), 1e-30f);
     mx *= inv; my *= inv; mz *= inv;
+    unsign_zeros(m, mx, my);
     const float theta_i = elevation(wix, wiy, wiz), phi_i = atan2f(wiy, wix);
     const float theta_m = elevation(mx, my, mz), phi_m = atan2f(my, mx);
     const float inv_2pi = 0.15915494309189533577f, pi = 3.14159265358979323846f;

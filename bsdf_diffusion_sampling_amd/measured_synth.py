@@ -28,16 +28,30 @@ def _smooth(g, *shape):
     return a.astype(np.float32)
 
 
-def write_anisotropic(path, seed=7, vndf_hw=(12, 20), rgb_hw=(6, 10), ndf_hw=(9, 17)):
-    """Anisotropic, reduction 4 (phi_i over Mitsuba's quadrant), jacobian 1: the fields of test_gpu_measured.py's synthetic file."""
+def write_anisotropic(path, seed=7, vndf_hw=(12, 20), rgb_hw=(6, 10), ndf_hw=(9, 17), phi_range=(-np.pi, -np.pi / 2), n_phi=4,
+                      closed=False):
+    """Anisotropic, jacobian 1, phi_i in ``n_phi`` slices over ``phi_range``: a quadrant (reduction 4; the default is Mitsuba's, and
+    the fields of test_gpu_measured.py's synthetic file), a half-plane (reduction 2) or the full circle (reduction 1), whose last
+    slice and whose last azimuth row of ``sigma`` repeat the first, as an acquisition's do.  ``closed``: the tables over the
+    half vector's azimuth (``vndf``, ``ndf``) and over the warped copy of it (``luminance``, ``rgb``: the VNDF warp takes the
+    two ends of the azimuth to their two ends) also end with the row they start with, as a measured material's do — the evaluator
+    wraps that azimuth at +pi onto -pi (Mitsuba's ``u - floor(u)``), where only such tables are continuous."""
     g = np.random.default_rng(seed)
-    phi_i = np.linspace(-np.pi, -np.pi / 2, 4).astype(np.float32)
+    phi_i = np.linspace(phi_range[0], phi_range[1], n_phi).astype(np.float32)
     theta_i = np.linspace(0.0, np.pi / 2, 5).astype(np.float32)
-    write_tensor_file(path, {
+    fields = {
         "version": np.array([1, 0], dtype=np.uint8), "description": np.frombuffer(b"synthetic anisotropic", dtype=np.uint8),
         "phi_i": phi_i, "theta_i": theta_i, "sigma": _smooth(g, *ndf_hw), "ndf": _smooth(g, *ndf_hw) * 3,
-        "vndf": _smooth(g, 4, 5, *vndf_hw), "luminance": _smooth(g, 4, 5, *rgb_hw), "rgb": _smooth(g, 4, 5, 3, *rgb_hw),
-        "jacobian": np.array([1], dtype=np.uint8)})
+        "vndf": _smooth(g, n_phi, 5, *vndf_hw), "luminance": _smooth(g, n_phi, 5, *rgb_hw), "rgb": _smooth(g, n_phi, 5, 3, *rgb_hw),
+        "jacobian": np.array([1], dtype=np.uint8)}
+    if closed:
+        for k in ("vndf", "ndf", "luminance", "rgb"):
+            fields[k][..., -1, :] = fields[k][..., 0, :]
+    if np.isclose(phi_range[1] - phi_range[0], 2 * np.pi):     # the full circle: phi_i ends on the angle it starts on
+        for k in ("vndf", "luminance", "rgb"):
+            fields[k][-1] = fields[k][0]
+        fields["sigma"][-1] = fields["sigma"][0]
+    write_tensor_file(path, fields)
     return path
 
 

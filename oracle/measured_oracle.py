@@ -211,21 +211,39 @@ class MeasuredBSDF:
         self.vndf = Marginal2D(t["vndf"], (phi_i, theta_i), normalize=True, sampling=True)
         self.spectra = Marginal2D(t["rgb"], (phi_i, theta_i, np.arange(3.0)), normalize=False, sampling=False)
 
+    def folded_azimuth(self, wi):
+        """phi_i as ``eval`` forms it: the azimuth of the folded incident direction (the tests hold it to the stored range)."""
+        wi = np.asarray(wi, dtype=np.float64).copy()
+        self._fold(wi, np.zeros_like(wi))
+        return np.arctan2(wi[:, 1], wi[:, 0])
+
+    def _fold(self, wi, wo):
+        """Folds wi onto the side of the file's phi_i range and wo with it, both in place."""
+        if self.reduction >= 2:
+            # only phi_i in a half-plane (reduction 2) or quadrant (reduction 4) is stored; Mitsuba folds with
+            # mulsign_neg into y <= 0 (x <= 0), where its files keep phi_i — here the stored side is read off the
+            # file's phi_i range.  A component on the wrong side is negated, in wi and wo alike; a ZERO component
+            # of either sign is on a symmetry plane: it flips nothing and takes the stored side's sign, so that
+            # arctan2 answers inside [phi_i[0], phi_i[-1]] (tests/test_measured_fold_cpu.py, on every stored range)
+            fy = wi[:, 1] * self.fold[1] < 0
+            fx = (wi[:, 0] * self.fold[0] < 0) if self.reduction == 4 else fy
+            wo[:, 0] = np.where(fx, -wo[:, 0], wo[:, 0])
+            wo[:, 1] = np.where(fy, -wo[:, 1], wo[:, 1])
+            # (reduction 2 stores both sides of x: a zero x is read as +0)
+            wi[:, 0] = np.copysign(wi[:, 0], self.fold[0]) if self.reduction == 4 else np.where(fx, -wi[:, 0], wi[:, 0]) + 0.0
+            wi[:, 1] = np.copysign(wi[:, 1], self.fold[1])
+
     def eval(self, wi, wo):
         """wi, wo [N,3] unit vectors in the local frame -> f(wi, wo) cos(theta_o), [N,3] rgb."""
         wi, wo = np.asarray(wi, dtype=np.float64).copy(), np.asarray(wo, dtype=np.float64).copy()
         active = (wi[:, 2] > 0) & (wo[:, 2] > 0)
-        if self.reduction >= 2:
-            # only phi_i in a half-plane (reduction 2) or quadrant (reduction 4) is stored; Mitsuba folds with
-            # mulsign_neg into y <= 0 (x <= 0), where its files keep phi_i — here the target quadrant is read
-            # off the file's phi_i range (untested against a real anisotropic file: none ships with the reference)
-            fy = wi[:, 1] * self.fold[1] < 0
-            fx = (wi[:, 0] * self.fold[0] < 0) if self.reduction == 4 else fy
-            for v in (wi, wo):
-                v[:, 0] = np.where(fx, -v[:, 0], v[:, 0])
-                v[:, 1] = np.where(fy, -v[:, 1], v[:, 1])
+        self._fold(wi, wo)
         wm = wi + wo
         wm /= np.maximum(np.linalg.norm(wm, axis=1, keepdims=True), 1e-30)
+        if self.reduction >= 2:
+            # a zero of wi carries the stored side's sign, so at the exact mirror direction wi + wo can hold -0, and the
+            # azimuth of (+-0, +-0) would be 0 or +-pi by the zeros' signs alone: -0 -> +0, the pole's azimuth is 0
+            wm[:, :2] += 0.0
         theta_i, phi_i = elevation(wi), np.arctan2(wi[:, 1], wi[:, 0])
         theta_m, phi_m = elevation(wm), np.arctan2(wm[:, 1], wm[:, 0])
         # unit-square coordinates: x = elevation, y = azimuth (tables are stored [azimuth][elevation])

@@ -151,12 +151,24 @@ class MeasuredSampler:
 
     # -- pieces -------------------------------------------------------------------------------------------------------
     def _fold(self, wi):
+        """-> (wi folded onto the stored side, flip_x [N], flip_y [N]): csrc/measured_dev.h's fold_wi.  A component on the wrong
+        side is negated (the flips are what the caller applies to wo); a zero component of either sign flips nothing and takes
+        the stored side's sign, so that arctan2 answers inside [phi_i[0], phi_i[-1]]."""
         n = len(wi)
         fx = fy = np.zeros(n, dtype=bool)
+        wif = wi.copy()
         if self.reduction >= 2:
-            fy = wi[:, 1] * self.dt.type(self.fold[1]) < 0
-            fx = (wi[:, 0] * self.dt.type(self.fold[0]) < 0) if self.reduction == 4 else fy
-        return fx, fy
+            sx, sy = self.dt.type(self.fold[0]), self.dt.type(self.fold[1])
+            fy = wi[:, 1] * sy < 0
+            fx = (wi[:, 0] * sx < 0) if self.reduction == 4 else fy
+            wif[:, 1] = np.copysign(wi[:, 1], sy)
+            # (reduction 2 stores both sides of x: a zero x is read as +0)
+            wif[:, 0] = np.copysign(wi[:, 0], sx) if self.reduction == 4 else np.where(fx, -wi[:, 0], wi[:, 0]) + self.dt.type(0)
+        return wif, fx, fy
+
+    def folded_azimuth(self, wi):
+        """phi_i as every call forms it: the azimuth of the folded incident direction (the tests hold it to the stored range)."""
+        return self._incident(self._fold(np.asarray(wi).astype(self.dt))[0])[1]
 
     @staticmethod
     def _flip(v, fx, fy):
@@ -201,8 +213,7 @@ class MeasuredSampler:
         dt, one = self.dt, self.dt.type(1)
         wi, u = np.asarray(wi).astype(dt), np.asarray(u).astype(dt)
         active = wi[:, 2] > 0
-        fx, fy = self._fold(wi)
-        wif = self._flip(wi, fx, fy)
+        wif, fx, fy = self._fold(wi)
         theta_i, phi_i, u_wi = self._incident(wif)
         param = (phi_i, theta_i)
         s = (u[:, 1].copy(), u[:, 0].copy())               # Mitsuba's swap
@@ -230,10 +241,12 @@ class MeasuredSampler:
 
     def _half_vector(self, wi, wo):
         dt = self.dt
-        fx, fy = self._fold(wi)
-        wif, wof = self._flip(wi, fx, fy), self._flip(wo, fx, fy)
+        wif, fx, fy = self._fold(wi)
+        wof = self._flip(wo, fx, fy)
         m = wif + wof
         m = (m / np.maximum(np.sqrt((m * m).sum(1, keepdims=True)), dt.type(1e-30))).astype(dt)
+        if self.reduction >= 2:                            # unsign_zeros: -0 -> +0, the pole (+-0, +-0) has the azimuth 0
+            m[:, :2] = m[:, :2] + dt.type(0)
         theta_i, phi_i, u_wi = self._incident(wif)
         theta_m, phi_m = self._elevation(m), np.arctan2(m[:, 1], m[:, 0])
         um_y = ((phi_m - phi_i if self.isotropic else phi_m) + self.pi) * (dt.type(0.5) / self.pi)
@@ -262,3 +275,26 @@ class MeasuredSampler:
         if tint is not None:
             f = f * np.asarray(tint).astype(dt)
         return np.where(active[:, None], f, 0).astype(dt)
+
+
+# -- the yardstick rule of the GPU tests (test_gpu_measured_sampling.py, test_gpu_measured_fold.py) -------------------------------
+def sample_errors(res, ref, rows):
+    """(wo, pdf, weight) against the fp64 reference on `rows` -> {quantity: per-row error}."""
+    wo, pdf, w = (np.asarray(a, dtype=np.float64)[rows] for a in res)
+    wo_r, pdf_r, w_r = (a[rows] for a in ref)
+    return {"wo": np.abs(wo - wo_r).max(1), "pdf": np.abs(pdf - pdf_r) / pdf_r,
+            "weight": np.abs(w - w_r).max(1) / (np.abs(w_r).max(1) + 1e-3)}
+
+
+def held_to_yardstick(label, got, yard, maxima=True):
+    """Each quantity's p99 (and max) of `got` is at most 4x the yardstick's; the message carries every figure."""
+    fig = {q: dict(gpu_p99=np.percentile(got[q], 99), yard_p99=np.percentile(yard[q], 99), gpu_max=got[q].max(), yard_max=yard[q].max())
+           for q in got}
+    msg = label + ": " + "; ".join(f"{q} p99 gpu {f['gpu_p99']:.3e} yardstick {f['yard_p99']:.3e}, max gpu {f['gpu_max']:.3e} "
+                                   f"yardstick {f['yard_max']:.3e}" for q, f in fig.items())
+    print(msg)
+    for q, f in fig.items():
+        assert f["gpu_p99"] <= 4 * f["yard_p99"], msg
+        if maxima:
+            assert f["gpu_max"] <= 4 * f["yard_max"], msg
+    return fig

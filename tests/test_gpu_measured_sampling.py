@@ -17,6 +17,7 @@ from bsdf_diffusion_sampling_amd import measured_synth  # noqa: E402
 from oracle import measured_oracle as M  # noqa: E402
 
 import measured_sampling_ref as R  # noqa: E402
+from measured_sampling_ref import held_to_yardstick as _held_to_yardstick, sample_errors as _sample_errors  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden")
@@ -65,28 +66,6 @@ def case(paths, gpu):
                                 wi_d=wi_d, u_d=u_d, got_d=got, got=tuple(t.cpu().numpy() for t in got))
         return cache[which]
     return get
-
-
-def _sample_errors(res, ref, rows):
-    """(wo, pdf, weight) against the fp64 reference on `rows` -> {quantity: per-row error}."""
-    wo, pdf, w = (np.asarray(a, dtype=np.float64)[rows] for a in res)
-    wo_r, pdf_r, w_r = (a[rows] for a in ref)
-    return {"wo": np.abs(wo - wo_r).max(1), "pdf": np.abs(pdf - pdf_r) / pdf_r,
-            "weight": np.abs(w - w_r).max(1) / (np.abs(w_r).max(1) + 1e-3)}
-
-
-def _held_to_yardstick(label, got, yard, maxima=True):
-    """Each quantity's p99 (and max) of `got` is at most 4x the yardstick's; the message carries every figure."""
-    fig = {q: dict(gpu_p99=np.percentile(got[q], 99), yard_p99=np.percentile(yard[q], 99), gpu_max=got[q].max(), yard_max=yard[q].max())
-           for q in got}
-    msg = label + ": " + "; ".join(f"{q} p99 gpu {f['gpu_p99']:.3e} yardstick {f['yard_p99']:.3e}, max gpu {f['gpu_max']:.3e} "
-                                   f"yardstick {f['yard_max']:.3e}" for q, f in fig.items())
-    print(msg)
-    for q, f in fig.items():
-        assert f["gpu_p99"] <= 4 * f["yard_p99"], msg
-        if maxima:
-            assert f["gpu_max"] <= 4 * f["yard_max"], msg
-    return fig
 
 
 @pytest.mark.parametrize("which", FILES)
