@@ -1,6 +1,7 @@
 // analytic_host.h — host side of the two analytic descriptors: their checks and what is derived from them, once per call
 // (principled.hip, dielectric.hip) or once per table (analytic_table.hip).  One statement of each, so that a table row is handed
-// the very descriptor the single-material kernel gets.
+// the very descriptor the single-material kernel gets.  (The device side the three share: analytic_rows.h; the count checks and
+// the launch: rows.h.)
 #pragma once
 #include <cmath>
 

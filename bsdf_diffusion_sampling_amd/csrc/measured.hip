@@ -115,20 +115,11 @@ std::vector<float> as_f32(const Field& f) {
     return v;
 }
 
-int measured_launch_checks(bsdfd_measured_handle h, int64_t n) {
-    if (!h) return bsdfd_fail_(BSDFD_EINVAL, "null handle");
-    if (n < 0) return bsdfd_fail_(BSDFD_EINVAL, "N must be >= 0");
-    int dev = -1;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev != h->device) return bsdfd_fail_(BSDFD_EINVAL, "measured handle belongs to another device");
-    if (((long long)n + 255) / 256 > 0x7fffffffLL) return bsdfd_fail_(BSDFD_EINVAL, "N too large for one launch");
-    return BSDFD_OK;
-}
-
 // the host path of the four launchers: `kernel` over N rows of h's material, `args` behind the descriptor
 template <class... P, class... A>
 int measured_launch(bsdfd_measured_handle h, int64_t n, bool pointers_given, void (*kernel)(P...), void* stream, A... args) {
-    if (int rc = measured_launch_checks(h, n)) return rc;
+    if (!h) return bsdfd_fail_(BSDFD_EINVAL, "null handle");
+    if (int rc = rows::launch_checks(n, rows::kMaxRowsSingle, "measured handle", &h->device)) return rc;
     return launch_rows(n, pointers_given ? nullptr : "null pointer", kernel, stream, h->dev, args...);
 }
 

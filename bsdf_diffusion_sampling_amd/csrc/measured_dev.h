@@ -1,9 +1,8 @@
-// measured_dev.h — device side of the RGL measured-BSDF model, and the launchers' common host path (the model and the rest
-// of the host part: measured.hip), shared by
-// the translation units that evaluate it: measured.hip (one material per launch) and measured_table.hip (a mixed-material
-// wavefront in one launch).  Both inline the same measured_f (eval), measured_sample and measured_pdf (the file's own importance
-// sampler), run the same row functions (eval_row, weight_row, sample_row, pdf_row) and compute the same bits (see the pragma
-// below); their launchers share launch_rows.
+// measured_dev.h — device side of the RGL measured-BSDF model (the model's host part: measured.hip), shared by the translation
+// units that evaluate it: measured.hip (one material per launch) and measured_table.hip (a mixed-material wavefront in one
+// launch).  Both inline the same measured_f (eval), measured_sample and measured_pdf (the file's own importance sampler), run the
+// same row functions (eval_row, weight_row, sample_row, pdf_row) and compute the same bits (see the pragma below).  What a row
+// kernel and its launcher need whatever the model — Tint, store3, launch_rows, the launch checks — is rows.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,14 +11,18 @@
 
 #include "bsdfd.h"
 #include "common.h"
+#include "rows.h"
 
-// Fused multiply-adds are formed per source expression, by the front end, from here to the end of the including translation
-// unit — not wherever the optimiser finds a product next to a sum (hipcc's default): that choice depends on the code around an
-// inlined copy (which pairs the vectoriser packs, which of a*b + c*d becomes the fma's product), and it made the kernels of
-// measured.hip and measured_table.hip round the same expressions differently.  With this both compute the same bits.
+// multiply-adds are fused per source expression, by the front end, from here to the end of the including translation unit
+// (rows.h explains why): measured.hip and measured_table.hip compute the same bits
 #pragma clang fp contract(on)
 
 namespace measured_dev {
+
+using rows::launch_rows;
+using rows::store3;
+using rows::Tint;
+using rows::TintArg;
 
 struct Table {        // [slices][h][w] fp32 on the device
     const float* data;
@@ -183,10 +186,6 @@ __device__ __forceinline__ bool measured_f(const MeasuredDev& m, float wix, floa
     for (int c = 0; c < 3; ++c) rgb[c] *= scale;
     return true;
 }
-
-struct Tint {
-    float r, g, b;
-};
 
 // ---- sample() and pdf(): the importance sampler every RGL file ships (Dupuy & Jakob 2018, Mitsuba's `measured` plugin) ----------
 // u -> luminance warp -> VNDF warp -> microfacet normal m -> wo = reflect(wi, m).  Both warps are the exact inverse of the
@@ -423,10 +422,6 @@ __device__ __forceinline__ float measured_pdf(const MeasuredDev& m, float wix, f
 }
 
 // ---- one row of each kernel: measured.hip runs them on its one material, measured_table.hip on the material of the row's id ----
-__device__ __forceinline__ void store3(float* __restrict__ out, long long q, float a, float b, float c) {
-    out[3 * q] = a; out[3 * q + 1] = b; out[3 * q + 2] = c;
-}
-
 // eval(): f_o = f(wi, wo) cos * tint and, with a second direction wl (null: none), f_l = f(wi, wl) cos * tint
 __device__ __forceinline__ void eval_row(const MeasuredDev& m, const float* __restrict__ wi, const float* __restrict__ wo,
                                          const float* __restrict__ wl, long long q, Tint tint, float* __restrict__ f_o,
@@ -480,23 +475,6 @@ __device__ __forceinline__ void pdf_row(const MeasuredDev& m, const float* __res
     float pdf = 0.0f;
     if (!active || active[q] != 0) pdf = measured_pdf(m, wi[3 * q], wi[3 * q + 1], wi[3 * q + 2], wo[3 * q], wo[3 * q + 1], wo[3 * q + 2]);
     pdf_out[q] = pdf;
-}
-
-// ---- host path shared by the launchers of measured.hip and measured_table.hip, after their own launch checks ----
-// a launcher's optional `tint` argument (null: white), read where it becomes the kernel's Tint: at the launch, after the checks
-struct TintArg {
-    const float* rgb;
-    operator Tint() const { return rgb ? Tint{rgb[0], rgb[1], rgb[2]} : Tint{1.0f, 1.0f, 1.0f}; }
-};
-
-// the empty call, `bad` (the first complaint about the arguments, or null), one thread per row in blocks of 256, the launch error
-template <class... P, class... A>
-int launch_rows(int64_t n, const char* bad, void (*kernel)(P...), void* stream, A... args) {
-    if (n == 0) return BSDFD_OK;
-    if (bad) return bsdfd_fail_(BSDFD_EINVAL, bad);
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(((long long)n + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), args...);
-    HIP_TRY(hipGetLastError());
-    return BSDFD_OK;
 }
 
 }  // namespace measured_dev

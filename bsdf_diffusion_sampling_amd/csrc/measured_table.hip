@@ -10,7 +10,8 @@
 //
 // Image-coherent lanes hit the same ball, so most waves carry ONE id: those take a wave-uniform path on which the descriptor
 // is addressed by a scalar and travels through uniform loads, as the kernel argument of the single-material kernel does;
-// waves with mixed ids load the descriptor's fields per lane.
+// waves with mixed ids load the descriptor's fields per lane.  That pick, and the host side of a table of materials, are
+// material_table.h's, shared with analytic_table.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -21,8 +22,15 @@
 #include "bsdfd.h"
 #include "common.h"
 #include "measured_dev.h"
+#include "material_table.h"
 
 using namespace measured_dev;
+using material_table::with_entry;
+using rows::quiet_nan;
+
+struct bsdfd_measured_table_ctx : material_table::Ctx<MeasuredDev> {   // a slot without ground truth is all zero
+    static constexpr const char* noun = "measured table";
+};
 
 namespace {
 
@@ -65,35 +73,15 @@ __device__ __forceinline__ MeasuredDev generic(const MeasuredDevG& s) {
 // slot of a material without ground truth: all zero (no tables)
 __device__ __forceinline__ bool has_ground_truth(const MeasuredDevG& m) { return m.rgb.data != nullptr; }
 
-__device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7fc00000); }
-
-// The row's material, once: a wave whose live lanes all carry one id (the first live lane's, held as a scalar) addresses the
-// descriptor with that scalar, any other wave per lane; `row(m)` serves a row whose id names a material with ground truth,
-// `none()` every other.  Call with the dead lanes (rows past N) already retired.
-template <class Row, class None>
-__device__ __forceinline__ void with_material(const MeasuredDevG* __restrict__ table, int n_materials, long long id, Row row,
-                                              None none) {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)id & 0xffffffffull));
-    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((unsigned long long)id >> 32));
-    const long long first = (long long)(((unsigned long long)hi << 32) | lo);
-    if (__ballot(id != first) == 0ull) {
-        if (first >= 0 && first < n_materials && has_ground_truth(table[first])) row(generic(table[first]));
-        else none();
-    } else {
-        if (id >= 0 && id < n_materials && has_ground_truth(table[id])) row(generic(table[id]));
-        else none();
-    }
-}
-
-// eval() of row q by the material its id names
+// eval() of row q by the material its id names (material_table.h: with_entry; a slot that has_ground_truth serves the row)
 __device__ __forceinline__ void eval_table_row(const MeasuredDevG* __restrict__ table, int n_materials,
                                                const long long* __restrict__ material_id, const float* __restrict__ wi,
                                                const float* __restrict__ wo, const float* __restrict__ wl, long long q, Tint tint,
                                                float* __restrict__ f_o, float* __restrict__ f_l) {
     const float nan = quiet_nan();
-    with_material(table, n_materials, material_id[q],
-                  [&](const MeasuredDev& m) { eval_row(m, wi, wo, wl, q, tint, f_o, f_l); },
-                  [&] { store3(f_o, q, nan, nan, nan); if (f_l) store3(f_l, q, nan, nan, nan); });
+    with_entry(table, n_materials, material_id[q], has_ground_truth,
+               [&](const MeasuredDevG& g) { eval_row(generic(g), wi, wo, wl, q, tint, f_o, f_l); },
+               [&] { store3(f_o, q, nan, nan, nan); if (f_l) store3(f_l, q, nan, nan, nan); });
 }
 
 // The four kernels: the rows of measured_dev.h, which the single-material kernels (measured.hip) run too; a row without
@@ -118,10 +106,8 @@ __global__ __launch_bounds__(256) void measured_eval_table_rows_kernel(const Mea
                                                                        const float* __restrict__ wl, long long n, Tint tint,
                                                                        float* __restrict__ f_o, float* __restrict__ f_l,
                                                                        const long long* __restrict__ rows, long long n_rows) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_rows) return;
-    const long long q = rows[t];
-    if ((unsigned long long)q >= (unsigned long long)n) return;   // (a contract violation: skipped, not followed)
+    long long q;
+    if (!material_table::listed_row(rows, n_rows, n, q)) return;
     eval_table_row(table, n_materials, material_id, wi, wo, wl, q, tint, f_o, f_l);
 }
 
@@ -136,9 +122,9 @@ __global__ __launch_bounds__(256) void measured_weight_table_kernel(const Measur
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n) return;
     const float nan = quiet_nan();
-    with_material(table, n_materials, material_id[q],
-                  [&](const MeasuredDev& m) { weight_row(m, wi, wo, pdf_in, active, q, tint, thr, weight, pdf_out); },
-                  [&] { pdf_out[q] = pdf_in[q]; store3(weight, q, nan, nan, nan); });
+    with_entry(table, n_materials, material_id[q], has_ground_truth,
+               [&](const MeasuredDevG& g) { weight_row(generic(g), wi, wo, pdf_in, active, q, tint, thr, weight, pdf_out); },
+               [&] { pdf_out[q] = pdf_in[q]; store3(weight, q, nan, nan, nan); });
 }
 
 __global__ __launch_bounds__(256) void measured_sample_table_kernel(const MeasuredDevG* __restrict__ table, int n_materials,
@@ -151,9 +137,9 @@ __global__ __launch_bounds__(256) void measured_sample_table_kernel(const Measur
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n) return;
     const float nan = quiet_nan();
-    with_material(table, n_materials, material_id[q],
-                  [&](const MeasuredDev& m) { sample_row(m, wi, u, active, q, tint, wo_out, pdf_out, weight_out); },
-                  [&] { store3(wo_out, q, nan, nan, nan); pdf_out[q] = nan; if (weight_out) store3(weight_out, q, nan, nan, nan); });
+    with_entry(table, n_materials, material_id[q], has_ground_truth,
+               [&](const MeasuredDevG& g) { sample_row(generic(g), wi, u, active, q, tint, wo_out, pdf_out, weight_out); },
+               [&] { store3(wo_out, q, nan, nan, nan); pdf_out[q] = nan; if (weight_out) store3(weight_out, q, nan, nan, nan); });
 }
 
 __global__ __launch_bounds__(256) void measured_pdf_table_kernel(const MeasuredDevG* __restrict__ table, int n_materials,
@@ -163,37 +149,8 @@ __global__ __launch_bounds__(256) void measured_pdf_table_kernel(const MeasuredD
                                                                  float* __restrict__ pdf_out) {
     const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= n) return;
-    with_material(table, n_materials, material_id[q], [&](const MeasuredDev& m) { pdf_row(m, wi, wo, active, q, pdf_out); },
-                  [&] { pdf_out[q] = quiet_nan(); });
-}
-
-}  // namespace
-
-struct bsdfd_measured_table_ctx {
-    MeasuredDev* dev;  // [n_materials] on the device; a slot without ground truth is all zero
-    int32_t n_materials;
-    int device;
-};
-
-namespace {
-
-int table_launch_checks(bsdfd_measured_table t, int64_t n) {
-    if (!t) return bsdfd_fail_(BSDFD_EINVAL, "null measured table");
-    if (n < 0) return bsdfd_fail_(BSDFD_EINVAL, "N must be >= 0");
-    int dev = -1;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev != t->device) return bsdfd_fail_(BSDFD_EINVAL, "measured table belongs to another device");
-    if ((long long)n > 0xffffffffLL - 255) return bsdfd_fail_(BSDFD_EINVAL, "N too large for one launch");   // grid * block < 2^32
-    return BSDFD_OK;
-}
-
-// the host path of the four launchers: `kernel` over N rows with their ids, `args` behind the table and the ids
-template <class... P, class... A>
-int table_launch(bsdfd_measured_table t, int64_t n, const int64_t* material_id, const char* bad, void (*kernel)(P...),
-                 void* stream, A... args) {
-    if (int rc = table_launch_checks(t, n)) return rc;
-    return launch_rows(n, bad, kernel, stream, reinterpret_cast<const MeasuredDevG*>(t->dev), (int)t->n_materials,
-                       reinterpret_cast<const long long*>(material_id), args...);
+    with_entry(table, n_materials, material_id[q], has_ground_truth,
+               [&](const MeasuredDevG& g) { pdf_row(generic(g), wi, wo, active, q, pdf_out); }, [&] { pdf_out[q] = quiet_nan(); });
 }
 
 }  // namespace
@@ -217,41 +174,27 @@ int bsdfd_measured_table_create(const bsdfd_measured_handle* handles, int32_t n_
             return bsdfd_fail_(BSDFD_EINVAL, "measured handle " + std::to_string(m) + " belongs to another device");
         host[(size_t)m] = handles[m]->dev;
     }
-    void* p = nullptr;
-    HIP_TRY(hipMalloc(&p, host.size() * sizeof(MeasuredDev)));
-    const hipError_t e = hipMemcpy(p, host.data(), host.size() * sizeof(MeasuredDev), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(p);
-        return bsdfd_fail_(BSDFD_EHIP, std::string("hipMemcpy of the material descriptors: ") + hipGetErrorString(e));
-    }
-    *out = new bsdfd_measured_table_ctx{static_cast<MeasuredDev*>(p), n_materials, devid};
-    return BSDFD_OK;
+    return material_table::upload(host, devid, "descriptors", out);
 }
 
-void bsdfd_measured_table_destroy(bsdfd_measured_table t) {
-    if (!t) return;
-    (void)hipFree(t->dev);
-    delete t;
-}
+void bsdfd_measured_table_destroy(bsdfd_measured_table t) { material_table::destroy(t); }
 
 int bsdfd_measured_eval_table(bsdfd_measured_table t, const int64_t* material_id, const float* wi, const float* wo,
                               const float* wl, int64_t n, const float* tint, float* f_o, float* f_l, void* stream) {
     const char* bad = (wl == nullptr) != (f_l == nullptr) ? "wl and f_l are both NULL or both given"
                       : !material_id || !wi || !wo || !f_o ? "null pointer" : nullptr;
-    return table_launch(t, n, material_id, bad, measured_eval_table_kernel, stream, wi, wo, wl, (long long)n, TintArg{tint},
-                        f_o, f_l);
+    return material_table::launch(t, n, n, material_id, bad, measured_eval_table_kernel, stream, wi, wo, wl, (long long)n,
+                                  TintArg{tint}, f_o, f_l);
 }
 
 int bsdfd_measured_eval_table_rows(bsdfd_measured_table t, const int64_t* material_id, const float* wi, const float* wo,
                                    const float* wl, int64_t n, const float* tint, float* f_o, float* f_l, const int64_t* rows,
                                    int64_t n_rows, void* stream) {
-    if (int rc = table_launch_checks(t, n)) return rc;
-    if (n_rows < 0 || n_rows > n) return bsdfd_fail_(BSDFD_EINVAL, "n_rows must be in [0, N]");
     const char* bad = (wl == nullptr) != (f_l == nullptr) ? "wl and f_l are both NULL or both given"
                       : !material_id || !wi || !wo || !f_o || !rows ? "null pointer" : nullptr;
-    return launch_rows(n_rows, bad, measured_eval_table_rows_kernel, stream, reinterpret_cast<const MeasuredDevG*>(t->dev),
-                       (int)t->n_materials, reinterpret_cast<const long long*>(material_id), wi, wo, wl, (long long)n, TintArg{tint},
-                       f_o, f_l, reinterpret_cast<const long long*>(rows), (long long)n_rows);
+    return material_table::launch(t, n, n_rows, material_id, bad, measured_eval_table_rows_kernel, stream, wi, wo, wl,
+                                  (long long)n, TintArg{tint}, f_o, f_l, reinterpret_cast<const long long*>(rows),
+                                  (long long)n_rows);
 }
 
 int bsdfd_measured_sample_weight_table(bsdfd_measured_table t, const int64_t* material_id, const float* wi,
@@ -259,23 +202,23 @@ int bsdfd_measured_sample_weight_table(bsdfd_measured_table t, const int64_t* ma
                                        const float* tint, float firefly_threshold, float* weight_out, float* pdf_out,
                                        void* stream) {
     const bool given = material_id && wi && wo && pdf_sa && weight_out && pdf_out;
-    return table_launch(t, n, material_id, given ? nullptr : "null pointer", measured_weight_table_kernel, stream, wi, wo, pdf_sa,
-                        active, (long long)n, TintArg{tint}, firefly_threshold, weight_out, pdf_out);
+    return material_table::launch(t, n, n, material_id, given ? nullptr : "null pointer", measured_weight_table_kernel, stream, wi,
+                                  wo, pdf_sa, active, (long long)n, TintArg{tint}, firefly_threshold, weight_out, pdf_out);
 }
 
 int bsdfd_measured_sample_table(bsdfd_measured_table t, const int64_t* material_id, const float* wi, const float* u,
                                 const unsigned char* active, int64_t n, const float* tint, float* wo_out, float* pdf_out,
                                 float* weight_out, void* stream) {
     const bool given = material_id && wi && u && wo_out && pdf_out;
-    return table_launch(t, n, material_id, given ? nullptr : "null pointer", measured_sample_table_kernel, stream, wi, u, active,
-                        (long long)n, TintArg{tint}, wo_out, pdf_out, weight_out);
+    return material_table::launch(t, n, n, material_id, given ? nullptr : "null pointer", measured_sample_table_kernel, stream, wi,
+                                  u, active, (long long)n, TintArg{tint}, wo_out, pdf_out, weight_out);
 }
 
 int bsdfd_measured_pdf_table(bsdfd_measured_table t, const int64_t* material_id, const float* wi, const float* wo,
                              const unsigned char* active, int64_t n, float* pdf_out, void* stream) {
     const bool given = material_id && wi && wo && pdf_out;
-    return table_launch(t, n, material_id, given ? nullptr : "null pointer", measured_pdf_table_kernel, stream, wi, wo, active,
-                        (long long)n, pdf_out);
+    return material_table::launch(t, n, n, material_id, given ? nullptr : "null pointer", measured_pdf_table_kernel, stream, wi, wo,
+                                  active, (long long)n, pdf_out);
 }
 
 }  // extern "C"
