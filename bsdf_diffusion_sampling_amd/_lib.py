@@ -64,6 +64,7 @@ EXPORTS = (
     "bsdfd_analytic_sample_weight_table", "bsdfd_analytic_sample_table", "bsdfd_analytic_pdf_table",
     "bsdfd_bucket_rows", "bsdfd_wf_bounce_rows", "bsdfd_wf_sample_emitter_rows", "bsdfd_wf_sample_env_rows",
     "bsdfd_measured_eval_table_rows", "bsdfd_analytic_eval_table_rows",
+    "bsdfd_wf_bounce_transmit", "bsdfd_wf_sample_inside", "bsdfd_wf_sample_inside_rows",
     "bsdfd_set_profiling", "bsdfd_profile_read", "bsdfd_profile_read_op", "bsdfd_profile_clock_mhz", "bsdfd_last_kernel_ms", "bsdfd_shader_clock_mhz",
     "bsdfd_last_error", "bsdfd_version", "bsdfd_abi_version",
 )
@@ -504,6 +505,11 @@ def lib():
                  "bsdfd_analytic_eval_table"):
         sibling = getattr(L, "bsdfd_wf_bounce_rr" if name == "bsdfd_wf_bounce" else name).argtypes
         getattr(L, name + "_rows").argtypes = sibling[:-1] + [fp, i64, vp]
+    # transmission: the bounce takes its list sibling's arguments; the inside sampler (table, bounce, seed, pass, path_offset, N,
+    # material, wi, wl, wo, pdf_o, pdf_l [, rows, n_rows], stream)
+    L.bsdfd_wf_bounce_transmit.argtypes = L.bsdfd_wf_bounce_rows.argtypes
+    L.bsdfd_wf_sample_inside.argtypes = [vp, i32, u64, u64, u64, i64] + [fp] * 6 + [vp]
+    L.bsdfd_wf_sample_inside_rows.argtypes = L.bsdfd_wf_sample_inside.argtypes[:-1] + [fp, i64, vp]
     L.bsdfd_bucket_rows.argtypes = L.bsdfd_bucket_by_material.argtypes[:1] + [fp] + L.bsdfd_bucket_by_material.argtypes[1:]
     L.bsdfd_bucket_wide_workspace_bytes.argtypes = [i64, i32]
     L.bsdfd_bucket_wide_workspace_bytes.restype = i64

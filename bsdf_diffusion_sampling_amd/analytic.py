@@ -18,9 +18,10 @@ launch per call (csrc/analytic_table.hip), where the classes above take one laun
 gets the bits of its own material's single-material call, and lanes without ground truth NaN.  Each entry carries an ``albedo``
 of its own, the per-ball colour of the reference's array scenes (rendering/bsdf_myresult.py:97,112), multiplied into the call's
 tint.  It is what ``wavefront.ArrayRenderer`` and ``pathtrace.PathArrayRenderer`` shade with when their ``ground_truth`` is
-analytic; ``ground_truth_for(names)`` builds that dict for the materials named ``bsdf_<idx>``.  Two limits of those renderers hold
-here too: under occlusion a BSDF sample below the surface is dropped (no transmission through the balls), and without occlusion
-such a direction looks the environment up weighted with the transmission lobe's ``f |cos|``.  Measured against the per-material
+analytic; ``ground_truth_for(names)`` builds that dict for the materials named ``bsdf_<idx>``.  Under occlusion those renderers drop
+a BSDF sample below the surface unless ``PathArrayRenderer(..., transmission=True)`` follows it through the ball — the vertices
+inside are then sampled here, by the models themselves (``AnalyticTable.sample_inside``) —, and without occlusion such a direction
+looks the environment up weighted with the transmission lobe's ``f |cos|``.  Measured against the per-material
 loop it replaces: profiles/analytic_table.json (tools/analytic_table_bench.py).
 """
 from __future__ import annotations
@@ -285,6 +286,35 @@ class AnalyticTable(RowKernels):
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``pdf_t`` of each lane's material in one launch -> [N]; NaN = no ground truth for that lane."""
         return self._pdf_t(material_id, wi, wo, active, out)
+
+    def sample_inside(self, material_id: torch.Tensor, wi: torch.Tensor, wl: torch.Tensor, bounce: int, seed: int, pass_idx: int,
+                      path_offset: int, out, rows: Optional[torch.Tensor] = None):
+        """The sampler's answer for a path tracer's vertices INSIDE a ball, in place: on every lane with ``0 <= material_id <
+        len(self)`` and ``wi.z < 0``, ``out`` = (wo [N,3], pdf_o [N], pdf_l [N]) receives ``sample_t(wi, u)``'s direction and
+        density and ``pdf_t(wi, wl)``, bit for bit, at variates of the lane's own: ``u_k = (word k >> 8) * 2^-24`` of
+        philox(key = seed, counter = (path_offset + lane, pass_idx, "Insd" + bounce)) — but ``pdf_o = 0`` where ``sample_t``'s weight
+        is 0 in every channel (a failed sample: the bounce, which weights with ``f(wi, wo) / pdf_o`` of the pair, must drop it).  A
+        None entry gets zeros.  Every other lane
+        keeps what it held.  ``rows`` (int64 [n_rows], distinct lanes): only the listed lanes are looked at
+        (``bsdfd_wf_sample_inside_rows``).  -> ``out``."""
+        from .ground_truth import check, launch
+        who = self.NAME + ".sample_inside"
+        if out is None or len(out) != 3:
+            raise ValueError(f"{who}: out is a (wo [N,3], pdf_o [N], pdf_l [N]) triple, written in place")
+        wo, pdf_o, pdf_l = out
+        check(who, (("wi", wi, 3), ("wl", wl, 3), ("wo", wo, 3), ("pdf_o", pdf_o, 0), ("pdf_l", pdf_l, 0)), material_id)
+        if rows is not None and not (isinstance(rows, torch.Tensor) and rows.dtype == torch.int64 and rows.dim() == 1
+                                     and rows.is_contiguous() and rows.device == wi.device and rows.shape[0] <= wi.shape[0]):
+            raise ValueError(f"{who}: rows must be a contiguous int64 tensor [n_rows <= N] on the device of wi")
+        m64 = 0xFFFFFFFFFFFFFFFF
+        args = (self._lead(), int(bounce), int(seed) & m64, int(pass_idx) & m64, int(path_offset) & m64, wi.shape[0], material_id,
+                wi, wl, wo, pdf_o, pdf_l)
+        if rows is None:
+            launch("bsdfd_wf_sample_inside", wi.device, *args)
+        else:
+            launch("bsdfd_wf_sample_inside_rows", wi.device, *args, rows, rows.shape[0])
+        torch.autograd.graph.increment_version([wo, pdf_o, pdf_l])
+        return out
 
 
 def ground_truth_for(names) -> dict:

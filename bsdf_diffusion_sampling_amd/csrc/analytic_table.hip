@@ -12,6 +12,9 @@
 // uniform loads, as the single-material kernels read their kernel argument; a wave with mixed ids reads per lane — the kind
 // first, then that kind's fields only — and runs the bodies of the kinds it holds under divergence.  That pick, and the host side
 // of a table of materials, are material_table.h's, shared with measured_table.hip.
+//
+// The table also answers for a path tracer's vertices INSIDE a ball (bsdfd_wf_sample_inside / _rows, below): there the models' own
+// samplers stand in for the flow nets.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -21,6 +24,7 @@
 
 #include "analytic_host.h"
 #include "analytic_rows.h"
+#include "bounce_dev.h"
 #include "bsdfd.h"
 #include "common.h"
 #include "material_table.h"
@@ -147,6 +151,59 @@ __global__ __launch_bounds__(256) void analytic_pdf_table_kernel(const AnalyticR
                   [&] { pdf_out[q] = quiet_nan(); });
 }
 
+// The sampler's answer for the vertices INSIDE a ball (wi.z < 0: the transmitting bounce of bounce_dev.h got them there), where the
+// flow nets have none worth keeping: the model's own importance sampler draws wo and states its density, and its density for the
+// light strategy's direction wl — sample_row's and pdf_row's statements on the lane's material, with variates of the lane's own,
+// u_k = (word k >> 8) 2^-24 of tagged_draw(.., "Insd", bounce), exact fp32 numbers keyed by the lane like "Roul" and "Envm".  A
+// sample the model itself weights with 0 — its f |cos| is 0 in every channel: the dielectric's wo on the wrong side for the lobe that
+// drew it — gets pdf_o = 0, because the bounce forms its own weight, f(wi, wo) / pdf_o, from the PAIR: pdf(wi, wo) classifies the
+// pair by its sides, so for such a wo it is the other lobe's density and the pair's f is not 0; followed, those samples would count
+// that lobe's directions twice (a glass ball in a white furnace came out 1.4 % too bright).  Dropped, the strategy's density for the
+// directions it does contribute is the model's pdf, which is what pdf_l states for wl.  A record without ground truth gets zeros.
+// Both end the path at the bounce.  Every other lane — floor, ended, outside (wi.z >= 0),
+// unlisted — keeps every byte.  LIST: thread t serves lane rows[t].
+template <bool LIST>
+__global__ __launch_bounds__(256) void sample_inside_kernel(const AnalyticRec* __restrict__ table, int n_materials,
+                                                            const long long* __restrict__ material_id, const float* __restrict__ wi,
+                                                            const float* __restrict__ wl, long long n, int bounce,
+                                                            unsigned long long seed, unsigned long long pass,
+                                                            unsigned long long path_offset, float* __restrict__ wo_out,
+                                                            float* __restrict__ pdf_o, float* __restrict__ pdf_l,
+                                                            const long long* __restrict__ rows, long long n_rows) {
+    long long q;
+    if constexpr (LIST) {
+        if (!material_table::listed_row(rows, n_rows, n, q)) return;
+    } else {
+        q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+        if (q >= n) return;
+    }
+    const long long id = material_id[q];
+    if (!(id >= 0 && id < n_materials) || !(wi[3 * q + 2] < 0.0f)) return;
+    unsigned w[4];
+    bounce_dev::tagged_draw(seed, pass, path_offset, q, 0x496E7364u /* "Insd" */, bounce, w);
+    const float u0 = (float)(w[0] >> 8) * (1.0f / 16777216.0f), u1 = (float)(w[1] >> 8) * (1.0f / 16777216.0f),
+                u2 = (float)(w[2] >> 8) * (1.0f / 16777216.0f);
+    with_material(table, n_materials, id, Tint{1.0f, 1.0f, 1.0f},
+                  [&](const auto& model, Tint) {
+                      const Vec i = load3(wi, q);
+                      Vec o{0.0f, 0.0f, 0.0f};
+                      float pdf = 0.0f, f[3] = {0.0f, 0.0f, 0.0f};
+                      model.sample(i, u0, u1, u2, o, pdf, f);
+                      const float pl = model.pdf(i, load3(wl, q));
+                      store3(wo_out, q, o.x, o.y, o.z);
+                      pdf_o[q] = fmaxf(fmaxf(f[0], f[1]), f[2]) > 0.0f ? pdf : 0.0f;
+                      pdf_l[q] = pl;
+                  },
+                  [&] { store3(wo_out, q, 0.0f, 0.0f, 0.0f); pdf_o[q] = 0.0f; pdf_l[q] = 0.0f; });
+}
+
+// the checks the two forms share, before the table's own
+inline const char* sample_inside_complaint(int32_t bounce, const int64_t* material_id, const float* wi, const float* wl,
+                                           const float* wo, const float* pdf_o, const float* pdf_l, bool rows_given) {
+    return bounce < 0 ? "bounce must be >= 0"
+           : !material_id || !wi || !wl || !wo || !pdf_o || !pdf_l || !rows_given ? "null pointer" : nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -228,6 +285,25 @@ int bsdfd_analytic_pdf_table(bsdfd_analytic_table t, const int64_t* material_id,
     const bool given = material_id && wi && wo && pdf_out;
     return material_table::launch(t, n, n, material_id, given ? nullptr : "null pointer", analytic_pdf_table_kernel, stream, wi, wo,
                                   active, (long long)n, pdf_out);
+}
+
+int bsdfd_wf_sample_inside(bsdfd_analytic_table t, int32_t bounce, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t n,
+                           const int64_t* material_id, const float* wi, const float* wl, float* wo, float* pdf_o, float* pdf_l,
+                           void* stream) {
+    return material_table::launch(t, n, n, material_id, sample_inside_complaint(bounce, material_id, wi, wl, wo, pdf_o, pdf_l, true),
+                                  sample_inside_kernel<false>, stream, wi, wl, (long long)n, (int)bounce, (unsigned long long)seed,
+                                  (unsigned long long)pass, (unsigned long long)path_offset, wo, pdf_o, pdf_l,
+                                  (const long long*)nullptr, 0LL);
+}
+
+int bsdfd_wf_sample_inside_rows(bsdfd_analytic_table t, int32_t bounce, uint64_t seed, uint64_t pass, uint64_t path_offset,
+                                int64_t n, const int64_t* material_id, const float* wi, const float* wl, float* wo, float* pdf_o,
+                                float* pdf_l, const int64_t* rows, int64_t n_rows, void* stream) {
+    return material_table::launch(t, n, n_rows, material_id,
+                                  sample_inside_complaint(bounce, material_id, wi, wl, wo, pdf_o, pdf_l, rows != nullptr),
+                                  sample_inside_kernel<true>, stream, wi, wl, (long long)n, (int)bounce, (unsigned long long)seed,
+                                  (unsigned long long)pass, (unsigned long long)path_offset, wo, pdf_o, pdf_l,
+                                  reinterpret_cast<const long long*>(rows), (long long)n_rows);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-// bounce.hip — the bounce of the array-scene path tracer: its six kernels, their list forms, their one launcher and its five entry
-// points.
+// bounce.hip — the bounce of the array-scene path tracer: its six kernels, their list forms, the six transmitting forms
+// (bounce_dev.h: TRANSMIT — a BSDF sample below the surface is followed through the ball), their one launcher and its entry points.
 //
 // The bounce itself is bounce_dev.h's bounce_vertex<Mode, RR>: rad += beta * (MIS estimate of what emits, seen from the vertex);
 // the path moves to the vertex its BSDF sample hits (org, nrm, wi, material, beta, a fresh light sample wl) or ends
@@ -26,6 +26,7 @@
 // ~125 B read and ~90 B written per live path, a few hundred flops.
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cstdint>
 
 #include "bounce_dev.h"
@@ -79,17 +80,34 @@ int launch_bounce_rows(int rr_depth, const Rows& rows, void* stream, A... args) 
                     : launch_lanes(rows.n, bounce_rows_kernel<M, false>, stream, args..., rr_depth, rows);
 }
 
+// The transmitting forms (bounce_dev.h: TRANSMIT): the same template once more, full width (LIST = false never reads `rows`) and over
+// a list, with roulette only — "no roulette" is rr_depth = INT_MAX, which costs one wave-uniform comparison per lane.
+template <int M, bool LIST>
+__global__ __launch_bounds__(256) void bounce_transmit_kernel(Scene sc, const float* __restrict__ env, EnvDist e, int n_e, int has_env,
+                                                              Step st, PathState ps, SamplerAnswer sa, EmitterSample es, int rr_depth,
+                                                              Rows rows) {
+    bounce_vertex<M, true, LIST, true>(sc, env, e, M == COSINE ? 1 : n_e, M == LIT ? has_env : 1, st, ps, sa, es, rr_depth, rows);
+}
+
+template <int M, class... A>
+int launch_bounce_transmit(int rr_depth, const Rows* list, long long N, void* stream, A... args) {
+    const int rr = rr_depth ? rr_depth : INT_MAX;
+    return list ? launch_lanes(list->n, bounce_transmit_kernel<M, true>, stream, args..., rr, *list)
+                : launch_lanes(N, bounce_transmit_kernel<M, false>, stream, args..., rr, Rows{});
+}
+
 // One bounce in `mode`, with Russian roulette from rr_depth on (0: none), over all N lanes or (`list`) over the lanes of a list.
 // The mode's own scene and emitter arguments are checked first, then what the modes share; a mode ignores the emitter arguments
 // it does not have.
 //   COSINE : none
 //   LIT    : lights, lsel, emit
 //   ENV    : dist, emit, lpdf; `lights` and `lsel` both NULL (n_e = 1) or both given (has_env set, n_e = n_lights + 1)
+// `transmit`: the transmitting kernels, which need the ground truth (f_o).
 int launch_bounce(Mode mode, int rr_depth, const bsdfd_wf_scene* scene, const float* env, int32_t bounce, int32_t last,
                   int32_t occlusion, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, float* org, float* nrm, float* wi,
                   float* wl, int64_t* material, float* beta, float* rad, const float* wo, const float* pdf_o, const float* pdf_l,
                   const float* f_o, const float* f_l, const bsdfd_wf_lights* lights, const int32_t* lsel, const float* emit,
-                  const float* lpdf, const bsdfd_env_dist* dist, void* stream, const Rows* list = nullptr) {
+                  const float* lpdf, const bsdfd_env_dist* dist, void* stream, const Rows* list = nullptr, bool transmit = false) {
     Scene sc;
     EnvDist e{};
     int n = 0, n_e = 1;
@@ -120,6 +138,15 @@ int launch_bounce(Mode mode, int rr_depth, const bsdfd_wf_scene* scene, const fl
     const PathState ps{org, nrm, wi, wl, reinterpret_cast<long long*>(material), beta, rad};
     const SamplerAnswer sa{wo, pdf_o, pdf_l, f_o, f_l};
     const EmitterSample es{reinterpret_cast<const int*>(lsel), mode == ENV ? lpdf : nullptr, emit};
+    if (transmit) {
+        if (!f_o) return bsdfd_fail_(BSDFD_EINVAL, "transmission needs the ground truth: null f_o");
+        if (list && list->n == 0) return BSDFD_OK;
+        switch (mode) {
+            case COSINE: return launch_bounce_transmit<COSINE>(rr_depth, list, N, stream, sc, env, e, n_e, n_e - n, st, ps, sa, es);
+            case LIT: return launch_bounce_transmit<LIT>(rr_depth, list, N, stream, sc, env, e, n_e, n_e - n, st, ps, sa, es);
+            default: return launch_bounce_transmit<ENV>(rr_depth, list, N, stream, sc, env, e, n_e, 1, st, ps, sa, es);
+        }
+    }
     if (list) {
         if (list->n == 0) return BSDFD_OK;
         switch (mode) {
@@ -193,6 +220,22 @@ int bsdfd_wf_bounce_rows(const bsdfd_wf_scene* scene, const float* env, int32_t 
     if (int rc = to_rows(rows, n_rows, N, list)) return rc;
     return launch_bounce(dist ? ENV : lights ? LIT : COSINE, (int)rr_depth, scene, env, bounce, last, occlusion, seed, pass, path_offset, N,
                          org, nrm, wi, wl, material, beta, rad, wo, pdf_o, pdf_l, f_o, f_l, lights, lsel, emit, lpdf, dist, stream, &list);
+}
+
+int bsdfd_wf_bounce_transmit(const bsdfd_wf_scene* scene, const float* env, int32_t bounce, int32_t last, int32_t occlusion,
+                             uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, float* org, float* nrm, float* wi,
+                             float* wl, int64_t* material, float* beta, float* rad, const float* wo, const float* pdf_o,
+                             const float* pdf_l, const float* f_o, const float* f_l, const bsdfd_wf_lights* lights,
+                             const int32_t* lsel, const float* emit, const float* lpdf, const bsdfd_env_dist* dist, int32_t rr_depth,
+                             const int64_t* rows, int64_t n_rows, void* stream) {
+    if (rr_depth < 0) return bsdfd_fail_(BSDFD_EINVAL, "rr_depth must be >= 0 (0: no Russian roulette)");
+    const bool full = !rows && n_rows == 0;   // no list at all: every lane
+    Rows list{};
+    if (!full)
+        if (int rc = to_rows(rows, n_rows, N, list)) return rc;
+    return launch_bounce(dist ? ENV : lights ? LIT : COSINE, (int)rr_depth, scene, env, bounce, last, occlusion, seed, pass, path_offset, N,
+                         org, nrm, wi, wl, material, beta, rad, wo, pdf_o, pdf_l, f_o, f_l, lights, lsel, emit, lpdf, dist, stream,
+                         full ? nullptr : &list, true);
 }
 
 }  // extern "C"

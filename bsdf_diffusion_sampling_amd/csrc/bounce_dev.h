@@ -107,7 +107,17 @@ __device__ __forceinline__ void store_local_direction(float* __restrict__ wl, V3
 // the roulette: only the `thr` that continue_path multiplies into beta does.
 //
 // LIST: the lanes are those of `rows` (the list forms of the six kernels); nothing else differs.
-template <int M, bool RR = false, bool LIST = false>
+//
+// TRANSMIT: a usable BSDF sample below the surface (o.z < 0, under occlusion) at a vertex with ground truth for wo is followed
+// into the ball instead of being dropped, if its throughput factor f_o / pb is positive in some channel: the ray enters, or stays
+// in, the ball it is on, and its hit is that ball's far side, t = -2 (x - c) . d — the far root of trace's quadratic for an origin
+// on the sphere, in the form that stays well conditioned down to grazing chords.  Nothing else is intersected inside a ball (the
+// host refuses scenes whose balls touch each other or the floor).  continue_path then writes the vertex as any other: it keeps
+// the OUTWARD normal, so a vertex reached from inside has wi.z < 0, and the rest of this body serves it unchanged — its light
+// strategy draws above the outward normal (the directions one transmission can reach), the shadow ray skips its own ball, and a
+// sample with o.z > 0 leaves the surface outward whichever side wi is on.  Without ground truth (the proxy) and with f_o == 0 in
+// every channel (an opaque material) such a sample ends the path as before.
+template <int M, bool RR = false, bool LIST = false, bool TRANSMIT = false>
 __device__ __forceinline__ void bounce_vertex(const Scene& sc, const float* __restrict__ env, const EnvDist& e, int n_e, int has_env,
                                               const Step& st, const PathState& ps, const SamplerAnswer& sa,
                                               const EmitterSample& es, int rr_depth = 0, const Rows& rows = Rows{}) {
@@ -178,6 +188,24 @@ __device__ __forceinline__ void bounce_vertex(const Scene& sc, const float* __re
                     // them, and with thr[c] this instantiation rounds differently from the recording
                     if constexpr (M == COSINE) L[c] += w * ev[c] * (gt_o ? sa.f_o[3 * p + c] / pb : sc.albedo[c]);
                     else L[c] += w * ev[c] * thr[c];
+                }
+            }
+        } else if constexpr (TRANSMIT) {
+            if (pb > 0.0f && o.z < 0.0f && gt_o) {   // (under occlusion: the sample the branch above drops)
+#pragma unroll
+                for (int c = 0; c < 3; ++c) thr[c] = sa.f_o[3 * p + c] / pb;
+                if (fmaxf(fmaxf(thr[0], thr[1]), thr[2]) > 0.0f) {
+                    d = o.x * fs + o.y * ft + o.z * nn;
+                    // its own ball, picked as trace picks the winner: a wave-uniform loop and a per-lane select (indexing sc.sph
+                    // with m would turn the kernel-argument array into scratch)
+                    for (int k = 0; k < sc.n_sph; ++k) {
+                        const V3 c = v3(sc.sph[k][0], sc.sph[k][1], sc.sph[k][2]);
+                        const float r = sc.sph[k][3];
+                        if (k == (int)m) { h.c = c; h.r = r; }
+                    }
+                    h.id = (int)m;
+                    h.t = -2.0f * dot(x - h.c, d);
+                    go = true;
                 }
             }
         }

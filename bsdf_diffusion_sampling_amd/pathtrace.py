@@ -68,12 +68,32 @@ profiles/pathtrace_compact.json (tools/pathtrace_bench.py --compact).
 The ground truth is ``ArrayRenderer``'s: {ball: ``MeasuredBSDF``}, or {ball: ``analytic.Principled`` / ``RoughDielectric``}
 (``analytic.ground_truth_for(names)`` for the ``mybsdf idx = N`` balls of matpreview/disney_bsdf_array2_spherical_*.xml), evaluated
 on the lane-ordered wavefront by ``measured.MeasuredTable`` or ``analytic.AnalyticTable``; with analytic ground truth on every ball
-``ball_albedo`` gives each ball the colour its scene file gives it (``wavefront.albedos_from_matpreview_xml``).  Two limits: under
-occlusion ``bounce`` keeps dropping a BSDF sample with ``wo.z <= 0`` ("blocked by the ball itself") — nothing is transmitted
-through the balls; the reference's plugin answers for ``cos_theta_i > 0`` only (rendering/bsdf_myresult.py:63), so a vertex inside
-would have no sampler — and without occlusion (``max_depth=1``) the estimator keeps looking the environment up along such a
-direction, which the analytic ``f |cos|`` of the transmission lobe now weights.  What the table costs a pass:
-profiles/analytic_table.json (tools/analytic_table_bench.py).
+``ball_albedo`` gives each ball the colour its scene file gives it (``wavefront.albedos_from_matpreview_xml``).  Without occlusion
+(``max_depth=1``) the estimator keeps looking the environment up along a BSDF sample below the surface, which the analytic
+``f |cos|`` of the transmission lobe weights.  What the table costs a pass: profiles/analytic_table.json
+(tools/analytic_table_bench.py).
+
+Under occlusion ``bounce`` drops a BSDF sample with ``wo.z <= 0`` ("blocked by the ball itself"): a glass ball is its reflection lobe
+on a black body.  ``transmission=True`` follows such a sample into the ball where the vertex has analytic ground truth and
+``f_o / pdf_o`` is positive in some channel (``bsdfd_wf_bounce_transmit`` stands in for every bounce call): the ray enters, or stays
+in, the ball it is on, and the next vertex is that ball's far side, ``t = -2 (x - c) . d`` along the ray.  Nothing else is
+intersected inside a ball, so the balls must be pairwise disjoint and above the floor plane (checked in fp64 by the constructor).
+A vertex keeps the OUTWARD normal, so one reached from inside has ``wi.z < 0``; its light strategy draws above the outward normal —
+the directions one transmission can reach —, its shadow ray skips its own ball, and a sample with ``wo.z > 0`` leaves the surface
+outward whichever side ``wi`` is on.  The reference's plugin answers for ``cos_theta_i > 0`` only (rendering/bsdf_myresult.py:63), so
+the vertices inside are sampled by the analytic models themselves, which sample both sides of the surface: a depth k >= 1 becomes
+
+    bucket -> sample_pdf -> sample_inside(k) -> eval_t -> bounce_transmit(k)            [compact: sample_inside over the material prefix]
+
+where ``sample_inside`` (``AnalyticTable.sample_inside``, ``bsdfd_wf_sample_inside`` / ``_rows``) overwrites ``wo``, ``pdf_o`` and
+``pdf_l`` on the lanes with ``wi.z < 0`` with the model's own sample, its density, and its density for ``wl``, at variates of the
+lane's own (one Philox draw, counter word 3 = "Insd" + depth); the flow still runs on those lanes and its answers are overwritten.
+The camera is outside, so bounce 0 has no such lane.  Limits: the roulette keeps ``eta = 1`` (Mitsuba rescales the throughput by
+``eta^2`` before the survival test; here the ``1 / eta^2`` a path carries while inside lowers its survival probability — unbiased,
+somewhat more variance); no absorption inside a ball; the balls are solid (the reference's shapes are a shell around a diffuse
+interior, on a mesh); inside vertices tint with the ball's albedo like any other vertex; ``WavefrontRenderer`` / ``ArrayRenderer`` are
+untouched; like the models, parity-unpinned against Mitsuba.  What it costs: profiles/pathtrace_transmission.json
+(tools/pathtrace_bench.py --transmission).
 
 There are no area or spot emitters.  There is no CPU fallback.
 """
@@ -171,6 +191,38 @@ def integrator_from_matpreview_xml(path: str):
     return (None if depth == -1 else depth - 1), rr
 
 
+def _array_arguments(args, kwargs):
+    """(floor, ground_truth, fused_ground_truth) of ``ArrayRenderer``'s arguments behind ``env``, given by position or by name."""
+    names = ("floor", "checker", "albedo", "ground_truth", "device", "fused_ground_truth")
+    given = dict(zip(names, args), **kwargs)
+    return given.get("floor", True), given.get("ground_truth"), given.get("fused_ground_truth", True)
+
+
+def _check_transmission(centers, radii, deep, occlusion, floor, ground_truth, fused_ground_truth, plane_y: float = 0.0):
+    """What ``transmission=True`` needs, before any device work: analytic ground truth behind an ``AnalyticTable`` (the inside
+    vertices' sampler), further bounces with occlusion (the rule it changes), and — the ray inside a ball tests nothing else —
+    balls that are pairwise disjoint and above the floor plane, checked in fp64."""
+    from .analytic import FullSphereGroundTruth
+    ground_truth = dict(ground_truth or {})
+    if not ground_truth:
+        raise ValueError("transmission needs ground truth: without f nothing transmits (ground_truth=analytic.ground_truth_for(...))")
+    if not all(isinstance(g, FullSphereGroundTruth) for g in ground_truth.values()) or not fused_ground_truth:
+        raise ValueError("transmission needs analytic ground truth behind an AnalyticTable (Principled / RoughDielectric objects, "
+                         "fused_ground_truth=True): its models sample the vertices inside a ball")
+    if not deep:
+        raise ValueError("transmission needs max_depth > 1: with one vertex no path gets inside a ball")
+    if not occlusion:
+        raise ValueError("transmission needs occlusion: it follows the samples occlusion would drop")
+    c = [[float(v) for v in ck] for ck in centers]
+    r = [float(v) for v in radii]
+    for i in range(len(c)):
+        if floor and not c[i][1] - r[i] >= plane_y:
+            raise ValueError(f"transmission: ball {i} reaches below the floor plane (the ray inside a ball intersects nothing else)")
+        for j in range(i):
+            if not math.dist(c[i], c[j]) > r[i] + r[j]:
+                raise ValueError(f"transmission: balls {j} and {i} touch or intersect (the ray inside a ball intersects nothing else)")
+
+
 class PathArrayRenderer(ArrayRenderer):
     """``ArrayRenderer`` with ``max_depth`` vertices per path and, with ``occlusion``, shadow rays.
 
@@ -197,13 +249,18 @@ class PathArrayRenderer(ArrayRenderer):
     ``compact``: False (the default: the renderer without the argument, call for call) or True: from bounce 1 on every per-depth
     kernel runs over the live-lane list the previous bounce's bucketing produced, not over all N lanes.  Same film, same path
     state, bit for bit.  ``stats["list_per_bounce"]``: the lanes the bucketing of each bounce read (N at bounce 0; with
-    ``compact=False`` N at every bounce)."""
+    ``compact=False`` N at every bounce).
+
+    ``transmission``: False (the default: the renderer without the argument, call for call and bit for bit) or True: a BSDF sample
+    below the surface is followed through the ball (the module docstring).  It needs analytic ground truth behind an
+    ``AnalyticTable``, ``max_depth > 1`` (with occlusion), and balls that touch neither each other nor the floor: ``ValueError``
+    otherwise.  ``compact=True`` keeps its property with it."""
 
     DEPTH_CAP = 1024   # bounces of a pass at max_depth=None; with roulette (q <= 0.95) a path outlives it with probability < 1e-22
 
     def __init__(self, table, centers, radii, camera=None, env: Optional[torch.Tensor] = None, *args, max_depth: Optional[int] = 1,
                  occlusion: Optional[bool] = None, lights: Optional[Sequence[PointLight]] = None, env_sampling: str = "cosine",
-                 rr_depth: Optional[int] = None, compact: bool = False, **kwargs):
+                 rr_depth: Optional[int] = None, compact: bool = False, transmission: bool = False, **kwargs):
         if rr_depth is not None:
             rr_depth = int(rr_depth)
             if rr_depth < 1:
@@ -221,6 +278,8 @@ class PathArrayRenderer(ArrayRenderer):
             raise ValueError("max_depth > 1 needs occlusion: without it every vertex would see the environment through the balls")
         if env_sampling not in ("cosine", "importance"):
             raise ValueError(f'env_sampling must be "cosine" or "importance", got {env_sampling!r}')
+        if transmission:
+            _check_transmission(centers, radii, deep, occlusion, *_array_arguments(args, kwargs))
         self.lights = None
         if lights is not None and len(lights):
             if env_sampling == "importance" and env is None:
@@ -238,6 +297,7 @@ class PathArrayRenderer(ArrayRenderer):
             from .envmap import EnvDistribution
             self.env_dist = EnvDistribution(self.env)
         self.compact = bool(compact)
+        self.transmission = bool(transmission)
         self.stats = {"lanes_per_bounce": [], "list_per_bounce": [], "depth": 0, "depth_cap_hit": False}
 
     def _buffers(self, n: int):
@@ -308,7 +368,9 @@ class PathArrayRenderer(ArrayRenderer):
         ``lsel`` and ``emit`` from ``sample_emitter``; with an ``EnvDistribution`` also ``lpdf`` and ``emit`` from ``sample_env``)
         and move the paths on.  ``rr_depth`` (default: the instance's): with an integer the same emitters go through
         ``bsdfd_wf_bounce_rr``, which plays Russian roulette on the paths that would continue once ``bounce + 1 >= rr_depth``.
-        ``rows`` (int64 [n_rows], distinct lanes): the listed vertices only, through ``bsdfd_wf_bounce_rows`` in every mode."""
+        ``rows`` (int64 [n_rows], distinct lanes): the listed vertices only, through ``bsdfd_wf_bounce_rows`` in every mode.
+        With ``self.transmission`` every mode, with or without ``rows``, goes through ``bsdfd_wf_bounce_transmit``, which follows a
+        BSDF sample below the surface into the ball (it needs ``f_o``)."""
         occlusion = self.occlusion if occlusion is None else occlusion
         lights = self.lights if lights is None else lights
         env_dist = self.env_dist if env_dist is None else env_dist
@@ -323,7 +385,12 @@ class PathArrayRenderer(ArrayRenderer):
             lit, env = lights is not None, env_dist is not None
             tail = [C.byref(lights) if lit else None, _p(b["lsel"]) if lit else None, _p(b["emit"]) if lit or env else None,
                     _p(b["lpdf"]) if env else None, C.byref(env_dist.struct(self.device)) if env else None]
-            if rows is not None:
+            if self.transmission:
+                if rows is not None and self._list(rows, b)[1] == 0:
+                    return   # an empty list serves no lane (the entry point reads rows = NULL, n_rows = 0 as "every lane")
+                fn = _lib.lib().bsdfd_wf_bounce_transmit
+                args = args + tail + [int(rr_depth or 0), *((None, 0) if rows is None else self._list(rows, b))]
+            elif rows is not None:
                 fn, args = _lib.lib().bsdfd_wf_bounce_rows, args + tail + [int(rr_depth or 0), *self._list(rows, b)]
             elif rr_depth is not None:
                 fn, args = _lib.lib().bsdfd_wf_bounce_rr, args + tail + [int(rr_depth)]
@@ -336,6 +403,12 @@ class PathArrayRenderer(ArrayRenderer):
             _lib.check(fn(*args, self._stream()))
         # written through raw pointers: tell torch (the plugin cores key their per-query context cache on wi._version)
         torch.autograd.graph.increment_version([b["wi"], b["wl"], b["nrm"], b["org"], b["mat"], b["beta"], b["rad"]])
+
+    def sample_inside(self, b, bounce: int, seed: int, pass_idx: int, path_offset: int, rows: Optional[torch.Tensor] = None):
+        """The sampler's answer for the vertices inside a ball (``wi.z < 0``): ``wo``, ``pdf_o``, ``pdf_l`` of those lanes from the
+        analytic model's own sampler (``AnalyticTable.sample_inside``), every other lane untouched."""
+        self.measured_table.sample_inside(b["mat"], b["wi"], b["wl"], bounce, seed, pass_idx, path_offset,
+                                          out=(b["wo"], b["pdf_o"], b["pdf_l"]), rows=rows)
 
     def resolve(self, row_begin: int, row_end: int, spp: int, b, film: torch.Tensor):
         """film [row_end-row_begin, width, 3] += the pass' estimate."""
@@ -383,12 +456,16 @@ class PathArrayRenderer(ArrayRenderer):
                 if rows is None:
                     b["wo"], b["pdf_o"], b["pdf_l"] = self.table.sample_pdf(plan, b["wi"], b["wl"], seed=key, offset=offset,
                                                                             direct=n <= WavefrontPipeline.DIRECT_MAX_LANES)
+                    if self.transmission and k >= 1:   # (the camera is outside: bounce 0 has no vertex inside a ball)
+                        self.sample_inside(b, k, seed, pass_idx, offset)
                     if self.use_ground_truth:
                         self.measured_table.eval_t(b["mat"], b["wi"], b["wo"], b["wl"], tint=self.plugin.albedo, out_o=b["f_o"],
                                                    out_l=b["f_l"])
                 else:   # into the arrays of bounce 0, no fill: bounce reads them on the material lanes of this list only
                     self.table.sample_pdf(plan, b["wi"], b["wl"], seed=key, offset=offset, direct=True,
                                           out=(b["wo"], b["pdf_o"], b["pdf_l"]))
+                    if self.transmission:
+                        self.sample_inside(b, k, seed, pass_idx, offset, rows=plan[0][:n_mat])
                     if self.use_ground_truth:
                         self.measured_table.eval_t(b["mat"], b["wi"], b["wo"], b["wl"], tint=self.plugin.albedo, out_o=b["f_o"],
                                                    out_l=b["f_l"], rows=plan[0][:n_mat])

@@ -56,7 +56,9 @@ extern "C" {
  *      of their own, bsdfd_analytic_entry: both analytic models for a mixed-material wavefront in one launch;
  *      bsdfd_bucket_rows(), bsdfd_wf_bounce_rows(), bsdfd_wf_sample_emitter_rows(), bsdfd_wf_sample_env_rows(),
  *      bsdfd_measured_eval_table_rows() and bsdfd_analytic_eval_table_rows(): the per-depth calls of the array scene over a
- *      live-lane list. */
+ *      live-lane list;
+ *      bsdfd_wf_bounce_transmit(), bsdfd_wf_sample_inside() and bsdfd_wf_sample_inside_rows(): transmitted paths through the
+ *      balls of the array scene. */
 #define BSDFD_ABI_VERSION 8
 
 #define BSDFD_OK 0
@@ -786,6 +788,40 @@ int bsdfd_measured_eval_table_rows(bsdfd_measured_table t, const int64_t* materi
 int bsdfd_analytic_eval_table_rows(bsdfd_analytic_table t, const int64_t* material_id, const float* wi, const float* wo,
                                    const float* wl, int64_t N, const float* tint, float* f_o, float* f_l, const int64_t* rows,
                                    int64_t n_rows, void* hip_stream);
+
+/* ---- transmission through the balls of the array scene (no new ABI version: three more entry points) ----
+ *
+ * bsdfd_wf_bounce_transmit is the bounce with one rule changed.  Under occlusion a usable BSDF sample (pdf_o > 0) BELOW the surface
+ * (wo.z < 0) at a vertex with ground truth (f_o not NaN) is followed into the ball instead of ending the path, if f_o / pdf_o is
+ * positive in some channel: the next vertex is the far side of the SAME ball, at t = -2 (x - c) . d along the ray, written like any
+ * other vertex — nrm stays the outward normal, so wi.z < 0 says "arrived from inside" — with beta *= f_o / pdf_o.  Nothing else
+ * is intersected inside a ball: the caller guarantees that the balls are pairwise disjoint and above the plane.  Without ground
+ * truth, or with f_o == 0 in every channel, such a sample ends the path as in the other bounces; a sample with wo.z > 0 leaves the
+ * surface outward and is traced against everything but its own ball, whichever side wi is on.  It takes bsdfd_wf_bounce_rows'
+ * arguments and selects the emitters as it does; rr_depth == 0 means no roulette; rows == NULL with n_rows == 0 serves every lane,
+ * anything else is a list under the list contract above.  f_o is required.
+ *
+ * bsdfd_wf_sample_inside / _rows is the sampler's answer for the vertices inside a ball.  A lane with 0 <= material[p] <
+ * n_materials of the table and wi.z < 0 gets, from its material's own importance sampler,
+ *     wo[p], pdf_o[p] = sample(wi[p], u0, u1, u2)        pdf_l[p] = pdf(wi[p], wl[p])
+ * bit for bit what bsdfd_analytic_sample_table / _pdf_table return for that row and those variates, which are
+ *     u_k = (word k >> 8) * 2^-24  of  philox4x32(key = seed, counter = (path lo, path hi, pass, "Insd" + bounce)),
+ * path = path_offset + p — except that pdf_o[p] = 0 where that sample's weight is 0 in every channel (the dielectric's wo on the
+ * wrong side for the lobe that drew it): the bounce weights a sample with f(wi, wo) / pdf_o of the pair, which is not 0 there.
+ * A record of kind BSDFD_ANALYTIC_NONE gets zeros in all three.  Either ends the path at the bounce.  Every
+ * other lane keeps every byte.  The checks and the list contract are those of bsdfd_analytic_eval_table_rows. */
+int bsdfd_wf_bounce_transmit(const bsdfd_wf_scene* scene, const float* env, int32_t bounce, int32_t last, int32_t occlusion,
+                             uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, float* org, float* nrm, float* wi,
+                             float* wl, int64_t* material, float* beta, float* rad, const float* wo, const float* pdf_o,
+                             const float* pdf_l, const float* f_o, const float* f_l, const bsdfd_wf_lights* lights,
+                             const int32_t* lsel, const float* emit, const float* lpdf, const bsdfd_env_dist* dist, int32_t rr_depth,
+                             const int64_t* rows, int64_t n_rows, void* hip_stream);
+int bsdfd_wf_sample_inside(bsdfd_analytic_table t, int32_t bounce, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N,
+                           const int64_t* material, const float* wi, const float* wl, float* wo, float* pdf_o, float* pdf_l,
+                           void* hip_stream);
+int bsdfd_wf_sample_inside_rows(bsdfd_analytic_table t, int32_t bounce, uint64_t seed, uint64_t pass, uint64_t path_offset,
+                                int64_t N, const int64_t* material, const float* wi, const float* wl, float* wo, float* pdf_o,
+                                float* pdf_l, const int64_t* rows, int64_t n_rows, void* hip_stream);
 
 const char* bsdfd_last_error(void);
 const char* bsdfd_version(void);

@@ -34,6 +34,14 @@ in the same process, alternating per round, at depths 1 / 2 / 4 / 8 and at max_d
 compared bit for bit first.  Recorded: ms per pass of both, the compact=False variant's own round-to-round spread (a difference
 inside it is "no difference this record resolves"), ms per bounce from device events, the list and the lanes per bounce, and the
 per-path variance x time of the unbounded case.
+
+``--transmission`` measures transmitted paths through the balls -> profiles/pathtrace_transmission.json: the 12 balls of
+matpreview/disney_bsdf_array2_spherical_envmap.xml (``mybsdf idx`` = 21, 20, 20, 1, 19, 4, 25, 7, 24, 12, 13, 14: their shipped
+full-sphere nets, their analytic ground truth) on the array0 layout — or, with ``--scene scene.xml``, that file's own layout, camera
+and per-ball albedo —, PathArrayRenderer(transmission=True) against transmission=False in the same process, alternating per round,
+at max_depth 4 / 8 and at max_depth=None, rr_depth=5.  Paths live longer with transmission, so a pass is expected to cost more: the
+record says what it costs — ms per pass of both, the transmission=False variant's own round-to-round spread, the lanes per bounce
+of both, the depth reached — and states no target.
 """
 import argparse
 import json
@@ -61,14 +69,19 @@ ap.add_argument("--rr-depth", type=int, default=None, metavar="R",
 ap.add_argument("--compact", action="store_true",
                 help="measure compact=True (bounces >= 1 on a live-lane list) against compact=False instead; combines with "
                      "--lights and --env-sampling")
+ap.add_argument("--transmission", action="store_true",
+                help="measure transmission=True (paths through the balls, analytic ground truth) against transmission=False instead")
+ap.add_argument("--scene", default=None, metavar="scene.xml",
+                help="with --transmission: layout, camera and per-ball albedo of a reference scene file instead of the array0 layout")
 ap.add_argument("--out", default=None, help="default: profiles/pathtrace.json, pathtrace_lights.json with --lights, "
                                             "pathtrace_envis.json with --env-sampling importance, pathtrace_rr.json with --rr-depth")
 a = ap.parse_args()
 envis = a.env_sampling == "importance"
-if (envis and a.lights) or (a.rr_depth is not None and (envis or a.lights or a.compact)):
-    sys.exit("--lights, --env-sampling importance and --rr-depth are measured one at a time")
+if (envis and a.lights) or (a.rr_depth is not None and (envis or a.lights or a.compact)) \
+        or (a.transmission and (envis or a.lights or a.compact or a.rr_depth is not None)):
+    sys.exit("--lights, --env-sampling importance, --rr-depth and --transmission are measured one at a time")
 a.out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles",
-                              "pathtrace_compact.json" if a.compact else "pathtrace_rr.json" if a.rr_depth is not None else "pathtrace_envis.json" if envis
+                              "pathtrace_transmission.json" if a.transmission else "pathtrace_compact.json" if a.compact else "pathtrace_rr.json" if a.rr_depth is not None else "pathtrace_envis.json" if envis
                               else "pathtrace_lights.json" if a.lights else "pathtrace.json")
 if not torch.cuda.is_available():
     sys.exit("tools/pathtrace_bench.py measures on the GPU: no device visible")
@@ -79,7 +92,26 @@ LIT_DEPTHS = (1, 2, 4)
 COMPACT_CASES = {"d1": dict(max_depth=1, occlusion=True), "d2": dict(max_depth=2), "d4": dict(max_depth=4), "d8": dict(max_depth=8),
                  "unbounded_rr5": dict(max_depth=None, rr_depth=5)}
 RR_INACTIVE = 9   # an rr_depth the depths 4 and 8 never reach: the RR kernels without a single decision
-if a.compact:
+TRANSMISSION_CASES = {"d4": dict(max_depth=4), "d8": dict(max_depth=8), "unbounded_rr5": dict(max_depth=None, rr_depth=5)}
+ARRAY2_IDX = (21, 20, 20, 1, 19, 4, 25, 7, 24, 12, 13, 14)   # matpreview/disney_bsdf_array2_spherical_envmap.xml
+if a.transmission:
+    from bsdf_diffusion_sampling_amd.analytic import ground_truth_for
+    extra = {}
+    if a.scene:
+        names, cam, centers, radii = WF.scene_from_matpreview_xml(a.scene, a.width, a.height)
+        gts = ground_truth_for(names)
+        if len(gts) == len(names):
+            extra["ball_albedo"] = WF.albedos_from_matpreview_xml(a.scene)
+    else:
+        names = [f"bsdf_{i}" for i in ARRAY2_IDX]
+        gts = ground_truth_for(names)
+    table = MaterialTable([m + "_spherical" if m.startswith("bsdf_") else m + "_" + a.domain for m in names])
+    variants = {}
+    for case, kw in TRANSMISSION_CASES.items():
+        for name, on in (("off", False), ("on", True)):
+            variants[f"{case}_{name}"] = PathArrayRenderer(table, centers, radii, camera=cam, ground_truth=gts, transmission=on, **kw,
+                                                           **extra)
+elif a.compact:
     emitters, section = {}, "cosine"
     if a.lights:
         from bsdf_diffusion_sampling_amd.pathtrace import PointLight
@@ -198,6 +230,32 @@ def per_bounce_ms(r):
     return [float(np.median([p[i] for p in per_pass])) for i in range(min(len(p) for p in per_pass))]
 
 
+if a.transmission:
+    res.update(workload=f"{os.path.splitext(os.path.basename(a.scene))[0] if a.scene else 'array0_layout_array2_materials'}_"
+                        f"{a.width}x{a.height}_{a.spp}spp_12balls_analytic", ground_truth_materials=len(gts),
+               ball_albedo="ball_albedo" in extra, case={})
+    for case in TRANSMISSION_CASES:
+        off, on = times[f"{case}_off"], times[f"{case}_on"]
+        stats = {}
+        for name in ("off", "on"):
+            r = variants[f"{case}_{name}"]
+            depths = []
+            for k in range(a.passes):
+                r.render_pass(film, 0, a.height, a.spp, 0, 1000 + k)
+                depths.append(r.stats["depth"])
+            torch.cuda.synchronize(dev)
+            stats[name] = {"pass_ms_median": med[f"{case}_{name}"], "pass_ms_min": float(min(times[f"{case}_{name}"])),
+                           "round_to_round_spread_ms": float(max(times[f"{case}_{name}"]) - min(times[f"{case}_{name}"])),
+                           "depth_reached_median": float(np.median(depths)), "depth_reached_max": int(max(depths)),
+                           "depth_cap_hit": bool(r.stats["depth_cap_hit"]), "lanes_per_bounce_last_pass": r.stats["lanes_per_bounce"]}
+        res["case"][case] = {"transmission_off": stats["off"], "transmission_on": stats["on"],
+                             "on_minus_off_ms": med[f"{case}_on"] - med[f"{case}_off"], "on_over_off": med[f"{case}_on"] / med[f"{case}_off"],
+                             "material_lanes_on_over_off": sum(stats["on"]["lanes_per_bounce_last_pass"])
+                                                           / max(sum(stats["off"]["lanes_per_bounce_last_pass"]), 1)}
+    for k in ("pass_ms_median", "pass_ms_min"):
+        res.pop(k)
+    write(res)
+    sys.exit(0)
 if a.compact:
     sec = {"films_bit_identical": True, "case": {}}
     for case in COMPACT_CASES:

@@ -19,6 +19,9 @@ ap.add_argument("--rr-depth", type=int, default=None, metavar="R",
 ap.add_argument("--compact", action="store_true",
                 help="run the bounces behind the first on the live-lane list of the bounce before (PathArrayRenderer(compact=True)): "
                      "the same image bit for bit")
+ap.add_argument("--transmission", action="store_true",
+                help="follow BSDF samples below the surface through the balls (PathArrayRenderer(transmission=True)): needs "
+                     "--scene with --analytic, --max-depth > 1 (or -1) and balls that touch neither each other nor the floor")
 ap.add_argument("--integrator-from", default=None, metavar="scene.xml",
                 help="--max-depth and --rr-depth from the <integrator> of a reference scene file (maxDepth = 2 is --max-depth 1, "
                      "-1 is unbounded; rrDepth defaults to 5); either option given explicitly wins")
@@ -85,14 +88,14 @@ elif a.measured_dir:
 if a.env_sampling == "importance" and a.no_env:
     ap.error("--env-sampling importance needs an emitting environment: drop --no-env")
 if (a.max_depth is None and not unbounded and a.rr_depth is None and a.occlusion is None and not lights and a.env_sampling == "cosine"
-        and not a.compact):
+        and not a.compact and not a.transmission):
     r = WF.ArrayRenderer(tab, centers, radii, camera=cam, ground_truth=gts, **extra)
 else:
     from bsdf_diffusion_sampling_amd.pathtrace import PathArrayRenderer
     r = PathArrayRenderer(tab, centers, radii, camera=cam, ground_truth=gts, **extra,
                           max_depth=None if unbounded else 1 if a.max_depth is None else a.max_depth, rr_depth=a.rr_depth,
                           occlusion=None if a.occlusion is None else bool(a.occlusion), lights=lights, env_sampling=a.env_sampling,
-                          env=None if a.no_env or not lights else WF.make_sky(), compact=a.compact)
+                          env=None if a.no_env or not lights else WF.make_sky(), compact=a.compact, transmission=a.transmission)
 r.render(2, a.spp, seed=9); torch.cuda.synchronize()
 t0 = time.perf_counter(); img = r.render(a.passes, a.spp, seed=0); torch.cuda.synchronize(); dt = time.perf_counter() - t0
 b = r.primary(0, a.height, 1, 0, 0); mat = b["mat"].cpu().numpy(); nb = len(tab)
@@ -102,7 +105,7 @@ print(json.dumps({"workload": f"{os.path.splitext(os.path.basename(a.scene))[0] 
                   "env_sampling": a.env_sampling, "rr_depth": getattr(r, "rr_depth", None),
                   "depth": getattr(r, "stats", {}).get("depth"), "depth_cap_hit": getattr(r, "stats", {}).get("depth_cap_hit"),
                   "lanes_per_bounce": getattr(r, "stats", {}).get("lanes_per_bounce"),
-                  "compact": getattr(r, "compact", False), "list_per_bounce": getattr(r, "stats", {}).get("list_per_bounce"),
+                  "compact": getattr(r, "compact", False), "transmission": getattr(r, "transmission", False), "list_per_bounce": getattr(r, "stats", {}).get("list_per_bounce"),
                   "ground_truth_materials": len(gts), "seconds": dt, "passes_per_s": a.passes / dt, "Mpaths_per_s": paths / dt / 1e6,
                   "ball_albedo": "ball_albedo" in extra,
                   "ball_fraction": float((mat < nb).mean()), "floor_fraction": float((mat == nb).mean()), "miss_fraction": float((mat == nb + 1).mean())}))
