@@ -24,12 +24,13 @@ SRC_PATHS = [SRC_PATH, SRC32_PATH, HOST_PATH, os.path.join(_HERE, "csrc", "wavef
              os.path.join(_HERE, "csrc", "bucket_wide.hip"), os.path.join(_HERE, "csrc", "live.hip"),
              os.path.join(_HERE, "csrc", "clock.hip"), os.path.join(_HERE, "csrc", "dielectric.hip"),
              os.path.join(_HERE, "csrc", "principled.hip"),
-             os.path.join(_HERE, "csrc", "analytic_table.hip")]  # translation units of libbsdfd.so
+             os.path.join(_HERE, "csrc", "analytic_table.hip"),
+             os.path.join(_HERE, "csrc", "mesh.hip")]  # translation units of libbsdfd.so
 FLOW_TUS = (SRC_PATH, SRC32_PATH)   # ... whose device assembly the build verifies (_asmcheck)
 DEP_PATHS = SRC_PATHS + [os.path.join(_HERE, "csrc", f) for f in ("common.h", "flow_dev.h", "flow_kernels.h", "bucket_scan.h",
                                                                      "measured_dev.h", "wavefront_dev.h", "env_dev.h", "bounce_dev.h",
                                                                      "dielectric_dev.h", "principled_dev.h", "analytic_host.h",
-                                                                     "rows.h", "analytic_rows.h", "material_table.h")]
+                                                                     "rows.h", "analytic_rows.h", "material_table.h", "mesh_dev.h")]
 INCLUDE_DIR = os.path.join(ROOT, "include")
 ASM_CACHE_DIR = os.path.join(ROOT, "build", "asm")   # device assembly of the last product build (bsdfd.s, flow32.s)
 
@@ -65,6 +66,8 @@ EXPORTS = (
     "bsdfd_bucket_rows", "bsdfd_wf_bounce_rows", "bsdfd_wf_sample_emitter_rows", "bsdfd_wf_sample_env_rows",
     "bsdfd_measured_eval_table_rows", "bsdfd_analytic_eval_table_rows",
     "bsdfd_wf_bounce_transmit", "bsdfd_wf_sample_inside", "bsdfd_wf_sample_inside_rows",
+    "bsdfd_mesh_bvh_build", "bsdfd_mesh_scene_create", "bsdfd_mesh_scene_destroy", "bsdfd_mesh_intersect", "bsdfd_mesh_occluded",
+    "bsdfd_mesh_primary",
     "bsdfd_set_profiling", "bsdfd_profile_read", "bsdfd_profile_read_op", "bsdfd_profile_clock_mhz", "bsdfd_last_kernel_ms", "bsdfd_shader_clock_mhz",
     "bsdfd_last_error", "bsdfd_version", "bsdfd_abi_version",
 )
@@ -120,6 +123,28 @@ class AnalyticDesc(C.Union):
 class AnalyticEntry(C.Structure):
     """bsdfd_analytic_entry (include/bsdfd.h)."""
     _fields_ = [("kind", C.c_int32), ("albedo", C.c_float * 3), ("desc", AnalyticDesc)]
+
+
+MESH_MATERIAL, MESH_DIFFUSE, MESH_CHECKER = 0, 1, 2   # BSDFD_MESH_*
+MESH_MAX_INSTANCES = 64                                # BSDFD_MESH_MAX_INSTANCES
+
+
+class MeshNode(C.Structure):
+    """bsdfd_mesh_node (include/bsdfd.h)."""
+    _fields_ = [("lo", C.c_float * 3), ("hi", C.c_float * 3), ("skip", C.c_int32), ("tris", C.c_int32)]
+
+
+class MeshDesc(C.Structure):
+    """bsdfd_mesh_desc (include/bsdfd.h)."""
+    _fields_ = [("positions", C.c_void_p), ("indices", C.c_void_p), ("normals", C.c_void_p), ("uvs", C.c_void_p),
+                ("n_vertices", C.c_int64), ("n_triangles", C.c_int64)]
+
+
+class MeshInstance(C.Structure):
+    """bsdfd_mesh_instance (include/bsdfd.h)."""
+    _fields_ = [("mesh", C.c_int32), ("surface", C.c_int32), ("material", C.c_int32), ("reserved", C.c_int32),
+                ("color0", C.c_float), ("color1", C.c_float), ("uscale", C.c_float), ("vscale", C.c_float),
+                ("to_world", C.c_float * 12)]
 
 
 class Opts(C.Structure):
@@ -510,6 +535,15 @@ def lib():
     L.bsdfd_wf_bounce_transmit.argtypes = L.bsdfd_wf_bounce_rows.argtypes
     L.bsdfd_wf_sample_inside.argtypes = [vp, i32, u64, u64, u64, i64] + [fp] * 6 + [vp]
     L.bsdfd_wf_sample_inside_rows.argtypes = L.bsdfd_wf_sample_inside.argtypes[:-1] + [fp, i64, vp]
+    # meshes: (positions, nv, indices, nt, nodes_out, node_cap, order_out, &n_nodes); (meshes, n, instances, n, &scene);
+    # (scene, N, org, dir, tmax, skip, t, prim, bary | out, stream); bsdfd_wf_primary's arguments behind the scene
+    L.bsdfd_mesh_bvh_build.argtypes = [fp, i64, fp, i64, fp, i64, fp, C.POINTER(i64)]
+    L.bsdfd_mesh_scene_create.argtypes = [C.POINTER(MeshDesc), i32, C.POINTER(MeshInstance), i32, C.POINTER(vp)]
+    L.bsdfd_mesh_scene_destroy.argtypes = [vp]
+    L.bsdfd_mesh_scene_destroy.restype = None
+    L.bsdfd_mesh_intersect.argtypes = [vp, i64, fp, fp, fp, fp, fp, fp, fp, vp]
+    L.bsdfd_mesh_occluded.argtypes = [vp, i64, fp, fp, fp, fp, fp, vp]
+    L.bsdfd_mesh_primary.argtypes = [vp] + L.bsdfd_wf_primary.argtypes
     L.bsdfd_bucket_rows.argtypes = L.bsdfd_bucket_by_material.argtypes[:1] + [fp] + L.bsdfd_bucket_by_material.argtypes[1:]
     L.bsdfd_bucket_wide_workspace_bytes.argtypes = [i64, i32]
     L.bsdfd_bucket_wide_workspace_bytes.restype = i64

@@ -823,6 +823,79 @@ int bsdfd_wf_sample_inside_rows(bsdfd_analytic_table t, int32_t bounce, uint64_t
                                 int64_t N, const int64_t* material, const float* wi, const float* wl, float* wo, float* pdf_o,
                                 float* pdf_l, const int64_t* rows, int64_t n_rows, void* hip_stream);
 
+/* ---- ray casting on instanced triangle meshes (no new ABI version: six more entry points) ----
+ *
+ * The array scenes' real geometry: a few triangle meshes, instanced under affine transforms.  csrc/mesh.hip, csrc/mesh_dev.h.
+ *
+ * bsdfd_mesh_bvh_build is a pure host function (no HIP call): a binary BVH over the nt triangles of (positions [nv,3], indices
+ * [nt,3]), split at the median of the triangle centroids along the longest axis of the centroid box, a leaf at <= 4 triangles,
+ * stored THREADED: nodes in depth-first order, an inner node's left child is the next node, and every node carries `skip`, the
+ * index of the first node behind its subtree (the root's is *n_nodes) — a traversal needs no stack.  A leaf has
+ * tris = first * 8 + count into the reordered triangle array, order_out[first + k] being that triangle's index in `indices`; an
+ * inner node has tris = 0.  node_cap >= 2 * nt - 1 always suffices; order_out is [nt].  nt must be in [1, 2^27]; an index >= nv
+ * or a non-finite vertex is refused. */
+typedef struct bsdfd_mesh_node {
+    float lo[3], hi[3];
+    int32_t skip;
+    int32_t tris;
+} bsdfd_mesh_node; /* 32 bytes */
+int bsdfd_mesh_bvh_build(const float* positions, int64_t nv, const uint32_t* indices, int64_t nt, bsdfd_mesh_node* nodes_out,
+                         int64_t node_cap, int32_t* order_out, int64_t* n_nodes);
+
+/* A scene: each mesh is uploaded once with its BVH (host pointers; normals [nv,3] and uvs [nv,2] may be NULL), then up to
+ * BSDFD_MESH_MAX_INSTANCES instances, each a mesh index, a 3x4 row-major affine to_world (inverted on the host in fp64; a singular
+ * one is refused, a mirroring one is fine) and a surface record: BSDFD_MESH_MATERIAL (lane `material` of the material table),
+ * BSDFD_MESH_DIFFUSE (constant reflectance color0) or BSDFD_MESH_CHECKER (color0 / color1 by the parity of
+ * floor(2 uscale u) + floor(2 vscale v) over the mesh's own uv, odd = color1; the mesh must have uvs).  Created on the current
+ * device; synchronises. */
+#define BSDFD_MESH_MAX_INSTANCES 64
+#define BSDFD_MESH_MATERIAL 0
+#define BSDFD_MESH_DIFFUSE 1
+#define BSDFD_MESH_CHECKER 2
+typedef struct bsdfd_mesh_desc {
+    const float* positions;
+    const uint32_t* indices;
+    const float* normals;
+    const float* uvs;
+    int64_t n_vertices, n_triangles;
+} bsdfd_mesh_desc;
+typedef struct bsdfd_mesh_instance {
+    int32_t mesh, surface, material, reserved;
+    float color0, color1, uscale, vscale;
+    float to_world[12];
+} bsdfd_mesh_instance;
+typedef struct bsdfd_mesh_scene_ctx* bsdfd_mesh_scene;
+int bsdfd_mesh_scene_create(const bsdfd_mesh_desc* meshes, int32_t n_meshes, const bsdfd_mesh_instance* instances,
+                            int32_t n_instances, bsdfd_mesh_scene* scene);
+void bsdfd_mesh_scene_destroy(bsdfd_mesh_scene scene);
+
+/* One ray per lane, org + t dir with dir of any length (t is the parameter, not a distance).  All arrays are device pointers.
+ *
+ * bsdfd_mesh_intersect: the closest hit with 0 < t <= tmax[p] (tmax NULL: unbounded), the primitive skip[p] = (instance, triangle)
+ * excepted — the primitive a secondary ray starts on; no epsilon; NULL or (-1, -1): none.  t [N], prim int32 [N,2] = (instance,
+ * the file's triangle index), bary [N,2] = the weights of the triangle's second and third vertex.  A miss writes t = 3.0e38,
+ * prim = (-1, -1), bary = 0.  Smaller t wins; on equal t the smaller (instance, triangle).  The ray/triangle test is watertight
+ * at shared edges and vertices (Woop, Benthin, Wald 2013); a ray in a triangle's plane does not hit it.
+ *
+ * bsdfd_mesh_occluded: out[p] = 1 where bsdfd_mesh_intersect would report a hit, else 0 (uint8 [N]), leaving at the first one.
+ *
+ * bsdfd_mesh_primary is bsdfd_wf_primary on the mesh scene: the camera, film, tile and n_materials = 1 + n_extra_spheres of
+ * `wf_scene` (its spheres and plane are not looked at), the same Philox key and counters, film position, ray and light sample, so
+ * dir and wl are bsdfd_wf_primary's.  nrm is the shading normal: the barycentric mix of the vertex normals through the inverse
+ * transpose, normalised, flipped into the hemisphere of the geometric normal (itself faced towards the ray); the geometric normal
+ * where the mesh has no normals or where -dir . nrm <= 0.  A material instance writes wi in the onb(nrm) frame and its lane;
+ * a diffuse one writes its reflectance in all three wi slots and n_materials; a miss writes a zero normal and n_materials + 1.
+ * An instance whose material is >= n_materials is refused.
+ *
+ * All three: N (or the tile) == 0 is a no-op; nothing behind the N-th lane is written; no allocation, no synchronisation. */
+int bsdfd_mesh_intersect(bsdfd_mesh_scene scene, int64_t N, const float* org, const float* dir, const float* tmax,
+                         const int32_t* skip, float* t, int32_t* prim, float* bary, void* hip_stream);
+int bsdfd_mesh_occluded(bsdfd_mesh_scene scene, int64_t N, const float* org, const float* dir, const float* tmax,
+                        const int32_t* skip, uint8_t* out, void* hip_stream);
+int bsdfd_mesh_primary(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, int32_t row_begin, int32_t row_end, int32_t spp,
+                       uint64_t seed, uint64_t pass, float* wi, float* wl, float* nrm, float* dir, int64_t* material,
+                       void* hip_stream);
+
 const char* bsdfd_last_error(void);
 const char* bsdfd_version(void);
 /* BSDFD_ABI_VERSION the library was compiled with (see the top of this header). */

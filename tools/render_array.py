@@ -43,9 +43,15 @@ ap.add_argument("--scene", default=None, metavar="scene.xml",
 ap.add_argument("--analytic", action="store_true",
                 help="with --scene: shade the bsdf_N balls with their analytic ground truth (analytic.ground_truth_for) and give "
                      "every ball the albedo vector the file gives it (wavefront.albedos_from_matpreview_xml)")
+ap.add_argument("--mesh-file", default=None, metavar="matpreview.serialized",
+                help="with --scene: render the file's own geometry — its 25 instances of the three meshes of this container, under "
+                     "their toWorld, and its lookAt camera — through mesh.MeshArrayRenderer (one bounce, unoccluded; parity-unpinned "
+                     "against Mitsuba) instead of twelve spheres on a plane")
 a = ap.parse_args()
 if a.analytic and not a.scene:
     ap.error("--analytic needs --scene")
+if a.mesh_file and not a.scene:
+    ap.error("--mesh-file needs --scene")
 unbounded = a.max_depth == -1
 if a.integrator_from:
     from bsdf_diffusion_sampling_amd.pathtrace import integrator_from_matpreview_xml
@@ -66,7 +72,12 @@ if a.lights_from or a.point_light:
         lights.append(PointLight(tuple(float(v) for v in pos.split(",")), rgb[0] if len(rgb) == 1 else tuple(rgb)))
 if a.no_env and not lights:
     ap.error("--no-env needs --point-light or --lights-from")
-if a.scene:
+mesh_scene = None
+if a.mesh_file:
+    from bsdf_diffusion_sampling_amd import mesh as MESH
+    materials, cam, mesh_scene, _ = MESH.mesh_scene_from_matpreview_xml(a.scene, a.mesh_file, a.width, a.height)
+    stems = [m + "_spherical" if m.startswith("bsdf_") else m + "_" + a.domain for m in materials]
+elif a.scene:
     materials, cam, centers, radii = WF.scene_from_matpreview_xml(a.scene, a.width, a.height)
     stems = [m + "_spherical" if m.startswith("bsdf_") else m + "_" + a.domain for m in materials]
 else:
@@ -87,7 +98,12 @@ elif a.measured_dir:
         if p: gts[i] = MeasuredBSDF(p)
 if a.env_sampling == "importance" and a.no_env:
     ap.error("--env-sampling importance needs an emitting environment: drop --no-env")
-if (a.max_depth is None and not unbounded and a.rr_depth is None and a.occlusion is None and not lights and a.env_sampling == "cosine"
+if mesh_scene is not None:
+    if not (a.max_depth is None and not unbounded and a.rr_depth is None and a.occlusion is None and not lights
+            and a.env_sampling == "cosine" and not a.compact and not a.transmission):
+        ap.error("--mesh-file renders one unoccluded bounce: the path tracer's options do not apply to it yet")
+    r = MESH.MeshArrayRenderer(tab, mesh_scene, camera=cam, ground_truth=gts, **extra)
+elif (a.max_depth is None and not unbounded and a.rr_depth is None and a.occlusion is None and not lights and a.env_sampling == "cosine"
         and not a.compact and not a.transmission):
     r = WF.ArrayRenderer(tab, centers, radii, camera=cam, ground_truth=gts, **extra)
 else:
