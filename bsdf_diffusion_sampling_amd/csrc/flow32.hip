@@ -144,8 +144,30 @@ __device__ __forceinline__ void split16(const float (&x)[16], Frag (&hi)[2], Fra
 }
 
 // a layer's 16 sigmoids: hs = zs sigma, g = silu' (flow_dev.h: silu_grad_scaled); WITH_G = false: hs alone (no Jacobian)
-template <bool WITH_G>
+// GROUP > 1 (the register-resident kernels): the same arithmetic with the sigmoids of GROUP units issued side by side — all their
+// v_exp, then the adds, then the v_rcp — so that no instruction directly follows the transcendental it depends on.  At 2 waves
+// per SIMD the compiler keeps the unit-by-unit order of the source and pads every such pair with an s_nop.
+template <bool WITH_G, int GROUP = 1>
 __device__ __forceinline__ void act16(const f32x16& z, float (&hs)[16], float (&g)[16]) {
+    if constexpr (GROUP > 1) {
+        static_assert(WITH_G && 16 % GROUP == 0, "grouped sigmoids: the Jacobian kernels, GROUP divides 16");
+#pragma unroll
+        for (int v0 = 0; v0 < 16; v0 += GROUP) {
+            float e[GROUP], s[GROUP];
+#pragma unroll
+            for (int i = 0; i < GROUP; ++i) e[i] = __builtin_amdgcn_exp2f(z[v0 + i]);
+#pragma unroll
+            for (int i = 0; i < GROUP; ++i) e[i] = 1.0f + e[i];
+#pragma unroll
+            for (int i = 0; i < GROUP; ++i) s[i] = __builtin_amdgcn_rcpf(e[i]);
+#pragma unroll
+            for (int i = 0; i < GROUP; ++i) {   // flow_dev.h: silu_grad_scaled
+                hs[v0 + i] = z[v0 + i] * s[i];
+                g[v0 + i] = fmaf(hs[v0 + i], fmaf(s[i], kLn2, -kLn2), s[i]);
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
         if (WITH_G) silu_grad_scaled(z[v], hs[v], g[v]);
@@ -212,6 +234,21 @@ __device__ __forceinline__ void split16_jac(const float (&x)[16], Frag (&hi)[2],
     if (BSDFD_T32_JAC2 == 1) split16<false>(x, hi, lo); else split16<true>(x, hi, lo);
 }
 
+// Issue order of a scheduling region of the register-resident kernels (between two sched_barrier(0)): LEAD MFMAs, then N times
+// [1 MFMA, TRANS transcendentals, VALU other vector instructions] — the region's own VALU work placed behind the MFMAs of its chain
+// instead of after it.  A group the region cannot fill stays short; what no group takes is scheduled freely.
+constexpr int SG_VALU = 0x002, SG_MFMA = 0x008, SG_TRANS = 0x400;
+template <int LEAD, int N, int TRANS, int VALU>
+__device__ __forceinline__ void issue_order() {
+    if constexpr (LEAD > 0) __builtin_amdgcn_sched_group_barrier(SG_MFMA, LEAD, 0);
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+        if constexpr (TRANS > 0) __builtin_amdgcn_sched_group_barrier(SG_TRANS, TRANS, 0);
+        if constexpr (VALU > 0) __builtin_amdgcn_sched_group_barrier(SG_VALU, VALU, 0);
+    }
+}
+
 // Best & Fisher rejection sampler, 32-query tiles: the 2 lanes of a query test 4 consecutive proposals of the query's Philox
 // stream per round (lane h: proposals 4 round + 2 h + {0, 1}); the first accepted one in stream order wins, so the draw equals
 // von_mises_sample's (flow_dev.h) and the sequential loop's of torch/distributions/von_mises.py::_rejection_sample.
@@ -270,13 +307,16 @@ __device__ __forceinline__ float von_mises_sample32(float mu, float kappa, unsig
 // plugins make: the disk net, split3 with the Jacobian, op = ROP (OP_SAMPLE | OP_PDF) and io = IO_PLUGIN as compile-time constants,
 // no segments, no context, no row_index / rng_index, no injected base point, T a power of two.  At 2 waves per SIMD (256 VGPRs) the
 // 24 hidden-layer fragments and the layer-1 fragment are read from LDS ONCE per workgroup and stay in registers across every tile and
-// Euler step; WOUT, the conditioning matrix and the base net stay in LDS.  The host (host.hip, run()) selects it; every other call
-// form runs the general kernel (ROP = -1), whose code this parameter does not touch.
+// Euler step; WOUT, the conditioning matrix and the base net stay in LDS.  With only one other wave on the SIMD to fill the shadow
+// of an MFMA, the step's issue order is fixed by hand (issue_order): every MFMA chain carries VALU work that does not depend on it.
+// The host (host.hip, run()) selects it; every other call form runs the general kernel (ROP = -1), whose code this parameter does
+// not touch.
 // ---------------------------------------------------------------------------------------------
 template <int DOMAIN, bool JAC, bool FUSED, bool SPLIT, int ROP = -1>
 __global__ __launch_bounds__(256, ROP >= 0 ? 2 : (FUSED && DOMAIN == BSDFD_DOMAIN_SPHERICAL) ? BSDFD_T32_FUSED_SPH_WAVES : BSDFD_T32_WAVES) void flow_kernel32(const KParams p) {
     static_assert(SPLIT || !JAC, "the single-product (f16) instantiations exist without the Jacobian only");
     constexpr bool RES = ROP >= 0;
+    constexpr int SIG_GROUP = 4;   // RES: sigmoids issued side by side, four at a time (act16<.., GROUP>)
     static_assert(!RES || (DOMAIN == BSDFD_DOMAIN_DISK && JAC && !FUSED && SPLIT && (ROP == OP_SAMPLE || ROP == OP_PDF)),
                   "the resident fast path serves the disk net's plugin sample / pdf calls only");
     using LY = L32<DOMAIN>;
@@ -577,7 +617,7 @@ __global__ __launch_bounds__(256, ROP >= 0 ? 2 : (FUSED && DOMAIN == BSDFD_DOMAI
         // ---------------- T explicit Euler steps ---------------------------------------------------
         float acc = 1.0f;
         for (int t = 0; t < p.T; ++t) {
-            asm volatile("s_nop 0");   // keeps the weight-fragment loads inside the loop (bsdfd.hip, the same statement)
+            if constexpr (!RES) asm volatile("s_nop 0");   // keeps the weight-fragment loads inside the loop (bsdfd.hip, the same statement; RES has none)
             float alpha;
             if (t_pow2) {
                 const float tf = (float)t * invT;
@@ -626,7 +666,29 @@ __global__ __launch_bounds__(256, ROP >= 0 ? 2 : (FUSED && DOMAIN == BSDFD_DOMAI
 #pragma unroll
                 for (int v = 0; v < 16; ++v) { U0[v] *= gm[v]; U1[v] *= gm[v]; }
             };
-            if (!SPH) {
+            if constexpr (RES) {
+                // ---- the general kernel's disk block below, statement for statement, in the issue order of DESIGN.md §4.3: at
+                //      2 waves per SIMD nothing else fills an MFMA chain, so each chain carries the VALU work that is independent
+                //      of it (regions fenced by sched_barrier(0), order inside them by issue_order) ----
+                __builtin_amdgcn_sched_barrier(0);
+                act16<true, SIG_GROUP>(z, hv, gv);
+                split16(hv, bh, bl);
+                __builtin_amdgcn_sched_barrier(0);
+                z = mm6<true>(rW2, bh, bl);                 // the W2 chain carries the split of g1
+                split16_jac(gv, gh, gl);
+                issue_order<0, 6, 0, 7>();
+                __builtin_amdgcn_sched_barrier(0);
+                mm6x2(rF0, gh, gl, rF1, gh, gl, U0, U1);    // the F0 / F1 chain carries layer 2's sigmoids and the split of its output
+                act16<true, SIG_GROUP>(z, hv, gm);
+                split16(hv, bh, bl);
+                issue_order<1, 11, 3, 7>();
+                __builtin_amdgcn_sched_barrier(0);
+                z = mm6<true>(rW3, bh, bl);                 // the W3 chain carries premul
+                premul();
+                issue_order<2, 3, 0, 6>();                   // (U0, U1 are still in flight behind the F chain: two MFMAs first)
+                issue_order<1, 0, 0, 0>();                   // the rest of premul stands behind the chain, under layer 3's latency
+                __builtin_amdgcn_sched_barrier(0);
+            } else if (!SPH) {
                 // ---- MIM, disk 25-32-32-32-2: U_i = F_i g1, R_j = G_j g3, J_ji = sum_k R_j[k] g2[k] U_i[k] (bsdfd.hip, block MIM)
                 if constexpr (SPLIT) { act16<JAC>(z, hv, gv); split16(hv, bh, bl); }
                 else act_pack16(z, bh);
@@ -687,10 +749,15 @@ __global__ __launch_bounds__(256, ROP >= 0 ? 2 : (FUSED && DOMAIN == BSDFD_DOMAI
                 z = mm6<SPLIT>(load_mat(smem, LY::WH + 2 * 4 * FR32, lane), bh, bl);
             }
             // ---- last hidden layer -> R0, R1 (MFMA), v (fp32 VALU dot over the lane's 16 units + one swap) ----
-            act16<JAC>(z, hv, gv);
+            if constexpr (RES) act16<true, SIG_GROUP>(z, hv, gv);
+            else act16<JAC>(z, hv, gv);
             f32x16 R0, R1;
             if constexpr (JAC) {
                 split16_jac(gv, gh, gl);
+                if constexpr (RES) {   // the G0 chain carries the output dot, the swap and the xs update
+                    __builtin_amdgcn_sched_barrier(0);
+                    R0 = mm6<true>(rG0, gh, gl);
+                } else
                 mm6x2(mat(rG0, LY::WG), gh, gl, mat(rG1, LY::WG + 4 * FR32), gh, gl, R0, R1);
             }
             {
@@ -706,9 +773,30 @@ __global__ __launch_bounds__(256, ROP >= 0 ? 2 : (FUSED && DOMAIN == BSDFD_DOMAI
                 swap32(pv0, pv1);            // lower: v0 over the lane pair | upper: v1
                 xs = fmaf(cstep, pv0 + pv1, xs);
             }
+            f32x2 ja2 = {0.f, 0.f}, jb2 = ja2, jc2 = ja2, jd2 = ja2;  // J00, J11, J01, J10
+            // R . (gm . U0), R . (gm . U1) over the lane's 16 units: one row of the sums below
+            auto jrow = [&](const f32x16& R, f32x2& s0, f32x2& s1) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) {
+                    const f32x2 r = {R[2 * k], R[2 * k + 1]};
+                    s0 = __builtin_elementwise_fma(r, (f32x2){U0[2 * k], U0[2 * k + 1]}, s0);
+                    s1 = __builtin_elementwise_fma(r, (f32x2){U1[2 * k], U1[2 * k + 1]}, s1);
+                }
+            };
+            if constexpr (RES) {
+                // R0 and R1 as two chains of six (per accumulator the order of mm6x2).  The output dot above spreads over the G0
+                // chain and the first two MFMAs of the G1 chain, by when R0 is complete; the last four carry R0's row of the
+                // J sums (each sum keeps its order of additions), whose rest stands behind the chain, where R1 is still in flight
+                R1 = mm6<true>(rG1, gh, gl);
+                jrow(R0, ja2, jc2);
+                issue_order<0, 8, 0, 2>();
+                issue_order<0, 4, 0, 4>();
+                __builtin_amdgcn_sched_barrier(0);
+                jrow(R1, jd2, jb2);
+            }
             // ---- J_ji = sum_k R_j[k] (gm[k] U_i[k]) over the lane's 16 units, then over the query's 2 lanes; det(I + c J) ----
             if constexpr (JAC) {
-                f32x2 ja2 = {0.f, 0.f}, jb2 = ja2, jc2 = ja2, jd2 = ja2;  // J00, J11, J01, J10
+                if constexpr (!RES)
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     const f32x2 r0 = {R0[2 * k], R0[2 * k + 1]}, r1 = {R1[2 * k], R1[2 * k + 1]};

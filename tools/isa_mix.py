@@ -7,8 +7,9 @@
 
 Finds the kernel's body, takes the innermost loop that holds the most MFMAs (the Euler step: a label
 and the backward branch to it) and prints the count per mnemonic, the issue-cycle estimate at the rates
-of tools/ubench/RESULTS.md, and the kernel's register / scratch footprint.  Used for the
-"VALU instructions per tile-step" column of DESIGN.md §4 and the issue-bound roofline of bench.py.
+of tools/ubench/RESULTS.md, how the loop's MFMAs are spaced (`mfma_bare`, `pad_cycles`: schedule()),
+and the kernel's register / scratch footprint.  Used for the "VALU instructions per tile-step" column
+of DESIGN.md §4 and the issue-bound roofline of bench.py.
 """
 import json
 import re
@@ -54,6 +55,7 @@ from bsdf_diffusion_sampling_amd._asmcheck import check_async_lines, check_file_
 
 KERNEL_OF_WORKLOAD = {  # bench.py workload -> mangled-name fragment of its flow kernel (split3, Jacobian; the library's default tile)
     "disk_1Mi_T8": "flow_kernel32ILi0ELb1ELb0ELb1ELi0E",     # T >= 8: the register-resident fast path (ROP = OP_SAMPLE)
+    "disk_1Mi_T8@pdf": "flow_kernel32ILi0ELb1ELb0ELb1ELi1E", # ... and its pdf launch (ROP = OP_PDF)
     "disk_1Mi_T4": "flow_kernel32ILi0ELb1ELb0ELb1ELin1E",    # the general kernel (ROP = -1)
     "spherical_16Mi_T8": "flow_kernel32ILi1ELb1ELb0ELb1ELin1E",
     "teacher_64x6_4Mi_T128": "flow_kernel32wE",
@@ -206,6 +208,25 @@ def main():
     print(json.dumps(model(sys.argv[1], sys.argv[2]), indent=1))
 
 
+def schedule(body, lo, hi):
+    """How the loop's MFMAs are spaced.  `mfma_bare`: MFMAs followed directly by another MFMA or by an s_nop (nothing of the
+    wave's own issues behind them); `pad_cycles`: the cycles of the loop's s_nop pads (s_nop N idles N + 1); with them the
+    longest run of MFMAs back to back, the number of pads and the pads longer than 4 cycles."""
+    ops = []
+    for l in body[lo:hi + 1]:
+        l = l.split(";")[0].strip()
+        if l and not l.endswith(":") and not l.startswith("."):
+            ops.append(l.split())
+    pads = [int(o[1], 0) + 1 for o in ops if o[0] == "s_nop"]
+    is_mfma = [o[0].startswith("v_mfma") for o in ops]
+    bare = sum(1 for i, m in enumerate(is_mfma[:-1]) if m and (is_mfma[i + 1] or ops[i + 1][0] == "s_nop"))
+    run = longest = 0
+    for m in is_mfma:
+        run = run + 1 if m else 0
+        longest = max(longest, run)
+    return {"mfma_bare": bare, "pad_cycles": sum(pads), "mfma_run_max": longest, "n_pads": len(pads), "pads_over_4": [p for p in pads if p > 4]}
+
+
 def model(path, key):
     lines = open(path).read().splitlines()
     body = kernel_body(lines, key)
@@ -245,6 +266,7 @@ def model(path, key):
         "matrix_pipe_cycles": round(sum(MATRIX_PIPE.get(k, 16.2) * v for k, v in mfma.items()), 1),
         "meta": meta,
     }
+    res.update(schedule(body, *best))
     # MFMA time and VALU time add (round 4, tools/ubench/mfma_src)
     res["issue_cycles_total"] = round(res["issue_cycles_mfma"] + res["issue_cycles_valu"], 1)
     return res
