@@ -67,7 +67,7 @@ EXPORTS = (
     "bsdfd_measured_eval_table_rows", "bsdfd_analytic_eval_table_rows",
     "bsdfd_wf_bounce_transmit", "bsdfd_wf_sample_inside", "bsdfd_wf_sample_inside_rows",
     "bsdfd_mesh_bvh_build", "bsdfd_mesh_scene_create", "bsdfd_mesh_scene_destroy", "bsdfd_mesh_intersect", "bsdfd_mesh_occluded",
-    "bsdfd_mesh_primary",
+    "bsdfd_mesh_primary", "bsdfd_mesh_path_primary", "bsdfd_mesh_sample_emitter", "bsdfd_mesh_bounce",
     "bsdfd_set_profiling", "bsdfd_profile_read", "bsdfd_profile_read_op", "bsdfd_profile_clock_mhz", "bsdfd_last_kernel_ms", "bsdfd_shader_clock_mhz",
     "bsdfd_last_error", "bsdfd_version", "bsdfd_abi_version",
 )
@@ -544,6 +544,11 @@ def lib():
     L.bsdfd_mesh_intersect.argtypes = [vp, i64, fp, fp, fp, fp, fp, fp, fp, vp]
     L.bsdfd_mesh_occluded.argtypes = [vp, i64, fp, fp, fp, fp, fp, vp]
     L.bsdfd_mesh_primary.argtypes = [vp] + L.bsdfd_wf_primary.argtypes
+    # the path tracer on meshes: the scene in front of the sibling's arguments, the additions in front of the stream — (env, org,
+    # prim, beta, rad) for the primary rays, prim for the other two
+    L.bsdfd_mesh_path_primary.argtypes = L.bsdfd_mesh_primary.argtypes[:-1] + [fp] * 5 + [vp]
+    L.bsdfd_mesh_sample_emitter.argtypes = [vp] + L.bsdfd_wf_sample_emitter.argtypes[:-1] + [fp, vp]
+    L.bsdfd_mesh_bounce.argtypes = [vp] + L.bsdfd_wf_bounce_rr.argtypes[:-1] + [fp, vp]
     L.bsdfd_bucket_rows.argtypes = L.bsdfd_bucket_by_material.argtypes[:1] + [fp] + L.bsdfd_bucket_by_material.argtypes[1:]
     L.bsdfd_bucket_wide_workspace_bytes.argtypes = [i64, i32]
     L.bsdfd_bucket_wide_workspace_bytes.restype = i64

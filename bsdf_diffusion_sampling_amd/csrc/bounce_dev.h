@@ -12,6 +12,10 @@
 // Each instantiation is straight-line code of its own.  RR = true is the same body with Russian roulette in front of
 // continue_path.
 //
+// What the scene is made of is a parameter too: a geometry policy (Spheres below, the scene of every kernel named above;
+// mesh_dev::PathGeom, which mesh.hip instantiates this body and sample_emitter_vertex with) answers for the closest hit, for a
+// shadow ray and for the next vertex.  The estimate, the MIS weights, the roulette and the Philox counters do not depend on it.
+//
 // The arrays travel in small structs passed by value (kernel arguments: scalar loads); no struct is indexed per lane.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -75,16 +79,40 @@ __device__ __forceinline__ void tagged_draw(unsigned long long seed, unsigned lo
     philox4x32((unsigned)seed, (unsigned)(seed >> 32), (unsigned)gp, (unsigned)(gp >> 32), (unsigned)pass, tag + (unsigned)bounce, u);
 }
 
-// An emitter sample along the world direction `dir` from the vertex (x, nn) of surface m: its cosine, and whether it arrives —
-// above the horizon and (occlusion) nothing nearer than `dist` in the way.
+// The geometry policy: the three things the path kernels ask of the scene — the closest hit of a ray that leaves the vertex of
+// lane p (own surface excepted), whether a shadow ray is blocked (at all: the environment; nearer than `dist`: a point light),
+// and the next vertex written at a hit.  `Spheres` is the analytic scene that travels in `Scene`: trace and continue_path, as
+// they are.  mesh_dev::PathGeom (mesh_dev.h) is the instanced triangle meshes.  ONE_WALK: a hit costs a run-time loop of its
+// own, so bounce_vertex forms the continuation ray of every lane first and asks once for the whole wave.
+struct Spheres {
+    using Hit = wf_dev::Hit;
+    static constexpr bool ONE_WALK = false;
+    __device__ __forceinline__ static Hit nothing() {
+        Hit h;
+        h.t = 3.0e38f; h.id = -1; h.c = v3(0.f, 0.f, 0.f); h.r = 1.0f;
+        return h;
+    }
+    __device__ __forceinline__ static bool is_hit(const Hit& h) { return h.id >= 0; }
+    __device__ __forceinline__ Hit closest(const Scene& sc, V3 x, V3 d, long long m, long long) const { return trace(sc, x, d, (int)m); }
+    __device__ __forceinline__ bool occluded(const Scene& sc, V3 x, V3 d, long long m, long long) const {
+        return trace(sc, x, d, (int)m).id >= 0;
+    }
+    __device__ __forceinline__ bool occluded(const Scene& sc, V3 x, V3 d, long long m, long long, float dist) const {
+        const Hit h = trace(sc, x, d, (int)m);
+        return h.id >= 0 && h.t < dist;
+    }
+    template <class... A>
+    __device__ __forceinline__ void advance(const Scene& sc, const Hit& h, A... a) const { continue_path(sc, h, a...); }
+};
+
+// An emitter sample along the world direction `dir` from the vertex (x, nn) of lane p, surface m: its cosine, and whether it
+// arrives — above the horizon and (occlusion) nothing nearer than `dist` in the way.
+template <class G = Spheres>
 __device__ __forceinline__ bool emitter_arrives(const Scene& sc, V3 x, V3 nn, V3 dir, long long m, int occlusion, float dist,
-                                                bool valid, float& cosl) {
+                                                bool valid, float& cosl, long long p = 0, const G& g = G{}) {
     cosl = dot(dir, nn);
     bool lit = valid && cosl > 0.0f;
-    if (lit && occlusion) {
-        const Hit h = trace(sc, x, dir, (int)m);
-        lit = !(h.id >= 0 && h.t < dist);
-    }
+    if (lit && occlusion) lit = !g.occluded(sc, x, dir, m, p, dist);
     return lit;
 }
 
@@ -108,6 +136,11 @@ __device__ __forceinline__ void store_local_direction(float* __restrict__ wl, V3
 //
 // LIST: the lanes are those of `rows` (the list forms of the six kernels); nothing else differs.
 //
+// G: the geometry policy.  With G::ONE_WALK the rays are formed in front of the two branches — the floor's cosine direction, the
+// ball's BSDF sample, and the shadow ray along wl of a ball that looks the environment up there (COSINE; LIT where the
+// environment was picked) — and the wave asks for its closest hits in one call and for its shadow rays in another: asked from inside the branches, floor lanes and ball lanes of one wave would walk one after the other.
+// The branches then read the answers; with Spheres they ask where they always did, and this block folds away.
+//
 // TRANSMIT: a usable BSDF sample below the surface (o.z < 0, under occlusion) at a vertex with ground truth for wo is followed
 // into the ball instead of being dropped, if its throughput factor f_o / pb is positive in some channel: the ray enters, or stays
 // in, the ball it is on, and its hit is that ball's far side, t = -2 (x - c) . d — the far root of trace's quadratic for an origin
@@ -117,10 +150,11 @@ __device__ __forceinline__ void store_local_direction(float* __restrict__ wl, V3
 // strategy draws above the outward normal (the directions one transmission can reach), the shadow ray skips its own ball, and a
 // sample with o.z > 0 leaves the surface outward whichever side wi is on.  Without ground truth (the proxy) and with f_o == 0 in
 // every channel (an opaque material) such a sample ends the path as before.
-template <int M, bool RR = false, bool LIST = false, bool TRANSMIT = false>
+template <int M, bool RR = false, bool LIST = false, bool TRANSMIT = false, class G = Spheres>
 __device__ __forceinline__ void bounce_vertex(const Scene& sc, const float* __restrict__ env, const EnvDist& e, int n_e, int has_env,
                                               const Step& st, const PathState& ps, const SamplerAnswer& sa,
-                                              const EmitterSample& es, int rr_depth = 0, const Rows& rows = Rows{}) {
+                                              const EmitterSample& es, int rr_depth = 0, const Rows& rows = Rows{}, const G& g = G{}) {
+    static_assert(!(G::ONE_WALK && (TRANSMIT || LIST || M == ENV)), "not on meshes yet");
     long long p, m;
     if (!live_lane<LIST>(sc, st.n, ps.mat, p, m, rows)) return;
     const int occlusion = st.occlusion;
@@ -143,15 +177,29 @@ __device__ __forceinline__ void bounce_vertex(const Scene& sc, const float* __re
     float L[3] = {0.f, 0.f, 0.f};   // the vertex' estimate, before the throughput
     float thr[3] = {1.f, 1.f, 1.f};  // throughput factor of the continuing direction
     V3 d = lw;                       // ... that direction
-    Hit h;
-    h.t = 3.0e38f; h.id = -1; h.c = v3(0.f, 0.f, 0.f); h.r = 1.0f;
+    typename G::Hit h = G::nothing();
     bool go = false;                 // the path continues at `h`
+    bool shadowed = false;           // ONE_WALK: something lies along the ball's cosine light sample
+    if constexpr (G::ONE_WALK) {
+        bool ask = occlusion, ask_shadow = false;
+        if (m != sc.n_sph) {
+            const V3 o = ld3(sa.wo + 3 * p);
+            d = o.x * fs + o.y * ft + o.z * nn;
+            ask = ask && usable_pdf(sa.pdf_o[p]) > 0.0f && o.z > 0.0f;
+            // (LIT: the vertices that picked the environment take the cosine strategy too)
+            ask_shadow = occlusion && !point && (usable_pdf(sa.pdf_l[p]) > 0.0f || has_ground_truth(sa.f_l, p)) && l.z * inv_pi * sel_p > 0.0f;
+        }
+        if (ask) h = g.closest(sc, x, d, m, p);
+        if (ask_shadow) shadowed = g.occluded(sc, x, lw, m, p);
+    }
     if (m == sc.n_sph) {
         // diffuse floor, cosine-sampled: f cos / pdf = reflectance (in the wi slot); the direction in wl is its BSDF sample — at
         // full weight towards the environment, or (ENV) weighted against the environment's own density — and the way on
         const float refl = ps.wi[3 * p];
-        if (occlusion) h = trace(sc, x, lw, (int)m);
-        if (h.id < 0) {
+        if constexpr (!G::ONE_WALK) {
+            if (occlusion) h = g.closest(sc, x, lw, m, p);
+        }
+        if (!G::is_hit(h)) {
             if (env_emits) floor_term(sc, env, lw, refl, L);
             if constexpr (M == ENV) {
                 const float w = mis_power(l.z * inv_pi, env_dev::env_pdf(e, lw) * sel_p);
@@ -170,11 +218,13 @@ __device__ __forceinline__ void bounce_vertex(const Scene& sc, const float* __re
         const V3 o = ld3(sa.wo + 3 * p);
         const float pb = usable_pdf(sa.pdf_o[p]);
         if (pb > 0.0f && (!occlusion || o.z > 0.0f)) {   // (a direction below the surface is blocked by the ball itself)
-            d = o.x * fs + o.y * ft + o.z * nn;
+            if constexpr (!G::ONE_WALK) d = o.x * fs + o.y * ft + o.z * nn;
 #pragma unroll
             for (int c = 0; c < 3; ++c) thr[c] = gt_o ? sa.f_o[3 * p + c] / pb : sc.albedo[c];
-            if (occlusion) h = trace(sc, x, d, (int)m);
-            if (h.id >= 0) {
+            if constexpr (!G::ONE_WALK) {
+                if (occlusion) h = g.closest(sc, x, d, m, p);
+            }
+            if (G::is_hit(h)) {
                 go = true;   // geometry does not emit, and a BSDF sample cannot hit a point
             } else if (env_emits) {
                 // the BSDF sample escapes: the environment, weighted against the light strategy's density for this direction
@@ -222,7 +272,10 @@ __device__ __forceinline__ void bounce_vertex(const Scene& sc, const float* __re
             } else {
                 // the environment along the cosine sample (pdf cos/pi, chosen with probability sel_p), unless something is in the way
                 const float pl = l.z * inv_pi * sel_p;
-                if (pl > 0.0f && !(occlusion && trace(sc, x, lw, (int)m).id >= 0)) {
+                bool open;   // the sample is drawn and nothing is in its way
+                if constexpr (G::ONE_WALK) open = pl > 0.0f && !shadowed;
+                else open = pl > 0.0f && !(occlusion && g.occluded(sc, x, lw, m, p));
+                if (open) {
                     const float w = mis_power(pl, pbl) / pl;
                     float ev[3];
                     env_lookup(env, sc.env_w, sc.env_h, lw, ev);
@@ -253,7 +306,50 @@ __device__ __forceinline__ void bounce_vertex(const Scene& sc, const float* __re
             for (int c = 0; c < 3; ++c) thr[c] *= inv_q;
         }
     }
-    continue_path(sc, h, x, d, b, thr, st.seed, st.pass, st.path_offset, st.bounce, p, ps.org, ps.nrm, ps.wi, ps.wl, ps.mat, ps.beta);
+    g.advance(sc, h, x, d, b, thr, st.seed, st.pass, st.path_offset, st.bounce, p, ps.org, ps.nrm, ps.wi, ps.wl, ps.mat, ps.beta);
+}
+
+// ---- the point emitters' sample (pathlights.hip; on meshes: mesh.hip) ----
+struct Lights {
+    int n;         // point emitters
+    int n_e;       // emitters: n, plus one if the environment emits
+    float pos[BSDFD_WF_MAX_LIGHTS][3];
+    float inten[BSDFD_WF_MAX_LIGHTS][3];
+};
+
+// The emitter sample of lane p's vertex (pathlights.hip's header has the rule).  LIST: the lanes of `rows`; G: the geometry the
+// shadow ray is cast in.
+template <bool LIST = false, class G = Spheres>
+__device__ __forceinline__ void sample_emitter_vertex(const Scene& sc, const Lights& lt, const Step& st, const float* __restrict__ org,
+                                                      const float* __restrict__ nrm, const float* __restrict__ wi,
+                                                      const long long* __restrict__ mat, float* __restrict__ wl,
+                                                      int* __restrict__ lsel, float* __restrict__ emit, const Rows& rows = Rows{},
+                                                      const G& g = G{}) {
+    long long p, m;
+    if (!live_lane<LIST>(sc, st.n, mat, p, m, rows)) return;
+    unsigned u[4];
+    tagged_draw(st.seed, st.pass, st.path_offset, p, 0x4C697465u /* "Lite" */, st.bounce, u);
+    const int pick = (int)(((unsigned long long)u[0] * (unsigned long long)lt.n_e) >> 32);
+    if (pick == lt.n) {   // the environment: the bounce looks it up along the cosine sample that is already in wl
+        lsel[p] = -1;
+        st3(emit + 3 * p, v3(0.f, 0.f, 0.f));
+        return;
+    }
+    V3 P = v3(0.f, 0.f, 0.f), I = v3(0.f, 0.f, 0.f);
+    for (int k = 0; k < lt.n; ++k)   // wave-uniform loop, per-lane select: no per-lane index into lt
+        if (pick == k) { P = v3(lt.pos[k][0], lt.pos[k][1], lt.pos[k][2]); I = v3(lt.inten[k][0], lt.inten[k][1], lt.inten[k][2]); }
+    const V3 nn = ld3(nrm + 3 * p), x = ld3(org + 3 * p);
+    const V3 v = P - x;
+    const float d2 = dot(v, v);
+    const float dist = sqrtf(d2);
+    const V3 dir = (1.0f / dist) * v;
+    float cosl;
+    const bool lit = emitter_arrives(sc, x, nn, dir, m, st.occlusion, dist, true, cosl, p, g);
+    float s = lit ? (float)lt.n_e / d2 : 0.0f;
+    if (m == sc.n_sph) s *= wi[3 * p] * 0.31830988618379067154f * cosl;   // diffuse floor: f cos = (reflectance / pi) cos
+    else store_local_direction(wl + 3 * p, nn, dir, cosl);
+    lsel[p] = pick;
+    st3(emit + 3 * p, s * I);
 }
 
 // ---- host side ----
@@ -276,6 +372,17 @@ inline int light_counts(const bsdfd_wf_lights* l, int& n, int& n_e) {
     if (l->n_lights < 1 || l->n_lights > BSDFD_WF_MAX_LIGHTS) return bsdfd_fail_(BSDFD_EINVAL, "1..8 point lights");
     n = l->n_lights;
     n_e = l->n_lights + (l->has_env ? 1 : 0);
+    return BSDFD_OK;
+}
+
+// the kernel-argument form of a bsdfd_wf_lights
+inline int to_lights(const bsdfd_wf_lights* l, Lights& lt) {
+    if (int rc = light_counts(l, lt.n, lt.n_e)) return rc;
+    for (int k = 0; k < BSDFD_WF_MAX_LIGHTS; ++k)
+        for (int c = 0; c < 3; ++c) {
+            lt.pos[k][c] = k < lt.n ? l->position[k][c] : 0.0f;
+            lt.inten[k][c] = k < lt.n ? l->intensity[k][c] : 0.0f;
+        }
     return BSDFD_OK;
 }
 

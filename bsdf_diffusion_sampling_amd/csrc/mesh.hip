@@ -5,7 +5,11 @@
 //             call, so C callers and the CPU suite can build and inspect one); bsdfd_mesh_scene_create — meshes uploaded once
 //             with their BVH, instances with the fp64 inverse of their to_world and a padded world box
 //   kernels : intersect (closest hit), occluded (any hit), primary (bsdfd_wf_primary's rays, closest hit, the five arrays
-//             shade_kernel reads) — one ray per lane, the walk of mesh_dev.h; no stack, no scratch
+//             shade_kernel reads; its path form also stores the hit, and path_begin makes the first vertex of a path from it) — one ray per lane, the walk of
+//             mesh_dev.h; no stack, no scratch
+//             bounce, sample_emitter — the path tracer's one bounce and its point emitters' sample (bounce_dev.h) with the mesh
+//             scene as their geometry: COSINE and LIT, with and without roulette, full width.  No ENV mode, no live-lane list
+//             and no transmission on meshes yet.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "bounce_dev.h"
 #include "bsdfd.h"
 #include "common.h"
 #include "mesh_dev.h"
@@ -30,7 +35,7 @@ struct bsdfd_mesh_scene_ctx {
 
 namespace {
 
-using namespace wf_dev;
+using namespace bounce_dev;   // (and wf_dev, which it opens)
 using mesh_dev::Inst;
 using mesh_dev::MeshHit;
 
@@ -136,14 +141,16 @@ __global__ __launch_bounds__(256) void occluded_kernel(const Inst* __restrict__ 
     out[p] = h.inst >= 0 ? 1 : 0;
 }
 
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
-
 // primary_kernel of wavefront.hip on the mesh scene: its path index, Philox words, film position, ray and light sample, statement
-// for statement (dir and wl are its bits), then the closest hit among the instances.
+// for statement (dir and wl are its bits), then the closest hit among the instances.  With `prim` (the path form; wave-uniform)
+// the hit itself is stored as well — prim = (instance, triangle) and t in the first slot of the lane's `hit_t` row (the path's org
+// array, which mesh_path_begin_kernel reads and overwrites).  Stores only: the compiler fuses the ray and vertex arithmetic by the
+// code around it, so the path form adds none here — dir and wl stay bsdfd_wf_primary's bits and wi, nrm the plain form's.
 __global__ __launch_bounds__(256) void mesh_primary_kernel(Scene sc, const Inst* __restrict__ insts, int n_inst, int row_begin,
                                                            int row_end, int spp, unsigned long long seed, unsigned long long pass,
                                                            float* __restrict__ wi, float* __restrict__ wl, float* __restrict__ nrm,
-                                                           float* __restrict__ dir, long long* __restrict__ mat) {
+                                                           float* __restrict__ dir, long long* __restrict__ mat,
+                                                           float* __restrict__ hit_t, int* __restrict__ prim) {
     const long long n = (long long)(row_end - row_begin) * sc.width * spp;
     const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
@@ -164,49 +171,53 @@ __global__ __launch_bounds__(256) void mesh_primary_kernel(Scene sc, const Inst*
     const MeshHit h = mesh_dev::walk<false>(insts, n_inst, sc.o, d, mesh_dev::NOTHING, -1, -1);
     V3 nn = v3(0.f, 0.f, 0.f), w_in = v3(0.f, 0.f, 1.f);
     long long material = sc.n_sph + 1;  // miss
-    if (h.inst >= 0) {
-        const Inst& in = insts[h.inst];
-        const unsigned i0 = in.idx[3 * h.tri], i1 = in.idx[3 * h.tri + 1], i2 = in.idx[3 * h.tri + 2];
-        const float b0 = 1.0f - h.b1 - h.b2;
-        const V3 p0 = ld3(in.pos + 3ll * i0), p1 = ld3(in.pos + 3ll * i1), p2 = ld3(in.pos + 3ll * i2);
-        // geometric normal, through the inverse transpose (a mirroring transform turns the winding: faced by the ray, not by it)
-        V3 ng = mesh_dev::normal_to_world(in.inv, cross(p1 - p0, p2 - p0));
-        ng = (1.0f / sqrtf(dot(ng, ng))) * ng;
-        if (dot(ng, d) > 0.0f) ng = -1.0f * ng;
-        nn = ng;
-        if (in.nrm) {
-            const V3 mix = b0 * ld3(in.nrm + 3ll * i0) + h.b1 * ld3(in.nrm + 3ll * i1) + h.b2 * ld3(in.nrm + 3ll * i2);
-            V3 ns = mesh_dev::normal_to_world(in.inv, mix);
-            const float l2 = dot(ns, ns);
-            if (l2 > 0.0f && l2 < INFINITY) {
-                ns = (1.0f / sqrtf(l2)) * ns;
-                if (dot(ns, ng) < 0.0f) ns = -1.0f * ns;
-                if (-dot(d, ns) > 0.0f) nn = ns;   // else the geometric normal: every material lane has wi.z > 0
-            }
-        }
-        if (in.surface == BSDFD_MESH_MATERIAL) {
-            V3 fs, ft;
-            onb(nn, fs, ft);
-            w_in = v3(-dot(d, fs), -dot(d, ft), -dot(d, nn));
-            material = in.material;
-        } else {   // not neural: the reflectance travels in the wi slot, the id is n_materials
-            float refl = in.c0;
-            if (in.surface == BSDFD_MESH_CHECKER) {
-                const float uu = b0 * in.uv[2ll * i0] + h.b1 * in.uv[2ll * i1] + h.b2 * in.uv[2ll * i2];
-                const float vv = b0 * in.uv[2ll * i0 + 1] + h.b1 * in.uv[2ll * i1 + 1] + h.b2 * in.uv[2ll * i2 + 1];
-                const int cu = (int)floorf(2.0f * in.uscale * uu), cv = (int)floorf(2.0f * in.vscale * vv);
-                refl = ((cu + cv) & 1) ? in.c1 : in.c0;
-            }
-            w_in = v3(refl, refl, refl);
-            material = sc.n_sph;
-        }
-    }
+    if (h.inst >= 0) mesh_dev::surface_vertex(insts, h, d, sc.n_sph, nn, w_in, material);
     const V3 w_l = cosine_sample(u[2], u[3]);
     st3(wi + 3 * p, w_in);
     st3(wl + 3 * p, w_l);
     st3(nrm + 3 * p, nn);
     st3(dir + 3 * p, d);
     if (mat) mat[p] = material;
+    if (prim) {
+        hit_t[3 * p] = h.t;
+        prim[2 * p] = h.inst; prim[2 * p + 1] = h.tri;
+    }
+}
+
+// path_begin_kernel of pathtrace.hip behind the kernel above: what it derives from dir, nrm and the id on the spheres comes from
+// the stored hit here — org = cam + t dir for a hit; org = 0 and rad = the environment along dir for a miss; beta = 1, rad = 0 on a hit.
+__global__ __launch_bounds__(256) void mesh_path_begin_kernel(Scene sc, const float* __restrict__ env, long long n,
+                                                              const float* __restrict__ dir, const int* __restrict__ prim,
+                                                              float* __restrict__ org, float* __restrict__ beta,
+                                                              float* __restrict__ rad) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n) return;
+    const V3 d = ld3(dir + 3 * p);
+    V3 o = v3(0.f, 0.f, 0.f);
+    float L[3] = {0.f, 0.f, 0.f};
+    if (prim[2 * p] >= 0) o = sc.o + org[3 * p] * d;
+    else env_lookup(env, sc.env_w, sc.env_h, d, L);   // the camera sees the environment
+    st3(org + 3 * p, o);
+    st3(beta + 3 * p, v3(1.f, 1.f, 1.f));
+    st3(rad + 3 * p, v3(L[0], L[1], L[2]));
+}
+
+// ---- the path kernels on the mesh scene: bounce_dev.h's one bounce and emitter sample with mesh_dev::PathGeom as their geometry ----
+// COSINE and LIT, each with and without roulette, full width.  One template with both modes' arguments; a mode reads its own.
+template <int M, bool RR>
+__global__ __launch_bounds__(256) void mesh_bounce_kernel(Scene sc, mesh_dev::PathGeom g, const float* __restrict__ env, int n_e,
+                                                          int has_env, Step st, PathState ps, SamplerAnswer sa, EmitterSample es,
+                                                          int rr_depth) {
+    bounce_vertex<M, RR, false, false, mesh_dev::PathGeom>(sc, env, EnvDist{}, M == COSINE ? 1 : n_e, M == LIT ? has_env : 1, st, ps, sa,
+                                                           es, rr_depth, Rows{}, g);
+}
+
+__global__ __launch_bounds__(256) void mesh_sample_emitter_kernel(Scene sc, mesh_dev::PathGeom g, Lights lt, Step st,
+                                                                  const float* __restrict__ org, const float* __restrict__ nrm,
+                                                                  const float* __restrict__ wi, const long long* __restrict__ mat,
+                                                                  float* __restrict__ wl, int* __restrict__ lsel,
+                                                                  float* __restrict__ emit) {
+    sample_emitter_vertex<false, mesh_dev::PathGeom>(sc, lt, st, org, nrm, wi, mat, wl, lsel, emit, Rows{}, g);
 }
 
 // ---- host side of the scene ----
@@ -299,13 +310,43 @@ int make_instance(const bsdfd_mesh_instance& s, const DevMesh& dm, Inst& in) {
     return BSDFD_OK;
 }
 
-// the checks the three launchers share, N known to be >= 0
+// the checks the launchers share, N known to be >= 0
 int check_scene(bsdfd_mesh_scene scene) {
     if (!scene) return bsdfd_fail_(BSDFD_EINVAL, "null mesh scene");
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
     if (dev != scene->device) return bsdfd_fail_(BSDFD_EINVAL, "the mesh scene lives on another device");
     return BSDFD_OK;
+}
+
+int check_materials(bsdfd_mesh_scene scene, const Scene& sc) {
+    if (scene->max_material >= sc.n_sph)
+        return bsdfd_fail_(BSDFD_EINVAL, "an instance's material index is not below n_materials = 1 + n_extra_spheres");
+    return BSDFD_OK;
+}
+
+// both forms of the primary rays: `path` carries env, org, prim, beta and rad, and launches mesh_path_begin_kernel behind the walk
+int launch_primary(bool path, bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, int32_t row_begin, int32_t row_end, int32_t spp,
+                   uint64_t seed, uint64_t pass, float* wi, float* wl, float* nrm, float* dir, int64_t* material, const float* env,
+                   float* org, int32_t* prim, float* beta, float* rad, void* stream) {
+    if (!scene) return bsdfd_fail_(BSDFD_EINVAL, "null mesh scene");
+    Scene sc;
+    if (int rc = to_scene(wf_scene, row_begin, row_end, spp, sc)) return rc;
+    if (path && (sc.env_w <= 0 || sc.env_h <= 0)) return bsdfd_fail_(BSDFD_EINVAL, "environment map size must be positive");
+    if (int rc = check_materials(scene, sc)) return rc;
+    const long long n = (long long)(row_end - row_begin) * sc.width * spp;
+    if (n == 0) return BSDFD_OK;
+    if (!wi || !wl || !nrm || !dir || (path && (!org || !prim || !beta || !rad))) return bsdfd_fail_(BSDFD_EINVAL, "null output pointer");
+    if (path && !env) return bsdfd_fail_(BSDFD_EINVAL, "null environment map");
+    if ((n + 255) / 256 > 0x7fffffffLL) return bsdfd_fail_(BSDFD_EINVAL, "tile too large for one launch");
+    if (int rc = check_scene(scene)) return rc;
+    if (int rc = launch_lanes(n, mesh_primary_kernel, stream, sc, (const Inst*)scene->d_inst, scene->n_inst, row_begin, row_end, spp,
+                              (unsigned long long)seed, (unsigned long long)pass, wi, wl, nrm, dir,
+                              reinterpret_cast<long long*>(material), org, reinterpret_cast<int*>(prim)))
+        return rc;
+    if (!path) return BSDFD_OK;
+    return launch_lanes(n, mesh_path_begin_kernel, stream, sc, env, n, (const float*)dir, (const int*)reinterpret_cast<int*>(prim), org,
+                        beta, rad);
 }
 
 }  // namespace
@@ -387,18 +428,68 @@ int bsdfd_mesh_occluded(bsdfd_mesh_scene scene, int64_t N, const float* org, con
 int bsdfd_mesh_primary(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, int32_t row_begin, int32_t row_end, int32_t spp,
                        uint64_t seed, uint64_t pass, float* wi, float* wl, float* nrm, float* dir, int64_t* material,
                        void* stream) {
+    return launch_primary(false, scene, wf_scene, row_begin, row_end, spp, seed, pass, wi, wl, nrm, dir, material, nullptr, nullptr,
+                          nullptr, nullptr, nullptr, stream);
+}
+
+int bsdfd_mesh_path_primary(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, int32_t row_begin, int32_t row_end, int32_t spp,
+                            uint64_t seed, uint64_t pass, float* wi, float* wl, float* nrm, float* dir, int64_t* material,
+                            const float* env, float* org, int32_t* prim, float* beta, float* rad, void* stream) {
+    return launch_primary(true, scene, wf_scene, row_begin, row_end, spp, seed, pass, wi, wl, nrm, dir, material, env, org, prim, beta,
+                          rad, stream);
+}
+
+int bsdfd_mesh_sample_emitter(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, const bsdfd_wf_lights* lights, int32_t bounce,
+                              int32_t occlusion, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, const float* org,
+                              const float* nrm, const float* wi, const int64_t* material, float* wl, int32_t* lsel, float* emit,
+                              const int32_t* prim, void* stream) {
     if (!scene) return bsdfd_fail_(BSDFD_EINVAL, "null mesh scene");
     Scene sc;
-    if (int rc = to_scene(wf_scene, row_begin, row_end, spp, sc)) return rc;
-    if (scene->max_material >= sc.n_sph)
-        return bsdfd_fail_(BSDFD_EINVAL, "an instance's material index is not below n_materials = 1 + n_extra_spheres");
-    const long long n = (long long)(row_end - row_begin) * sc.width * spp;
-    if (n == 0) return BSDFD_OK;
-    if (!wi || !wl || !nrm || !dir) return bsdfd_fail_(BSDFD_EINVAL, "null output pointer");
-    if ((n + 255) / 256 > 0x7fffffffLL) return bsdfd_fail_(BSDFD_EINVAL, "tile too large for one launch");
+    Lights lt;
+    if (int rc = to_scene(wf_scene, 0, 0, 1, sc)) return rc;
+    if (int rc = to_lights(lights, lt)) return rc;
+    if (bounce < 0) return bsdfd_fail_(BSDFD_EINVAL, "bounce must be >= 0");
+    if (N < 0) return bsdfd_fail_(BSDFD_EINVAL, "negative path count");
+    if ((N + 255) / 256 > 0x7fffffffLL) return bsdfd_fail_(BSDFD_EINVAL, "wavefront too large for one launch");
+    if (N == 0) return BSDFD_OK;
+    if (!org || !nrm || !wi || !material || !prim || !wl || !lsel || !emit) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
+    if (int rc = check_materials(scene, sc)) return rc;
     if (int rc = check_scene(scene)) return rc;
-    return launch_lanes(n, mesh_primary_kernel, stream, sc, (const Inst*)scene->d_inst, scene->n_inst, row_begin, row_end, spp,
-                        (unsigned long long)seed, (unsigned long long)pass, wi, wl, nrm, dir, reinterpret_cast<long long*>(material));
+    // (the emitter sample reads prim and never writes it)
+    const mesh_dev::PathGeom g{scene->d_inst, scene->n_inst, const_cast<int*>(reinterpret_cast<const int*>(prim))};
+    return launch_lanes(N, mesh_sample_emitter_kernel, stream, sc, g, lt, make_step(bounce, 0, occlusion, seed, pass, path_offset, N), org,
+                        nrm, wi, reinterpret_cast<const long long*>(material), wl, reinterpret_cast<int*>(lsel), emit);
+}
+
+int bsdfd_mesh_bounce(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, const float* env, int32_t bounce, int32_t last,
+                      int32_t occlusion, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, float* org, float* nrm,
+                      float* wi, float* wl, int64_t* material, float* beta, float* rad, const float* wo, const float* pdf_o,
+                      const float* pdf_l, const float* f_o, const float* f_l, const bsdfd_wf_lights* lights, const int32_t* lsel,
+                      const float* emit, const float* lpdf, const bsdfd_env_dist* dist, int32_t rr_depth, int32_t* prim,
+                      void* stream) {
+    if (!scene) return bsdfd_fail_(BSDFD_EINVAL, "null mesh scene");
+    if (lpdf || dist) return bsdfd_fail_(BSDFD_EINVAL, "importance sampling of the environment is not on meshes yet: lpdf and dist must be NULL");
+    if (rr_depth < 0) return bsdfd_fail_(BSDFD_EINVAL, "rr_depth must be >= 0 (0: no Russian roulette)");
+    Scene sc;
+    if (int rc = path_scene(wf_scene, env, N, sc)) return rc;
+    int n = 0, n_e = 1;
+    if (lights)
+        if (int rc = light_counts(lights, n, n_e)) return rc;
+    if (bounce < 0) return bsdfd_fail_(BSDFD_EINVAL, "bounce must be >= 0");
+    if ((f_o == nullptr) != (f_l == nullptr)) return bsdfd_fail_(BSDFD_EINVAL, "f_o and f_l are both NULL or both given");
+    if (N == 0) return BSDFD_OK;
+    if (!org || !nrm || !wi || !wl || !material || !prim || !beta || !rad || !wo || !pdf_o || !pdf_l || (lights && (!lsel || !emit)))
+        return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
+    if (int rc = check_materials(scene, sc)) return rc;
+    if (int rc = check_scene(scene)) return rc;
+    const mesh_dev::PathGeom g{scene->d_inst, scene->n_inst, reinterpret_cast<int*>(prim)};
+    const Step st = make_step(bounce, last, occlusion, seed, pass, path_offset, N);
+    const PathState ps{org, nrm, wi, wl, reinterpret_cast<long long*>(material), beta, rad};
+    const SamplerAnswer sa{wo, pdf_o, pdf_l, f_o, f_l};
+    const EmitterSample es{reinterpret_cast<const int*>(lsel), nullptr, emit};
+    auto launch = [&](auto kernel) { return launch_lanes(N, kernel, stream, sc, g, env, n_e, n_e - n, st, ps, sa, es, (int)rr_depth); };
+    if (lights) return rr_depth ? launch(mesh_bounce_kernel<LIT, true>) : launch(mesh_bounce_kernel<LIT, false>);
+    return rr_depth ? launch(mesh_bounce_kernel<COSINE, true>) : launch(mesh_bounce_kernel<COSINE, false>);
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // mesh_dev.h — the ray caster over instanced triangle meshes (mesh.hip): the instance record, the conservative slab test, the
 // watertight ray/triangle test and the stackless walk of a threaded BVH.  One ray per lane.  `walk<false>` is the closest hit,
-// `walk<true>` leaves at the first accepted hit; both skip the primitive a ray starts on.  A path kernel that intersects
-// meshes includes this header and calls `walk` where it calls wf_dev::trace today.
+// `walk<true>` leaves at the first accepted hit; both skip the primitive a ray starts on.  `surface_vertex` is the vertex at a hit,
+// and `PathGeom` hands both to the path kernels (bounce_dev.h's bounce_vertex and sample_emitter_vertex, instantiated in mesh.hip)
+// in the place of wf_dev::trace and continue_path.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -188,5 +189,86 @@ __device__ __forceinline__ MeshHit walk(const Inst* __restrict__ insts, int n_in
     }
     return best;
 }
+
+__device__ __forceinline__ V3 cross(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+
+// The vertex at the hit `h` (h.inst >= 0) of a ray of direction d, as the primary kernel and the path kernels write it: the normal
+// — the interpolated shading normal, faced like the geometric one, where the mesh has normals and the ray arrives above it; else
+// the geometric normal, faced towards the ray — then wi in the onb(nrm) frame and the material's lane for a material instance, the
+// reflectance in all three wi slots and the id n_materials for a diffuse or checker instance.
+__device__ __forceinline__ void surface_vertex(const Inst* __restrict__ insts, const MeshHit& h, V3 d, int n_materials, V3& nn,
+                                               V3& w_in, long long& material) {
+    const Inst& in = insts[h.inst];
+    const unsigned i0 = in.idx[3 * h.tri], i1 = in.idx[3 * h.tri + 1], i2 = in.idx[3 * h.tri + 2];
+    const float b0 = 1.0f - h.b1 - h.b2;
+    const V3 p0 = wf_dev::ld3(in.pos + 3ll * i0), p1 = wf_dev::ld3(in.pos + 3ll * i1), p2 = wf_dev::ld3(in.pos + 3ll * i2);
+    // geometric normal, through the inverse transpose (a mirroring transform turns the winding: faced by the ray, not by it)
+    V3 ng = normal_to_world(in.inv, cross(p1 - p0, p2 - p0));
+    ng = (1.0f / sqrtf(dot(ng, ng))) * ng;
+    if (dot(ng, d) > 0.0f) ng = -1.0f * ng;
+    nn = ng;
+    if (in.nrm) {
+        const V3 mix = b0 * wf_dev::ld3(in.nrm + 3ll * i0) + h.b1 * wf_dev::ld3(in.nrm + 3ll * i1) + h.b2 * wf_dev::ld3(in.nrm + 3ll * i2);
+        V3 ns = normal_to_world(in.inv, mix);
+        const float l2 = dot(ns, ns);
+        if (l2 > 0.0f && l2 < INFINITY) {
+            ns = (1.0f / sqrtf(l2)) * ns;
+            if (dot(ns, ng) < 0.0f) ns = -1.0f * ns;
+            if (-dot(d, ns) > 0.0f) nn = ns;   // else the geometric normal: every material lane has wi.z > 0
+        }
+    }
+    if (in.surface == BSDFD_MESH_MATERIAL) {
+        V3 fs, ft;
+        wf_dev::onb(nn, fs, ft);
+        w_in = v3(-dot(d, fs), -dot(d, ft), -dot(d, nn));
+        material = in.material;
+    } else {   // not neural: the reflectance travels in the wi slot, the id is n_materials
+        float refl = in.c0;
+        if (in.surface == BSDFD_MESH_CHECKER) {
+            const float uu = b0 * in.uv[2ll * i0] + h.b1 * in.uv[2ll * i1] + h.b2 * in.uv[2ll * i2];
+            const float vv = b0 * in.uv[2ll * i0 + 1] + h.b1 * in.uv[2ll * i1 + 1] + h.b2 * in.uv[2ll * i2 + 1];
+            const int cu = (int)floorf(2.0f * in.uscale * uu), cv = (int)floorf(2.0f * in.vscale * vv);
+            refl = ((cu + cv) & 1) ? in.c1 : in.c0;
+        }
+        w_in = v3(refl, refl, refl);
+        material = n_materials;
+    }
+}
+
+// The mesh scene as the geometry policy of the path kernels (bounce_dev.h: Spheres is its sibling).  prim [N,2] is one more array
+// of the path state: the (instance, triangle) lane p's vertex lies on, which its rays skip — no epsilon, the rule of
+// bsdfd_mesh_intersect — and which `advance` moves on with the vertex.  The walks are whole-wave calls (ONE_WALK): their instance
+// loop is wave-uniform and the records arrive through scalar loads, as anywhere else.
+struct PathGeom {
+    using Hit = MeshHit;
+    static constexpr bool ONE_WALK = true;
+    const Inst* insts;
+    int n_inst;
+    int* prim;
+    __device__ __forceinline__ static Hit nothing() {
+        Hit h;
+        h.t = NOTHING; h.inst = -1; h.tri = -1; h.b1 = 0.0f; h.b2 = 0.0f;
+        MESH_COUNT(h.nodes = 0; h.tris = 0;)
+        return h;
+    }
+    __device__ __forceinline__ static bool is_hit(const Hit& h) { return h.inst >= 0; }
+    __device__ __forceinline__ Hit closest(const wf_dev::Scene&, V3 x, V3 d, long long, long long p) const {
+        return walk<false>(insts, n_inst, x, d, NOTHING, prim[2 * p], prim[2 * p + 1]);
+    }
+    __device__ __forceinline__ bool occluded(const wf_dev::Scene&, V3 x, V3 d, long long, long long p, float dist = NOTHING) const {
+        return walk<true>(insts, n_inst, x, d, dist, prim[2 * p], prim[2 * p + 1]).inst >= 0;
+    }
+    __device__ __forceinline__ void advance(const wf_dev::Scene& sc, const Hit& h, V3 x, V3 d, V3 b, const float thr[3],
+                                            unsigned long long seed, unsigned long long pass, unsigned long long path_offset,
+                                            int bounce, long long p, float* __restrict__ org, float* __restrict__ nrm,
+                                            float* __restrict__ wi, float* __restrict__ wl, long long* __restrict__ mat,
+                                            float* __restrict__ beta) const {
+        V3 nn, w_in;
+        long long material;
+        surface_vertex(insts, h, d, sc.n_sph, nn, w_in, material);
+        prim[2 * p] = h.inst; prim[2 * p + 1] = h.tri;
+        wf_dev::store_vertex(x + h.t * d, nn, w_in, material, b, thr, seed, pass, path_offset, bounce, p, org, nrm, wi, wl, mat, beta);
+    }
+};
 
 }  // namespace mesh_dev

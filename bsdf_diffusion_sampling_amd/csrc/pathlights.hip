@@ -11,6 +11,7 @@
 //                    and emit = n_e I_k / d^2, 0 below the horizon or (occlusion) behind another surface.  Point k on the floor:
 //                    wl stays (the path continues along it), emit = the whole term n_e (refl / pi) cos I_k / d^2.
 //
+// The kernel's body is bounce_dev.h's sample_emitter_vertex, which mesh.hip instantiates once more on the mesh scene.
 // The bounce that reads lsel and emit is bounce.hip's LIT kernel.  bsdfd_wf_sample_emitter_rows is the same kernel over the lanes of
 // a live-lane list (bounce_dev.h's Rows), for the deep bounces of a wavefront that has mostly ended.
 // The lights travel by value in the kernel arguments like the scene; the picked light is selected by a wave-uniform loop
@@ -29,55 +30,13 @@ namespace {
 
 using namespace bounce_dev;
 
-struct Lights {
-    int n;         // point emitters
-    int n_e;       // emitters: n, plus one if the environment emits
-    float pos[BSDFD_WF_MAX_LIGHTS][3];
-    float inten[BSDFD_WF_MAX_LIGHTS][3];
-};
-
 // `list`: nothing (every lane of the wavefront), or one Rows (the list form: the lanes of a live-lane list)
 template <class... List>
 __global__ __launch_bounds__(256) void sample_emitter_kernel(Scene sc, Lights lt, Step st, const float* __restrict__ org,
                                                              const float* __restrict__ nrm, const float* __restrict__ wi,
                                                              const long long* __restrict__ mat, float* __restrict__ wl,
                                                              int* __restrict__ lsel, float* __restrict__ emit, List... list) {
-    long long p, m;
-    if (!live_lane<sizeof...(List) != 0>(sc, st.n, mat, p, m, list...)) return;
-    unsigned u[4];
-    tagged_draw(st.seed, st.pass, st.path_offset, p, 0x4C697465u /* "Lite" */, st.bounce, u);
-    const int pick = (int)(((unsigned long long)u[0] * (unsigned long long)lt.n_e) >> 32);
-    if (pick == lt.n) {   // the environment: the bounce looks it up along the cosine sample that is already in wl
-        lsel[p] = -1;
-        st3(emit + 3 * p, v3(0.f, 0.f, 0.f));
-        return;
-    }
-    V3 P = v3(0.f, 0.f, 0.f), I = v3(0.f, 0.f, 0.f);
-    for (int k = 0; k < lt.n; ++k)   // wave-uniform loop, per-lane select: no per-lane index into lt
-        if (pick == k) { P = v3(lt.pos[k][0], lt.pos[k][1], lt.pos[k][2]); I = v3(lt.inten[k][0], lt.inten[k][1], lt.inten[k][2]); }
-    const V3 nn = ld3(nrm + 3 * p), x = ld3(org + 3 * p);
-    const V3 v = P - x;
-    const float d2 = dot(v, v);
-    const float dist = sqrtf(d2);
-    const V3 dir = (1.0f / dist) * v;
-    float cosl;
-    const bool lit = emitter_arrives(sc, x, nn, dir, m, st.occlusion, dist, true, cosl);
-    float s = lit ? (float)lt.n_e / d2 : 0.0f;
-    if (m == sc.n_sph) s *= wi[3 * p] * 0.31830988618379067154f * cosl;   // diffuse floor: f cos = (reflectance / pi) cos
-    else store_local_direction(wl + 3 * p, nn, dir, cosl);
-    lsel[p] = pick;
-    st3(emit + 3 * p, s * I);
-}
-
-// the kernel-argument form of a bsdfd_wf_lights
-int to_lights(const bsdfd_wf_lights* l, Lights& lt) {
-    if (int rc = light_counts(l, lt.n, lt.n_e)) return rc;
-    for (int k = 0; k < BSDFD_WF_MAX_LIGHTS; ++k)
-        for (int c = 0; c < 3; ++c) {
-            lt.pos[k][c] = k < lt.n ? l->position[k][c] : 0.0f;
-            lt.inten[k][c] = k < lt.n ? l->intensity[k][c] : 0.0f;
-        }
-    return BSDFD_OK;
+    sample_emitter_vertex<sizeof...(List) != 0>(sc, lt, st, org, nrm, wi, mat, wl, lsel, emit, list...);
 }
 
 // the checks of both entry points and the launch: over all N lanes, or (`list`) over the lanes of a list

@@ -150,6 +150,24 @@ __device__ __forceinline__ Hit trace(const Scene& sc, V3 org, V3 d, int own) {
     return h;
 }
 
+// What every geometry writes for the next vertex (xv, nv, w_in, id) of lane p: the vertex, the throughput b * thr, and its light
+// sample — primary's Philox key and counter, counter word 3 advanced by the depth of the new vertex.
+__device__ __forceinline__ void store_vertex(V3 xv, V3 nv, V3 w_in, long long id, V3 b, const float thr[3], unsigned long long seed,
+                                             unsigned long long pass, unsigned long long path_offset, int bounce, long long p,
+                                             float* __restrict__ org, float* __restrict__ nrm, float* __restrict__ wi,
+                                             float* __restrict__ wl, long long* __restrict__ mat, float* __restrict__ beta) {
+    const unsigned long long gp = path_offset + (unsigned long long)p;
+    unsigned u[4];
+    philox4x32((unsigned)seed, (unsigned)(seed >> 32), (unsigned)gp, (unsigned)(gp >> 32), (unsigned)pass,
+               0x57617665u + (unsigned)(bounce + 1), u);
+    st3(wl + 3 * p, cosine_sample(u[2], u[3]));
+    st3(org + 3 * p, xv);
+    st3(nrm + 3 * p, nv);
+    st3(wi + 3 * p, w_in);
+    st3(beta + 3 * p, v3(b.x * thr[0], b.y * thr[1], b.z * thr[2]));
+    mat[p] = id;
+}
+
 // The path of lane p moves on to the hit `h` of the ray x + t d: the next vertex, written the way primary_kernel writes the first,
 // the throughput b * thr, and the vertex' light sample.
 __device__ __forceinline__ void continue_path(const Scene& sc, const Hit& h, V3 x, V3 d, V3 b, const float thr[3],
@@ -174,17 +192,7 @@ __device__ __forceinline__ void continue_path(const Scene& sc, const Hit& h, V3 
         nv = v3(0.f, 1.f, 0.f);
         w_in = v3(refl, refl, refl);
     }
-    // its light sample: primary's Philox key and counter, counter word 3 advanced by the depth of the new vertex
-    const unsigned long long gp = path_offset + (unsigned long long)p;
-    unsigned u[4];
-    philox4x32((unsigned)seed, (unsigned)(seed >> 32), (unsigned)gp, (unsigned)(gp >> 32), (unsigned)pass,
-               0x57617665u + (unsigned)(bounce + 1), u);
-    st3(wl + 3 * p, cosine_sample(u[2], u[3]));
-    st3(org + 3 * p, xv);
-    st3(nrm + 3 * p, nv);
-    st3(wi + 3 * p, w_in);
-    st3(beta + 3 * p, v3(b.x * thr[0], b.y * thr[1], b.z * thr[2]));
-    mat[p] = h.id;
+    store_vertex(xv, nv, w_in, h.id, b, thr, seed, pass, path_offset, bounce, p, org, nrm, wi, wl, mat, beta);
 }
 
 // ---- host side ----

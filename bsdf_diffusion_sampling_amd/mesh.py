@@ -1,11 +1,15 @@
 """Triangle meshes for the array scenes: the reference renders ``matpreview.serialized`` (a plane, an interior and a shell),
 instanced 25 times per ``disney_bsdf_array*.xml``; this module reads that container, builds the scene the native ray caster walks
 (csrc/mesh.hip: a threaded BVH per mesh, instances under affine transforms, ``bsdfd_mesh_intersect`` / ``_occluded`` /
-``_primary``) and renders it through ``ArrayRenderer``'s own pipeline (``MeshArrayRenderer``: only ``primary()`` differs).
+``_primary``) and renders it through ``ArrayRenderer``'s own pipeline (``MeshArrayRenderer``: only ``primary()`` differs) or
+through ``PathArrayRenderer``'s (``MeshPathArrayRenderer``: shadows, interreflection, point lights and Russian roulette, with
+``bsdfd_mesh_path_primary`` / ``_sample_emitter`` / ``_bounce`` in the place of the sphere kernels).
 
-Limits: one-bounce, unoccluded shading only — ``PathArrayRenderer``'s bounce kernels still intersect spheres — and, like everything
-at this level, PARITY-UNPINNED against Mitsuba: image handedness, which checker colour lands on which cell and the v0.5-to-v3
-scene upgrade rules are this module's reading of the files, not a comparison with Mitsuba's images.
+Limits of the path tracer on meshes: no geometric-normal test — a BSDF sample above the shading normal but below the triangle's
+plane enters the shell and is followed there; the shell's inside is shaded like its outside; no transmission, no importance
+sampling of the environment and no live-lane list on meshes yet.  Like everything at this level it is PARITY-UNPINNED against
+Mitsuba: image handedness, which checker colour lands on which cell and the v0.5-to-v3 scene upgrade rules are this module's
+reading of the files, not a comparison with Mitsuba's images.
 
 There is no CPU fallback for the rays: every one goes through libbsdfd.so.  The reader, the XML parser and the BVH builder
 (``bsdfd_mesh_bvh_build``, pure host code) need no device.
@@ -23,6 +27,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
+from .pathtrace import PathArrayRenderer
 from .wavefront import ArrayRenderer
 
 FLAG_NORMALS, FLAG_UV, FLAG_COLORS, FLAG_DOUBLE = 0x1, 0x2, 0x8, 0x2000   # the flags word of a serialized shape
@@ -452,14 +457,12 @@ class MeshArrayRenderer(ArrayRenderer):
     they keep ``n_sph = len(table)``, so that the diffuse id and the miss id are where ``shade_kernel`` and the bucketing expect
     them — and ``primary()`` calls ``bsdfd_mesh_primary`` on the same buffers.  ``render_pass``, the bucketing, the direct and
     gathered sampler forms, both ground-truth tables and ``shade`` are the base class's.  The instances' material indices must be
-    exactly 0 .. len(table) - 1.  One bounce, unoccluded; parity-unpinned against Mitsuba."""
+    exactly 0 .. len(table) - 1.  One bounce, unoccluded (``MeshPathArrayRenderer`` traces the rest); parity-unpinned against
+    Mitsuba."""
 
     def __init__(self, table, mesh_scene: MeshScene, camera=None, env=None, albedo=(1.0, 1.0, 1.0), ground_truth=None,
                  ball_albedo=None, device=None, fused_ground_truth: bool = True):
-        if not isinstance(mesh_scene, MeshScene):
-            raise ValueError("mesh_scene must be a mesh.MeshScene")
-        if mesh_scene.material_indices != list(range(len(table))):
-            raise ValueError(f"the instances' material indices {mesh_scene.material_indices} must cover 0 .. {len(table) - 1} exactly")
+        _check_mesh_scene(table, mesh_scene)
         n = len(table)
         super().__init__(table, [(0.0, 0.0, 0.0)] * n, [1.0] * n, camera=camera, env=env, floor=False, albedo=albedo,
                          ground_truth=ground_truth, device=device, fused_ground_truth=fused_ground_truth, ball_albedo=ball_albedo)
@@ -470,3 +473,106 @@ class MeshArrayRenderer(ArrayRenderer):
         n = (row_end - row_begin) * self.camera.width * spp
         b = out or self._buffers(n)
         return self.mesh_scene.primary(self.scene, row_begin, row_end, spp, seed, pass_idx, b)
+
+
+def _check_mesh_scene(table, mesh_scene):
+    if not isinstance(mesh_scene, MeshScene):
+        raise ValueError("mesh_scene must be a mesh.MeshScene")
+    if mesh_scene.material_indices != list(range(len(table))):
+        raise ValueError(f"the instances' material indices {mesh_scene.material_indices} must cover 0 .. {len(table) - 1} exactly")
+
+
+class MeshPathArrayRenderer(PathArrayRenderer):
+    """``PathArrayRenderer`` on a ``MeshScene``: the base class gets one placeholder sphere per material, as ``MeshArrayRenderer``
+    gives its own, and the stages that touch geometry go to the mesh entry points:
+
+    * ``primary`` calls ``bsdfd_mesh_path_primary``, which writes the first vertex of the path as well (``org``, ``prim``, ``beta``,
+      ``rad``), so ``path_begin`` has nothing left to do;
+    * ``sample_emitter`` and ``bounce`` call ``bsdfd_mesh_sample_emitter`` and ``bsdfd_mesh_bounce``;
+    * the path state has one more array, ``prim`` int32 [N,2]: the (instance, triangle) a vertex lies on, which its rays skip.
+
+    ``render_pass``, the bucketing, the sampler launches, both ground-truth tables, ``resolve`` and ``stats`` are inherited, and
+    ``max_depth``, ``occlusion``, ``lights``, ``rr_depth`` and ``DEPTH_CAP`` mean what they mean there.  ``env_sampling`` other than
+    ``"cosine"``, ``compact=True`` and ``transmission=True`` are refused: not on meshes yet.  Limits: the module docstring's.
+    Parity-unpinned against Mitsuba."""
+
+    def __init__(self, table, mesh_scene: MeshScene, camera=None, env=None, *, max_depth: Optional[int] = 1,
+                 occlusion: Optional[bool] = None, lights=None, rr_depth: Optional[int] = None, albedo=(1.0, 1.0, 1.0),
+                 ground_truth=None, ball_albedo=None, device=None, fused_ground_truth: bool = True, env_sampling: str = "cosine",
+                 compact: bool = False, transmission: bool = False):
+        if env_sampling != "cosine":
+            raise ValueError(f"env_sampling={env_sampling!r}: importance sampling of the environment is not on meshes yet")
+        if compact:
+            raise ValueError("compact=True: the live-lane list is not on meshes yet")
+        if transmission:
+            raise ValueError("transmission=True: transmitted paths are not on meshes yet")
+        if not isinstance(mesh_scene, MeshScene):
+            raise ValueError("mesh_scene must be a mesh.MeshScene: other geometry is not on meshes yet")
+        _check_mesh_scene(table, mesh_scene)
+        n = len(table)
+        super().__init__(table, [(0.0, 0.0, 0.0)] * n, [1.0] * n, camera, env, max_depth=max_depth, occlusion=occlusion, lights=lights,
+                         rr_depth=rr_depth, floor=False, albedo=albedo, ground_truth=ground_truth, device=device,
+                         fused_ground_truth=fused_ground_truth, ball_albedo=ball_albedo)
+        self.mesh_scene = mesh_scene
+
+    def _buffers(self, n: int):
+        import torch
+        b = super()._buffers(n)
+        if "prim" not in b:
+            b["prim"] = torch.empty((n, 2), dtype=torch.int32, device=self.device)
+        return b
+
+    def primary(self, row_begin: int, row_end: int, spp: int, seed: int, pass_idx: int, out=None):
+        """-> dict(wi, wl, nrm, dir, mat, org, prim, beta, rad): the mesh scene's closest hits as ``MeshArrayRenderer.primary``
+        writes them, and the first vertex of every path."""
+        import torch
+        n = (row_end - row_begin) * self.camera.width * spp
+        b = out or self._buffers(n)
+        p = lambda a: C.c_void_p(a.data_ptr())
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().bsdfd_mesh_path_primary(
+                self.mesh_scene.handle(), C.byref(self.scene), row_begin, row_end, spp, seed, pass_idx, p(b["wi"]), p(b["wl"]),
+                p(b["nrm"]), p(b["dir"]), p(b["mat"]), p(self.env), p(b["org"]), p(b["prim"]), p(b["beta"]), p(b["rad"]),
+                self._stream()))
+        torch.autograd.graph.increment_version([b[k] for k in ("wi", "wl", "nrm", "dir", "mat", "org", "prim", "beta", "rad")])
+        return b
+
+    def path_begin(self, b):
+        """Nothing: ``primary`` has written ``org``, ``prim``, ``beta`` and ``rad`` (the hit's t is known there and nowhere else)."""
+
+    def sample_emitter(self, b, bounce: int, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
+                       lights: Optional[_lib.WfLights] = None, rows=None):
+        """``PathArrayRenderer.sample_emitter`` with the shadow rays cast in the mesh scene (``bsdfd_mesh_sample_emitter``)."""
+        import torch
+        if rows is not None:
+            raise ValueError("rows: the live-lane list is not on meshes yet")
+        occlusion = self.occlusion if occlusion is None else occlusion
+        p = lambda a: C.c_void_p(a.data_ptr())
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().bsdfd_mesh_sample_emitter(
+                self.mesh_scene.handle(), C.byref(self.scene), C.byref(self.lights if lights is None else lights), bounce,
+                int(bool(occlusion)), seed, pass_idx, path_offset, b["mat"].shape[0], p(b["org"]), p(b["nrm"]), p(b["wi"]),
+                p(b["mat"]), p(b["wl"]), p(b["lsel"]), p(b["emit"]), p(b["prim"]), self._stream()))
+        torch.autograd.graph.increment_version([b["wl"], b["lsel"], b["emit"]])
+
+    def bounce(self, b, bounce: int, last: bool, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
+               lights: Optional[_lib.WfLights] = None, env_dist=None, rr_depth: Optional[int] = None, rows=None):
+        """``PathArrayRenderer.bounce`` on the mesh scene (``bsdfd_mesh_bounce``): the cosine light strategy without ``lights``, one
+        emitter sample per vertex with them, Russian roulette with ``rr_depth``."""
+        import torch
+        if rows is not None or env_dist is not None:
+            raise ValueError("rows / env_dist: the live-lane list and the environment's importance sampling are not on meshes yet")
+        occlusion = self.occlusion if occlusion is None else occlusion
+        lights = self.lights if lights is None else lights
+        rr_depth = self.rr_depth if rr_depth is None else rr_depth
+        p = lambda a: None if a is None else C.c_void_p(a.data_ptr())
+        lit = lights is not None
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().bsdfd_mesh_bounce(
+                self.mesh_scene.handle(), C.byref(self.scene), p(self.env), bounce, int(bool(last)), int(bool(occlusion)), seed,
+                pass_idx, path_offset, b["mat"].shape[0], p(b["org"]), p(b["nrm"]), p(b["wi"]), p(b["wl"]), p(b["mat"]), p(b["beta"]),
+                p(b["rad"]), p(b["wo"]), p(b["pdf_o"]), p(b["pdf_l"]), p(b.get("f_o")), p(b.get("f_l")),
+                C.byref(lights) if lit else None, p(b["lsel"]) if lit else None, p(b["emit"]) if lit else None, None, None,
+                int(rr_depth or 0), p(b["prim"]), self._stream()))
+        # written through raw pointers: tell torch (the plugin cores key their per-query context cache on wi._version)
+        torch.autograd.graph.increment_version([b["wi"], b["wl"], b["nrm"], b["org"], b["mat"], b["beta"], b["rad"], b["prim"]])

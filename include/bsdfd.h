@@ -58,7 +58,12 @@ extern "C" {
  *      bsdfd_measured_eval_table_rows() and bsdfd_analytic_eval_table_rows(): the per-depth calls of the array scene over a
  *      live-lane list;
  *      bsdfd_wf_bounce_transmit(), bsdfd_wf_sample_inside() and bsdfd_wf_sample_inside_rows(): transmitted paths through the
- *      balls of the array scene. */
+ *      balls of the array scene;
+ *      bsdfd_mesh_bvh_build(), bsdfd_mesh_scene_create(), bsdfd_mesh_scene_destroy(), bsdfd_mesh_intersect(),
+ *      bsdfd_mesh_occluded() and bsdfd_mesh_primary(), which take structs of their own, bsdfd_mesh_desc and bsdfd_mesh_instance:
+ *      ray casting on the array scenes' triangle meshes;
+ *      bsdfd_mesh_path_primary(), bsdfd_mesh_sample_emitter() and bsdfd_mesh_bounce(): the path tracer of the array scene on
+ *      those meshes. */
 #define BSDFD_ABI_VERSION 8
 
 #define BSDFD_OK 0
@@ -895,6 +900,47 @@ int bsdfd_mesh_occluded(bsdfd_mesh_scene scene, int64_t N, const float* org, con
 int bsdfd_mesh_primary(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, int32_t row_begin, int32_t row_end, int32_t spp,
                        uint64_t seed, uint64_t pass, float* wi, float* wl, float* nrm, float* dir, int64_t* material,
                        void* hip_stream);
+
+/* ---- the path tracer of the array scene on the mesh scene (no new ABI version: three more entry points) ----
+ *
+ * The per-depth calls of the array scene (bsdfd_wf_path_begin / _sample_emitter / _bounce*) with the triangle meshes as their
+ * geometry.  The path state gains one array, prim int32 [N,2]: the (instance, triangle) a path's vertex lies on.  A ray that
+ * leaves the vertex skips that primitive — no epsilon, bsdfd_mesh_intersect's rule — and nothing else.  `wf_scene` gives the
+ * camera, the film, the proxy albedo, the environment's size and n_materials = 1 + n_extra_spheres; its spheres and plane are not
+ * looked at.  The diffuse and checker instances take the part of the floor (id n_materials, reflectance in the wi slots); the
+ * miss id is n_materials + 1.  An instance whose material is >= n_materials is refused.
+ *
+ * bsdfd_mesh_path_primary is bsdfd_mesh_primary (the same kernel: wi, wl, nrm, dir and material are its bits; one walk per lane)
+ * and, in a second small launch on the same stream, bsdfd_wf_path_begin: for a hit org = cam + t dir, prim = the hit, rad = 0; for a miss org = 0, prim = (-1, -1) and rad = the environment
+ * along dir (env [env_height, env_width, 3]); beta = 1 on every lane.
+ *
+ * bsdfd_mesh_sample_emitter is bsdfd_wf_sample_emitter: the shadow ray to the picked point light is an any-hit walk bounded by the
+ * distance to the light.  prim is read only.
+ *
+ * bsdfd_mesh_bounce is bsdfd_wf_bounce_rr's argument list, with lights, lsel and emit NULL where only the environment emits (the
+ * cosine light strategy) and rr_depth = 0 for no roulette.  lpdf and dist must be NULL (BSDFD_EINVAL): the environment is not
+ * importance-sampled on meshes yet; nor is there a live-lane list or transmission.  The estimate, the MIS weights, the roulette
+ * and the Philox counters are those of the sphere kernels (one body, csrc/bounce_dev.h); the closest hit is one walk per lane,
+ * the cosine strategy's shadow ray one unbounded any-hit walk, and the next vertex is written as bsdfd_mesh_primary writes the
+ * first: org = x + t d, the shading-normal rule for a ray of direction d, prim = the hit.  A sample above the shading normal but
+ * below the triangle's plane is followed into the mesh (no geometric-normal test), and a surface is shaded alike from both
+ * sides.  A path that has ended keeps every byte of its state, prim included.
+ *
+ * All three: a null scene, a negative or too-large N and null arrays are refused before any device work; N (or the tile) == 0 is
+ * a no-op; nothing behind the N-th lane is written; no allocation, no synchronisation. */
+int bsdfd_mesh_path_primary(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, int32_t row_begin, int32_t row_end, int32_t spp,
+                            uint64_t seed, uint64_t pass, float* wi, float* wl, float* nrm, float* dir, int64_t* material,
+                            const float* env, float* org, int32_t* prim, float* beta, float* rad, void* hip_stream);
+int bsdfd_mesh_sample_emitter(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, const bsdfd_wf_lights* lights, int32_t bounce,
+                              int32_t occlusion, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, const float* org,
+                              const float* nrm, const float* wi, const int64_t* material, float* wl, int32_t* lsel, float* emit,
+                              const int32_t* prim, void* hip_stream);
+int bsdfd_mesh_bounce(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, const float* env, int32_t bounce, int32_t last,
+                      int32_t occlusion, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, float* org, float* nrm,
+                      float* wi, float* wl, int64_t* material, float* beta, float* rad, const float* wo, const float* pdf_o,
+                      const float* pdf_l, const float* f_o, const float* f_l, const bsdfd_wf_lights* lights, const int32_t* lsel,
+                      const float* emit, const float* lpdf, const bsdfd_env_dist* dist, int32_t rr_depth, int32_t* prim,
+                      void* hip_stream);
 
 const char* bsdfd_last_error(void);
 const char* bsdfd_version(void);

@@ -14,6 +14,13 @@ instances, 12 shells of 57 152 triangles) at 683x512, 4 spp.  Every timing is th
   fp32 against fp64, on that file's own cases);
 * VGPRs, scratch and occupancy per kernel, from the metadata of a compilation of csrc/mesh.hip.
 
+``--path`` measures the path tracer on meshes instead (``mesh.MeshPathArrayRenderer``) -> profiles/mesh_path.json: a pass at
+max_depth 1 (with and without occlusion), 2, 4 and unbounded with rr_depth = 5, next to the ``MeshArrayRenderer`` pass and to the
+sphere ``PathArrayRenderer`` at the same depths (variants alternate in one process, medians over the rounds, a host clock that
+ends in a synchronise); and, per bounce of the unbounded pass, the ``bounce`` launch between two device events with that bounce's
+live-lane count, next to ``MeshScene.intersect`` plus ``occluded`` on the same rays — the continuation rays and the cosine
+strategy's shadow rays the fused kernel walks — which is the yardstick for what the fusion costs or saves.
+
 Nothing here is a gate.  The record is there to decide whether an ordered traversal with a stack in LDS, or a wider node, is
 worth a change of its own, and what a bounce of the path tracer on meshes will cost.
 """
@@ -44,8 +51,10 @@ ap.add_argument("--scene", default=os.path.join(ROOT, "tests", "golden", "disney
 ap.add_argument("--mesh-file", default=os.path.join(ROOT, "tests", "golden", "matpreview.serialized"))
 ap.add_argument("--no-counting", action="store_true", help="skip the counting build (needs hipcc)")
 ap.add_argument("--no-errors", action="store_true", help="skip the fp32 error figures (a minute of numpy brute force)")
-ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh.json"))
+ap.add_argument("--path", action="store_true", help="measure the path tracer on meshes instead -> profiles/mesh_path.json")
+ap.add_argument("--out", default=None)
 a = ap.parse_args()
+a.out = a.out or os.path.join(ROOT, "profiles", "mesh_path.json" if a.path else "mesh.json")
 if not torch.cuda.is_available():
     sys.exit("tools/mesh_bench.py measures on the GPU: no device visible")
 dev = torch.device("cuda", 0)
@@ -61,6 +70,108 @@ sphere_r = WF.ArrayRenderer(table, centers, radii, camera=cam_s)
 n = a.width * a.height * a.spp
 rec = {"workload": f"{os.path.basename(a.scene)} {a.width}x{a.height}x{a.spp}", "rays": n, "rounds": a.rounds, "reps": a.reps,
        "device": torch.cuda.get_device_name(dev), "library": L.bsdfd_version().decode(), "bvh": scene.stats}
+
+
+
+def median_ms(variants, rounds, reps):
+    """{name: ms} -> medians over interleaved rounds: each variant once per round, ``reps`` calls per timing, a synchronise at the end."""
+    times = {k: [] for k in variants}
+    for fn in variants.values():   # warm-up
+        fn()
+    torch.cuda.synchronize()
+    for _ in range(rounds):
+        for k, fn in variants.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                fn()
+            torch.cuda.synchronize()
+            times[k].append((time.perf_counter() - t0) / reps)
+    return {k: {"ms": 1e3 * float(np.median(v)), "ms_min": 1e3 * min(v), "ms_max": 1e3 * max(v)} for k, v in times.items()}
+
+
+def measure_paths():
+    from bsdf_diffusion_sampling_amd.pathtrace import PathArrayRenderer
+    cfgs = {"depth1": dict(max_depth=1, occlusion=False), "depth1_occlusion": dict(max_depth=1, occlusion=True),
+            "depth2": dict(max_depth=2), "depth4": dict(max_depth=4), "unbounded_rr5": dict(max_depth=None, rr_depth=5)}
+    mesh_p = {k: M.MeshPathArrayRenderer(table, scene, camera=cam, **kw) for k, kw in cfgs.items()}
+    sphere_p = {k: PathArrayRenderer(table, centers, radii, camera=cam_s, **kw) for k, kw in cfgs.items()}
+    films = {}
+
+    def one_pass(r):
+        film = films.setdefault(id(r), torch.zeros((a.height, a.width, 3), device=dev))
+        return lambda: r.render_pass(film, 0, a.height, a.spp, 0, 0)
+    variants = {"mesh_array_renderer_pass": one_pass(mesh_r), "array_renderer_pass_spheres": one_pass(sphere_r)}
+    variants.update({"mesh_path_" + k: one_pass(r) for k, r in mesh_p.items()})
+    variants.update({"sphere_path_" + k: one_pass(r) for k, r in sphere_p.items()})
+    rec["pass_ms"] = median_ms(variants, a.rounds, a.reps)
+    rec["lanes_per_bounce"] = {k: r.stats["lanes_per_bounce"] for k, r in mesh_p.items()}
+    rec["lanes_per_bounce_spheres"] = {k: r.stats["lanes_per_bounce"] for k, r in sphere_p.items()}
+    # ---- per bounce of the unbounded pass: the launch between two device events, the live lanes, and the rays it walks ----
+    r = mesh_p["unbounded_rr5"]
+    n_b, inner = len(table), r.bounce
+    per, rays, capture = [], [], [True]
+
+    def timed(b, k, *args, **kwargs):
+        if capture[0]:   # first instrumented pass only: the rays of this bounce, as the kernel forms them
+            mat, nv = b["mat"], b["nrm"]
+            live, floor = mat <= n_b, mat == n_b
+            sign = torch.copysign(torch.ones_like(nv[:, 2]), nv[:, 2])
+            aa = -1.0 / (sign + nv[:, 2]); bb = nv[:, 0] * nv[:, 1] * aa
+            fs = torch.stack([1.0 + sign * nv[:, 0] ** 2 * aa, sign * bb, -sign * nv[:, 0]], 1)
+            ft = torch.stack([bb, sign + nv[:, 1] ** 2 * aa, -nv[:, 1]], 1)
+            world = lambda v: v[:, 0:1] * fs + v[:, 1:2] * ft + v[:, 2:3] * nv
+            ball = live & ~floor
+            follow = ball & torch.isfinite(b["pdf_o"]) & (b["pdf_o"] > 0) & (b["wo"][:, 2] > 0)
+            ask = floor | follow
+            shadow = ball & torch.isfinite(b["pdf_l"]) & (b["pdf_l"] > 0) & (b["wl"][:, 2] > 0)
+            dc = torch.where(floor[:, None], world(b["wl"]), world(b["wo"]))
+            rays.append(dict(live=int(live.sum()), material_lanes=int(ball.sum()),
+                             closest=(b["org"][ask].contiguous(), dc[ask].contiguous(), b["prim"][ask].contiguous()),
+                             shadow=(b["org"][shadow].contiguous(), world(b["wl"])[shadow].contiguous(), b["prim"][shadow].contiguous())))
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        inner(b, k, *args, **kwargs)
+        e1.record()
+        per[-1].append((e0, e1))
+    r.bounce = timed
+    film = torch.zeros((a.height, a.width, 3), device=dev)
+    for _ in range(a.rounds):
+        per.append([])
+        r.render_pass(film, 0, a.height, a.spp, 0, 0)
+        torch.cuda.synchronize()
+        per[-1] = [e0.elapsed_time(e1) for e0, e1 in per[-1]]
+        capture[0] = False
+    r.bounce = inner
+    depth = len(per[0])
+    assert all(len(p) == depth for p in per)   # (the same seed and pass: the same paths)
+    bounces = []
+    for k in range(depth):
+        row = {"bounce": k, "live_lanes": rays[k]["live"], "material_lanes": rays[k]["material_lanes"],
+               "closest_hit_rays": int(rays[k]["closest"][0].shape[0]), "shadow_rays": int(rays[k]["shadow"][0].shape[0]),
+               "fused_bounce_ms": float(np.median([p[k] for p in per]))}
+        if k < 6:   # the unfused pair on the same rays
+            (o1, d1, s1), (o2, d2, s2) = rays[k]["closest"], rays[k]["shadow"]
+            pair = {}
+            if o1.shape[0]:
+                pair["intersect"] = lambda: scene.intersect(o1, d1, None, s1)
+            if o2.shape[0]:
+                pair["occluded"] = lambda: scene.occluded(o2, d2, None, s2)
+            got = median_ms(pair, a.rounds, a.reps)
+            row["intersect_ms"] = got.get("intersect", {"ms": 0.0})["ms"]
+            row["occluded_ms"] = got.get("occluded", {"ms": 0.0})["ms"]
+        bounces.append(row)
+    rec["bounces_unbounded_rr5"] = bounces
+    rec["depth_unbounded_rr5"] = depth
+
+
+if a.path:
+    measure_paths()
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(rec, f, indent=1)
+    print(json.dumps({k: rec[k] for k in ("pass_ms", "bounces_unbounded_rr5")}))
+    sys.exit(0)
 
 # ---- BVH build time per mesh (host) ----
 for k, m in enumerate(scene.meshes):

@@ -45,8 +45,10 @@ ap.add_argument("--analytic", action="store_true",
                      "every ball the albedo vector the file gives it (wavefront.albedos_from_matpreview_xml)")
 ap.add_argument("--mesh-file", default=None, metavar="matpreview.serialized",
                 help="with --scene: render the file's own geometry — its 25 instances of the three meshes of this container, under "
-                     "their toWorld, and its lookAt camera — through mesh.MeshArrayRenderer (one bounce, unoccluded; parity-unpinned "
-                     "against Mitsuba) instead of twelve spheres on a plane")
+                     "their toWorld, and its lookAt camera — instead of twelve spheres on a plane: through mesh.MeshArrayRenderer (one "
+                     "bounce, unoccluded), or, with any of --max-depth, --occlusion, --rr-depth, --integrator-from, --point-light, "
+                     "--lights-from, --no-env, through mesh.MeshPathArrayRenderer.  No --compact, --transmission or --env-sampling "
+                     "importance on meshes yet; parity-unpinned against Mitsuba")
 a = ap.parse_args()
 if a.analytic and not a.scene:
     ap.error("--analytic needs --scene")
@@ -99,10 +101,15 @@ elif a.measured_dir:
 if a.env_sampling == "importance" and a.no_env:
     ap.error("--env-sampling importance needs an emitting environment: drop --no-env")
 if mesh_scene is not None:
-    if not (a.max_depth is None and not unbounded and a.rr_depth is None and a.occlusion is None and not lights
-            and a.env_sampling == "cosine" and not a.compact and not a.transmission):
-        ap.error("--mesh-file renders one unoccluded bounce: the path tracer's options do not apply to it yet")
-    r = MESH.MeshArrayRenderer(tab, mesh_scene, camera=cam, ground_truth=gts, **extra)
+    if a.env_sampling != "cosine" or a.compact or a.transmission:
+        ap.error("--compact, --transmission and --env-sampling importance are not on meshes yet")
+    if a.max_depth is None and not unbounded and a.rr_depth is None and a.occlusion is None and not lights:
+        r = MESH.MeshArrayRenderer(tab, mesh_scene, camera=cam, ground_truth=gts, **extra)
+    else:
+        r = MESH.MeshPathArrayRenderer(tab, mesh_scene, camera=cam, ground_truth=gts, **extra,
+                                       max_depth=None if unbounded else 1 if a.max_depth is None else a.max_depth, rr_depth=a.rr_depth,
+                                       occlusion=None if a.occlusion is None else bool(a.occlusion), lights=lights,
+                                       env=None if a.no_env or not lights else WF.make_sky())
 elif (a.max_depth is None and not unbounded and a.rr_depth is None and a.occlusion is None and not lights and a.env_sampling == "cosine"
         and not a.compact and not a.transmission):
     r = WF.ArrayRenderer(tab, centers, radii, camera=cam, ground_truth=gts, **extra)
