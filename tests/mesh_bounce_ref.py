@@ -29,14 +29,17 @@ F = np.float32
 MODES = ("cosine", "lit")
 
 
-def cast_rays(geom: dict, org, d, prim, ask, tmax=None):
-    """``mesh_ref.brute_force`` on the rows ``ask`` (the others: no hit, nothing marginal), each ray skipping ``prim`` of its row."""
+def cast_rays(geom: dict, org, d, prim, ask, tmax=None, cast=None):
+    """``mesh_ref.brute_force`` on the rows ``ask`` (the others: no hit, nothing marginal), each ray skipping ``prim`` of its row.
+    ``cast``: another hit source with ``brute_force``'s signature and record, ``cast(meshes, instances, org, dir, tmax=, skip=)``
+    (``mesh_ref.bvh_walk`` over the library's BVHs, where every ray against every triangle costs too much)."""
     n = len(org)
     out = MR._result(n)
     r = np.nonzero(ask)[0]
     if r.size:
-        got = MR.brute_force(geom["meshes"], geom["instances"], np.asarray(org, dtype=np.float64)[r], np.asarray(d, dtype=np.float64)[r],
-                             tmax=None if tmax is None else np.asarray(tmax, dtype=np.float64)[r], skip=np.asarray(prim)[r])
+        got = (cast or MR.brute_force)(
+            geom["meshes"], geom["instances"], np.asarray(org, dtype=np.float64)[r], np.asarray(d, dtype=np.float64)[r],
+            tmax=None if tmax is None else np.asarray(tmax, dtype=np.float64)[r], skip=np.asarray(prim)[r])
         for k in out:
             out[k][r] = got[k]
     return out
@@ -50,18 +53,18 @@ def bounce(*args, **kwargs):
 
 def _bounce(geom: dict, env, mode: str, bounce: int, last: bool, occlusion: bool, seed: int, pass_idx: int, path_offset: int,
             org, nrm, wi, wl, material, prim, beta, rad, wo, pdf_o, pdf_l, f_o=None, f_l=None, n_e: int = 1, has_env: bool = True,
-            lsel=None, emit=None, rr_depth=None, bary_tol: float = 0.0, dtype=np.float64):
+            lsel=None, emit=None, rr_depth=None, bary_tol: float = 0.0, dtype=np.float64, cast=None):
     """One call of bsdfd_mesh_bounce -> dict(org, nrm, wi, wl, material, prim, beta, rad, thr): the arrays after the call (rows the
     kernel does not write keep their input values), and what the comparisons need: ``hit`` (the brute-force record of the
     continuation rays: t, prim, bary, marginal), ``shadow`` (of the cosine strategy's shadow rays), ``t`` [N] and ``d`` [N,3] of the
     continuation, ``fragile`` and ``mix_len`` of ``primary_arrays`` (with ``bary_tol``), ``would`` (rows that continue before the
-    roulette) and, with ``rr_depth``, ``u``, ``q``, ``survive``, ``killed`` as tests/bounce_ref.py returns them."""
+    roulette) and, with ``rr_depth``, ``u``, ``q``, ``survive``, ``killed`` as tests/bounce_ref.py returns them.  ``cast``: ``cast_rays``'s hit source."""
     assert mode in MODES and (f_o is None) == (f_l is None) and (rr_depth is None or rr_depth >= 1)
     n_b = geom["n_materials"]
     n = len(material)
-    cast = lambda a: np.asarray(a).astype(dtype)
+    to = lambda a: np.asarray(a).astype(dtype)
     x64 = np.asarray(org, dtype=np.float64)
-    org, nrm, wi, wl, beta, rad, wo = (cast(a) for a in (org, nrm, wi, wl, beta, rad, wo))
+    org, nrm, wi, wl, beta, rad, wo = (to(a) for a in (org, nrm, wi, wl, beta, rad, wo))
     live = (material >= 0) & (material <= n_b)
     floor = live & (material == n_b)
     ball = live & ~floor
@@ -75,7 +78,7 @@ def _bounce(geom: dict, env, mode: str, bounce: int, last: bool, occlusion: bool
     env_emits = mode != "lit" or has_env
     point = np.zeros(n, dtype=bool) if mode == "cosine" or lsel is None else live & (lsel >= 0)
     sampled = point
-    emit = np.zeros((n, 3), dtype=dtype) if mode == "cosine" else cast(emit)
+    emit = np.zeros((n, 3), dtype=dtype) if mode == "cosine" else to(emit)
 
     lw, dw = to_world(wl), to_world(wo)
     pb = np.where(np.isfinite(pdf_o) & (pdf_o > 0), pdf_o, 0).astype(dtype)
@@ -90,8 +93,8 @@ def _bounce(geom: dict, env, mode: str, bounce: int, last: bool, occlusion: bool
     # ---- the rays: one closest-hit walk along the continuation ray of floor and ball lanes alike, one any-hit walk along the
     # cosine strategy's light sample; both skip the primitive the vertex lies on ----
     d = np.where(floor[:, None], lw, dw)
-    hit = cast_rays(geom, x64, d, prim, (floor | follow) & bool(occlusion))
-    shadow = cast_rays(geom, x64, lw, prim, ok_l & ~sampled & (pl > 0) & bool(occlusion))
+    hit = cast_rays(geom, x64, d, prim, (floor | follow) & bool(occlusion), cast=cast)
+    shadow = cast_rays(geom, x64, lw, prim, ok_l & ~sampled & (pl > 0) & bool(occlusion), cast=cast)
     is_hit = hit["prim"][:, 0] >= 0
     hit_l = np.where(floor, is_hit, shadow["prim"][:, 0] >= 0)   # something along wl
     hit_o = is_hit & ~floor
@@ -138,10 +141,10 @@ def _bounce(geom: dict, env, mode: str, bounce: int, last: bool, occlusion: bool
 
 
 def sample_emitter(geom: dict, lights: dict, has_env: bool, bounce: int, occlusion: bool, seed: int, pass_idx: int, path_offset: int,
-                   org, nrm, wi, material, prim, wl, dtype=np.float64):
+                   org, nrm, wi, material, prim, wl, dtype=np.float64, cast=None):
     """One call of bsdfd_mesh_sample_emitter -> dict(wl, lsel, emit, lit, shadow, cos): tests/pathtrace_lights_ref.py's
     ``sample_emitter`` with the shadow ray cast in the mesh scene, bounded by the distance to the light (``shadow``: its brute-force
-    record; ``cos``: the light's cosine at the vertex)."""
+    record; ``cos``: the light's cosine at the vertex).  ``cast``: ``cast_rays``'s hit source."""
     with np.errstate(all="ignore"):
         n_b, n = geom["n_materials"], len(material)
         n_l = len(lights["position"])
@@ -161,7 +164,7 @@ def sample_emitter(geom: dict, lights: dict, has_env: bool, bounce: int, occlusi
         d = (dtype(1) / dist)[:, None] * v
         cosl = R._dot(d, nn)
         lit = point & (cosl > 0)
-        shadow = cast_rays(geom, x64, d, prim, lit & bool(occlusion), tmax=dist)
+        shadow = cast_rays(geom, x64, d, prim, lit & bool(occlusion), tmax=dist, cast=cast)
         lit &= ~(shadow["prim"][:, 0] >= 0)
         s = np.where(lit, dtype(n_e) / d2, dtype(0))
         s = np.where(floor, s * wi[:, 0] * dtype(LR.INV_PI) * cosl, s)

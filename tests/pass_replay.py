@@ -11,6 +11,10 @@ strings the kernels together — ``render_pass`` — is held here:
                     stages (oracle/wavefront_oracle.py ``primary``, tests/pathtrace_ref.py, tests/pathtrace_lights_ref.py,
                     tests/envmap_ref.py, tests/bounce_ref.py), fp64 by default, fp32 on request.  The sampler and the evaluator are inputs
                     (``answers``), exactly as in the kernel tests.
+``reference_mesh_pass``  the same for ``mesh.MeshPathArrayRenderer``, from its class docstring: the camera rays of the oracle, the
+                    hits of tests/mesh_ref.py, the vertices of ``mesh_ref.primary_arrays``, the stages of tests/mesh_bounce_ref.py,
+                    with ``prim`` in the state.  The ``Recorder`` serves that renderer as it is: it wraps whatever the instance's
+                    class defines, and snapshots every tensor of the buffer dict, ``prim`` among them.
 """
 from __future__ import annotations
 
@@ -66,7 +70,10 @@ class Recorder:
     """``with Recorder(r) as rec: r.render_pass(...)`` -> ``rec.stages``: one dict per stage call, in call order:
     ``name``, ``args`` (the scalars), ``before`` / ``after`` ({array name: numpy copy} of the buffer dict; ``before`` is None for
     ``primary``, which is where the dict comes from), for ``bucket`` also ``counts`` and ``perm``, for ``resolve`` also
-    ``film_before`` / ``film_after``.  The ids are called ``mat`` as in the renderer's dict."""
+    ``film_before`` / ``film_after``.  The ids are called ``mat`` as in the renderer's dict.  A stage on the dict that was called
+    with keywords beyond its documented scalars (``lights=``, ``rows=``, ``env_dist=``, ``rr_depth=``) hands them on and keeps
+    them as ``extra``; ``render_pass`` passes ``rows=`` with ``compact=True`` and nothing otherwise: its stages then have no
+    such entry."""
 
     def __init__(self, r):
         self.r, self.stages, self.b, self._wrapped = r, [], None, []
@@ -109,7 +116,11 @@ class Recorder:
                         args["occlusion"] = rec._effective_occlusion(args.get("occlusion"))
                     before = rec._snap()
                     out = inner(b, *a, **kw)
-                    rec.stages.append(dict(name=name, args=args, before=before, after=rec._snap()))
+                    stage = dict(name=name, args=args, before=before, after=rec._snap())
+                    extra = {k: v for k, v in kw.items() if k not in keys}
+                    if extra:          # keywords beyond the documented scalars (lights=, rows=, env_dist=, rr_depth=): handed on, and kept
+                        stage["extra"] = extra
+                    rec.stages.append(stage)
                     return out
                 return f
             return make
@@ -310,3 +321,137 @@ def capacity_lights() -> dict:
     return LR.make_lights([(0.0, 2.5, 0.5), (-1.5, 1.2, 1.0), (1.4, 0.45, 0.9), (2.6, 0.9, -1.3), (-2.7, 0.6, 0.2), (0.3, 0.75, 0.33),
                            (-0.9, 3.0, -2.0), (1.0, 1.6, 1.9)],
                           [4.0, (3.0, 2.0, 1.0), (0.5, 1.0, 2.0), 1.0, 2.0, (0.2, 0.3, 0.1), 6.0, 0.0])
+
+
+# ---- the pass on meshes: mesh.MeshPathArrayRenderer ---------------------------------------------------------------------------------
+MESH_STATE = ("org", "nrm", "wi", "wl", "material", "prim", "beta", "rad")
+
+
+def camera_scene(camera) -> dict:
+    """The oracle's scene dict of a camera alone (one placeholder ball, which no mesh pass intersects): what
+    ``wavefront_oracle.primary`` needs for ``dir`` and ``wl``."""
+    return scene_dict(camera, [(0.0, 0.0, 0.0)], [1.0], floor=False)
+
+
+def mesh_decision_code(geom: dict, material, prim, wi):
+    """What a vertex on a mesh decided, as one integer per row: the material id, for a diffuse or checker vertex which of its
+    instance's two reflectances sits in the ``wi`` slot (bit 40: the second colour of a checker; a plain diffuse instance has one),
+    and both components of ``prim`` (bits 24 .. 39: instance + 1, bits 0 .. 23: triangle + 1) — on meshes the primitive is part of
+    the decision, because the next ray skips it.  An ended row (id above ``n_materials``) keeps the ``prim`` it had; that is no
+    decision of the stage that ended it (the byte comparisons hold it), and the code carries 0 there."""
+    material, prim = np.asarray(material).astype(np.int64), np.asarray(prim).astype(np.int64)
+    n_b = geom["n_materials"]
+    live = (material >= 0) & (material <= n_b)
+    c0 = np.array([i.checker[0] if i.checker is not None else i.diffuse if i.diffuse is not None else 0.0 for i in geom["instances"]])
+    c1 = np.array([i.checker[1] if i.checker is not None else i.diffuse if i.diffuse is not None else 0.0 for i in geom["instances"]])
+    k = np.clip(prim[:, 0], 0, len(c0) - 1)
+    w0 = np.nan_to_num(np.asarray(wi)[:, 0].astype(np.float64))
+    odd = live & (material == n_b) & (np.abs(w0 - F(c1[k])) < np.abs(w0 - F(c0[k])))
+    assert prim.max(initial=0) < (1 << 24) - 1 and len(c0) < (1 << 16) - 1
+    where = np.where(live, ((prim[:, 0] + 1) << 24) | (prim[:, 1] + 1), 0)
+    return ((material * 2 + odd) << 40) | where
+
+
+def mesh_ids_of(code):
+    return np.asarray(code) >> 41
+
+
+def _no_rays(meshes, instances, org, dir, tmax=None, skip=None):
+    """A hit source that hits nothing (for a run of the bounce of which only the roulette's ``q`` is read)."""
+    import mesh_ref as MR
+    return MR._result(len(org))
+
+
+def too_close_to_call(want: dict, q_other):
+    """Rows [N] of a bounce with roulette (``want``: ``mesh_bounce_ref.bounce``'s dict) whose decision another precision may make
+    differently — the rule of test_mesh_bounce_matches_reference: the path would continue and its variate is no farther from ``q``
+    than the largest distance, over the rows that would continue, between ``q`` and the other precision's ``q_other``.
+    -> (rows, that distance)."""
+    would = want["would"]
+    with np.errstate(invalid="ignore"):
+        eq = np.abs(np.asarray(q_other, dtype=np.float64) - want["q"].astype(np.float64))[would].max(initial=0.0)
+        near = ~(np.abs(want["u"].astype(np.float64) - want["q"].astype(np.float64)) > eq)
+    return would & near, float(eq)
+
+
+def reference_mesh_pass(geom: dict, camera_scene: dict, env, lights, row_begin: int, row_end: int, spp: int, seed: int, pass_idx: int,
+                        max_depth, occlusion: bool, answers, dtype=np.float64, rr_depth=None, depth_cap: int = 1024, cast=None):
+    """One pass of ``mesh.MeshPathArrayRenderer`` over rows [row_begin, row_end), written from its class docstring and the module
+    docstring of pathtrace.py:
+
+        primary: the camera rays, their closest hits, the first vertex (org, prim, beta = 1, rad = env for a miss); path_begin: nothing
+        per bounce k:  [sample_emitter(k)] -> the sampler's and the evaluator's answers -> bounce(k, last)
+        resolve
+
+    ``geom``: mesh_bounce_ref's geometry dict; ``camera_scene``: the oracle's scene dict of the camera (``camera_scene(cam)`` or
+    ``scene_of(renderer)``), of which ``wavefront_oracle.primary`` gives ``dir`` and ``wl`` — ``bsdfd_wf_primary``'s bits, which
+    ``bsdfd_mesh_primary`` is tested to reproduce.  The first vertex is the hit from the camera's origin and
+    ``mesh_ref.primary_arrays``; ``org = o + t d``, ``prim`` the hit or (-1, -1).  ``env`` None (with ``lights`` only): black, and no
+    emitter.  ``answers``, ``rr_depth``, ``max_depth`` None and ``depth_cap``: as in ``reference_pass``.  ``cast``: the hit source
+    in place of ``mesh_ref.brute_force`` (mesh_bounce_ref.cast_rays), for the camera rays too.
+    -> what ``reference_pass`` returns (stages, history: ``mesh_decision_code`` after primary and after every bounce, rad, film,
+    depth, depth_cap_hit) and, per path [N], the union over all rays the path cast — camera, continuation and shadow rays — of
+    ``marginal``, of ``fragile`` (next vertices the path went on to), and with roulette of ``close``: decisions too close to call
+    (``too_close_to_call`` against the other one of fp32 / fp64)."""
+    import mesh_bounce_ref as MB
+    import mesh_ref as MR
+    assert max_depth is not None or rr_depth is not None
+    has_env = env is not None
+    assert has_env or lights is not None
+    env = np.zeros((2, 4, 3), F) if env is None else np.asarray(env, dtype=F)
+    meshes, instances, n_b = geom["meshes"], geom["instances"], geom["n_materials"]
+    width = camera_scene["width"]
+    n_l = 0 if lights is None else len(lights["position"])
+    n_e = n_l + int(has_env)
+    mode = "cosine" if lights is None else "lit"
+    offset = row_begin * width * spp
+    _, wl, _, dir_ = WO.primary(camera_scene, row_begin, row_end, spp, seed, pass_idx)
+    n = len(dir_)
+    o = np.tile(np.asarray(camera_scene["origin"], dtype=F).astype(np.float64), (n, 1))
+    d64 = dir_.astype(np.float64)
+    hit = (cast or MR.brute_force)(meshes, instances, o, d64)
+    is_hit = hit["prim"][:, 0] >= 0
+    v = MR.primary_arrays(meshes, instances, n_b, d64, hit)
+    org = np.where(is_hit[:, None], o + np.where(is_hit, hit["t"], 0.0)[:, None] * d64, 0.0)
+    rad = np.where(is_hit[:, None], 0.0, WO.env_lookup(env.astype(np.float64), dir_).astype(np.float64))
+    st = dict(org=org, nrm=v["nrm"], wi=v["wi"], wl=wl, beta=np.ones((n, 3)), rad=rad)
+    st = {k: a.astype(dtype) for k, a in st.items()}
+    st.update(material=v["material"].astype(np.int64), prim=hit["prim"].astype(np.int64))
+    marginal, fragile, close = hit["marginal"].copy(), v["fragile"] & is_hit, np.zeros(n, dtype=bool)
+    code = lambda s: mesh_decision_code(geom, s["material"], s["prim"], s["wi"])
+    stages = [("primary", None, dict(st, dir=dir_, hit=hit)), ("path_begin", None, dict(st))]
+    history = [code(st)]
+    depth = depth_cap if max_depth is None else max_depth
+    other = np.float32 if np.dtype(dtype) == np.float64 else np.float64
+    ran = 0
+    for k in range(depth):
+        live = (st["material"] >= 0) & (st["material"] <= n_b)
+        if not live.any() or (not callable(answers) and k >= len(answers)):
+            break
+        if lights is not None:
+            s = MB.sample_emitter(geom, lights, has_env, k, occlusion, seed, pass_idx, offset,
+                                  *[st[name] for name in ("org", "nrm", "wi", "material", "prim", "wl")], dtype=dtype, cast=cast)
+            st.update(wl=s["wl"].astype(dtype), lsel=s["lsel"], emit=s["emit"].astype(dtype), lit_point=s["lit"])
+            marginal |= s["shadow"]["marginal"]
+            stages.append(("sample_emitter", k, dict(st)))
+        a = answers(k, st) if callable(answers) else answers[k]
+        args = (geom, env, mode, k, k == depth - 1, occlusion, seed, pass_idx, offset, *[st[name] for name in MESH_STATE],
+                a["wo"], a["pdf_o"], a["pdf_l"], a.get("f_o"), a.get("f_l"))
+        kw = dict(n_e=n_e, has_env=has_env, lsel=st.get("lsel"), emit=st.get("emit"), rr_depth=rr_depth)
+        out = MB.bounce(*args, dtype=dtype, cast=cast, **kw)
+        marginal |= out["hit"]["marginal"] | out["shadow"]["marginal"]
+        rr = {}
+        if rr_depth is not None:
+            rr = {name: out[name] for name in ("u", "q", "survive", "killed", "would")}
+            if k != depth - 1 and k + 1 >= rr_depth:
+                # (q is formed of beta and the vertex' throughput alone: the other precision's needs no ray)
+                near, _ = too_close_to_call(out, MB.bounce(*args, dtype=other, cast=_no_rays, **kw)["q"])
+                close |= near
+        st.update({name: (out[name] if name in ("material", "prim") else out[name].astype(dtype)) for name in MESH_STATE})
+        fragile |= out["fragile"] & (st["material"] <= n_b)
+        stages.append(("bounce", k, dict(st, **rr)))
+        history.append(code(st))
+        ran = k + 1
+    film = R.resolve(st["rad"], spp).reshape(row_end - row_begin, width, 3)
+    return dict(stages=stages, history=history, rad=st["rad"], film=film, depth=ran, depth_cap_hit=max_depth is None and ran == depth,
+                marginal=marginal, fragile=fragile, close=close)
