@@ -68,6 +68,7 @@ EXPORTS = (
     "bsdfd_wf_bounce_transmit", "bsdfd_wf_sample_inside", "bsdfd_wf_sample_inside_rows",
     "bsdfd_mesh_bvh_build", "bsdfd_mesh_scene_create", "bsdfd_mesh_scene_destroy", "bsdfd_mesh_intersect", "bsdfd_mesh_occluded",
     "bsdfd_mesh_primary", "bsdfd_mesh_path_primary", "bsdfd_mesh_sample_emitter", "bsdfd_mesh_bounce",
+    "bsdfd_mesh_sample_emitter_rows", "bsdfd_mesh_bounce_rows",
     "bsdfd_set_profiling", "bsdfd_profile_read", "bsdfd_profile_read_op", "bsdfd_profile_clock_mhz", "bsdfd_last_kernel_ms", "bsdfd_shader_clock_mhz",
     "bsdfd_last_error", "bsdfd_version", "bsdfd_abi_version",
 )
@@ -549,6 +550,8 @@ def lib():
     L.bsdfd_mesh_path_primary.argtypes = L.bsdfd_mesh_primary.argtypes[:-1] + [fp] * 5 + [vp]
     L.bsdfd_mesh_sample_emitter.argtypes = [vp] + L.bsdfd_wf_sample_emitter.argtypes[:-1] + [fp, vp]
     L.bsdfd_mesh_bounce.argtypes = [vp] + L.bsdfd_wf_bounce_rr.argtypes[:-1] + [fp, vp]
+    for name in ("bsdfd_mesh_sample_emitter", "bsdfd_mesh_bounce"):   # their list forms: (rows, n_rows) in front of the stream
+        getattr(L, name + "_rows").argtypes = getattr(L, name).argtypes[:-1] + [fp, i64, vp]
     L.bsdfd_bucket_rows.argtypes = L.bsdfd_bucket_by_material.argtypes[:1] + [fp] + L.bsdfd_bucket_by_material.argtypes[1:]
     L.bsdfd_bucket_wide_workspace_bytes.argtypes = [i64, i32]
     L.bsdfd_bucket_wide_workspace_bytes.restype = i64

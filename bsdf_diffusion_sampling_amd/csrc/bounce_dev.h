@@ -134,7 +134,8 @@ __device__ __forceinline__ void store_local_direction(float* __restrict__ wl, V3
 // that is killed ends exactly as one that escaped; `rad` is formed and stored before, and where a survivor goes does not depend on
 // the roulette: only the `thr` that continue_path multiplies into beta does.
 //
-// LIST: the lanes are those of `rows` (the list forms of the six kernels); nothing else differs.
+// LIST: the lanes are those of `rows` (the list forms of the six kernels, and of the mesh kernels); nothing else differs.  With
+// G::ONE_WALK the threads beyond the list and the listed paths that have ended leave in front of the walks, as ended lanes do.
 //
 // G: the geometry policy.  With G::ONE_WALK the rays are formed in front of the two branches — the floor's cosine direction, the
 // ball's BSDF sample, and the shadow ray along wl of a ball that looks the environment up there (COSINE; LIT where the
@@ -154,7 +155,7 @@ template <int M, bool RR = false, bool LIST = false, bool TRANSMIT = false, clas
 __device__ __forceinline__ void bounce_vertex(const Scene& sc, const float* __restrict__ env, const EnvDist& e, int n_e, int has_env,
                                               const Step& st, const PathState& ps, const SamplerAnswer& sa,
                                               const EmitterSample& es, int rr_depth = 0, const Rows& rows = Rows{}, const G& g = G{}) {
-    static_assert(!(G::ONE_WALK && (TRANSMIT || LIST || M == ENV)), "not on meshes yet");
+    static_assert(!(G::ONE_WALK && (TRANSMIT || M == ENV)), "not on meshes yet");
     long long p, m;
     if (!live_lane<LIST>(sc, st.n, ps.mat, p, m, rows)) return;
     const int occlusion = st.occlusion;

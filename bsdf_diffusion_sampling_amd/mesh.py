@@ -6,8 +6,9 @@ through ``PathArrayRenderer``'s (``MeshPathArrayRenderer``: shadows, interreflec
 ``bsdfd_mesh_path_primary`` / ``_sample_emitter`` / ``_bounce`` in the place of the sphere kernels).
 
 Limits of the path tracer on meshes: no geometric-normal test — a BSDF sample above the shading normal but below the triangle's
-plane enters the shell and is followed there; the shell's inside is shaded like its outside; no transmission, no importance
-sampling of the environment and no live-lane list on meshes yet.  Like everything at this level it is PARITY-UNPINNED against
+plane enters the shell and is followed there; the shell's inside is shaded like its outside; no transmission and no importance
+sampling of the environment on meshes yet.  ``CompactMeshPathArrayRenderer`` is the same renderer with the bounces behind the first
+on a live-lane list (``bsdfd_mesh_sample_emitter_rows`` / ``bsdfd_mesh_bounce_rows``): the same film bit for bit.  Like everything at this level it is PARITY-UNPINNED against
 Mitsuba: image handedness, which checker colour lands on which cell and the v0.5-to-v3 scene upgrade rules are this module's
 reading of the files, not a comparison with Mitsuba's images.
 
@@ -493,7 +494,9 @@ class MeshPathArrayRenderer(PathArrayRenderer):
 
     ``render_pass``, the bucketing, the sampler launches, both ground-truth tables, ``resolve`` and ``stats`` are inherited, and
     ``max_depth``, ``occlusion``, ``lights``, ``rr_depth`` and ``DEPTH_CAP`` mean what they mean there.  ``env_sampling`` other than
-    ``"cosine"``, ``compact=True`` and ``transmission=True`` are refused: not on meshes yet.  Limits: the module docstring's.
+    ``"cosine"`` and ``transmission=True`` are refused: not on meshes yet.  ``sample_emitter`` and ``bounce`` take a live-lane list
+    (``rows=``: ``bsdfd_mesh_sample_emitter_rows`` / ``bsdfd_mesh_bounce_rows``); the renderer that runs its deep bounces on one is
+    ``CompactMeshPathArrayRenderer``, and ``compact=True`` here is refused and points there.  Limits: the module docstring's.
     Parity-unpinned against Mitsuba."""
 
     def __init__(self, table, mesh_scene: MeshScene, camera=None, env=None, *, max_depth: Optional[int] = 1,
@@ -503,7 +506,7 @@ class MeshPathArrayRenderer(PathArrayRenderer):
         if env_sampling != "cosine":
             raise ValueError(f"env_sampling={env_sampling!r}: importance sampling of the environment is not on meshes yet")
         if compact:
-            raise ValueError("compact=True: the live-lane list is not on meshes yet")
+            raise ValueError("compact=True is not on meshes yet as an argument: the live-lane list is mesh.CompactMeshPathArrayRenderer")
         if transmission:
             raise ValueError("transmission=True: transmitted paths are not on meshes yet")
         if not isinstance(mesh_scene, MeshScene):
@@ -542,37 +545,71 @@ class MeshPathArrayRenderer(PathArrayRenderer):
 
     def sample_emitter(self, b, bounce: int, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
                        lights: Optional[_lib.WfLights] = None, rows=None):
-        """``PathArrayRenderer.sample_emitter`` with the shadow rays cast in the mesh scene (``bsdfd_mesh_sample_emitter``)."""
+        """``PathArrayRenderer.sample_emitter`` with the shadow rays cast in the mesh scene (``bsdfd_mesh_sample_emitter``).  ``rows``
+        (int64 [n_rows], distinct lanes): of the listed vertices only (``bsdfd_mesh_sample_emitter_rows``); an empty list returns
+        without a launch."""
         import torch
-        if rows is not None:
-            raise ValueError("rows: the live-lane list is not on meshes yet")
+        listed = () if rows is None else self._list(rows, b)
+        if listed and listed[1] == 0:
+            return
         occlusion = self.occlusion if occlusion is None else occlusion
         p = lambda a: C.c_void_p(a.data_ptr())
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().bsdfd_mesh_sample_emitter(
+            fn = _lib.lib().bsdfd_mesh_sample_emitter_rows if listed else _lib.lib().bsdfd_mesh_sample_emitter
+            _lib.check(fn(
                 self.mesh_scene.handle(), C.byref(self.scene), C.byref(self.lights if lights is None else lights), bounce,
                 int(bool(occlusion)), seed, pass_idx, path_offset, b["mat"].shape[0], p(b["org"]), p(b["nrm"]), p(b["wi"]),
-                p(b["mat"]), p(b["wl"]), p(b["lsel"]), p(b["emit"]), p(b["prim"]), self._stream()))
+                p(b["mat"]), p(b["wl"]), p(b["lsel"]), p(b["emit"]), p(b["prim"]), *listed, self._stream()))
         torch.autograd.graph.increment_version([b["wl"], b["lsel"], b["emit"]])
 
     def bounce(self, b, bounce: int, last: bool, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
                lights: Optional[_lib.WfLights] = None, env_dist=None, rr_depth: Optional[int] = None, rows=None):
         """``PathArrayRenderer.bounce`` on the mesh scene (``bsdfd_mesh_bounce``): the cosine light strategy without ``lights``, one
-        emitter sample per vertex with them, Russian roulette with ``rr_depth``."""
+        emitter sample per vertex with them, Russian roulette with ``rr_depth``.  ``rows`` (int64 [n_rows], distinct lanes): the
+        listed vertices only (``bsdfd_mesh_bounce_rows``), ``prim`` included; an empty list returns without a launch."""
         import torch
-        if rows is not None or env_dist is not None:
-            raise ValueError("rows / env_dist: the live-lane list and the environment's importance sampling are not on meshes yet")
+        if env_dist is not None:
+            raise ValueError("env_dist: the environment's importance sampling is not on meshes yet")
+        listed = () if rows is None else self._list(rows, b)
+        if listed and listed[1] == 0:
+            return
         occlusion = self.occlusion if occlusion is None else occlusion
         lights = self.lights if lights is None else lights
         rr_depth = self.rr_depth if rr_depth is None else rr_depth
         p = lambda a: None if a is None else C.c_void_p(a.data_ptr())
         lit = lights is not None
         with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().bsdfd_mesh_bounce(
+            fn = _lib.lib().bsdfd_mesh_bounce_rows if listed else _lib.lib().bsdfd_mesh_bounce
+            _lib.check(fn(
                 self.mesh_scene.handle(), C.byref(self.scene), p(self.env), bounce, int(bool(last)), int(bool(occlusion)), seed,
                 pass_idx, path_offset, b["mat"].shape[0], p(b["org"]), p(b["nrm"]), p(b["wi"]), p(b["wl"]), p(b["mat"]), p(b["beta"]),
                 p(b["rad"]), p(b["wo"]), p(b["pdf_o"]), p(b["pdf_l"]), p(b.get("f_o")), p(b.get("f_l")),
                 C.byref(lights) if lit else None, p(b["lsel"]) if lit else None, p(b["emit"]) if lit else None, None, None,
-                int(rr_depth or 0), p(b["prim"]), self._stream()))
+                int(rr_depth or 0), p(b["prim"]), *listed, self._stream()))
         # written through raw pointers: tell torch (the plugin cores key their per-query context cache on wi._version)
         torch.autograd.graph.increment_version([b["wi"], b["wl"], b["nrm"], b["org"], b["mat"], b["beta"], b["rad"], b["prim"]])
+
+
+class CompactMeshPathArrayRenderer(MeshPathArrayRenderer):
+    """``MeshPathArrayRenderer`` with ``PathArrayRenderer``'s ``compact=True``: bounce 0 runs over all N lanes as before; from
+    bounce 1 on ``sample_emitter`` and ``bounce`` run over the live-lane list the bucketing of the bounce before left (the front of
+    ``bucket_rows``' permutation: sorted by material, stable in lane order, ended paths left out), through
+    ``bsdfd_mesh_sample_emitter_rows`` and ``bsdfd_mesh_bounce_rows``, and the sampler and the ground-truth table serve the list's
+    material prefix.  ``render_pass`` is inherited unchanged — it forms the list and hands ``rows=`` on wherever ``self.compact``
+    is set.  The film, the path state and ``stats`` are the plain renderer's bit for bit (a lane's Philox counters are keyed by the
+    lane, never by the thread); ``stats["list_per_bounce"]`` holds the list lengths.  What it buys (profiles/mesh_path_compact.json,
+    tools/mesh_bench.py --path --compact; the fixture scene): 1.16x at ``max_depth=2`` and 1.20x at 4 — while more than ~5 % of
+    the lanes live, fewer waves walk — and 1.39x SLOWER at ``max_depth=None``: a short list packs 64 unrelated rays into a wave
+    whose walk lasts ~2 ms, where the full-width launch runs the same rays one to a wave, side by side.  Use it at fixed depths.
+
+    The constructor's arguments are ``MeshPathArrayRenderer``'s without ``compact``, and so are its refusals.  A class of its own,
+    not an argument: ``MeshPathArrayRenderer(..., compact=True)`` keeps its refusal."""
+
+    def __init__(self, table, mesh_scene: MeshScene, camera=None, env=None, *, max_depth: Optional[int] = 1,
+                 occlusion: Optional[bool] = None, lights=None, rr_depth: Optional[int] = None, albedo=(1.0, 1.0, 1.0),
+                 ground_truth=None, ball_albedo=None, device=None, fused_ground_truth: bool = True, env_sampling: str = "cosine",
+                 transmission: bool = False):
+        super().__init__(table, mesh_scene, camera, env, max_depth=max_depth, occlusion=occlusion, lights=lights, rr_depth=rr_depth,
+                         albedo=albedo, ground_truth=ground_truth, ball_albedo=ball_albedo, device=device,
+                         fused_ground_truth=fused_ground_truth, env_sampling=env_sampling, transmission=transmission)
+        self.compact = True

@@ -63,7 +63,8 @@ extern "C" {
  *      bsdfd_mesh_occluded() and bsdfd_mesh_primary(), which take structs of their own, bsdfd_mesh_desc and bsdfd_mesh_instance:
  *      ray casting on the array scenes' triangle meshes;
  *      bsdfd_mesh_path_primary(), bsdfd_mesh_sample_emitter() and bsdfd_mesh_bounce(): the path tracer of the array scene on
- *      those meshes. */
+ *      those meshes;
+ *      bsdfd_mesh_sample_emitter_rows() and bsdfd_mesh_bounce_rows(): its per-depth calls over a live-lane list. */
 #define BSDFD_ABI_VERSION 8
 
 #define BSDFD_OK 0
@@ -919,7 +920,7 @@ int bsdfd_mesh_primary(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, i
  *
  * bsdfd_mesh_bounce is bsdfd_wf_bounce_rr's argument list, with lights, lsel and emit NULL where only the environment emits (the
  * cosine light strategy) and rr_depth = 0 for no roulette.  lpdf and dist must be NULL (BSDFD_EINVAL): the environment is not
- * importance-sampled on meshes yet; nor is there a live-lane list or transmission.  The estimate, the MIS weights, the roulette
+ * importance-sampled on meshes yet; nor is there transmission (the live-lane list: below).  The estimate, the MIS weights, the roulette
  * and the Philox counters are those of the sphere kernels (one body, csrc/bounce_dev.h); the closest hit is one walk per lane,
  * the cosine strategy's shadow ray one unbounded any-hit walk, and the next vertex is written as bsdfd_mesh_primary writes the
  * first: org = x + t d, the shading-normal rule for a ray of direction d, prim = the hit.  A sample above the shading normal but
@@ -941,6 +942,31 @@ int bsdfd_mesh_bounce(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, co
                       const float* pdf_l, const float* f_o, const float* f_l, const bsdfd_wf_lights* lights, const int32_t* lsel,
                       const float* emit, const float* lpdf, const bsdfd_env_dist* dist, int32_t rr_depth, int32_t* prim,
                       void* hip_stream);
+
+/* ---- the same two per-depth calls over a live-lane list (no new ABI version: two more entry points) ----
+ *
+ * bsdfd_mesh_sample_emitter_rows and bsdfd_mesh_bounce_rows take their full-width sibling's arguments and, in front of the stream,
+ * `rows` (int64 [n_rows], device) and n_rows, as bsdfd_wf_sample_emitter_rows and bsdfd_wf_bounce_rows do, under the contract of
+ * those list forms: thread t serves lane rows[t] exactly as the full-width call serves that lane — prim is read and written at
+ * rows[t], the Philox counters are keyed by path_offset + lane — so a listed lane gets the full-width call's result bit for bit;
+ *   - the entries of `rows` are distinct and in [0, N) (an entry outside is skipped, not followed);  0 <= n_rows <= N;
+ *   - a row that is not listed keeps every byte of every array, prim included;
+ *   - n_rows == 0 is a no-op that returns BSDFD_OK whatever the pointers (rows may then be NULL); otherwise every check of the
+ *     full-width sibling applies (lpdf and dist must be NULL here too).
+ * A null scene, n_rows < 0, n_rows > N and rows == NULL with n_rows > 0 are refused before any device work.  The grid covers
+ * n_rows threads, not N: a wave's two walks serve 64 listed lanes, where the full-width call's serve what is left alive among 64
+ * neighbouring lanes.  Listed paths that have ended leave in front of the walks, as ended lanes do at full width. */
+int bsdfd_mesh_sample_emitter_rows(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, const bsdfd_wf_lights* lights,
+                                   int32_t bounce, int32_t occlusion, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N,
+                                   const float* org, const float* nrm, const float* wi, const int64_t* material, float* wl,
+                                   int32_t* lsel, float* emit, const int32_t* prim, const int64_t* rows, int64_t n_rows,
+                                   void* hip_stream);
+int bsdfd_mesh_bounce_rows(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, const float* env, int32_t bounce, int32_t last,
+                           int32_t occlusion, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, float* org, float* nrm,
+                           float* wi, float* wl, int64_t* material, float* beta, float* rad, const float* wo, const float* pdf_o,
+                           const float* pdf_l, const float* f_o, const float* f_l, const bsdfd_wf_lights* lights,
+                           const int32_t* lsel, const float* emit, const float* lpdf, const bsdfd_env_dist* dist, int32_t rr_depth,
+                           int32_t* prim, const int64_t* rows, int64_t n_rows, void* hip_stream);
 
 const char* bsdfd_last_error(void);
 const char* bsdfd_version(void);

@@ -21,6 +21,12 @@ ends in a synchronise); and, per bounce of the unbounded pass, the ``bounce`` la
 live-lane count, next to ``MeshScene.intersect`` plus ``occluded`` on the same rays — the continuation rays and the cosine
 strategy's shadow rays the fused kernel walks — which is the yardstick for what the fusion costs or saves.
 
+``--path --compact`` measures the live-lane list on meshes (``mesh.CompactMeshPathArrayRenderer``) -> profiles/mesh_path_compact.json,
+by the protocol of ``--path``: a pass at max_depth 1, 2 and 4 and unbounded with rr_depth = 5 of the plain ``MeshPathArrayRenderer``
+and of the compact one, the two alternating within every round of one process; the medians, the difference round by round with its
+spread, whether the two films are equal byte for byte; and, per bounce of the unbounded pass, the ``bounce`` launch of either
+renderer between two device events, with the lanes alive, the list's length and the lanes the list form is launched over.
+
 Nothing here is a gate.  The record is there to decide whether an ordered traversal with a stack in LDS, or a wider node, is
 worth a change of its own, and what a bounce of the path tracer on meshes will cost.
 """
@@ -52,9 +58,14 @@ ap.add_argument("--mesh-file", default=os.path.join(ROOT, "tests", "golden", "ma
 ap.add_argument("--no-counting", action="store_true", help="skip the counting build (needs hipcc)")
 ap.add_argument("--no-errors", action="store_true", help="skip the fp32 error figures (a minute of numpy brute force)")
 ap.add_argument("--path", action="store_true", help="measure the path tracer on meshes instead -> profiles/mesh_path.json")
+ap.add_argument("--compact", action="store_true",
+                help="with --path: the live-lane list (mesh.CompactMeshPathArrayRenderer) against the plain renderer -> "
+                     "profiles/mesh_path_compact.json")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
-a.out = a.out or os.path.join(ROOT, "profiles", "mesh_path.json" if a.path else "mesh.json")
+if a.compact and not a.path:
+    ap.error("--compact needs --path")
+a.out = a.out or os.path.join(ROOT, "profiles", "mesh_path_compact.json" if a.compact else "mesh_path.json" if a.path else "mesh.json")
 if not torch.cuda.is_available():
     sys.exit("tools/mesh_bench.py measures on the GPU: no device visible")
 dev = torch.device("cuda", 0)
@@ -73,8 +84,9 @@ rec = {"workload": f"{os.path.basename(a.scene)} {a.width}x{a.height}x{a.spp}", 
 
 
 
-def median_ms(variants, rounds, reps):
-    """{name: ms} -> medians over interleaved rounds: each variant once per round, ``reps`` calls per timing, a synchronise at the end."""
+def median_ms(variants, rounds, reps, keep=False):
+    """{name: ms} -> medians over interleaved rounds: each variant once per round, ``reps`` calls per timing, a synchronise at the end.
+    ``keep``: every round's figure as well ("rounds_ms")."""
     times = {k: [] for k in variants}
     for fn in variants.values():   # warm-up
         fn()
@@ -87,7 +99,8 @@ def median_ms(variants, rounds, reps):
                 fn()
             torch.cuda.synchronize()
             times[k].append((time.perf_counter() - t0) / reps)
-    return {k: {"ms": 1e3 * float(np.median(v)), "ms_min": 1e3 * min(v), "ms_max": 1e3 * max(v)} for k, v in times.items()}
+    return {k: dict({"ms": 1e3 * float(np.median(v)), "ms_min": 1e3 * min(v), "ms_max": 1e3 * max(v)},
+                    **({"rounds_ms": [1e3 * x for x in v]} if keep else {})) for k, v in times.items()}
 
 
 def measure_paths():
@@ -165,12 +178,93 @@ def measure_paths():
     rec["depth_unbounded_rr5"] = depth
 
 
+def measure_compact():
+    """The live-lane list on meshes: ``CompactMeshPathArrayRenderer`` against the plain ``MeshPathArrayRenderer`` (the yardstick) in
+    one process, the two alternating within every round."""
+    cfgs = {"depth1": dict(max_depth=1, occlusion=True), "depth2": dict(max_depth=2), "depth4": dict(max_depth=4),
+            "unbounded_rr5": dict(max_depth=None, rr_depth=5)}
+    plain = {k: M.MeshPathArrayRenderer(table, scene, camera=cam, **kw) for k, kw in cfgs.items()}
+    comp = {k: M.CompactMeshPathArrayRenderer(table, scene, camera=cam, **kw) for k, kw in cfgs.items()}
+    films = {}
+
+    def one_pass(r):
+        film = films.setdefault(id(r), torch.zeros((a.height, a.width, 3), device=dev))
+        return lambda: r.render_pass(film, 0, a.height, a.spp, 0, 0)
+    variants = {}
+    for k in cfgs:
+        variants["plain_" + k], variants["compact_" + k] = one_pass(plain[k]), one_pass(comp[k])
+    got = median_ms(variants, a.rounds, a.reps, keep=True)
+    rec["pass_ms"] = {k: {x: y for x, y in v.items() if x != "rounds_ms"} for k, v in got.items()}
+    rec["plain_minus_compact_ms"] = {}
+    for k in cfgs:   # the difference round by round (the two ran back to back in it), its median and its spread
+        d = [p - c for p, c in zip(got["plain_" + k]["rounds_ms"], got["compact_" + k]["rounds_ms"])]
+        rec["plain_minus_compact_ms"][k] = {"median": float(np.median(d)), "min": min(d), "max": max(d),
+                                            "ratio_of_medians": got["plain_" + k]["ms"] / got["compact_" + k]["ms"]}
+    # the same film: one pass of each into a fresh film, compared byte for byte
+    rec["films_equal"] = {}
+    for k in cfgs:
+        fp, fc = (torch.zeros((a.height, a.width, 3), device=dev) for _ in range(2))
+        plain[k].render_pass(fp, 0, a.height, a.spp, 0, 0)
+        comp[k].render_pass(fc, 0, a.height, a.spp, 0, 0)
+        torch.cuda.synchronize()
+        rec["films_equal"][k] = bool(torch.equal(fp.view(torch.int32), fc.view(torch.int32)))
+    rec["lanes_per_bounce"] = {k: r.stats["lanes_per_bounce"] for k, r in plain.items()}
+    rec["list_per_bounce"] = {k: r.stats["list_per_bounce"] for k, r in comp.items()}
+    # ---- per bounce of the unbounded pass: the bounce launch of either renderer between two device events ----
+    rp, rc = plain["unbounded_rr5"], comp["unbounded_rr5"]
+    n_b = len(table)
+    live, launched, per = [], [], {"plain": [], "compact": []}
+
+    def instrument(r, name, count):
+        inner = r.bounce
+
+        def timed(b, k, *args, **kwargs):
+            if count:   # the untimed first pass: the lanes alive entering this bounce
+                live.append(int((b["mat"] <= n_b).sum()))
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            inner(b, k, *args, **kwargs)
+            e1.record()
+            per[name][-1].append((e0, e1))
+            if name == "compact" and len(per[name]) == 1:   # the lanes this launch is given: the list without its ended paths
+                launched.append(n if kwargs.get("rows") is None else int(kwargs["rows"].shape[0]))
+        r.bounce = timed
+        return inner
+    film = torch.zeros((a.height, a.width, 3), device=dev)
+    inner_p = instrument(rp, "plain", True)
+    per["plain"].append([])
+    rp.render_pass(film, 0, a.height, a.spp, 0, 0)
+    torch.cuda.synchronize()
+    per["plain"].clear()
+    rp.bounce = inner_p
+    inner_p, inner_c = instrument(rp, "plain", False), instrument(rc, "compact", False)
+    for _ in range(a.rounds):
+        for name, r in (("plain", rp), ("compact", rc)):
+            per[name].append([])
+            r.render_pass(film, 0, a.height, a.spp, 0, 0)
+            torch.cuda.synchronize()
+            per[name][-1] = [e0.elapsed_time(e1) for e0, e1 in per[name][-1]]
+    rp.bounce, rc.bounce = inner_p, inner_c
+    depth = len(live)
+    assert all(len(p) == depth for v in per.values() for p in v)   # (the same seed and pass: the same paths)
+    lists = rc.stats["list_per_bounce"]
+    rec["bounces_unbounded_rr5"] = [
+        {"bounce": k, "live_lanes": live[k], "list_length": lists[k], "lanes_launched": launched[k],
+         "full_width_bounce_ms": float(np.median([p[k] for p in per["plain"]])),
+         "list_bounce_ms": float(np.median([p[k] for p in per["compact"]])),
+         "list_bounce_ms_min": min(p[k] for p in per["compact"]), "list_bounce_ms_max": max(p[k] for p in per["compact"])}
+        for k in range(depth)]
+    rec["depth_unbounded_rr5"] = depth
+    rec["bounce_launches_ms"] = {name: float(np.median([sum(p) for p in v])) for name, v in per.items()}
+
+
 if a.path:
-    measure_paths()
+    measure_compact() if a.compact else measure_paths()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(rec, f, indent=1)
-    print(json.dumps({k: rec[k] for k in ("pass_ms", "bounces_unbounded_rr5")}))
+    print(json.dumps({k: rec[k] for k in ("pass_ms", "plain_minus_compact_ms", "films_equal", "bounce_launches_ms",
+                                          "bounces_unbounded_rr5") if k in rec}))
     sys.exit(0)
 
 # ---- BVH build time per mesh (host) ----

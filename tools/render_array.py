@@ -17,8 +17,8 @@ ap.add_argument("--max-depth", type=int, default=None, help="path vertices (Path
 ap.add_argument("--rr-depth", type=int, default=None, metavar="R",
                 help="Russian roulette from the R-th vertex on (Mitsuba's rule; its default is 5).  Default: none")
 ap.add_argument("--compact", action="store_true",
-                help="run the bounces behind the first on the live-lane list of the bounce before (PathArrayRenderer(compact=True)): "
-                     "the same image bit for bit")
+                help="run the bounces behind the first on the live-lane list of the bounce before (PathArrayRenderer(compact=True); "
+                     "with --mesh-file: mesh.CompactMeshPathArrayRenderer): the same image bit for bit")
 ap.add_argument("--transmission", action="store_true",
                 help="follow BSDF samples below the surface through the balls (PathArrayRenderer(transmission=True)): needs "
                      "--scene with --analytic, --max-depth > 1 (or -1) and balls that touch neither each other nor the floor")
@@ -47,7 +47,8 @@ ap.add_argument("--mesh-file", default=None, metavar="matpreview.serialized",
                 help="with --scene: render the file's own geometry — its 25 instances of the three meshes of this container, under "
                      "their toWorld, and its lookAt camera — instead of twelve spheres on a plane: through mesh.MeshArrayRenderer (one "
                      "bounce, unoccluded), or, with any of --max-depth, --occlusion, --rr-depth, --integrator-from, --point-light, "
-                     "--lights-from, --no-env, through mesh.MeshPathArrayRenderer.  No --compact, --transmission or --env-sampling "
+                     "--lights-from, --no-env, --compact, through mesh.MeshPathArrayRenderer (--compact: "
+                     "mesh.CompactMeshPathArrayRenderer, the same image bit for bit).  No --transmission or --env-sampling "
                      "importance on meshes yet; parity-unpinned against Mitsuba")
 a = ap.parse_args()
 if a.analytic and not a.scene:
@@ -101,15 +102,16 @@ elif a.measured_dir:
 if a.env_sampling == "importance" and a.no_env:
     ap.error("--env-sampling importance needs an emitting environment: drop --no-env")
 if mesh_scene is not None:
-    if a.env_sampling != "cosine" or a.compact or a.transmission:
-        ap.error("--compact, --transmission and --env-sampling importance are not on meshes yet")
-    if a.max_depth is None and not unbounded and a.rr_depth is None and a.occlusion is None and not lights:
+    if a.env_sampling != "cosine" or a.transmission:
+        ap.error("--transmission and --env-sampling importance are not on meshes yet")
+    if a.max_depth is None and not unbounded and a.rr_depth is None and a.occlusion is None and not lights and not a.compact:
         r = MESH.MeshArrayRenderer(tab, mesh_scene, camera=cam, ground_truth=gts, **extra)
     else:
-        r = MESH.MeshPathArrayRenderer(tab, mesh_scene, camera=cam, ground_truth=gts, **extra,
-                                       max_depth=None if unbounded else 1 if a.max_depth is None else a.max_depth, rr_depth=a.rr_depth,
-                                       occlusion=None if a.occlusion is None else bool(a.occlusion), lights=lights,
-                                       env=None if a.no_env or not lights else WF.make_sky())
+        cls = MESH.CompactMeshPathArrayRenderer if a.compact else MESH.MeshPathArrayRenderer
+        r = cls(tab, mesh_scene, camera=cam, ground_truth=gts, **extra,
+                max_depth=None if unbounded else 1 if a.max_depth is None else a.max_depth, rr_depth=a.rr_depth,
+                occlusion=None if a.occlusion is None else bool(a.occlusion), lights=lights,
+                env=None if a.no_env or not lights else WF.make_sky())
 elif (a.max_depth is None and not unbounded and a.rr_depth is None and a.occlusion is None and not lights and a.env_sampling == "cosine"
         and not a.compact and not a.transmission):
     r = WF.ArrayRenderer(tab, centers, radii, camera=cam, ground_truth=gts, **extra)
