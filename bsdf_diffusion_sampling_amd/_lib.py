@@ -28,7 +28,7 @@ SRC_PATHS = [SRC_PATH, SRC32_PATH, HOST_PATH, os.path.join(_HERE, "csrc", "wavef
              os.path.join(_HERE, "csrc", "mesh.hip")]  # translation units of libbsdfd.so
 FLOW_TUS = (SRC_PATH, SRC32_PATH)   # ... whose device assembly the build verifies (_asmcheck)
 DEP_PATHS = SRC_PATHS + [os.path.join(_HERE, "csrc", f) for f in ("common.h", "flow_dev.h", "flow_kernels.h", "bucket_scan.h",
-                                                                     "measured_dev.h", "wavefront_dev.h", "env_dev.h", "bounce_dev.h",
+                                                                     "measured_dev.h", "wavefront_dev.h", "env_dev.h", "bounce_dev.h", "bounce_launch.h",
                                                                      "dielectric_dev.h", "principled_dev.h", "analytic_host.h",
                                                                      "rows.h", "analytic_rows.h", "material_table.h", "mesh_dev.h")]
 INCLUDE_DIR = os.path.join(ROOT, "include")

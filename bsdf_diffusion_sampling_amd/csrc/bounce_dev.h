@@ -1,5 +1,6 @@
-// bounce_dev.h — the one bounce of the array-scene path tracer, and what its launcher (bounce.hip) and the two emitter samplers
-// (pathlights.hip, pathenv.hip) share.  bounce.hip instantiates bounce_vertex<Mode, RR> in six thin __global__ stubs:
+// bounce_dev.h — the one bounce of the array-scene path tracer, and what its launcher (bounce_launch.h) and the two emitter
+// samplers (pathlights.hip, pathenv.hip) share.  bounce_launch.h instantiates bounce_vertex<Mode, RR, LIST, TRANSMIT, G> behind one
+// __global__ template, bounce_kernel, with those template arguments:
 //
 //   COSINE : only the environment emits; the light strategy is the cosine-weighted direction primary / bounce left in wl
 //   LIT    : one emitter sample per vertex, uniform among n_e = point lights [+ the environment] (sample_emitter: lsel, emit)
@@ -12,9 +13,9 @@
 // Each instantiation is straight-line code of its own.  RR = true is the same body with Russian roulette in front of
 // continue_path.
 //
-// What the scene is made of is a parameter too: a geometry policy (Spheres below, the scene of every kernel named above;
-// mesh_dev::PathGeom, which mesh.hip instantiates this body and sample_emitter_vertex with) answers for the closest hit, for a
-// shadow ray and for the next vertex.  The estimate, the MIS weights, the roulette and the Philox counters do not depend on it.
+// What the scene is made of is a parameter too: a geometry policy (Spheres below, the scene of bounce.hip's and pathlights.hip's
+// entry points; mesh_dev::PathGeom, the scene of mesh.hip's) answers for the closest hit, for a shadow ray and for the next
+// vertex.  The estimate, the MIS weights, the roulette and the Philox counters do not depend on it.
 //
 // The arrays travel in small structs passed by value (kernel arguments: scalar loads); no struct is indexed per lane.
 #pragma once
@@ -134,7 +135,7 @@ __device__ __forceinline__ void store_local_direction(float* __restrict__ wl, V3
 // that is killed ends exactly as one that escaped; `rad` is formed and stored before, and where a survivor goes does not depend on
 // the roulette: only the `thr` that continue_path multiplies into beta does.
 //
-// LIST: the lanes are those of `rows` (the list forms of the six kernels, and of the mesh kernels); nothing else differs.  With
+// LIST: the lanes are those of `rows` (the `_rows` entry points, on either geometry); nothing else differs.  With
 // G::ONE_WALK the threads beyond the list and the listed paths that have ended leave in front of the walks, as ended lanes do.
 //
 // G: the geometry policy.  With G::ONE_WALK the rays are formed in front of the two branches — the floor's cosine direction, the

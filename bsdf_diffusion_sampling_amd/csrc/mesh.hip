@@ -7,9 +7,10 @@
 //   kernels : intersect (closest hit), occluded (any hit), primary (bsdfd_wf_primary's rays, closest hit, the five arrays
 //             shade_kernel reads; its path form also stores the hit, and path_begin makes the first vertex of a path from it) — one ray per lane, the walk of
 //             mesh_dev.h; no stack, no scratch
-//             bounce, sample_emitter — the path tracer's one bounce and its point emitters' sample (bounce_dev.h) with the mesh
-//             scene as their geometry: COSINE and LIT, with and without roulette, full width and over a live-lane list.  No ENV
-//             mode and no transmission on meshes yet.
+//             bounce, sample_emitter — the path tracer's one bounce and its point emitters' sample: bounce_launch.h's kernel
+//             templates and launchers with mesh_dev::PathGeom as their geometry and MeshHost below as its host side.  COSINE
+//             and LIT, with and without roulette, full width and over a live-lane list.  No ENV mode and no transmission on
+//             meshes yet.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,6 +21,7 @@
 #include <vector>
 
 #include "bounce_dev.h"
+#include "bounce_launch.h"
 #include "bsdfd.h"
 #include "common.h"
 #include "mesh_dev.h"
@@ -202,46 +204,6 @@ __global__ __launch_bounds__(256) void mesh_path_begin_kernel(Scene sc, const fl
     st3(rad + 3 * p, v3(L[0], L[1], L[2]));
 }
 
-// ---- the path kernels on the mesh scene: bounce_dev.h's one bounce and emitter sample with mesh_dev::PathGeom as their geometry ----
-// COSINE and LIT, each with and without roulette, full width.  One template with both modes' arguments; a mode reads its own.
-template <int M, bool RR>
-__global__ __launch_bounds__(256) void mesh_bounce_kernel(Scene sc, mesh_dev::PathGeom g, const float* __restrict__ env, int n_e,
-                                                          int has_env, Step st, PathState ps, SamplerAnswer sa, EmitterSample es,
-                                                          int rr_depth) {
-    bounce_vertex<M, RR, false, false, mesh_dev::PathGeom>(sc, env, EnvDist{}, M == COSINE ? 1 : n_e, M == LIT ? has_env : 1, st, ps, sa,
-                                                           es, rr_depth, Rows{}, g);
-}
-
-__global__ __launch_bounds__(256) void mesh_sample_emitter_kernel(Scene sc, mesh_dev::PathGeom g, Lights lt, Step st,
-                                                                  const float* __restrict__ org, const float* __restrict__ nrm,
-                                                                  const float* __restrict__ wi, const long long* __restrict__ mat,
-                                                                  float* __restrict__ wl, int* __restrict__ lsel,
-                                                                  float* __restrict__ emit) {
-    sample_emitter_vertex<false, mesh_dev::PathGeom>(sc, lt, st, org, nrm, wi, mat, wl, lsel, emit, Rows{}, g);
-}
-
-// The list forms: the same bodies over the lanes of a live-lane list (bounce_dev.h's Rows) — thread t serves lane rows[t], prim
-// is read and written at that lane, and the Philox counters are the lane's, so a listed lane gets its full-width sibling's bits.
-// Kernels of their own: the full-width ones above keep their arguments and their code.  The grid covers the list, so a wave's
-// walks are shared by 64 listed lanes instead of by whatever is left alive among 64 neighbours: fewer waves walk while more than
-// ~5 % of the lanes live, but a short list packs 64 unrelated rays into a wave that lasts as long as the longest of them in every
-// instance, where the full-width launch runs them one to a wave (measured: profiles/mesh_path_compact.json).
-template <int M, bool RR>
-__global__ __launch_bounds__(256) void mesh_bounce_rows_kernel(Scene sc, mesh_dev::PathGeom g, const float* __restrict__ env, int n_e,
-                                                               int has_env, Step st, PathState ps, SamplerAnswer sa,
-                                                               EmitterSample es, int rr_depth, Rows rows) {
-    bounce_vertex<M, RR, true, false, mesh_dev::PathGeom>(sc, env, EnvDist{}, M == COSINE ? 1 : n_e, M == LIT ? has_env : 1, st, ps, sa,
-                                                          es, rr_depth, rows, g);
-}
-
-__global__ __launch_bounds__(256) void mesh_sample_emitter_rows_kernel(Scene sc, mesh_dev::PathGeom g, Lights lt, Step st,
-                                                                       const float* __restrict__ org, const float* __restrict__ nrm,
-                                                                       const float* __restrict__ wi, const long long* __restrict__ mat,
-                                                                       float* __restrict__ wl, int* __restrict__ lsel,
-                                                                       float* __restrict__ emit, Rows rows) {
-    sample_emitter_vertex<true, mesh_dev::PathGeom>(sc, lt, st, org, nrm, wi, mat, wl, lsel, emit, rows, g);
-}
-
 // ---- host side of the scene ----
 template <class T>
 int upload(bsdfd_mesh_scene_ctx* ctx, const T* host, size_t count, const T** dev) {
@@ -371,72 +333,30 @@ int launch_primary(bool path, bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_s
                         beta, rad);
 }
 
-// The emitter sample and the bounce, full width (`list` null) or over a live-lane list (to_rows has checked it against N, behind the
-// null scene).  An empty list is a no-op whatever the pointers, as N == 0 is: it is given to the checks that
-// go by the lane count in N's place.  A list fits one launch where N does, n_rows <= N.
-int launch_sample_emitter(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, const bsdfd_wf_lights* lights, int32_t bounce,
-                          int32_t occlusion, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, const float* org,
-                          const float* nrm, const float* wi, const int64_t* material, float* wl, int32_t* lsel, float* emit,
-                          const int32_t* prim, void* stream, const Rows* list) {
-    if (!scene) return bsdfd_fail_(BSDFD_EINVAL, "null mesh scene");
-    Scene sc;
-    Lights lt;
-    if (int rc = to_scene(wf_scene, 0, 0, 1, sc)) return rc;
-    if (int rc = to_lights(lights, lt)) return rc;
-    if (bounce < 0) return bsdfd_fail_(BSDFD_EINVAL, "bounce must be >= 0");
-    if (N < 0) return bsdfd_fail_(BSDFD_EINVAL, "negative path count");
-    if ((N + 255) / 256 > 0x7fffffffLL) return bsdfd_fail_(BSDFD_EINVAL, "wavefront too large for one launch");
-    if (N == 0 || (list && list->n == 0)) return BSDFD_OK;
-    if (!org || !nrm || !wi || !material || !prim || !wl || !lsel || !emit) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
-    if (int rc = check_materials(scene, sc)) return rc;
-    if (int rc = check_scene(scene)) return rc;
-    // (the emitter sample reads prim and never writes it)
-    const mesh_dev::PathGeom g{scene->d_inst, scene->n_inst, const_cast<int*>(reinterpret_cast<const int*>(prim))};
-    const Step st = make_step(bounce, 0, occlusion, seed, pass, path_offset, N);
-    const long long* mat = reinterpret_cast<const long long*>(material);
-    if (list)
-        return launch_lanes(list->n, mesh_sample_emitter_rows_kernel, stream, sc, g, lt, st, org, nrm, wi, mat, wl,
-                            reinterpret_cast<int*>(lsel), emit, *list);
-    return launch_lanes(N, mesh_sample_emitter_kernel, stream, sc, g, lt, st, org, nrm, wi, mat, wl, reinterpret_cast<int*>(lsel), emit);
-}
-
-int launch_bounce(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, const float* env, int32_t bounce, int32_t last,
-                  int32_t occlusion, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, float* org, float* nrm, float* wi,
-                  float* wl, int64_t* material, float* beta, float* rad, const float* wo, const float* pdf_o, const float* pdf_l,
-                  const float* f_o, const float* f_l, const bsdfd_wf_lights* lights, const int32_t* lsel, const float* emit,
-                  const float* lpdf, const bsdfd_env_dist* dist, int32_t rr_depth, int32_t* prim, void* stream, const Rows* list) {
-    if (!scene) return bsdfd_fail_(BSDFD_EINVAL, "null mesh scene");
-    if (lpdf || dist) return bsdfd_fail_(BSDFD_EINVAL, "importance sampling of the environment is not on meshes yet: lpdf and dist must be NULL");
-    if (rr_depth < 0) return bsdfd_fail_(BSDFD_EINVAL, "rr_depth must be >= 0 (0: no Russian roulette)");
-    const bool nothing = N == 0 || (list && list->n == 0);
-    Scene sc;
-    if (int rc = path_scene(wf_scene, env, nothing ? 0 : N, sc)) return rc;
-    int n = 0, n_e = 1;
-    if (lights)
-        if (int rc = light_counts(lights, n, n_e)) return rc;
-    if (bounce < 0) return bsdfd_fail_(BSDFD_EINVAL, "bounce must be >= 0");
-    if ((f_o == nullptr) != (f_l == nullptr)) return bsdfd_fail_(BSDFD_EINVAL, "f_o and f_l are both NULL or both given");
-    if (nothing) return BSDFD_OK;
-    if (!org || !nrm || !wi || !wl || !material || !prim || !beta || !rad || !wo || !pdf_o || !pdf_l || (lights && (!lsel || !emit)))
-        return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
-    if (int rc = check_materials(scene, sc)) return rc;
-    if (int rc = check_scene(scene)) return rc;
-    const mesh_dev::PathGeom g{scene->d_inst, scene->n_inst, reinterpret_cast<int*>(prim)};
-    const Step st = make_step(bounce, last, occlusion, seed, pass, path_offset, N);
-    const PathState ps{org, nrm, wi, wl, reinterpret_cast<long long*>(material), beta, rad};
-    const SamplerAnswer sa{wo, pdf_o, pdf_l, f_o, f_l};
-    const EmitterSample es{reinterpret_cast<const int*>(lsel), nullptr, emit};
-    if (list) {
-        auto launch = [&](auto kernel) {
-            return launch_lanes(list->n, kernel, stream, sc, g, env, n_e, n_e - n, st, ps, sa, es, (int)rr_depth, *list);
-        };
-        if (lights) return rr_depth ? launch(mesh_bounce_rows_kernel<LIT, true>) : launch(mesh_bounce_rows_kernel<LIT, false>);
-        return rr_depth ? launch(mesh_bounce_rows_kernel<COSINE, true>) : launch(mesh_bounce_rows_kernel<COSINE, false>);
+// The mesh scene as the host side of the path launchers' geometry (bounce_launch.h; SpheresHost is its sibling).  prim is the
+// policy's own array; the emitter sample reads it and never writes it.  A list's grid covers the list, so a wave's walks are
+// shared by 64 listed lanes instead of by whatever is left alive among 64 neighbours: fewer waves walk while more than ~5 % of the
+// lanes live, but a short list packs 64 unrelated rays into a wave that lasts as long as the longest of them in every instance,
+// where the full-width launch runs them one to a wave (measured: profiles/mesh_path_compact.json).
+struct MeshHost {
+    using Geom = mesh_dev::PathGeom;
+    static constexpr bool EMPTY_LIST_FIRST = true;
+    bsdfd_mesh_scene scene;
+    int32_t* prim;
+    int admit(const float* lpdf, const bsdfd_env_dist* dist) const {
+        if (!scene) return bsdfd_fail_(BSDFD_EINVAL, "null mesh scene");
+        if (lpdf || dist)
+            return bsdfd_fail_(BSDFD_EINVAL, "importance sampling of the environment is not on meshes yet: lpdf and dist must be NULL");
+        return BSDFD_OK;
     }
-    auto launch = [&](auto kernel) { return launch_lanes(N, kernel, stream, sc, g, env, n_e, n_e - n, st, ps, sa, es, (int)rr_depth); };
-    if (lights) return rr_depth ? launch(mesh_bounce_kernel<LIT, true>) : launch(mesh_bounce_kernel<LIT, false>);
-    return rr_depth ? launch(mesh_bounce_kernel<COSINE, true>) : launch(mesh_bounce_kernel<COSINE, false>);
-}
+    bool arrays() const { return prim != nullptr; }
+    int geometry(const Scene& sc, Geom& g) const {
+        if (int rc = check_materials(scene, sc)) return rc;
+        if (int rc = check_scene(scene)) return rc;
+        g = Geom{scene->d_inst, scene->n_inst, reinterpret_cast<int*>(prim)};
+        return BSDFD_OK;
+    }
+};
 
 }  // namespace
 
@@ -532,8 +452,8 @@ int bsdfd_mesh_sample_emitter(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_s
                               int32_t occlusion, uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, const float* org,
                               const float* nrm, const float* wi, const int64_t* material, float* wl, int32_t* lsel, float* emit,
                               const int32_t* prim, void* stream) {
-    return launch_sample_emitter(scene, wf_scene, lights, bounce, occlusion, seed, pass, path_offset, N, org, nrm, wi, material, wl, lsel,
-                                 emit, prim, stream, nullptr);
+    return launch_sample_emitter(MeshHost{scene, const_cast<int32_t*>(prim)}, wf_scene, lights, bounce, occlusion, seed, pass, path_offset,
+                                 N, org, nrm, wi, material, wl, lsel, emit, stream, nullptr);
 }
 
 int bsdfd_mesh_bounce(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, const float* env, int32_t bounce, int32_t last,
@@ -542,8 +462,9 @@ int bsdfd_mesh_bounce(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, co
                       const float* pdf_l, const float* f_o, const float* f_l, const bsdfd_wf_lights* lights, const int32_t* lsel,
                       const float* emit, const float* lpdf, const bsdfd_env_dist* dist, int32_t rr_depth, int32_t* prim,
                       void* stream) {
-    return launch_bounce(scene, wf_scene, env, bounce, last, occlusion, seed, pass, path_offset, N, org, nrm, wi, wl, material, beta, rad,
-                         wo, pdf_o, pdf_l, f_o, f_l, lights, lsel, emit, lpdf, dist, rr_depth, prim, stream, nullptr);
+    return launch_bounce(MeshHost{scene, prim}, lights ? LIT : COSINE, (int)rr_depth, wf_scene, env, bounce, last, occlusion, seed, pass,
+                         path_offset, N, org, nrm, wi, wl, material, beta, rad, wo, pdf_o, pdf_l, f_o, f_l, lights, lsel, emit, lpdf, dist,
+                         stream);
 }
 
 int bsdfd_mesh_sample_emitter_rows(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, const bsdfd_wf_lights* lights,
@@ -554,8 +475,8 @@ int bsdfd_mesh_sample_emitter_rows(bsdfd_mesh_scene scene, const bsdfd_wf_scene*
     if (!scene) return bsdfd_fail_(BSDFD_EINVAL, "null mesh scene");
     Rows list;
     if (int rc = to_rows(rows, n_rows, N, list)) return rc;
-    return launch_sample_emitter(scene, wf_scene, lights, bounce, occlusion, seed, pass, path_offset, N, org, nrm, wi, material, wl, lsel,
-                                 emit, prim, stream, &list);
+    return launch_sample_emitter(MeshHost{scene, const_cast<int32_t*>(prim)}, wf_scene, lights, bounce, occlusion, seed, pass, path_offset,
+                                 N, org, nrm, wi, material, wl, lsel, emit, stream, &list);
 }
 
 int bsdfd_mesh_bounce_rows(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scene, const float* env, int32_t bounce, int32_t last,
@@ -567,8 +488,9 @@ int bsdfd_mesh_bounce_rows(bsdfd_mesh_scene scene, const bsdfd_wf_scene* wf_scen
     if (!scene) return bsdfd_fail_(BSDFD_EINVAL, "null mesh scene");
     Rows list;
     if (int rc = to_rows(rows, n_rows, N, list)) return rc;
-    return launch_bounce(scene, wf_scene, env, bounce, last, occlusion, seed, pass, path_offset, N, org, nrm, wi, wl, material, beta, rad,
-                         wo, pdf_o, pdf_l, f_o, f_l, lights, lsel, emit, lpdf, dist, rr_depth, prim, stream, &list);
+    return launch_bounce(MeshHost{scene, prim}, lights ? LIT : COSINE, (int)rr_depth, wf_scene, env, bounce, last, occlusion, seed, pass,
+                         path_offset, N, org, nrm, wi, wl, material, beta, rad, wo, pdf_o, pdf_l, f_o, f_l, lights, lsel, emit, lpdf, dist,
+                         stream, &list);
 }
 
 }  // extern "C"

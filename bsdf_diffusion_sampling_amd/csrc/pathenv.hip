@@ -45,15 +45,15 @@ __global__ __launch_bounds__(256) void env_pdf_kernel(EnvDist e, long long n, co
     pdf[q] = env_dev::env_pdf(e, ld3(dir + 3 * q));
 }
 
-// `list`: nothing (every lane of the wavefront), or one Rows (the list form: the lanes of a live-lane list)
-template <class... List>
+// LIST: the lanes of `rows` (the list form) instead of every lane of the wavefront
+template <bool LIST>
 __global__ __launch_bounds__(256) void sample_env_kernel(Scene sc, const float* __restrict__ env, EnvDist e, int n_e, Step st,
                                                          const float* __restrict__ org, const float* __restrict__ nrm,
                                                          const float* __restrict__ wi, const long long* __restrict__ mat,
                                                          const int* __restrict__ lsel, float* __restrict__ wl,
-                                                         float* __restrict__ lpdf, float* __restrict__ emit, List... list) {
+                                                         float* __restrict__ lpdf, float* __restrict__ emit, Rows rows) {
     long long p, m;
-    if (!live_lane<sizeof...(List) != 0>(sc, st.n, mat, p, m, list...)) return;
+    if (!live_lane<LIST>(sc, st.n, mat, p, m, rows)) return;
     if (lsel && lsel[p] != -1) return;   // a point light was picked: sample_emitter's wl and emit stand
     unsigned u[4];
     tagged_draw(st.seed, st.pass, st.path_offset, p, 0x456E766Du /* "Envm" */, st.bounce, u);
@@ -93,13 +93,13 @@ int launch_sample_env(const bsdfd_wf_scene* scene, const float* env, const bsdfd
     if (N == 0) return BSDFD_OK;
     if (!org || !nrm || !wi || !material || !wl || !lpdf || !emit) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
     const Step st = make_step(bounce, 0, occlusion, seed, pass, path_offset, N);
-    if (list) {
-        if (list->n == 0) return BSDFD_OK;
-        return launch_lanes(list->n, sample_env_kernel<Rows>, stream, sc, env, e, (int)n_e, st, org, nrm, wi,
-                            reinterpret_cast<const long long*>(material), reinterpret_cast<const int*>(lsel), wl, lpdf, emit, *list);
-    }
-    return launch_lanes(N, sample_env_kernel<>, stream, sc, env, e, (int)n_e, st, org, nrm, wi, reinterpret_cast<const long long*>(material),
-                        reinterpret_cast<const int*>(lsel), wl, lpdf, emit);
+    if (list && list->n == 0) return BSDFD_OK;
+    const long long* mat = reinterpret_cast<const long long*>(material);
+    const int* sel = reinterpret_cast<const int*>(lsel);
+    return list ? launch_lanes(list->n, sample_env_kernel<true>, stream, sc, env, e, (int)n_e, st, org, nrm, wi, mat, sel, wl, lpdf, emit,
+                               *list)
+                : launch_lanes(N, sample_env_kernel<false>, stream, sc, env, e, (int)n_e, st, org, nrm, wi, mat, sel, wl, lpdf, emit,
+                               Rows{});
 }
 
 }  // namespace

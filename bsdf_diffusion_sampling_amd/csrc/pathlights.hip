@@ -11,7 +11,8 @@
 //                    and emit = n_e I_k / d^2, 0 below the horizon or (occlusion) behind another surface.  Point k on the floor:
 //                    wl stays (the path continues along it), emit = the whole term n_e (refl / pi) cos I_k / d^2.
 //
-// The kernel's body is bounce_dev.h's sample_emitter_vertex, which mesh.hip instantiates once more on the mesh scene.
+// The kernel's body is bounce_dev.h's sample_emitter_vertex; the kernel template and the launcher are bounce_launch.h's, which
+// mesh.hip instantiates once more on the mesh scene.  These are the entry points on the analytic spheres.
 // The bounce that reads lsel and emit is bounce.hip's LIT kernel.  bsdfd_wf_sample_emitter_rows is the same kernel over the lanes of
 // a live-lane list (bounce_dev.h's Rows), for the deep bounces of a wavefront that has mostly ended.
 // The lights travel by value in the kernel arguments like the scene; the picked light is selected by a wave-uniform loop
@@ -22,55 +23,19 @@
 #include <cmath>
 #include <cstdint>
 
-#include "bounce_dev.h"
+#include "bounce_launch.h"
 #include "bsdfd.h"
 #include "common.h"
 
-namespace {
-
 using namespace bounce_dev;
-
-// `list`: nothing (every lane of the wavefront), or one Rows (the list form: the lanes of a live-lane list)
-template <class... List>
-__global__ __launch_bounds__(256) void sample_emitter_kernel(Scene sc, Lights lt, Step st, const float* __restrict__ org,
-                                                             const float* __restrict__ nrm, const float* __restrict__ wi,
-                                                             const long long* __restrict__ mat, float* __restrict__ wl,
-                                                             int* __restrict__ lsel, float* __restrict__ emit, List... list) {
-    sample_emitter_vertex<sizeof...(List) != 0>(sc, lt, st, org, nrm, wi, mat, wl, lsel, emit, list...);
-}
-
-// the checks of both entry points and the launch: over all N lanes, or (`list`) over the lanes of a list
-int launch_sample_emitter(const bsdfd_wf_scene* scene, const bsdfd_wf_lights* lights, int32_t bounce, int32_t occlusion, uint64_t seed,
-                          uint64_t pass, uint64_t path_offset, int64_t N, const float* org, const float* nrm, const float* wi,
-                          const int64_t* material, float* wl, int32_t* lsel, float* emit, void* stream, const Rows* list) {
-    Scene sc;
-    Lights lt;
-    if (int rc = to_scene(scene, 0, 0, 1, sc)) return rc;
-    if (int rc = to_lights(lights, lt)) return rc;
-    if (bounce < 0) return bsdfd_fail_(BSDFD_EINVAL, "bounce must be >= 0");
-    if (N < 0) return bsdfd_fail_(BSDFD_EINVAL, "negative path count");
-    if ((N + 255) / 256 > 0x7fffffffLL) return bsdfd_fail_(BSDFD_EINVAL, "wavefront too large for one launch");
-    if (N == 0) return BSDFD_OK;
-    if (!org || !nrm || !wi || !material || !wl || !lsel || !emit) return bsdfd_fail_(BSDFD_EINVAL, "null pointer");
-    const Step st = make_step(bounce, 0, occlusion, seed, pass, path_offset, N);
-    if (list) {
-        if (list->n == 0) return BSDFD_OK;
-        return launch_lanes(list->n, sample_emitter_kernel<Rows>, stream, sc, lt, st, org, nrm, wi,
-                            reinterpret_cast<const long long*>(material), wl, reinterpret_cast<int*>(lsel), emit, *list);
-    }
-    return launch_lanes(N, sample_emitter_kernel<>, stream, sc, lt, st, org, nrm, wi, reinterpret_cast<const long long*>(material), wl,
-                        reinterpret_cast<int*>(lsel), emit);
-}
-
-}  // namespace
 
 extern "C" {
 
 int bsdfd_wf_sample_emitter(const bsdfd_wf_scene* scene, const bsdfd_wf_lights* lights, int32_t bounce, int32_t occlusion,
                             uint64_t seed, uint64_t pass, uint64_t path_offset, int64_t N, const float* org, const float* nrm,
                             const float* wi, const int64_t* material, float* wl, int32_t* lsel, float* emit, void* stream) {
-    return launch_sample_emitter(scene, lights, bounce, occlusion, seed, pass, path_offset, N, org, nrm, wi, material, wl, lsel, emit,
-                                 stream, nullptr);
+    return launch_sample_emitter(SpheresHost{}, scene, lights, bounce, occlusion, seed, pass, path_offset, N, org, nrm, wi, material, wl,
+                                 lsel, emit, stream, nullptr);
 }
 
 int bsdfd_wf_sample_emitter_rows(const bsdfd_wf_scene* scene, const bsdfd_wf_lights* lights, int32_t bounce, int32_t occlusion,
@@ -79,8 +44,8 @@ int bsdfd_wf_sample_emitter_rows(const bsdfd_wf_scene* scene, const bsdfd_wf_lig
                                  const int64_t* rows, int64_t n_rows, void* stream) {
     Rows list;
     if (int rc = to_rows(rows, n_rows, N, list)) return rc;
-    return launch_sample_emitter(scene, lights, bounce, occlusion, seed, pass, path_offset, N, org, nrm, wi, material, wl, lsel, emit,
-                                 stream, &list);
+    return launch_sample_emitter(SpheresHost{}, scene, lights, bounce, occlusion, seed, pass, path_offset, N, org, nrm, wi, material, wl,
+                                 lsel, emit, stream, &list);
 }
 
 }  // extern "C"

@@ -28,7 +28,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .pathtrace import PathArrayRenderer
+from .pathtrace import PathArrayRenderer, _Geometry, _p
 from .wavefront import ArrayRenderer
 
 FLAG_NORMALS, FLAG_UV, FLAG_COLORS, FLAG_DOUBLE = 0x1, 0x2, 0x8, 0x2000   # the flags word of a serialized shape
@@ -282,9 +282,8 @@ class MeshScene:
         t = torch.empty(n, dtype=torch.float32, device=org.device)
         prim = torch.empty((n, 2), dtype=torch.int32, device=org.device)
         bary = torch.empty((n, 2), dtype=torch.float32, device=org.device)
-        p = lambda a: None if a is None else C.c_void_p(a.data_ptr())
         with torch.cuda.device(org.device):
-            _lib.check(_lib.lib().bsdfd_mesh_intersect(self.handle(), n, p(org), p(dir), p(tmax), p(skip), p(t), p(prim), p(bary),
+            _lib.check(_lib.lib().bsdfd_mesh_intersect(self.handle(), n, _p(org), _p(dir), _p(tmax), _p(skip), _p(t), _p(prim), _p(bary),
                                                        C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return t, prim, bary
 
@@ -293,9 +292,8 @@ class MeshScene:
         import torch
         n = self._rays(org, dir, tmax, skip)
         out = torch.empty(n, dtype=torch.uint8, device=org.device)
-        p = lambda a: None if a is None else C.c_void_p(a.data_ptr())
         with torch.cuda.device(org.device):
-            _lib.check(_lib.lib().bsdfd_mesh_occluded(self.handle(), n, p(org), p(dir), p(tmax), p(skip), p(out),
+            _lib.check(_lib.lib().bsdfd_mesh_occluded(self.handle(), n, _p(org), _p(dir), _p(tmax), _p(skip), _p(out),
                                                       C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return out
 
@@ -303,12 +301,11 @@ class MeshScene:
         """``bsdfd_wf_primary`` on this scene: fills b["wi"], b["wl"], b["nrm"], b["dir"] ([N,3] fp32) and b["mat"] (int64 [N], if
         present) for the camera, film and material count (1 + n_extra_spheres) of the ``_lib.WfScene``."""
         import torch
-        p = lambda a: C.c_void_p(a.data_ptr())
         dev = b["wi"].device
         with torch.cuda.device(dev):
             _lib.check(_lib.lib().bsdfd_mesh_primary(self.handle(), C.byref(wf_scene), row_begin, row_end, spp, seed, pass_idx,
-                                                     p(b["wi"]), p(b["wl"]), p(b["nrm"]), p(b["dir"]),
-                                                     p(b["mat"]) if "mat" in b else None,
+                                                     _p(b["wi"]), _p(b["wl"]), _p(b["nrm"]), _p(b["dir"]),
+                                                     _p(b["mat"]) if "mat" in b else None,
                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         torch.autograd.graph.increment_version([b["wi"], b["wl"], b["nrm"], b["dir"]])
         return b
@@ -489,13 +486,15 @@ class MeshPathArrayRenderer(PathArrayRenderer):
 
     * ``primary`` calls ``bsdfd_mesh_path_primary``, which writes the first vertex of the path as well (``org``, ``prim``, ``beta``,
       ``rad``), so ``path_begin`` has nothing left to do;
-    * ``sample_emitter`` and ``bounce`` call ``bsdfd_mesh_sample_emitter`` and ``bsdfd_mesh_bounce``;
+    * ``sample_emitter`` and ``bounce`` are the base class's methods; ``_geometry`` sends them to ``bsdfd_mesh_sample_emitter`` and
+      ``bsdfd_mesh_bounce`` with the scene's handle in front and ``prim`` behind;
     * the path state has one more array, ``prim`` int32 [N,2]: the (instance, triangle) a vertex lies on, which its rays skip.
 
     ``render_pass``, the bucketing, the sampler launches, both ground-truth tables, ``resolve`` and ``stats`` are inherited, and
     ``max_depth``, ``occlusion``, ``lights``, ``rr_depth`` and ``DEPTH_CAP`` mean what they mean there.  ``env_sampling`` other than
     ``"cosine"`` and ``transmission=True`` are refused: not on meshes yet.  ``sample_emitter`` and ``bounce`` take a live-lane list
-    (``rows=``: ``bsdfd_mesh_sample_emitter_rows`` / ``bsdfd_mesh_bounce_rows``); the renderer that runs its deep bounces on one is
+    (``rows=``: ``bsdfd_mesh_sample_emitter_rows`` / ``bsdfd_mesh_bounce_rows``; an empty list returns without a launch, and an
+    ``env_dist`` is a ``ValueError``); the renderer that runs its deep bounces on one is
     ``CompactMeshPathArrayRenderer``, and ``compact=True`` here is refused and points there.  Limits: the module docstring's.
     Parity-unpinned against Mitsuba."""
 
@@ -531,11 +530,10 @@ class MeshPathArrayRenderer(PathArrayRenderer):
         import torch
         n = (row_end - row_begin) * self.camera.width * spp
         b = out or self._buffers(n)
-        p = lambda a: C.c_void_p(a.data_ptr())
         with torch.cuda.device(self.device):
             _lib.check(_lib.lib().bsdfd_mesh_path_primary(
-                self.mesh_scene.handle(), C.byref(self.scene), row_begin, row_end, spp, seed, pass_idx, p(b["wi"]), p(b["wl"]),
-                p(b["nrm"]), p(b["dir"]), p(b["mat"]), p(self.env), p(b["org"]), p(b["prim"]), p(b["beta"]), p(b["rad"]),
+                self.mesh_scene.handle(), C.byref(self.scene), row_begin, row_end, spp, seed, pass_idx, _p(b["wi"]), _p(b["wl"]),
+                _p(b["nrm"]), _p(b["dir"]), _p(b["mat"]), _p(self.env), _p(b["org"]), _p(b["prim"]), _p(b["beta"]), _p(b["rad"]),
                 self._stream()))
         torch.autograd.graph.increment_version([b[k] for k in ("wi", "wl", "nrm", "dir", "mat", "org", "prim", "beta", "rad")])
         return b
@@ -543,51 +541,12 @@ class MeshPathArrayRenderer(PathArrayRenderer):
     def path_begin(self, b):
         """Nothing: ``primary`` has written ``org``, ``prim``, ``beta`` and ``rad`` (the hit's t is known there and nowhere else)."""
 
-    def sample_emitter(self, b, bounce: int, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
-                       lights: Optional[_lib.WfLights] = None, rows=None):
-        """``PathArrayRenderer.sample_emitter`` with the shadow rays cast in the mesh scene (``bsdfd_mesh_sample_emitter``).  ``rows``
-        (int64 [n_rows], distinct lanes): of the listed vertices only (``bsdfd_mesh_sample_emitter_rows``); an empty list returns
-        without a launch."""
-        import torch
-        listed = () if rows is None else self._list(rows, b)
-        if listed and listed[1] == 0:
-            return
-        occlusion = self.occlusion if occlusion is None else occlusion
-        p = lambda a: C.c_void_p(a.data_ptr())
-        with torch.cuda.device(self.device):
-            fn = _lib.lib().bsdfd_mesh_sample_emitter_rows if listed else _lib.lib().bsdfd_mesh_sample_emitter
-            _lib.check(fn(
-                self.mesh_scene.handle(), C.byref(self.scene), C.byref(self.lights if lights is None else lights), bounce,
-                int(bool(occlusion)), seed, pass_idx, path_offset, b["mat"].shape[0], p(b["org"]), p(b["nrm"]), p(b["wi"]),
-                p(b["mat"]), p(b["wl"]), p(b["lsel"]), p(b["emit"]), p(b["prim"]), *listed, self._stream()))
-        torch.autograd.graph.increment_version([b["wl"], b["lsel"], b["emit"]])
-
-    def bounce(self, b, bounce: int, last: bool, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
-               lights: Optional[_lib.WfLights] = None, env_dist=None, rr_depth: Optional[int] = None, rows=None):
-        """``PathArrayRenderer.bounce`` on the mesh scene (``bsdfd_mesh_bounce``): the cosine light strategy without ``lights``, one
-        emitter sample per vertex with them, Russian roulette with ``rr_depth``.  ``rows`` (int64 [n_rows], distinct lanes): the
-        listed vertices only (``bsdfd_mesh_bounce_rows``), ``prim`` included; an empty list returns without a launch."""
-        import torch
+    def _geometry(self, b, env_dist=None) -> _Geometry:
+        """The mesh scene's part of the two stages: its handle in front, ``prim`` behind — the shadow rays and the continuation rays
+        skip it, and the bounce moves it on with the vertex.  An empty list returns without a launch."""
         if env_dist is not None:
             raise ValueError("env_dist: the environment's importance sampling is not on meshes yet")
-        listed = () if rows is None else self._list(rows, b)
-        if listed and listed[1] == 0:
-            return
-        occlusion = self.occlusion if occlusion is None else occlusion
-        lights = self.lights if lights is None else lights
-        rr_depth = self.rr_depth if rr_depth is None else rr_depth
-        p = lambda a: None if a is None else C.c_void_p(a.data_ptr())
-        lit = lights is not None
-        with torch.cuda.device(self.device):
-            fn = _lib.lib().bsdfd_mesh_bounce_rows if listed else _lib.lib().bsdfd_mesh_bounce
-            _lib.check(fn(
-                self.mesh_scene.handle(), C.byref(self.scene), p(self.env), bounce, int(bool(last)), int(bool(occlusion)), seed,
-                pass_idx, path_offset, b["mat"].shape[0], p(b["org"]), p(b["nrm"]), p(b["wi"]), p(b["wl"]), p(b["mat"]), p(b["beta"]),
-                p(b["rad"]), p(b["wo"]), p(b["pdf_o"]), p(b["pdf_l"]), p(b.get("f_o")), p(b.get("f_l")),
-                C.byref(lights) if lit else None, p(b["lsel"]) if lit else None, p(b["emit"]) if lit else None, None, None,
-                int(rr_depth or 0), p(b["prim"]), *listed, self._stream()))
-        # written through raw pointers: tell torch (the plugin cores key their per-query context cache on wi._version)
-        torch.autograd.graph.increment_version([b["wi"], b["wl"], b["nrm"], b["org"], b["mat"], b["beta"], b["rad"], b["prim"]])
+        return _Geometry("bsdfd_mesh_", True, [self.mesh_scene.handle()], [_p(b["prim"])], [b["prim"]])
 
 
 class CompactMeshPathArrayRenderer(MeshPathArrayRenderer):

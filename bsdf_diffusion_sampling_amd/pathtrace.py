@@ -120,6 +120,13 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+# What the geometry adds to the two stages that ask it something, ``sample_emitter`` and ``bounce`` (``PathArrayRenderer._geometry``):
+# ``prefix`` of the entry points' names; ``one_form``: the family is one full-argument entry point per stage (the bounce: every emitter
+# argument and ``rr_depth``) and its ``_rows`` form, for which an empty list is nothing to call — not the spheres' per-mode forms;
+# the arguments in ``front`` of the shared list and ``behind`` it; the arrays the bounce has ``written`` besides the path state.
+_Geometry = namedtuple("_Geometry", "prefix one_form front behind written")
+
+
 def wf_lights(lights: Sequence[PointLight], has_env: bool) -> _lib.WfLights:
     """The ``bsdfd_wf_lights`` of 1..8 point lights; ``ValueError`` for anything the kernels should not see."""
     lights = list(lights)
@@ -328,19 +335,24 @@ class PathArrayRenderer(ArrayRenderer):
                                                       _p(b["nrm"]), _p(b["mat"]), _p(b["org"]), _p(b["beta"]), _p(b["rad"]),
                                                       self._stream()))
 
+    def _geometry(self, b, env_dist=None) -> _Geometry:
+        """The geometry's part of ``sample_emitter`` and ``bounce`` over ``b``; here: the analytic spheres, which travel in the scene."""
+        return _Geometry("bsdfd_wf_", False, [], [], [])
+
     def sample_emitter(self, b, bounce: int, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
                        lights: Optional[_lib.WfLights] = None, rows: Optional[torch.Tensor] = None):
         """The emitter sample of the vertices in ``b``: ``lsel``, ``emit``, and ``wl`` towards a picked point light.  ``rows``
         (int64 [n_rows], distinct lanes): of the listed vertices only (``bsdfd_wf_sample_emitter_rows``)."""
+        geo = self._geometry(b)
+        listed = () if rows is None else self._list(rows, b)
+        if geo.one_form and listed and listed[1] == 0:
+            return
         occlusion = self.occlusion if occlusion is None else occlusion
         with torch.cuda.device(self.device):
-            args = [C.byref(self.scene), C.byref(self.lights if lights is None else lights), bounce, int(bool(occlusion)), seed,
-                    pass_idx, path_offset, b["mat"].shape[0], _p(b["org"]), _p(b["nrm"]), _p(b["wi"]), _p(b["mat"]), _p(b["wl"]),
-                    _p(b["lsel"]), _p(b["emit"])]
-            if rows is None:
-                _lib.check(_lib.lib().bsdfd_wf_sample_emitter(*args, self._stream()))
-            else:
-                _lib.check(_lib.lib().bsdfd_wf_sample_emitter_rows(*args, *self._list(rows, b), self._stream()))
+            fn = getattr(_lib.lib(), geo.prefix + ("sample_emitter_rows" if listed else "sample_emitter"))
+            _lib.check(fn(*geo.front, C.byref(self.scene), C.byref(self.lights if lights is None else lights), bounce,
+                          int(bool(occlusion)), seed, pass_idx, path_offset, b["mat"].shape[0], _p(b["org"]), _p(b["nrm"]), _p(b["wi"]),
+                          _p(b["mat"]), _p(b["wl"]), _p(b["lsel"]), _p(b["emit"]), *geo.behind, *listed, self._stream()))
         torch.autograd.graph.increment_version([b["wl"], b["lsel"], b["emit"]])
 
     def sample_env(self, b, bounce: int, seed: int, pass_idx: int, path_offset: int, occlusion: Optional[bool] = None,
@@ -370,39 +382,44 @@ class PathArrayRenderer(ArrayRenderer):
         ``bsdfd_wf_bounce_rr``, which plays Russian roulette on the paths that would continue once ``bounce + 1 >= rr_depth``.
         ``rows`` (int64 [n_rows], distinct lanes): the listed vertices only, through ``bsdfd_wf_bounce_rows`` in every mode.
         With ``self.transmission`` every mode, with or without ``rows``, goes through ``bsdfd_wf_bounce_transmit``, which follows a
-        BSDF sample below the surface into the ball (it needs ``f_o``)."""
+        BSDF sample below the surface into the ball (it needs ``f_o``).  Other geometry (``_geometry``: a subclass's) has one entry
+        point for all of these and its ``_rows`` form."""
         occlusion = self.occlusion if occlusion is None else occlusion
         lights = self.lights if lights is None else lights
         env_dist = self.env_dist if env_dist is None else env_dist
         rr_depth = self.rr_depth if rr_depth is None else rr_depth
+        geo = self._geometry(b, env_dist)
+        listed = () if rows is None else self._list(rows, b)
+        if listed and listed[1] == 0 and (geo.one_form or self.transmission):
+            return   # an empty list serves no lane (bsdfd_wf_bounce_transmit reads rows = NULL, n_rows = 0 as "every lane")
         with torch.cuda.device(self.device):
             args = [
                 C.byref(self.scene), _p(self.env), bounce, int(bool(last)), int(bool(occlusion)), seed, pass_idx, path_offset,
                 b["mat"].shape[0], _p(b["org"]), _p(b["nrm"]), _p(b["wi"]), _p(b["wl"]), _p(b["mat"]), _p(b["beta"]), _p(b["rad"]),
                 _p(b["wo"]), _p(b["pdf_o"]), _p(b["pdf_l"]), _p(b.get("f_o")), _p(b.get("f_l"))]
             # the emitter tail (lights, lsel, emit, lpdf, dist), None where the mode has none: bounce takes none of it, bounce_lit
-            # the first three, bounce_env all five, bounce_rr all five + rr_depth
+            # the first three, bounce_env all five; bounce_rr, bounce_rows, bounce_transmit and a one-form family all five + rr_depth
             lit, env = lights is not None, env_dist is not None
             tail = [C.byref(lights) if lit else None, _p(b["lsel"]) if lit else None, _p(b["emit"]) if lit or env else None,
                     _p(b["lpdf"]) if env else None, C.byref(env_dist.struct(self.device)) if env else None]
+            full = args + tail + [int(rr_depth or 0)]
             if self.transmission:
-                if rows is not None and self._list(rows, b)[1] == 0:
-                    return   # an empty list serves no lane (the entry point reads rows = NULL, n_rows = 0 as "every lane")
-                fn = _lib.lib().bsdfd_wf_bounce_transmit
-                args = args + tail + [int(rr_depth or 0), *((None, 0) if rows is None else self._list(rows, b))]
-            elif rows is not None:
-                fn, args = _lib.lib().bsdfd_wf_bounce_rows, args + tail + [int(rr_depth or 0), *self._list(rows, b)]
+                name, args, listed = "bounce_transmit", full, listed or (None, 0)
+            elif listed:
+                name, args = "bounce_rows", full
+            elif geo.one_form:
+                name, args = "bounce", full
             elif rr_depth is not None:
-                fn, args = _lib.lib().bsdfd_wf_bounce_rr, args + tail + [int(rr_depth)]
+                name, args = "bounce_rr", full
             elif env:
-                fn, args = _lib.lib().bsdfd_wf_bounce_env, args + tail
+                name, args = "bounce_env", args + tail
             elif lit:
-                fn, args = _lib.lib().bsdfd_wf_bounce_lit, args + tail[:3]
+                name, args = "bounce_lit", args + tail[:3]
             else:
-                fn = _lib.lib().bsdfd_wf_bounce
-            _lib.check(fn(*args, self._stream()))
+                name = "bounce"
+            _lib.check(getattr(_lib.lib(), geo.prefix + name)(*geo.front, *args, *geo.behind, *listed, self._stream()))
         # written through raw pointers: tell torch (the plugin cores key their per-query context cache on wi._version)
-        torch.autograd.graph.increment_version([b["wi"], b["wl"], b["nrm"], b["org"], b["mat"], b["beta"], b["rad"]])
+        torch.autograd.graph.increment_version([b["wi"], b["wl"], b["nrm"], b["org"], b["mat"], b["beta"], b["rad"]] + geo.written)
 
     def sample_inside(self, b, bounce: int, seed: int, pass_idx: int, path_offset: int, rows: Optional[torch.Tensor] = None):
         """The sampler's answer for the vertices inside a ball (``wi.z < 0``): ``wo``, ``pdf_o``, ``pdf_l`` of those lanes from the

@@ -10,7 +10,9 @@ What is held to what (kernels):
 * continuing rows: ``org`` to 4 et of t (et, eb: mesh_ref.fp32_restatement_error on the same rays), ``nrm`` / ``wi`` to
   tests/test_gpu_mesh.py's ``tol_n`` / ``4 tol_n``, diffuse reflectances exact, ``wl`` 2e-6, ``beta`` 2e-5;
 * ``rad`` (and the emitter sample's ``emit``) to the sphere tests' ``_shade_bound``: p99.9 < 2e-4, max < 5e-3;
-* ended rows keep every byte, ``prim`` included; nothing behind lane N is written.
+* ended rows keep every byte, ``prim`` included; nothing behind lane N is written;
+* across commits: the full-width entry points reproduce tests/golden/mesh_path_before_unify.npz bit for bit, and their ``_rows``
+  forms write those bits on the listed lanes and nothing else (section 3b).
 Every figure is printed before it is asserted."""
 import ctypes as C
 import math
@@ -75,15 +77,19 @@ def wf_scene(cam, n_materials, albedo=(1.0, 1.0, 1.0), env_shape=(8, 16)):
 
 
 # ---- the kernel scene: made once, with every reference the tests share ----
-@pytest.fixture(scope="module")
-def kernel_case():
+def make_kernel_case(n=4096):
     geom = MB.kernel_scene(M)
-    v = MB.synthetic_vertices(geom)
+    v = MB.synthetic_vertices(geom, n=n, seed=7)
     env = R.synthetic_env()
     lights = LR.make_lights([(1.0, 4.0, 2.0), (-2.5, 3.0, -1.0)], [40.0, (30.0, 20.0, 10.0)])
     cam = WF.Camera(origin=(0.0, 1.0, 8.0), width=8, height=8)
     return dict(geom=geom, v=v, env=env, lights=lights, scene=M.MeshScene(geom["meshes"], geom["instances"]),
                 sc=wf_scene(cam, geom["n_materials"], geom["albedo"], env.shape[:2]), emitter={})
+
+
+@pytest.fixture(scope="module")
+def kernel_case():
+    return make_kernel_case()
 
 
 def _emitter(kc, occlusion, has_env):
@@ -109,20 +115,26 @@ def _guarded(a, n_rows):
     return torch.cat([t[:n_rows], pad]).contiguous()
 
 
-def run_bounce(kc, v, n, mode, last, occlusion, rr_depth, lsel=None, emit=None, has_env=1):
-    """One bsdfd_mesh_bounce call over the first n rows of ``v`` -> the eight state arrays (n + GUARD rows) as numpy."""
+def run_bounce(kc, v, n, mode, last, occlusion, rr_depth, lsel=None, emit=None, has_env=1, rows=None, bounce=BOUNCE):
+    """One bsdfd_mesh_bounce call over the first n rows of ``v`` -> the eight state arrays (n + GUARD rows) as numpy.  ``rows`` (a
+    host int64 array): bsdfd_mesh_bounce_rows over that list instead."""
     b = {k: _guarded(v[k], n) for k in MB.STATE if v.get(k) is not None}
     env = torch.from_numpy(kc["env"]).to(dev())
     lit = mode == "lit"
     if lit:
         lights = _device_lights(kc["lights"], has_env)
         b["lsel"], b["emit"] = _guarded(lsel, n), _guarded(emit, n)
+    fn, listed = _lib.lib().bsdfd_mesh_bounce, ()
+    if rows is not None:
+        rows = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)).to(dev())
+        fn, listed = _lib.lib().bsdfd_mesh_bounce_rows, (_p(rows), rows.shape[0])
     with torch.cuda.device(dev()):
-        _lib.check(_lib.lib().bsdfd_mesh_bounce(
-            kc["scene"].handle(), C.byref(kc["sc"]), _p(env), BOUNCE, int(last), int(occlusion), SEED, PASS, OFFSET, n,
+        _lib.check(fn(
+            kc["scene"].handle(), C.byref(kc["sc"]), _p(env), bounce, int(last), int(occlusion), SEED, PASS, OFFSET, n,
             _p(b["org"]), _p(b["nrm"]), _p(b["wi"]), _p(b["wl"]), _p(b["material"]), _p(b["beta"]), _p(b["rad"]), _p(b["wo"]),
             _p(b["pdf_o"]), _p(b["pdf_l"]), _p(b.get("f_o")), _p(b.get("f_l")), C.byref(lights) if lit else None,
-            _p(b["lsel"]) if lit else None, _p(b["emit"]) if lit else None, None, None, int(rr_depth or 0), _p(b["prim"]), None))
+            _p(b["lsel"]) if lit else None, _p(b["emit"]) if lit else None, None, None, int(rr_depth or 0), _p(b["prim"]),
+            *listed, None))
     torch.cuda.synchronize()
     return {k: b[k].cpu().numpy() for k in KEYS}
 
@@ -277,6 +289,104 @@ def test_mesh_sample_emitter_matches_reference(kernel_case, occlusion, has_env):
     print(f"  wl: max error {e_wl:.2e}; emit: p99.9 {p999:.2e} max {worst:.2e}")
     assert e_wl < 2e-5
     assert np.isfinite(emit[live]).all() and p999 < 2e-4 and worst < 5e-3
+
+
+# ---- 3b. the kernels' bits across commits ----
+# tests/golden/mesh_path_before_unify.npz (tests/golden/make_mesh_path_golden.py, run on the commit before the sphere and mesh
+# kernels got one __global__ template and one launcher per stage): 1024 synthetic vertices on the kernel scene, ONE call each.
+#   emitter_{wl,lsel,emit}       : bsdfd_mesh_sample_emitter (occlusion = 1, has_env = 1) over lsel / emit filled with the sentinels
+#   {cosine,lit}_rr{0,2}_{KEYS}  : bsdfd_mesh_bounce (occlusion = 1, last = 0, bounce = 1) with rr_depth 0 and 2 — at bounce 1 the
+#                                  roulette of rr_depth = 2 decides; LIT reads the recorded emitter sample (wl, lsel, emit)
+RECORDING = os.path.join(GOLDEN, "mesh_path_before_unify.npz")
+RECORDED_N, RECORDED_BOUNCE = 1024, 1
+RECORDED_CASES = [(mode, rr) for mode in ("cosine", "lit") for rr in (0, 2)]
+
+
+def run_sample_emitter(kc, v, n, occlusion, has_env, rows=None, bounce=BOUNCE):
+    """One bsdfd_mesh_sample_emitter call over the first n rows of ``v``, lsel and emit filled with the sentinels -> wl, lsel, emit
+    (n + GUARD rows) as numpy.  ``rows`` (a host int64 array): bsdfd_mesh_sample_emitter_rows over that list instead."""
+    b = {k: _guarded(v[k], n) for k in ("org", "nrm", "wi", "material", "prim", "wl")}
+    b["lsel"] = torch.full((n + GUARD,), LSEL_SENTINEL, dtype=torch.int32, device=dev())
+    b["emit"] = torch.full((n + GUARD, 3), EMIT_SENTINEL, dtype=torch.float32, device=dev())
+    lights = _device_lights(kc["lights"], has_env)
+    fn, listed = _lib.lib().bsdfd_mesh_sample_emitter, ()
+    if rows is not None:
+        rows = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64)).to(dev())
+        fn, listed = _lib.lib().bsdfd_mesh_sample_emitter_rows, (_p(rows), rows.shape[0])
+    with torch.cuda.device(dev()):
+        _lib.check(fn(kc["scene"].handle(), C.byref(kc["sc"]), C.byref(lights), bounce, occlusion, SEED, PASS, OFFSET, n, _p(b["org"]),
+                      _p(b["nrm"]), _p(b["wi"]), _p(b["material"]), _p(b["wl"]), _p(b["lsel"]), _p(b["emit"]), _p(b["prim"]), *listed,
+                      None))
+    torch.cuda.synchronize()
+    return {k: b[k].cpu().numpy() for k in ("wl", "lsel", "emit")}
+
+
+def recorded_emitter(kc, rows=None):
+    """The emitter sample of the recording's vertices, keyed as the recording keys it (n + GUARD rows)."""
+    v = kc["v"]
+    return {"emitter_" + k: a for k, a in run_sample_emitter(kc, v, len(v["material"]), 1, 1, rows, RECORDED_BOUNCE).items()}
+
+
+def recorded_bounces(kc, emitter, rows=None):
+    """The four bounces of the recording, keyed as the recording keys them (n + GUARD rows); ``emitter``: the emitter sample LIT
+    reads, n rows under the recording's keys."""
+    v, out = kc["v"], {}
+    n = len(v["material"])
+    lit = dict(v, wl=emitter["emitter_wl"][:n])
+    for mode, rr in RECORDED_CASES:
+        args = (lit, n, mode, 0, 1, rr, emitter["emitter_lsel"][:n], emitter["emitter_emit"][:n]) if mode == "lit" else \
+            (v, n, mode, 0, 1, rr)
+        got = run_bounce(kc, *args, rows=rows, bounce=RECORDED_BOUNCE)
+        out.update({f"{mode}_rr{rr}_{k}": got[k] for k in KEYS})
+    return out
+
+
+def recorded_arrays(kc):
+    """What tests/golden/make_mesh_path_golden.py saves: every key above, n rows each."""
+    n = len(kc["v"]["material"])
+    em = recorded_emitter(kc)
+    return {k: a[:n] for k, a in dict(em, **recorded_bounces(kc, em)).items()}
+
+
+@pytest.fixture(scope="module")
+def recorded_case():
+    return make_kernel_case(RECORDED_N), dict(np.load(RECORDING))
+
+
+def test_mesh_kernels_are_bit_identical_to_the_recording(recorded_case):
+    kc, rec = recorded_case
+    n = RECORDED_N
+    got = dict(recorded_emitter(kc), **recorded_bounces(kc, rec))
+    assert sorted(got) == sorted(rec) and len(rec) == 3 + 8 * len(RECORDED_CASES)
+    for k in sorted(rec):
+        assert _bytes_equal(got[k][:n], rec[k]), k
+    # the recording exercises what it pins: both roulette outcomes, continuing and ending paths, every emitter
+    live = kc["v"]["material"] <= kc["geom"]["n_materials"]
+    for mode in ("cosine", "lit"):
+        on0, on2 = (rec[f"{mode}_rr{rr}_material"] <= kc["geom"]["n_materials"] for rr in (0, 2))
+        print(f"{mode}: {int(live.sum())} live vertices, {int(on0.sum())} continue without roulette, {int(on2.sum())} survive rr_depth = 2")
+        assert 0 < on2.sum() < on0.sum() < live.sum() and not (on2 & ~on0).any()
+    assert all((rec["emitter_lsel"][live] == k).sum() > 50 for k in (-1, 0, 1))
+
+
+def test_mesh_list_forms_write_the_recording_on_their_lanes(recorded_case):
+    """The _rows entry points over every second live lane: the recording's bits on the listed lanes, every other byte as it was."""
+    kc, rec = recorded_case
+    v, n = kc["v"], RECORDED_N
+    rows = np.nonzero(v["material"] <= kc["geom"]["n_materials"])[0][::2]
+    assert rows.size > 256                                                 # (more than one block)
+    listed = np.zeros(n, dtype=bool)
+    listed[rows] = True
+    got = dict(recorded_emitter(kc, rows), **recorded_bounces(kc, rec, rows))
+    before = {"emitter_wl": v["wl"], "emitter_lsel": np.full(n, LSEL_SENTINEL, dtype=np.int32),
+              "emitter_emit": np.full((n, 3), EMIT_SENTINEL, dtype=np.float32)}
+    for mode, rr in RECORDED_CASES:
+        before.update({f"{mode}_rr{rr}_{k}": rec["emitter_wl"] if (mode, k) == ("lit", "wl") else v[k] for k in KEYS})
+    for k in sorted(rec):
+        assert (got[k][n:] == -7).all() or k in ("emitter_lsel", "emitter_emit"), k
+        assert _bytes_equal(got[k][:n][listed], rec[k][listed]), k
+        assert _bytes_equal(got[k][:n][~listed], before[k][~listed]), k
+    assert (got["emitter_lsel"][n:] == LSEL_SENTINEL).all() and (got["emitter_emit"][n:] == EMIT_SENTINEL).all()
 
 
 # ---- 4. the primary rays of a path ----
